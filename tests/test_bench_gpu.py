@@ -9,18 +9,20 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def test_bench_self_launch_two_ranks_over_gloo(device):
+def test_bench_self_launch_two_ranks_over_gloo(device, tmp_path):
     env = dict(os.environ, KD_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
+    dump = tmp_path / "outputs"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--line-grid-steps", "1", "--grid-n", "2"]
+           "--line-grid-steps", "1", "--grid-n", "2", "--dump-outputs", str(dump)]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -29,6 +31,14 @@ def test_bench_self_launch_two_ranks_over_gloo(device):
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["collective_backend"] == "gloo"
     assert d["metric"].startswith("denoising-steps/sec") and d["scaling"] == "weak" and d["value"] > 0
     assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "denoising-steps/s"
+    assert d["ms_per_step"] > 0
+    # --dump-outputs: rank 0's last timed step, float32, within 64 MB
+    got = {f.name: np.load(f) for f in dump.iterdir()}
+    assert set(got) == {"x_prev.npy", "pred.npy", "x0.npy", "thresholds.npy"}
+    for name in ("x_prev.npy", "pred.npy", "x0.npy"):
+        assert got[name].shape == (16, 3, 256, 256) and got[name].dtype == np.float32 and np.isfinite(got[name]).all()
+    assert got["thresholds.npy"].shape == (16,) and (got["thresholds.npy"] >= 1).all()
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
     g = d["grid"]
     for key, ncan in (("canvases_1", 1), ("canvases_3", 3)):
         assert g[key]["patches"] == 4 * ncan and g[key]["patches_per_s"] > 0

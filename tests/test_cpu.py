@@ -447,6 +447,20 @@ def test_bench_launches_its_own_ranks_when_called_without_a_launcher(monkeypatch
     assert not calls
 
 
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--warmup", "-1"], ["--workload", "grid", "--dump-outputs", "d"]])
+def test_bench_rejects_arguments_it_cannot_honour(monkeypatch, argv):
+    """No timed step to divide by, or outputs asked of a workload that does not dump them: refused before any GPU call."""
+    import importlib
+    import sys
+
+    sys.path.insert(0, str(ROOT))
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_philox_host_reference_is_standard_normal_and_keyed():
     from oracle.philox_ref import philox4x32_10, philox_normal
 
