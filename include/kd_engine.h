@@ -288,8 +288,54 @@ int kd_sample_finalize(kd_unet_t* u, const kd_sample_args_t* args, float* d_img,
 /* What the last executed iteration left behind (parity checks against p_mean_variance of the library):
  * which = 0: the UNet's output eps-hat / v-hat after guidance [B,3,S,S]; 1: the x0 estimate before the
  * threshold clamp [B,3,S,S]; 2: the per-sample dynamic thresholds max(1, quantile_p |x0|) [B].
+ * which = 3 / 4 (after an EDM step only, kd_edm_sample_steps): x_hat / d of that step [B,3,S,S].
  * Stream-ordered device-to-device copy into d_out. */
 int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * EDM sampler.  Replaces `ElucidatedImagen.sample` / `one_unet_sample` / `preconditioned_network_forward` of
+ * imagen-pytorch 1.18.x (the sampler of the reference's commented-out constructor, train.py:97-110): Karras et al.'s
+ * stochastic Heun sampler - churn, two preconditioned UNet forwards per step (one on the last step), dynamic
+ * threshold of each denoised estimate, RePaint re-noise when inpainting.
+ * ---------------------------------------------------------------------------------------- */
+/* Per-step scalars for steps k = 0..N-1, computed by the host as the library does: sigma_hat = sigma + gamma sigma,
+ * churn = sqrt(sigma_hat^2 - sigma^2), euler_step = sigma_next - sigma_hat, heun_step = 0.5 (sigma_next - sigma_hat),
+ * renoise = sigma - sigma_next in double, rounded to fp32; c_in / c_skip / c_out / c_noise (the UNet's time input) of
+ * sigma_hat and of sigma_next by fp32 torch ops.  A step with sigma_next == 0 (only the last may have it) runs without
+ * the second-order correction.  All arrays have N entries. */
+typedef struct kd_edm_schedule {
+  int N;
+  float S_noise;              /* churn noise = S_noise * N(0,1) */
+  const float* sigma;
+  const float* sigma_hat;
+  const float* sigma_next;
+  const float* churn;
+  const float* euler_step;
+  const float* heun_step;
+  const float* renoise;
+  const float* c_in_hat;
+  const float* c_skip_hat;
+  const float* c_out_hat;
+  const float* c_noise_hat;
+  const float* c_in_next;
+  const float* c_skip_next;
+  const float* c_out_next;
+  const float* c_noise_next;
+} kd_edm_schedule_t;
+
+/* In: d_img = sigma_0 * N(0,1) [B,3,S,S].  Out: d_img = unnormalised sample in [0,1] (kd_sample_finalize included).
+ * kd_sample_args_t as for kd_sample_loop, with these differences: `objective` is ignored (the UNet is EDM-
+ * preconditioned); d_noise_step [N*R,B,3,S,S] holds the churn draws N(0,1) (before S_noise), d_noise_renoise the
+ * re-noise draws, both indexed (k*R + (R-1-r)); d_noise_inpaint is not read.  The conditioning table holds 2N rows
+ * (the time input at sigma_hat and at sigma_next of every step).  One captured graph per step kind (with and without
+ * the Heun correction), replayed. */
+int kd_edm_sample_loop(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                       void* stream);
+/* Steps [k_begin, k_end) only, without the final clamp / unnormalise.  kd_sample_last then reports the last forward of
+ * the last iteration: which = 0 its UNet output after guidance, 1 the denoised estimate c_skip x + c_out net before
+ * the threshold, 2 the thresholds; 3 x_hat and 4 d = (x_hat - thr(den)) / sigma_hat of that iteration. */
+int kd_edm_sample_steps(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                        int k_begin, int k_end, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Individual kernels, exported so that tests/ can check each one against the oracle through

@@ -32,7 +32,8 @@ struct SamplerCtx {
   bool cond_tab = false;   // the iteration restores the conditioning from kd_unet::cond_tab instead of computing it
 };
 
-static int sampler_prepare(kd_unet* u, const kd_schedule_t* sc, SamplerCtx& ctx, hipStream_t s) {
+// the sampler scratch both samplers use (UNet output, x0 estimate, thresholds, iteration, seed, quantile workspace)
+static int sampler_scratch(kd_unet* u) {
   const int B = u->cfg.batch, S = u->cfg.image_size;
   const size_t img_bytes = (size_t)B * 3 * S * S * sizeof(float);
   if (!u->s_pred) {
@@ -44,6 +45,11 @@ static int sampler_prepare(kd_unet* u, const kd_schedule_t* sc, SamplerCtx& ctx,
     KD_HIP_CHECK(hipMalloc((void**)&u->s_seed, sizeof(uint64_t)));
     KD_HIP_CHECK(hipMalloc(&u->s_qws, quantile_ws_bytes(B)));
   }
+  return 0;
+}
+
+static int sampler_prepare(kd_unet* u, const kd_schedule_t* sc, SamplerCtx& ctx, hipStream_t s) {
+  if (sampler_scratch(u)) return 1;
   const int T = sc->T;
   KD_REQUIRE(T >= 1, "schedule must have at least one step");
   if (u->s_tables_cap < T) {
@@ -102,15 +108,17 @@ static int sampler_prepare(kd_unet* u, const kd_schedule_t* sc, SamplerCtx& ctx,
 // gather instead of 21 launches (SR UNet; ~60 for a batch-1 patch of stage 1) and the 113 MB time-MLP GEMM.  The table is
 // keyed on the schedule's content, T and the low-res level, so every patch of a grid and every call of a traced run
 // reuse it.  Same kernels on the same inputs: results are bit-identical with the table off (args->cond_table < 0).
-static int sampler_cond_table(kd_unet* u, const kd_schedule_t* sc, const kd_sample_args_t* a, SamplerCtx& ctx, int k_begin,
-                              int k_end, hipStream_t s, bool force = false) {
+// `key`: the content the rows are a function of (the DDPM step tables; the EDM tables for its 2N rows, ctx.tb.log_snr then
+// pointing at its time inputs).
+static int sampler_cond_table(kd_unet* u, const std::vector<float>& key, const kd_sample_args_t* a, SamplerCtx& ctx,
+                              int k_begin, int k_end, hipStream_t s, bool force = false) {
   ctx.cond_tab = false;
   const bool lowres = u->cfg.lowres_cond != 0;
   if (a->cond_table < 0 || u->cond_bytes == 0 || u->cfg.text_tokens > 0 || cfg_on(a)) return 0;
   if (lowres && !a->lowres_log_snr_uniform) return 0;   // per-sample levels: computed in the step, as before
   const size_t need = (size_t)ctx.T * u->cond_bytes;
   const bool same = u->cond_tab != nullptr && u->cond_tab_bytes >= need && u->cond_tab_T == ctx.T &&
-                    (int)u->cond_tab_row_ok.size() == ctx.T && u->cond_tab_sched == u->s_tables_host &&
+                    (int)u->cond_tab_row_ok.size() == ctx.T && u->cond_tab_sched == key &&
                     (!lowres || u->cond_tab_lowres == a->lowres_log_snr_value);
   if (!same) {
     // every row of the old table is stale from here on, whatever happens below
@@ -128,10 +136,7 @@ static int sampler_cond_table(kd_unet* u, const kd_schedule_t* sc, const kd_samp
     if (u->cond_tab_bytes < need) {
       if (u->cond_tab) {
         KD_HIP_CHECK(hipStreamSynchronize(s));   // (a replay of the old table may still be running)
-        if (u->graph_exec) {   // the captured graph holds the old table pointer
-          (void)hipGraphExecDestroy(u->graph_exec);
-          u->graph_exec = nullptr;
-        }
+        u->drop_graphs();   // the captured graphs hold the old table pointer
         KD_HIP_CHECK(hipFree(u->cond_tab));
         u->cond_tab = nullptr;
         u->cond_tab_bytes = 0;
@@ -144,7 +149,7 @@ static int sampler_cond_table(kd_unet* u, const kd_schedule_t* sc, const kd_samp
       }
       u->cond_tab_bytes = need;
     }
-    u->cond_tab_sched = u->s_tables_host;
+    u->cond_tab_sched = key;
     u->cond_tab_T = ctx.T;
     u->cond_tab_lowres = a->lowres_log_snr_value;
     u->cond_tab_row_ok.assign((size_t)ctx.T, 0);
@@ -284,7 +289,7 @@ static int sample_steps(kd_unet* u, const kd_schedule_t* sc, const kd_sample_arg
   u->in_lowres = a->d_lowres;
   u->in_cond = a->d_cond_images;
   if (run_static(u, s)) return 1;  // conditioning planes are constant over the loop
-  if (sampler_cond_table(u, sc, a, ctx, k_begin, k_end, s)) return 1;
+  if (sampler_cond_table(u, u->s_tables_host, a, ctx, k_begin, k_end, s)) return 1;
   if (launch_iter_set(u->s_iter, k_begin * ctx.R, s)) return 1;
   if (!a->use_graph) {
     for (int i = 0; i < n_iter; ++i)
@@ -319,6 +324,187 @@ static int sample_steps(kd_unet* u, const kd_schedule_t* sc, const kd_sample_arg
     u->graph_key = key;
   }
   for (int i = 0; i < n_iter; ++i) KD_HIP_CHECK(hipGraphLaunch(u->graph_exec, s));
+  return 0;
+}
+
+
+// ------------------------------------------------------------------------------ EDM Heun sampler
+// Per-step tables of kd_edm_schedule_t -> u->e_tables [16][N] (stride N, so that c_noise_hat and c_noise_next form one
+// [2N] time table for the conditioning table).  Content-keyed: an unchanged schedule uploads nothing.
+static const int EDM_NTAB = 15;
+static int edm_prepare(kd_unet* u, const kd_edm_schedule_t* sc, EdmTables& tb, hipStream_t s) {
+  const int B = u->cfg.batch, S = u->cfg.image_size;
+  const size_t img_bytes = (size_t)B * 3 * S * S * sizeof(float);
+  const int N = sc->N;
+  KD_REQUIRE(N >= 1, "EDM schedule must have at least one step");
+  const float* src[EDM_NTAB] = {sc->sigma,      sc->sigma_hat,  sc->sigma_next, sc->churn,       sc->euler_step,
+                                sc->heun_step,  sc->renoise,    sc->c_in_hat,   sc->c_skip_hat,  sc->c_out_hat,
+                                sc->c_in_next,  sc->c_skip_next, sc->c_out_next, sc->c_noise_hat, sc->c_noise_next};
+  std::vector<float> host((size_t)EDM_NTAB * N + 1);
+  for (int i = 0; i < EDM_NTAB; ++i) {
+    KD_REQUIRE(src[i] != nullptr, "every array of kd_edm_schedule_t is required");
+    memcpy(host.data() + (size_t)i * N, src[i], (size_t)N * sizeof(float));
+  }
+  host[(size_t)EDM_NTAB * N] = sc->S_noise;   // (part of the key only)
+  for (int k = 0; k + 1 < N; ++k)   // the Heun kernel re-noises by step index: only the last step may skip the correction
+    KD_REQUIRE(src[2][k] != 0.0f, "EDM schedule: sigma_next == 0 before the last step");
+  if (!u->e_xhat) {
+    KD_HIP_CHECK(hipMalloc((void**)&u->e_xhat, img_bytes));
+    KD_HIP_CHECK(hipMalloc((void**)&u->e_d, img_bytes));
+    KD_HIP_CHECK(hipMalloc((void**)&u->e_in, img_bytes));
+  }
+  const int need = EDM_NTAB * N;
+  if (host != u->e_tables_host) {
+    if (u->e_tables_ev) KD_HIP_CHECK(hipEventSynchronize(u->e_tables_ev));   // the staging buffer's last upload
+    if (u->e_tables_cap < need) {   // (graphs captured on the old tables are re-captured: their key holds the address)
+      KD_HIP_CHECK(hipStreamSynchronize(s));   // replays on `s` may still read the old tables
+      if (u->e_tables) KD_HIP_CHECK(hipFree(u->e_tables));
+      if (u->e_tables_pinned) KD_HIP_CHECK(hipHostFree(u->e_tables_pinned));
+      u->e_tables = nullptr;
+      u->e_tables_pinned = nullptr;
+      u->e_tables_cap = 0;
+      KD_HIP_CHECK(hipMalloc((void**)&u->e_tables, (size_t)need * sizeof(float)));
+      KD_HIP_CHECK(hipHostMalloc((void**)&u->e_tables_pinned, (size_t)need * sizeof(float), hipHostMallocDefault));
+      u->e_tables_cap = need;
+    }
+    memcpy(u->e_tables_pinned, host.data(), (size_t)need * sizeof(float));
+    KD_HIP_CHECK(hipMemcpyAsync(u->e_tables, u->e_tables_pinned, (size_t)need * sizeof(float), hipMemcpyHostToDevice, s));
+    if (!u->e_tables_ev) KD_HIP_CHECK(hipEventCreateWithFlags(&u->e_tables_ev, hipEventDisableTiming));
+    KD_HIP_CHECK(hipEventRecord(u->e_tables_ev, s));
+    u->e_tables_host.swap(host);
+  }
+  const float* t = u->e_tables;
+  const float** dst[EDM_NTAB] = {&tb.sigma,     &tb.sigma_hat,   &tb.sigma_next, &tb.churn,       &tb.euler_step,
+                                 &tb.heun_step, &tb.renoise,     &tb.c_in_hat,   &tb.c_skip_hat,  &tb.c_out_hat,
+                                 &tb.c_in_next, &tb.c_skip_next, &tb.c_out_next, &tb.c_noise_hat, &tb.c_noise_next};
+  for (int i = 0; i < EDM_NTAB; ++i) *dst[i] = t + (size_t)i * N;
+  return 0;
+}
+
+// UNet forward j of the step (0: at sigma_hat, 1: at sigma_next) on u->e_in -> s_pred (+ the guidance forward), then
+// den = c_skip x + c_out net -> s_x0 and its per-sample quantile -> s_thresh
+static int edm_forward(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, const kd_sample_args_t* a, const float* x,
+                       int j, hipStream_t s) {
+  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, N = ctx.T / 2;
+  const int64_t per = (int64_t)3 * S * S;
+  if (launch_fill_time(j ? tb.c_noise_next : tb.c_noise_hat, u->s_iter, R, u->s_time, B, s)) return 1;
+  u->in_x = u->e_in;
+  u->in_lowres = a->d_lowres;
+  u->in_cond = a->d_cond_images;
+  u->in_log_snr = u->s_time;
+  u->in_lowres_log_snr = a->d_lowres_log_snr;
+  u->in_text_tokens = a->d_text_tokens;
+  u->in_text_hiddens = a->d_text_hiddens;
+  u->out = u->s_pred;
+  if (ctx.cond_tab)   // rows [0, N): time input at sigma_hat, [N, 2N): at sigma_next
+    if (launch_cond_gather(u->cond_tab + (size_t)j * N * u->cond_bytes, u->cond_ws, u->cond_bytes, u->s_iter, R, s))
+      return 1;
+  if (run_forward(u, s, ctx.cond_tab)) return 1;
+  if (cfg_on(a)) {
+    u->in_text_tokens = a->d_null_text_tokens;
+    u->in_text_hiddens = a->d_null_text_hiddens;
+    u->out = u->s_pred_null;
+    if (run_forward(u, s)) return 1;
+    if (launch_cfg_combine(u->s_pred, u->s_pred_null, u->s_pred, a->cond_scale, B * per, s)) return 1;
+  }
+  if (launch_edm_precond_out(x, u->s_pred, u->s_x0, j ? tb.c_skip_next : tb.c_skip_hat, j ? tb.c_out_next : tb.c_out_hat,
+                             u->s_iter, R, B * per, s))
+    return 1;
+  if (a->dynamic_threshold)
+    if (launch_quantile_abs(u->s_x0, u->s_thresh, B, per, a->percentile, u->s_qws, s)) return 1;
+  return 0;
+}
+
+// One EDM iteration: churn, forward at sigma_hat, Euler; with `heun` the forward at sigma_next and the correction
+// (+ re-noise).  Everything on `s`, in order: no side streams (a captured graph with parallel branches can crash the
+// runtime's replay).
+static int emit_edm_iteration(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, float s_noise,
+                              const kd_sample_args_t* a, float* d_img, bool heun, hipStream_t s) {
+  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, N = ctx.T / 2;
+  const int64_t hw = (int64_t)S * S, per = 3 * hw;
+  const bool inpaint = a->d_inpaint_images != nullptr;
+  if (launch_edm_churn(d_img, u->e_xhat, u->e_in, a->d_inpaint_images, a->d_inpaint_masks, a->d_noise_step, B * per,
+                       u->s_seed, tb, s_noise, u->s_iter, R, B, 3, hw, s))
+    return 1;
+  if (edm_forward(u, ctx, tb, a, u->e_xhat, 0, s)) return 1;
+  if (launch_edm_euler(u->e_xhat, u->s_x0, u->s_thresh, u->e_d, d_img, u->e_in, tb, u->s_iter, R, a->dynamic_threshold, B,
+                       per, s))
+    return 1;
+  if (heun) {
+    if (edm_forward(u, ctx, tb, a, d_img, 1, s)) return 1;
+    if (launch_edm_heun(d_img, u->e_xhat, u->e_d, u->s_x0, u->s_thresh, a->d_noise_renoise, B * per, u->s_seed, tb,
+                        u->s_iter, R, N, inpaint && R > 1, a->dynamic_threshold, B, per, s))
+      return 1;
+  }
+  return launch_iter_inc(u->s_iter, s);
+}
+
+static int edm_sample_steps(kd_unet* u, const kd_edm_schedule_t* sc, const kd_sample_args_t* a, float* d_img, int k_begin,
+                            int k_end, hipStream_t s) {
+  KD_REQUIRE(u && sc && a && d_img, "null argument");
+  KD_REQUIRE((a->d_inpaint_images == nullptr) == (a->d_inpaint_masks == nullptr),
+             "inpaint_images and inpaint_masks must be given together");
+  SamplerCtx ctx;
+  ctx.R = a->d_inpaint_images ? (a->resample_times < 1 ? 1 : a->resample_times) : 1;
+  if (sampler_scratch(u)) return 1;
+  EdmTables tb{};
+  if (edm_prepare(u, sc, tb, s)) return 1;
+  const int N = sc->N;
+  ctx.T = 2 * N;   // rows of the conditioning table; its time inputs: c_noise_hat | c_noise_next
+  ctx.tb = StepTables{};
+  ctx.tb.log_snr = tb.c_noise_hat;
+  if (cfg_on(a)) {
+    KD_REQUIRE(a->d_null_text_tokens && a->d_null_text_hiddens && a->d_text_tokens && a->d_text_hiddens,
+               "cond_scale != 1 needs the conditional and the null text conditioning");
+    if (!u->s_pred_null)
+      KD_HIP_CHECK(hipMalloc((void**)&u->s_pred_null,
+                             (size_t)u->cfg.batch * 3 * u->cfg.image_size * u->cfg.image_size * sizeof(float)));
+  }
+  KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= N, "step range out of bounds");
+  if (launch_seed_set(u->s_seed, a->seed, s)) return 1;
+  u->in_lowres = a->d_lowres;
+  u->in_cond = a->d_cond_images;
+  if (run_static(u, s)) return 1;
+  // rows k of both halves for the steps walked (the rows in between come along; each row is built once per schedule)
+  if (sampler_cond_table(u, u->e_tables_host, a, ctx, k_begin, k_end > k_begin ? N + k_end : k_begin, s)) return 1;
+  if (launch_iter_set(u->s_iter, k_begin * ctx.R, s)) return 1;
+  for (int k = k_begin; k < k_end; ++k) {
+    const bool heun = sc->sigma_next[k] != 0.0f;
+    if (!a->use_graph) {
+      for (int r = 0; r < ctx.R; ++r)
+        if (emit_edm_iteration(u, ctx, tb, sc->S_noise, a, d_img, heun, s)) return 1;
+      continue;
+    }
+    const int g = heun ? 0 : 1;
+    std::vector<uint64_t> key = graph_key_of(a, d_img, ctx.T, ctx.R, ctx.cond_tab);
+    uint32_t sn_bits;
+    memcpy(&sn_bits, &sc->S_noise, sizeof(float));
+    key.push_back((uint64_t)(uintptr_t)u->e_tables);   // (the stride N of the tables is in the key as T = 2N)
+    key.push_back(sn_bits);
+    if (!u->e_graph[g] || key != u->e_graph_key[g]) {
+      if (u->e_graph[g]) {
+        (void)hipGraphExecDestroy(u->e_graph[g]);
+        u->e_graph[g] = nullptr;
+      }
+      // captured on the engine-owned stream (one stream, no forks), replayed on `s`
+      if (!u->cap_stream) KD_HIP_CHECK(hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking));
+      hipGraph_t graph = nullptr;
+      KD_HIP_CHECK(hipStreamBeginCapture(u->cap_stream, hipStreamCaptureModeThreadLocal));
+      int rc = emit_edm_iteration(u, ctx, tb, sc->S_noise, a, d_img, heun, u->cap_stream);
+      hipError_t e = hipStreamEndCapture(u->cap_stream, &graph);
+      if (rc || e != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        if (rc) return 1;
+        KD_HIP_CHECK(e);
+      }
+      e = hipGraphInstantiate(&u->e_graph[g], graph, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(graph);
+      if (e != hipSuccess) u->e_graph[g] = nullptr;
+      KD_HIP_CHECK(e);
+      u->e_graph_key[g] = key;
+    }
+    for (int r = 0; r < ctx.R; ++r) KD_HIP_CHECK(hipGraphLaunch(u->e_graph[g], s));
+  }
   return 0;
 }
 
@@ -519,9 +705,24 @@ int kd_sample_build_cond_table(kd_unet_t* u, const kd_schedule_t* sched, const k
   if (sampler_prepare(u, sched, ctx, s)) return 1;
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= ctx.T, "step range out of bounds");
   u->cond_tab_build_rows = 0;
-  if (sampler_cond_table(u, sched, args, ctx, k_begin, k_end, s, force != 0)) return 1;
+  if (sampler_cond_table(u, u->s_tables_host, args, ctx, k_begin, k_end, s, force != 0)) return 1;
   if (built) *built = ctx.cond_tab ? u->cond_tab_build_rows : 0;
   return 0;
+}
+
+int kd_edm_sample_steps(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                        int k_begin, int k_end, void* stream) {
+  return edm_sample_steps(u, sched, args, d_img, k_begin, k_end, (hipStream_t)stream);
+}
+
+int kd_edm_sample_loop(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                       void* stream) {
+  if (!sched) {
+    set_error("kd_edm_sample_loop: null schedule");
+    return 1;
+  }
+  if (edm_sample_steps(u, sched, args, d_img, 0, sched->N, (hipStream_t)stream)) return 1;
+  return kd_sample_finalize(u, args, d_img, stream);
 }
 
 int kd_sample_loop(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
@@ -543,9 +744,10 @@ int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream) {
     return 1;
   }
   KD_REQUIRE(u->s_pred, "kd_sample_last: no sampling step has run on this plan");
-  KD_REQUIRE(which >= 0 && which <= 2, "kd_sample_last: which must be 0 (pred), 1 (x0) or 2 (thresholds)");
+  KD_REQUIRE(which >= 0 && which <= 4, "kd_sample_last: which must be 0 (pred), 1 (x0), 2 (thresholds), 3 / 4 (EDM x_hat / d)");
+  KD_REQUIRE(which <= 2 || u->e_xhat, "kd_sample_last: no EDM step has run on this plan");
   const int B = u->cfg.batch, S = u->cfg.image_size;
-  const float* src = which == 0 ? u->s_pred : which == 1 ? u->s_x0 : u->s_thresh;
+  const float* src = which == 0 ? u->s_pred : which == 1 ? u->s_x0 : which == 2 ? u->s_thresh : which == 3 ? u->e_xhat : u->e_d;
   const size_t bytes = (which == 2 ? (size_t)B : (size_t)B * 3 * S * S) * sizeof(float);
   KD_HIP_CHECK(hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;

@@ -348,6 +348,25 @@ int launch_fill_time_rows(const float* table, int k0, int T, float* out, int B, 
 int launch_cond_scatter(const float* ws, float* tab, const CondSeg* d_segs, int nseg, uint32_t row_total, int B, int k0, int T,
                         int64_t cond_floats, hipStream_t s);
 int launch_finalize(float* x, const float* inp, const float* mask, int B, int C, int64_t hw, hipStream_t s);
+// EDM Heun sampler (ElucidatedImagen): device arrays of N floats, one per sampling step (kd_edm_schedule_t);
+// c_noise_hat and c_noise_next are adjacent ([2N]: the time input of the first and of the second forward)
+struct EdmTables {
+  const float *sigma, *sigma_hat, *sigma_next, *churn, *euler_step, *heun_step, *renoise, *c_in_hat, *c_skip_hat,
+      *c_out_hat, *c_in_next, *c_skip_next, *c_out_next, *c_noise_hat, *c_noise_next;
+};
+int launch_edm_churn(const float* x, float* xh, float* net_in, const float* inp, const float* mask, const float* noise,
+                     int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb, float s_noise, const int* d_iter,
+                     int R, int B, int C, int64_t hw, hipStream_t s);
+int launch_edm_precond_out(const float* x, const float* net, float* den, const float* c_skip_tab, const float* c_out_tab,
+                           const int* d_iter, int R, int64_t n, hipStream_t s);
+int launch_edm_euler(const float* xh, const float* den, const float* s_thresh, float* d_out, float* x, float* net_in,
+                     const EdmTables& tb, const int* d_iter, int R, int dynamic_threshold, int B, int64_t per,
+                     hipStream_t s);
+int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* den, const float* s_thresh,
+                    const float* noise, int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb,
+                    const int* d_iter, int R, int N, int renoise, int dynamic_threshold, int B, int64_t per,
+                    hipStream_t s);
+
 int launch_iter_inc(int* d_iter, hipStream_t s);
 int launch_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);
 

@@ -179,6 +179,23 @@ struct kd_unet {
   hipGraphExec_t graph_exec = nullptr;
   hipStream_t cap_stream = nullptr;
   std::vector<uint64_t> graph_key;
+  // EDM sampler (kd_edm_sample_*): x_hat, d and the UNet input of the step, its per-step tables (16 x N, stride N,
+  // content-keyed like s_tables) and one captured iteration per step kind (0: with the Heun correction, 1: without)
+  float *e_xhat = nullptr, *e_d = nullptr, *e_in = nullptr, *e_tables = nullptr;
+  int e_tables_cap = 0;   // floats
+  std::vector<float> e_tables_host;
+  float* e_tables_pinned = nullptr;
+  hipEvent_t e_tables_ev = nullptr;
+  hipGraphExec_t e_graph[2] = {nullptr, nullptr};
+  std::vector<uint64_t> e_graph_key[2];
+  void drop_graphs() {   // every captured graph: they hold the addresses of the tables / buffers being replaced
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    graph_exec = nullptr;
+    for (auto& g : e_graph) {
+      if (g) (void)hipGraphExecDestroy(g);
+      g = nullptr;
+    }
+  }
 
   // ---- step-invariant-per-schedule-index conditioning (time embeddings, FiLM scale / shift, time tokens and their
   // cross-attention K / V): ops flagged op_is_cond write only into the `cond_ws` region (offsets carry COND_FLAG); the
@@ -208,14 +225,16 @@ struct kd_unet {
 
   float* P(size_t off) const { return (float*)((off & COND_FLAG) ? cond_ws + (off & ~COND_FLAG) : ws + off); }
   ~kd_unet() {
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    drop_graphs();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     void* frees[] = {ws, s_pred, s_x0, s_thresh, s_time, s_tables, s_iter, s_seed, s_qws, s_pred_null, cond_ws, cond_tab,
-                     d_cond_segs, x3_ws};
+                     d_cond_segs, x3_ws, e_xhat, e_d, e_in, e_tables};
     for (void* p : frees)
       if (p) (void)hipFree(p);
     if (s_tables_pinned) (void)hipHostFree(s_tables_pinned);
     if (s_tables_ev) (void)hipEventDestroy(s_tables_ev);
+    if (e_tables_pinned) (void)hipHostFree(e_tables_pinned);
+    if (e_tables_ev) (void)hipEventDestroy(e_tables_ev);
     if (cond_ev0) (void)hipEventDestroy(cond_ev0);
     if (cond_ev1) (void)hipEventDestroy(cond_ev1);
   }

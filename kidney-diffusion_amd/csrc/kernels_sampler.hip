@@ -55,7 +55,8 @@ __device__ __forceinline__ f32x4 philox_normal4(uint64_t seed, uint64_t sid, uin
 }
 // stream ids: purpose in the top 32 bits, iteration in the low 32
 __device__ __forceinline__ uint64_t stream_id(uint32_t purpose, uint32_t it) { return ((uint64_t)purpose << 32) | it; }
-enum { PURPOSE_STEP = 1, PURPOSE_INPAINT = 2, PURPOSE_RENOISE = 3, PURPOSE_USER = 16 };
+enum { PURPOSE_STEP = 1, PURPOSE_INPAINT = 2, PURPOSE_RENOISE = 3, PURPOSE_EDM_CHURN = 4, PURPOSE_EDM_RENOISE = 5,
+       PURPOSE_USER = 16 };
 
 __global__ void philox_normal_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t sid) {
   int64_t n4 = (n + 3) / 4;
@@ -430,6 +431,150 @@ int launch_renoise(float* x, const float* noise, int64_t noise_stride, const uin
   int64_t total4 = (int64_t)B * per / 4;
   hipLaunchKernelGGL(renoise_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, noise, noise_stride, d_seed, tb,
                      d_iter, R, T, total4);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- EDM Heun sampler (ElucidatedImagen)
+// One step k (iteration it, k = it / R):  x_hat = x + churn_k * (S_noise * N(0,1))  [known pixels: inp + the same
+// added noise]; den = thr(c_skip(sh) x_hat + c_out(sh) net(c_in(sh) x_hat)); d = (x_hat - den) / sh;
+// x_next = x_hat + (sn - sh) d; Heun: den2 = thr(c_skip(sn) x_next + c_out(sn) net(c_in(sn) x_next)),
+// d2 = (x_next - den2) / sn, x = x_hat + 0.5 (sn - sh) (d + d2) (+ RePaint re-noise).  The host computes every
+// per-step scalar as the library does (python doubles for sh / churn / step sizes, fp32 torch ops for the c_*).
+
+// x_hat (inpaint mix included) -> xh, and c_in(sh) * x_hat -> net_in (the UNet's input)
+__global__ void edm_churn_kernel(const float* __restrict__ x, float* __restrict__ xh, float* __restrict__ net_in,
+                                 const float* __restrict__ inp, const float* __restrict__ mask,
+                                 const float* __restrict__ noise, int64_t noise_stride, const uint64_t* __restrict__ d_seed,
+                                 EdmTables tb, float s_noise, const int* __restrict__ d_iter, int R, int C, int64_t hw4,
+                                 int64_t total4) {
+  const uint64_t seed = *d_seed;
+  const int it = *d_iter;
+  const int k = it / R;
+  const float churn = tb.churn[k], c_in = tb.c_in_hat[k];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 xv = *(const f32x4*)(x + i * 4);
+    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_EDM_CHURN, it, i), o, ci;
+    f32x4 m = {0.f, 0.f, 0.f, 0.f}, iv = {0.f, 0.f, 0.f, 0.f};
+    if (inp) {
+      const int64_t plane = i / hw4, p4 = i - plane * hw4, b = plane / C;
+      m = *(const f32x4*)(mask + (b * hw4 + p4) * 4);
+      iv = *(const f32x4*)(inp + i * 4);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float added = churn * (s_noise * z[e]);
+      o[e] = m[e] != 0.f ? iv[e] + added : xv[e] + added;   // x_hat*~mask + (inp + added)*mask, boolean mask
+      ci[e] = c_in * o[e];
+    }
+    *(f32x4*)(xh + i * 4) = o;
+    *(f32x4*)(net_in + i * 4) = ci;
+  }
+}
+int launch_edm_churn(const float* x, float* xh, float* net_in, const float* inp, const float* mask, const float* noise,
+                     int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb, float s_noise, const int* d_iter,
+                     int R, int B, int C, int64_t hw, hipStream_t s) {
+  KD_REQUIRE(hw % 4 == 0, "H*W must be a multiple of 4");
+  const int64_t total4 = (int64_t)B * C * hw / 4;
+  hipLaunchKernelGGL(edm_churn_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, xh, net_in, inp, mask, noise,
+                     noise_stride, d_seed, tb, s_noise, d_iter, R, C, hw / 4, total4);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// den = c_skip[k] * x + c_out[k] * net   (before the threshold: the x0 estimate kd_sample_last reports)
+__global__ void edm_precond_out_kernel(const float* __restrict__ x, const float* __restrict__ net, float* __restrict__ den,
+                                       const float* __restrict__ c_skip_tab, const float* __restrict__ c_out_tab,
+                                       const int* __restrict__ d_iter, int R, int64_t n4) {
+  const int k = *d_iter / R;
+  const float c_skip = c_skip_tab[k], c_out = c_out_tab[k];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 xv = *(const f32x4*)(x + i * 4), nv = *(const f32x4*)(net + i * 4), o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = c_skip * xv[e] + c_out * nv[e];
+    *(f32x4*)(den + i * 4) = o;
+  }
+}
+int launch_edm_precond_out(const float* x, const float* net, float* den, const float* c_skip_tab, const float* c_out_tab,
+                           const int* d_iter, int R, int64_t n, hipStream_t s) {
+  KD_REQUIRE(n % 4 == 0, "image element count must be a multiple of 4");
+  hipLaunchKernelGGL(edm_precond_out_kernel, dim3(grid_for(n / 4)), dim3(256), 0, s, x, net, den, c_skip_tab, c_out_tab,
+                     d_iter, R, n / 4);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+__device__ __forceinline__ float edm_thr(float v, float s) { return fminf(fmaxf(v, -s), s) / s; }
+
+// Euler: d = (x_hat - thr(den)) / sh -> d_out ; x_next = x_hat + (sn - sh) d -> x ; c_in(sn) x_next -> net_in
+__global__ void edm_euler_kernel(const float* __restrict__ xh, const float* __restrict__ den,
+                                 const float* __restrict__ s_thresh, float* __restrict__ d_out, float* __restrict__ x,
+                                 float* __restrict__ net_in, EdmTables tb, const int* __restrict__ d_iter, int R,
+                                 int dynamic_threshold, int64_t per4, int64_t total4) {
+  const int k = *d_iter / R;
+  const float sh = tb.sigma_hat[k], step = tb.euler_step[k], c_in = tb.c_in_next[k];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float s = dynamic_threshold ? fmaxf(s_thresh[i / per4], 1.0f) : 1.0f;
+    f32x4 hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(den + i * 4), d, xn, ci;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      d[e] = (hv[e] - edm_thr(dv[e], s)) / sh;
+      xn[e] = hv[e] + step * d[e];
+      ci[e] = c_in * xn[e];
+    }
+    *(f32x4*)(d_out + i * 4) = d;
+    *(f32x4*)(x + i * 4) = xn;
+    *(f32x4*)(net_in + i * 4) = ci;
+  }
+}
+int launch_edm_euler(const float* xh, const float* den, const float* s_thresh, float* d_out, float* x, float* net_in,
+                     const EdmTables& tb, const int* d_iter, int R, int dynamic_threshold, int B, int64_t per,
+                     hipStream_t s) {
+  KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
+  const int64_t total4 = (int64_t)B * per / 4;
+  hipLaunchKernelGGL(edm_euler_kernel, dim3(grid_for(total4)), dim3(256), 0, s, xh, den, s_thresh, d_out, x, net_in, tb,
+                     d_iter, R, dynamic_threshold, per / 4, total4);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Heun: d2 = (x_next - thr(den2)) / sn ; x = x_hat + 0.5 (sn - sh) (d + d2) ; RePaint re-noise x += (s - sn) N(0,1)
+// after every resample but the last (r == 0) and never on the last step.  x holds x_next on entry (in place).
+__global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__ xh, const float* __restrict__ d_in,
+                                const float* __restrict__ den, const float* __restrict__ s_thresh,
+                                const float* __restrict__ noise, int64_t noise_stride, const uint64_t* __restrict__ d_seed,
+                                EdmTables tb, const int* __restrict__ d_iter, int R, int N, int renoise,
+                                int dynamic_threshold, int64_t per4, int64_t total4) {
+  const uint64_t seed = *d_seed;
+  const int it = *d_iter;
+  const int k = it / R, ri = it - k * R;
+  const bool rn = renoise && ri != R - 1 && k != N - 1;
+  const float sn = tb.sigma_next[k], step = tb.heun_step[k], rs = tb.renoise[k];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float s = dynamic_threshold ? fmaxf(s_thresh[i / per4], 1.0f) : 1.0f;
+    f32x4 xv = *(const f32x4*)(x + i * 4), hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(d_in + i * 4),
+          nv = *(const f32x4*)(den + i * 4), o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d2 = (xv[e] - edm_thr(nv[e], s)) / sn;
+      o[e] = hv[e] + step * (dv[e] + d2);
+    }
+    if (rn) {
+      f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_EDM_RENOISE, it, i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = o[e] + rs * z[e];
+    }
+    *(f32x4*)(x + i * 4) = o;
+  }
+}
+int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* den, const float* s_thresh,
+                    const float* noise, int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb,
+                    const int* d_iter, int R, int N, int renoise, int dynamic_threshold, int B, int64_t per,
+                    hipStream_t s) {
+  KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
+  const int64_t total4 = (int64_t)B * per / 4;
+  hipLaunchKernelGGL(edm_heun_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, xh, d_in, den, s_thresh, noise,
+                     noise_stride, d_seed, tb, d_iter, R, N, renoise, dynamic_threshold, per / 4, total4);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -99,6 +99,14 @@ class kd_sample_args_t(C.Structure):
     ]
 
 
+
+class kd_edm_schedule_t(C.Structure):
+    _fields_ = [("N", C.c_int), ("S_noise", C.c_float)] + [
+        (n, C.POINTER(C.c_float))
+        for n in ("sigma", "sigma_hat", "sigma_next", "churn", "euler_step", "heun_step", "renoise", "c_in_hat",
+                  "c_skip_hat", "c_out_hat", "c_noise_hat", "c_in_next", "c_skip_next", "c_out_next", "c_noise_next")
+    ]
+
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
 SIGNATURES = {
     "kd_last_error": (C.c_char_p, []),
@@ -130,6 +138,10 @@ SIGNATURES = {
                                              C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "kd_sample_finalize": (C.c_int, [C.c_void_p, C.POINTER(kd_sample_args_t), C.c_void_p, C.c_void_p]),
     "kd_sample_last": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "kd_edm_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                     C.c_void_p]),
+    "kd_edm_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                      C.c_int, C.c_int, C.c_void_p]),
     "kd_conv2d_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
     "kd_conv3x3_winograd_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "kd_conv3x3_winograd4_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),

@@ -700,13 +700,6 @@ class SRUnet1024(Unet):
         super().__init__(*args, **{**d, **kwargs})
 
 
-class ElucidatedImagen(nn.Module):
-    """Imported by the reference, only used in commented-out code (train.py:97-110)."""
-
-    def __init__(self, *a, **k):
-        raise NotImplementedError("ElucidatedImagen is outside the reference's live sampling path")
-
-
 # ============================================================================ schedules (host scalars)
 def _log(t, eps=1e-12):
     return torch.log(t.clamp(min=eps))
@@ -948,14 +941,7 @@ class Imagen(nn.Module):
             if has_inpaint:
                 inp = stable("inpaint", f32(resize_image_to(f32(inpaint_images) * 2 - 1, size)))
                 msk = stable("mask", f32(resize_image_to(f32(inpaint_masks)[:, None], size).bool().float()))
-            T = sched.num_timesteps
-            tables = sched.step_tables()
-            sc = E.kd_schedule_t()
-            sc.T = T
-            for name, v in tables.items():
-                setattr(sc, name, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
             args = E.kd_sample_args_t()
-            args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
             args.dynamic_threshold = int(bool(dynamic_threshold))
             args.percentile = self.dynamic_thresholding_percentile
             args.resample_times = R
@@ -968,17 +954,6 @@ class Imagen(nn.Module):
                 args.lowres_log_snr_value = float(ls[0])
             args.cond_table = int(getattr(self, "cond_table", 0))   # engine extension: < 0 switches the table off
             keep = []
-            if exists(noise_fn):
-                def stack(kind):
-                    ts = [noise_fn((kind, stage, k, r), shape) for k in range(T) for r in reversed(range(R))]
-                    t = f32(torch.stack(ts))
-                    keep.append(t)
-                    return E.ptr(t)
-                args.d_noise_step = stack("step")
-                if has_inpaint:
-                    args.d_noise_inpaint = stack("inpaint")
-                    if R > 1:
-                        args.d_noise_renoise = stack("renoise")
             img = stable("img", gauss(("init", stage), shape, (16 << 32) | 2))
             with_text = exists(text_embeds) and unet.cond_on_text
             h = unet.engine(batch, size, device, with_text=with_text)
@@ -993,16 +968,133 @@ class Imagen(nn.Module):
                     ntok, nhid = stable("null_text_tokens", ntok), stable("null_text_hiddens", nhid)
                     keep += [ntok, nhid]
                     args.d_null_text_tokens, args.d_null_text_hiddens = E.ptr(ntok), E.ptr(nhid)
-            if exists(trace):
-                for k in range(T):
-                    E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
-                    trace.append(img.clone())
-                E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
-            else:
-                E.check(lib.kd_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
+
+            def stack(kind, T):   # injected noise of every iteration, [T*R, *shape], indexed k*R + (R-1-r)
+                ts = [noise_fn((kind, stage, k, r), shape) for k in range(T) for r in reversed(range(R))]
+                t = f32(torch.stack(ts))
+                keep.append(t)
+                return E.ptr(t)
+
+            self._stage_loop(lib, h, args, img, stage=stage, sched=sched, objective=objective, has_inpaint=has_inpaint,
+                             R=R, stack=stack if exists(noise_fn) else None, trace=trace)
             # No host synchronisation here: the engine copies the schedule tables into its own staging buffer inside
             # the call, and the injected-noise tensors in `keep` are device memory of torch's current stream - the
             # caching allocator re-uses it for later allocations of that stream only, i.e. after these launches.
             del keep
             img = img.clone()  # the stable buffer is overwritten by the next call (stream-ordered copy)
         return img
+
+    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace):
+        """The sampler proper of one stage, in place on `img` (x_T in, the unnormalised sample out): the DDPM loop of
+        p_sample_loop.  `stack(kind, T)` gives the injected noise of a kind (None: on-device Philox)."""
+        T = sched.num_timesteps
+        tables = sched.step_tables()
+        sc = E.kd_schedule_t()
+        sc.T = T
+        for name, v in tables.items():
+            setattr(sc, name, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
+        args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
+        if exists(stack):
+            args.d_noise_step = stack("step", T)
+            if has_inpaint:
+                args.d_noise_inpaint = stack("inpaint", T)
+                if R > 1:
+                    args.d_noise_renoise = stack("renoise", T)
+        if exists(trace):
+            for k in range(T):
+                E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
+                trace.append(img.clone())
+            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
+        else:
+            E.check(lib.kd_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
+
+
+# ============================================================================ ElucidatedImagen (EDM)
+EDM_HPARAMS = ("num_sample_steps", "sigma_min", "sigma_max", "sigma_data", "rho", "P_mean", "P_std", "S_churn", "S_tmin",
+               "S_tmax", "S_noise")
+
+
+def edm_step_tables(num_sample_steps=32, sigma_min=0.002, sigma_max=80, sigma_data=0.5, rho=7, S_churn=80, S_tmin=0.05,
+                    S_tmax=50, S_noise=1.003, **_):
+    """Host scalars of imagen-pytorch 1.18.x's ElucidatedImagen sampler for one UNet (the arrays of kd_edm_schedule_t):
+    the Karras schedule and churn in fp32 torch ops, the step's sigmas as python floats (`.item()`), hence sigma_hat,
+    the churn scale and the step sizes in double, and the preconditioning c_* of sigma_hat / sigma_next as fp32 torch
+    ops on the rounded sigmas - the library's op order throughout."""
+    N = num_sample_steps
+    inv_rho = 1 / rho
+    steps = torch.arange(N, dtype=torch.float32)
+    sigmas = (sigma_max ** inv_rho + steps / (N - 1) * (sigma_min ** inv_rho - sigma_max ** inv_rho)) ** rho
+    sigmas = F.pad(sigmas, (0, 1), value=0.0)
+    gammas = torch.where((sigmas >= S_tmin) & (sigmas <= S_tmax), min(S_churn / N, math.sqrt(2) - 1), 0.0)
+    sd = sigma_data
+    c_skip = lambda sg: (sd ** 2) / (sg ** 2 + sd ** 2)
+    c_out = lambda sg: sg * sd * (sd ** 2 + sg ** 2) ** -0.5
+    c_in = lambda sg: 1 * (sg ** 2 + sd ** 2) ** -0.5
+    c_noise = lambda sg: _log(sg, eps=1e-20) * 0.25
+    rows = {n: [] for n in ("sigma", "sigma_hat", "sigma_next", "churn", "euler_step", "heun_step", "renoise")}
+    for sigma, sigma_next, gamma in zip(sigmas[:-1].tolist(), sigmas[1:].tolist(), gammas[:-1].tolist()):
+        sigma_hat = sigma + gamma * sigma
+        for n, v in (("sigma", sigma), ("sigma_hat", sigma_hat), ("sigma_next", sigma_next),
+                     ("churn", math.sqrt(sigma_hat ** 2 - sigma ** 2)), ("euler_step", sigma_next - sigma_hat),
+                     ("heun_step", 0.5 * (sigma_next - sigma_hat)), ("renoise", sigma - sigma_next)):
+            rows[n].append(v)
+    out = {n: torch.tensor(v, dtype=torch.float64).to(torch.float32) for n, v in rows.items()}
+    for tag, sg in (("hat", out["sigma_hat"]), ("next", out["sigma_next"])):
+        out[f"c_in_{tag}"], out[f"c_skip_{tag}"] = c_in(sg), c_skip(sg)
+        out[f"c_out_{tag}"], out[f"c_noise_{tag}"] = c_out(sg), c_noise(sg)
+    out["init_sigma"] = sigmas[0]
+    return {n: v.to(torch.float32).contiguous() for n, v in out.items()}
+
+
+class ElucidatedImagen(Imagen):
+    """imagen-pytorch 1.18.x's ElucidatedImagen for sampling: the UNets, checkpoint layout, low-res augmentation,
+    guidance, thresholding and inpainting inputs of `Imagen` (state_dict keys equal), the per-stage loop replaced by
+    the EDM stochastic Heun sampler of the engine (kd_edm_sample_loop).  Constructor as train.py:97-110 writes it;
+    the per-UNet hyperparameters are cast to the number of UNets.  Training (`forward`) is not provided."""
+
+    def __init__(self, unets, *, image_sizes, text_encoder_name=None, text_embed_dim=None, channels=3, cond_drop_prob=0.1,
+                 random_crop_sizes=None, lowres_noise_schedule="linear", lowres_sample_noise_level=0.2,
+                 per_sample_random_aug_noise_level=False, condition_on_text=True, auto_normalize_img=True,
+                 dynamic_thresholding=True, dynamic_thresholding_percentile=0.95, only_train_unet_number=None,
+                 num_sample_steps=32, sigma_min=0.002, sigma_max=80, sigma_data=0.5, rho=7, P_mean=-1.2, P_std=1.2,
+                 S_churn=80, S_tmin=0.05, S_tmax=50, S_noise=1.003, **ignored_training_kwargs):
+        super().__init__(unets, image_sizes=image_sizes, text_encoder_name=text_encoder_name, text_embed_dim=text_embed_dim,
+                         channels=channels, cond_drop_prob=cond_drop_prob, random_crop_sizes=random_crop_sizes,
+                         lowres_noise_schedule=lowres_noise_schedule, lowres_sample_noise_level=lowres_sample_noise_level,
+                         per_sample_random_aug_noise_level=per_sample_random_aug_noise_level,
+                         condition_on_text=condition_on_text, auto_normalize_img=auto_normalize_img,
+                         dynamic_thresholding=dynamic_thresholding,
+                         dynamic_thresholding_percentile=dynamic_thresholding_percentile,
+                         only_train_unet_number=only_train_unet_number, **ignored_training_kwargs)
+        n = len(self.unets)
+        vals = dict(num_sample_steps=num_sample_steps, sigma_min=sigma_min, sigma_max=sigma_max, sigma_data=sigma_data,
+                    rho=rho, P_mean=P_mean, P_std=P_std, S_churn=S_churn, S_tmin=S_tmin, S_tmax=S_tmax, S_noise=S_noise)
+        cast = {k: cast_tuple(v, n) for k, v in vals.items()}
+        self.hparams = [{k: cast[k][i] for k in EDM_HPARAMS} for i in range(n)]   # per UNet
+
+    def step_tables(self, unet_number):
+        """Host tables of UNet `unet_number`'s sampler (edm_step_tables)."""
+        return edm_step_tables(**self.hparams[unet_number - 1])
+
+    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace):
+        """one_unet_sample of the library's ElucidatedImagen on the engine: x = sigma_0 * N(0,1), then per step churn,
+        a preconditioned forward and the Euler step, and (not on the last step) a second forward and the Heun
+        correction; RePaint re-noise between resamples.  Noise tags ("churn" | "renoise", stage, k, r)."""
+        tab = self.step_tables(stage)
+        N = self.hparams[stage - 1]["num_sample_steps"]
+        sc = E.kd_edm_schedule_t()
+        sc.N, sc.S_noise = N, float(self.hparams[stage - 1]["S_noise"])
+        for name, _ in E.kd_edm_schedule_t._fields_[2:]:
+            setattr(sc, name, tab[name].numpy().ctypes.data_as(C.POINTER(C.c_float)))
+        img.mul_(float(tab["init_sigma"]))   # x = sigma_0 * N(0,1), fp32 as the library's tensor product
+        if exists(stack):
+            args.d_noise_step = stack("churn", N)
+            if has_inpaint and R > 1:
+                args.d_noise_renoise = stack("renoise", N)
+        if exists(trace):
+            for k in range(N):
+                E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
+                trace.append(img.clone())
+            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
+        else:
+            E.check(lib.kd_edm_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
