@@ -146,6 +146,11 @@ int kd_unet_create(const kd_unet_config_t* cfg, const kd_param_t* params, int n_
  * values as when `share_with` was created.  The store lives until the last plan is destroyed. */
 int kd_unet_create_shared(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
                           const kd_unet_t* share_with, kd_unet_t** out);
+/* Same, for a self-conditioned UNet (library `Unet(self_cond=True)`) when self_cond != 0: its init conv reads
+ * cat(cond_images, x, self_cond, lowres) (init_conv.convs.*.weight with 3 more input channels), and the samplers carry
+ * the thresholded x0 estimate of each step into the next forward.  share_with must have the same self_cond. */
+int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
+                             const kd_unet_t* share_with, int self_cond, kd_unet_t** out);
 void kd_unet_destroy(kd_unet_t* u);
 /* bytes of HBM held (weights + workspace) and algorithmic MACs of one forward (whole batch) */
 int64_t kd_unet_hbm_bytes(const kd_unet_t* u);
@@ -198,6 +203,11 @@ int kd_unet_forward(kd_unet_t* u, const float* d_x, const float* d_lowres,
                     const float* d_cond_images, const float* d_log_snr,
                     const float* d_lowres_log_snr, const float* d_text_tokens,
                     const float* d_text_hiddens, float* d_out, void* stream);
+/* Same with the self-conditioning image d_self_cond [B,3,S,S] (NULL = zeros, the library's self_cond = None).  A plan
+ * without self_cond ignores it; kd_unet_forward == this with d_self_cond = NULL. */
+int kd_unet_forward_self_cond(kd_unet_t* u, const float* d_x, const float* d_self_cond, const float* d_lowres,
+                              const float* d_cond_images, const float* d_log_snr, const float* d_lowres_log_snr,
+                              const float* d_text_tokens, const float* d_text_hiddens, float* d_out, void* stream);
 
 /* Classifier-free guidance combine of `Unet.forward_with_cond_scale` (sample.py:55-59 reaches it with
  * cond_scale != 1): out = null + (cond - null) * cond_scale over n floats; out may alias cond. */
@@ -274,7 +284,8 @@ typedef struct kd_sample_args {
 int kd_sample_loop(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_args_t* args,
                    float* d_img, void* stream);
 /* Runs iterations [k_begin, k_end) only, without the final clamp/unnormalise (used by bench.py
- * to time exactly K steps, and by tests to compare intermediate states). */
+ * to time exactly K steps, and by tests to compare intermediate states).  Self-conditioned plans: k_begin == 0 starts
+ * from self_cond = zeros; k_begin > 0 continues from the estimate the plan holds (kd_sample_set_self_cond). */
 int kd_sample_steps(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_args_t* args,
                     float* d_img, int k_begin, int k_end, void* stream);
 /* Builds (force != 0: rebuilds) the conditioning-table rows of schedule steps [k_begin, k_end) without sampling, so
@@ -291,6 +302,11 @@ int kd_sample_finalize(kd_unet_t* u, const kd_sample_args_t* args, float* d_img,
  * which = 3 / 4 (after an EDM step only, kd_edm_sample_steps): x_hat / d of that step [B,3,S,S].
  * Stream-ordered device-to-device copy into d_out. */
 int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream);
+/* which = 5 (self_cond plans): the self-conditioning planes the plan holds [B,3,S,S] - after a step, the thresholded x0
+ * estimate the next forward will read.
+ * Self_cond plans: sets that estimate (d_x_start [B,3,S,S], NULL = zeros) before a kd_sample_steps /
+ * kd_edm_sample_steps call with k_begin > 0. */
+int kd_sample_set_self_cond(kd_unet_t* u, const float* d_x_start, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * EDM sampler.  Replaces `ElucidatedImagen.sample` / `one_unet_sample` / `preconditioned_network_forward` of
@@ -413,6 +429,13 @@ int kd_gn_conv3x3_winograd_fused_nhwc(const float* d_x, const float* d_gamma, co
  * d_w3 / d_w7 / d_w15: OIHW [n][3][k][k].  Needs S % 32 == 0, n3 <= 64, n7 <= 32, n15 <= 32, each a multiple of 4. */
 int kd_init_conv_nchw(const float* d_x, const float* d_w3, const float* d_w7, const float* d_w15,
                       const float* d_bias, float* d_y, int B, int S, int n3, int n7, int n15, void* stream);
+/* Same kernel over the per-step planes of any init conv: d_w*: OIHW [n][Itot][k][k], of which input channels c0 .. c0 + 2
+ * are x's planes, and with d_self_cond != NULL c0 + 3 .. c0 + 5 its planes (the 6-plane form of self-conditioned UNets).
+ * y = conv(planes) + (d_bias | d_res: dense NHWC [B][S][S][n3+n7+n15], may be NULL).  Runs `iters` times; ms != NULL:
+ * the device time of one run (ms), averaged over the iters. */
+int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
+                             const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
+                             int S, int n3, int n7, int n15, int iters, float* ms, void* stream);
 /* GroupNorm(G) + optional FiLM (scale+1, shift: [B,2C] = [scale | shift]) + SiLU, NHWC. */
 int kd_groupnorm_silu_nhwc(const float* d_x, const float* d_gamma, const float* d_beta,
                            const float* d_scale_shift, float* d_y, int B, int HW, int C, int G,

@@ -45,6 +45,18 @@ static int sampler_scratch(kd_unet* u) {
     KD_HIP_CHECK(hipMalloc((void**)&u->s_seed, sizeof(uint64_t)));
     KD_HIP_CHECK(hipMalloc(&u->s_qws, quantile_ws_bytes(B)));
   }
+  if (u->self_cond && !u->s_sc) {
+    KD_HIP_CHECK(hipMalloc((void**)&u->s_sc, img_bytes));
+    KD_HIP_CHECK(hipMemset(u->s_sc, 0, img_bytes));
+  }
+  return 0;
+}
+// self_cond plans: the carried x0 estimate starts as zeros (the library's self_cond = None) at the first step of a call;
+// outside any captured graph
+static int self_cond_reset(kd_unet* u, hipStream_t s) {
+  if (!u->self_cond) return 0;
+  const size_t bytes = (size_t)u->cfg.batch * 3 * u->cfg.image_size * u->cfg.image_size * sizeof(float);
+  KD_HIP_CHECK(hipMemsetAsync(u->s_sc, 0, bytes, s));
   return 0;
 }
 
@@ -229,6 +241,7 @@ static int emit_iteration(kd_unet* u, const SamplerCtx& ctx, const kd_sample_arg
   u->in_lowres_log_snr = a->d_lowres_log_snr;
   u->in_text_tokens = a->d_text_tokens;
   u->in_text_hiddens = a->d_text_hiddens;
+  u->in_self_cond = u->s_sc;   // (nullptr unless self_cond; both guidance forwards read the same estimate)
   u->out = u->s_pred;
   if (ctx.cond_tab)
     if (launch_cond_gather(u->cond_tab, u->cond_ws, u->cond_bytes, u->s_iter, R, s)) return 1;
@@ -244,7 +257,7 @@ static int emit_iteration(kd_unet* u, const SamplerCtx& ctx, const kd_sample_arg
   if (a->dynamic_threshold)
     if (launch_quantile_abs(u->s_x0, u->s_thresh, B, per, a->percentile, u->s_qws, s)) return 1;
   if (launch_ddpm_update(d_img, u->s_x0, u->s_thresh, a->d_noise_step, B * per, u->s_seed, ctx.tb, u->s_iter, R,
-                         a->dynamic_threshold, B, per, s))
+                         a->dynamic_threshold, B, per, s, u->s_sc))
     return 1;
   if (inpaint && R > 1)
     if (launch_renoise(d_img, a->d_noise_renoise, B * per, u->s_seed, ctx.tb, u->s_iter, R, ctx.T, B, per, s))
@@ -284,6 +297,7 @@ static int sample_steps(kd_unet* u, const kd_schedule_t* sc, const kd_sample_arg
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= ctx.T, "step range out of bounds");
   if (ctx.R > 1) KD_REQUIRE(sc->rn_a && sc->rn_b, "re-noise tables are required when resampling");
   const int n_iter = (k_end - k_begin) * ctx.R;
+  if (k_begin == 0 && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
   if (launch_iter_set(u->s_iter, k_begin * ctx.R, s)) return 1;
   if (launch_seed_set(u->s_seed, a->seed, s)) return 1;
   u->in_lowres = a->d_lowres;
@@ -395,6 +409,7 @@ static int edm_forward(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, c
   u->in_lowres_log_snr = a->d_lowres_log_snr;
   u->in_text_tokens = a->d_text_tokens;
   u->in_text_hiddens = a->d_text_hiddens;
+  u->in_self_cond = u->s_sc;
   u->out = u->s_pred;
   if (ctx.cond_tab)   // rows [0, N): time input at sigma_hat, [N, 2N): at sigma_next
     if (launch_cond_gather(u->cond_tab + (size_t)j * N * u->cond_bytes, u->cond_ws, u->cond_bytes, u->s_iter, R, s))
@@ -427,13 +442,15 @@ static int emit_edm_iteration(kd_unet* u, const SamplerCtx& ctx, const EdmTables
                        u->s_seed, tb, s_noise, u->s_iter, R, B, 3, hw, s))
     return 1;
   if (edm_forward(u, ctx, tb, a, u->e_xhat, 0, s)) return 1;
+  // self_cond: Euler leaves the first forward's thresholded estimate for the Heun forward (and, on the last step, for
+  // the caller); Heun leaves the second's for the next step
   if (launch_edm_euler(u->e_xhat, u->s_x0, u->s_thresh, u->e_d, d_img, u->e_in, tb, u->s_iter, R, a->dynamic_threshold, B,
-                       per, s))
+                       per, s, u->s_sc))
     return 1;
   if (heun) {
     if (edm_forward(u, ctx, tb, a, d_img, 1, s)) return 1;
     if (launch_edm_heun(d_img, u->e_xhat, u->e_d, u->s_x0, u->s_thresh, a->d_noise_renoise, B * per, u->s_seed, tb,
-                        u->s_iter, R, N, inpaint && R > 1, a->dynamic_threshold, B, per, s))
+                        u->s_iter, R, N, inpaint && R > 1, a->dynamic_threshold, B, per, s, u->s_sc))
       return 1;
   }
   return launch_iter_inc(u->s_iter, s);
@@ -461,6 +478,7 @@ static int edm_sample_steps(kd_unet* u, const kd_edm_schedule_t* sc, const kd_sa
                              (size_t)u->cfg.batch * 3 * u->cfg.image_size * u->cfg.image_size * sizeof(float)));
   }
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= N, "step range out of bounds");
+  if (k_begin == 0 && self_cond_reset(u, s)) return 1;
   if (launch_seed_set(u->s_seed, a->seed, s)) return 1;
   u->in_lowres = a->d_lowres;
   u->in_cond = a->d_cond_images;
@@ -522,6 +540,11 @@ int kd_unet_create(const kd_unet_config_t* cfg, const kd_param_t* params, int n_
 
 int kd_unet_create_shared(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
                           const kd_unet_t* share_with, kd_unet_t** out) {
+  return kd_unet_create_self_cond(cfg, params, n_params, share_with, 0, out);
+}
+
+int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
+                             const kd_unet_t* share_with, int self_cond, kd_unet_t** out) {
   if (!cfg || !params || !out) {
     set_error("kd_unet_create: null argument");
     return 1;
@@ -531,8 +554,13 @@ int kd_unet_create_shared(const kd_unet_config_t* cfg, const kd_param_t* params,
     set_error("kd_unet_create: no HIP device visible — the engine has no CPU path");
     return 1;
   }
+  if (share_with && (share_with->self_cond != 0) != (self_cond != 0)) {
+    set_error("kd_unet_create: a shared plan must have the same self_cond");
+    return 1;
+  }
   kd_unet* u = new kd_unet();
   u->cfg = *cfg;
+  u->self_cond = self_cond != 0;
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   try {
@@ -609,6 +637,13 @@ int kd_unet_num_cond_launches(const kd_unet_t* u) {
 int kd_unet_forward(kd_unet_t* u, const float* d_x, const float* d_lowres, const float* d_cond_images,
                     const float* d_log_snr, const float* d_lowres_log_snr, const float* d_text_tokens,
                     const float* d_text_hiddens, float* d_out, void* stream) {
+  return kd_unet_forward_self_cond(u, d_x, nullptr, d_lowres, d_cond_images, d_log_snr, d_lowres_log_snr, d_text_tokens,
+                                   d_text_hiddens, d_out, stream);
+}
+
+int kd_unet_forward_self_cond(kd_unet_t* u, const float* d_x, const float* d_self_cond, const float* d_lowres,
+                              const float* d_cond_images, const float* d_log_snr, const float* d_lowres_log_snr,
+                              const float* d_text_tokens, const float* d_text_hiddens, float* d_out, void* stream) {
   if (!u || !d_x || !d_out || !d_log_snr) {
     set_error("kd_unet_forward: null argument");
     return 1;
@@ -620,6 +655,7 @@ int kd_unet_forward(kd_unet_t* u, const float* d_x, const float* d_lowres, const
   u->in_lowres_log_snr = d_lowres_log_snr;
   u->in_text_tokens = d_text_tokens;
   u->in_text_hiddens = d_text_hiddens;
+  u->in_self_cond = d_self_cond;   // (a plan without self_cond ignores it, as the library does)
   u->out = d_out;
   if (run_static(u, (hipStream_t)stream)) return 1;
   return run_forward(u, (hipStream_t)stream);
@@ -744,12 +780,33 @@ int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream) {
     return 1;
   }
   KD_REQUIRE(u->s_pred, "kd_sample_last: no sampling step has run on this plan");
-  KD_REQUIRE(which >= 0 && which <= 4, "kd_sample_last: which must be 0 (pred), 1 (x0), 2 (thresholds), 3 / 4 (EDM x_hat / d)");
-  KD_REQUIRE(which <= 2 || u->e_xhat, "kd_sample_last: no EDM step has run on this plan");
+  KD_REQUIRE(which >= 0 && which <= 5,
+             "kd_sample_last: which must be 0 (pred), 1 (x0), 2 (thresholds), 3 / 4 (EDM x_hat / d), 5 (self-cond planes)");
+  KD_REQUIRE(which <= 2 || which == 5 || u->e_xhat, "kd_sample_last: no EDM step has run on this plan");
+  KD_REQUIRE(which != 5 || u->s_sc, "kd_sample_last: which = 5 needs a plan with self_cond");
   const int B = u->cfg.batch, S = u->cfg.image_size;
-  const float* src = which == 0 ? u->s_pred : which == 1 ? u->s_x0 : which == 2 ? u->s_thresh : which == 3 ? u->e_xhat : u->e_d;
+  const float* src = which == 0 ? u->s_pred : which == 1 ? u->s_x0 : which == 2 ? u->s_thresh : which == 3 ? u->e_xhat
+                   : which == 4 ? u->e_d : u->s_sc;
   const size_t bytes = (which == 2 ? (size_t)B : (size_t)B * 3 * S * S) * sizeof(float);
   KD_HIP_CHECK(hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+// Seeds the self-conditioning estimate a self_cond plan carries (d_x_start [B,3,S,S], NULL = zeros), so that
+// kd_sample_steps / kd_edm_sample_steps with k_begin > 0 continue from a chosen state.  Stream-ordered.
+int kd_sample_set_self_cond(kd_unet_t* u, const float* d_x_start, void* stream) {
+  if (!u) {
+    set_error("kd_sample_set_self_cond: null argument");
+    return 1;
+  }
+  KD_REQUIRE(u->self_cond, "kd_sample_set_self_cond: the plan was created without self_cond");
+  if (sampler_scratch(u)) return 1;
+  const size_t bytes = (size_t)u->cfg.batch * 3 * u->cfg.image_size * u->cfg.image_size * sizeof(float);
+  hipStream_t s = (hipStream_t)stream;
+  if (d_x_start)
+    KD_HIP_CHECK(hipMemcpyAsync(u->s_sc, d_x_start, bytes, hipMemcpyDeviceToDevice, s));
+  else
+    KD_HIP_CHECK(hipMemsetAsync(u->s_sc, 0, bytes, s));
   return 0;
 }
 
@@ -1056,13 +1113,40 @@ int kd_gn_conv3x3_winograd_fused_nhwc(const float* d_x, const float* d_gamma, co
 // y NHWC [B][S][S][n3+n7+n15] = cat(conv3, conv7, conv15)(x) + bias.  d_w*: OIHW [n][3][k][k].
 int kd_init_conv_nchw(const float* d_x, const float* d_w3, const float* d_w7, const float* d_w15, const float* d_bias,
                       float* d_y, int B, int S, int n3, int n7, int n15, void* stream) {
+  return kd_init_conv_planes_nchw(d_x, nullptr, d_w3, d_w7, d_w15, 3, 0, d_bias, nullptr, d_y, B, S, n3, n7, n15, 1, nullptr,
+                                  stream);
+}
+
+int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
+                             const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
+                             int S, int n3, int n7, int n15, int iters, float* ms, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15), "init conv kernel: S % 32 == 0 and the weights must fit LDS");
+  const int np = d_self_cond ? 6 : 3;
+  KD_REQUIRE(d_x && d_w3 && d_w7 && d_w15 && d_y && iters >= 1, "kd_init_conv_planes_nchw: null argument or iters < 1");
+  KD_REQUIRE(c0 >= 0 && c0 + np <= Itot, "kd_init_conv_planes_nchw: input channels c0 .. c0 + planes - 1 out of range");
+  KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15, np), "init conv kernel: S % 32 == 0 and the weights must fit LDS");
   float* wp = nullptr;
-  KD_HIP_CHECK(hipMalloc((void**)&wp, init_conv_weight_floats(n3, n7, n15) * sizeof(float)));
-  int rc = launch_init_conv_pack(d_w3, d_w7, d_w15, wp, n3, n7, n15, 3, 0, s);
-  if (!rc) rc = launch_init_conv(d_x, wp, d_bias, nullptr, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, s);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  KD_HIP_CHECK(hipMalloc((void**)&wp, init_conv_weight_floats(n3, n7, n15, np) * sizeof(float)));
+  int rc = launch_init_conv_pack(d_w3, d_w7, d_w15, wp, n3, n7, n15, Itot, c0, np, s);
+  if (!rc && ms) {
+    rc = hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, s) != hipSuccess;
+    if (rc) set_error("kd_init_conv_planes_nchw: event setup failed");
+  }
+  for (int i = 0; i < iters && !rc; ++i)
+    rc = launch_init_conv(d_x, d_self_cond, np, wp, d_bias, d_res, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, s);
+  if (!rc && ms && hipEventRecord(e1, s) != hipSuccess) {
+    set_error("kd_init_conv_planes_nchw: event record failed");
+    rc = 1;
+  }
   hipError_t e = hipStreamSynchronize(s);
+  if (!rc && ms && e == hipSuccess) {
+    float t = 0.f;
+    e = hipEventElapsedTime(&t, e0, e1);
+    *ms = t / iters;
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
   (void)hipFree(wp);
   if (rc) return rc;
   KD_HIP_CHECK(e);

@@ -294,16 +294,17 @@ int launch_gca_gate(const float* x, const float* wk, const float* bk, float* scr
 // time embedding: out[b][0]=t, [1..h]=sin(t*w*2pi), [h+1..2h]=cos
 int launch_sinu_emb(const float* t, const float* w, float* out, int B, int half, hipStream_t s);
 
-// ---- the init cross-embed convs over x's 3 planes in one kernel (kernels_init.hip)
-bool init_conv_fused_ok(int S, int n3, int n7, int n15);
-size_t init_conv_weight_floats(int n3, int n7, int n15);
-// w3 / w7 / w15: OIHW weights over Itot input channels, of which c0 .. c0 + 2 are x's planes
+// ---- the init cross-embed convs over the per-step planes in one kernel (kernels_init.hip): np = 3 (x) or 6 (x | the
+// self-conditioning image)
+bool init_conv_fused_ok(int S, int n3, int n7, int n15, int np);
+size_t init_conv_weight_floats(int n3, int n7, int n15, int np);
+// w3 / w7 / w15: OIHW weights over Itot input channels, of which c0 .. c0 + np - 1 are the per-step planes
 int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, float* out, int n3, int n7, int n15, int Itot,
-                          int c0, hipStream_t s);
-// y[b][py][px][0 .. n3+n7+n15) (row stride ldy) = cat(conv3, conv7, conv15)(x) + (bias | res); seg: GroupNorm partials
-// [B][C/16][S*S/32][2] or nullptr
-int launch_init_conv(const float* x_nchw, const float* wp, const float* bias, const float* res, float* y, int ldy,
-                     double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
+                          int c0, int np, hipStream_t s);
+// y[b][py][px][0 .. n3+n7+n15) (row stride ldy) = cat(conv3, conv7, conv15)(x | sc) + (bias | res); sc (np = 6 only,
+// nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
+int launch_init_conv(const float* x_nchw, const float* sc_nchw, int np, const float* wp, const float* bias, const float* res,
+                     float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
 
 // ---- final conv to 3 channels (kernels_final.hip)
 int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, hipStream_t s);
@@ -332,7 +333,7 @@ int launch_quantile_abs(const float* x, float* out, int B, int64_t n, float q, v
 size_t quantile_ws_bytes(int B);
 int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int dynamic_threshold,
-                       int B, int64_t per, hipStream_t s);
+                       int B, int64_t per, hipStream_t s, float* sc_out = nullptr);   // sc_out: thresholded x0 (self_cond)
 int launch_inpaint_mix(float* x, const float* inp, const float* mask, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int B, int C, int64_t hw,
                        hipStream_t s);
@@ -361,11 +362,11 @@ int launch_edm_precond_out(const float* x, const float* net, float* den, const f
                            const int* d_iter, int R, int64_t n, hipStream_t s);
 int launch_edm_euler(const float* xh, const float* den, const float* s_thresh, float* d_out, float* x, float* net_in,
                      const EdmTables& tb, const int* d_iter, int R, int dynamic_threshold, int B, int64_t per,
-                     hipStream_t s);
+                     hipStream_t s, float* sc_out = nullptr);
 int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* den, const float* s_thresh,
                     const float* noise, int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb,
                     const int* d_iter, int R, int N, int renoise, int dynamic_threshold, int B, int64_t per,
-                    hipStream_t s);
+                    hipStream_t s, float* sc_out = nullptr);
 
 int launch_iter_inc(int* d_iter, hipStream_t s);
 int launch_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);

@@ -151,9 +151,11 @@ struct kd_unet {
   int64_t mfma_macs = 0;  // MACs the per-step conv / GEMM launches issue on the matrix cores
   int64_t mfma_bf16_macs = 0;  // ... bf16 MACs of the bf16x3 GEMMs (six per fp32 MAC; not part of mfma_macs)
   int time_cond_dim = 0;
+  int self_cond = 0;   // Unet(self_cond=True): the init conv also reads in_self_cond (kd_unet_create_self_cond)
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
+  const float* in_self_cond = nullptr;   // [B,3,S,S] or nullptr (zeros); read only by self_cond plans
   float* out = nullptr;
   // text-conditioning sub-plan (present iff cfg.cond_on_text && cfg.text_tokens > 0)
   std::vector<std::function<int(hipStream_t)>> text_ops;
@@ -168,6 +170,9 @@ struct kd_unet {
   // sampler scratch (allocated on first use)
   float *s_pred = nullptr, *s_x0 = nullptr, *s_thresh = nullptr, *s_time = nullptr, *s_tables = nullptr;
   int* s_iter = nullptr;
+  // self_cond plans: the thresholded x0 estimate the sampler carries to the next forward [B,3,S,S], at a fixed address
+  // (the captured step reads and writes it)
+  float* s_sc = nullptr;
   uint64_t* s_seed = nullptr;  // Philox key, device-resident so the step graph does not depend on it
   void* s_qws = nullptr;
   int s_tables_cap = 0;
@@ -228,7 +233,7 @@ struct kd_unet {
     drop_graphs();
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
     void* frees[] = {ws, s_pred, s_x0, s_thresh, s_time, s_tables, s_iter, s_seed, s_qws, s_pred_null, cond_ws, cond_tab,
-                     d_cond_segs, x3_ws, e_xhat, e_d, e_in, e_tables};
+                     d_cond_segs, x3_ws, e_xhat, e_d, e_in, e_tables, s_sc};
     for (void* p : frees)
       if (p) (void)hipFree(p);
     if (s_tables_pinned) (void)hipHostFree(s_tables_pinned);

@@ -17,6 +17,13 @@
 //     both operand reads are free of bank conflicts;
 //   * the epilogue adds bias or the step-invariant residual, stores NHWC (optionally into a channel slice of a
 //     wider buffer) and leaves the GroupNorm partials of the output (SegSrc, common.h).
+//
+// Self-conditioned UNets (Unet(self_cond=True)) feed a second per-step image, the previous step's x0 estimate, whose
+// 3 planes sit right after x's in the conv's input: the per-step share becomes a 6-plane conv (NP = 6), K = 54 / 294
+// / 1350.  Its weights no longer fit LDS whole (dim 128: 219.5 KiB; the k = 15 group alone 169 KiB), so at NP = 6
+// the k = 3 / 7 weights stay resident and the k = 15 weights STREAM through a two-slot LDS ring, one kernel row
+// (32 rows x 90 values, 11.4 KiB) per slot: all eight waves run the k = 15 conv in lockstep, one barrier per kernel
+// row, the next row's weights loaded into registers under the current row's MFMAs.
 #include "common.h"
 #include "epilogue.h"
 
@@ -25,50 +32,83 @@
 namespace kd {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IC_TW = 32, IC_TH = 8;            // output tile
 constexpr int IC_PW = IC_TW + 14, IC_PH = IC_TH + 14;   // halo patch (k = 15)
-constexpr int IC_PATCH = IC_PH * IC_PW * 3 + 8;  // floats (+ zeroed tail: the padded last run reads one float past a row)
 constexpr int IC_SCRATCH = 8 * 1024;             // floats: one 32 x 32 epilogue tile per wave
-constexpr int IC_RUN15 = 46, IC_RUN7 = 22, IC_RUN3 = 10;          // (15|7|3) x 3 values, padded to even
-constexpr int IC_K15 = 15 * IC_RUN15 + 1, IC_K7 = 7 * IC_RUN7 + 1, IC_K3 = 3 * IC_RUN3 + 1;   // odd row strides
+// floats of the halo patch of NP planes (+ zeroed tail: the padded last run reads one float past a row)
+__host__ __device__ constexpr int ic_patch(int np) { return IC_PH * IC_PW * np + 8; }
+// K run of one kernel row ((k | NP) values, padded to even) and the odd row stride of a resident weight group
+__host__ __device__ constexpr int ic_run(int k, int np) { return (k * np + 1) / 2 * 2; }
+__host__ __device__ constexpr int ic_ldk(int k, int np) { return k * ic_run(k, np) + 1; }
+constexpr int IC_RUN15 = ic_run(15, 3);   // 46
+constexpr int IC_K15 = ic_ldk(15, 3), IC_K7 = ic_ldk(7, 3), IC_K3 = ic_ldk(3, 3);                // odd row strides
+// NP = 6: the k = 15 weights as 15 kernel-row chunks [ky][32 rows][IC_LD15R] (odd stride); two chunks in LDS at a time
+constexpr int IC_LD15R = ic_run(15, 6) + 1, IC_CHUNK15 = 32 * IC_LD15R;   // 91, 2912 floats
 
 // floats of LDS for the packed weights of (n3, n7, n15) output channels, each padded to a multiple of 32 rows
 __host__ __device__ constexpr int ic_rows(int n) { return (n + 31) / 32 * 32; }
-size_t init_conv_weight_floats(int n3, int n7, int n15) {
+size_t init_conv_weight_floats(int n3, int n7, int n15, int np) {
+  if (np == 6) return (size_t)ic_rows(n3) * ic_ldk(3, 6) + (size_t)ic_rows(n7) * ic_ldk(7, 6) + (size_t)15 * IC_CHUNK15;
   return (size_t)ic_rows(n3) * IC_K3 + (size_t)ic_rows(n7) * IC_K7 + (size_t)ic_rows(n15) * IC_K15;
 }
-bool init_conv_fused_ok(int S, int n3, int n7, int n15) {
-  const size_t lds = (init_conv_weight_floats(n3, n7, n15) + IC_PATCH + IC_SCRATCH) * sizeof(float);
+// LDS of the kernel: resident weights (NP = 6: + the two ring slots) + patch + epilogue scratch
+static size_t init_conv_lds_floats(int n3, int n7, int n15, int np) {
+  const size_t w = np == 6 ? (size_t)ic_rows(n3) * ic_ldk(3, 6) + (size_t)ic_rows(n7) * ic_ldk(7, 6) + 2 * IC_CHUNK15
+                           : init_conv_weight_floats(n3, n7, n15, 3);
+  return w + ic_patch(np) + IC_SCRATCH;
+}
+bool init_conv_fused_ok(int S, int n3, int n7, int n15, int np) {
+  if (np != 3 && np != 6) return false;
+  const size_t lds = init_conv_lds_floats(n3, n7, n15, np) * sizeof(float);
   return S % IC_TW == 0 && S % IC_TH == 0 && lds <= 160 * 1024 && ic_rows(n3) <= 64 && ic_rows(n7) <= 32 &&
          ic_rows(n15) <= 32 && n3 % 4 == 0 && n7 % 4 == 0 && n15 % 4 == 0;
 }
 
-// OIHW [n][Itot][k][k] -> rows [n][ky][kx*3 + c] over input channels c0..c0+2, runs padded to `run`, rows to `ldk`
-// (zeros), n padded to a multiple of 32 rows (zeros)
+// OIHW [n][Itot][k][k] -> rows [n][ky][kx*np + c] over input channels c0..c0+np-1, runs padded to `run`, rows to `ldk`
+// (zeros), n padded to a multiple of 32 rows (zeros).  chunked: [ky][n][r] with row stride ldk (the NP = 6 k = 15 ring)
 __global__ void init_conv_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int n_real, int Itot, int c0,
-                                      int k, int run, int ldk, int rows) {
-  const int total = rows * ldk;
+                                      int np, int k, int run, int ldk, int rows, int chunked) {
+  const int total = chunked ? k * rows * ldk : rows * ldk;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int n = idx / ldk, kk = idx - n * ldk;
-    const int ky = kk / run, r = kk - ky * run;
+    int n, ky, r;
+    if (chunked) {
+      ky = idx / (rows * ldk);
+      const int rem = idx - ky * rows * ldk;
+      n = rem / ldk;
+      r = rem - n * ldk;
+    } else {
+      n = idx / ldk;
+      const int kk = idx - n * ldk;
+      ky = kk / run;
+      r = kk - ky * run;
+    }
     float v = 0.f;
-    if (n < n_real && ky < k && r < 3 * k) {
-      const int kx = r / 3, c = r - kx * 3;
+    if (n < n_real && ky < k && r < np * k) {
+      const int kx = r / np, c = r - kx * np;
       v = w[(((int64_t)n * Itot + c0 + c) * k + ky) * k + kx];
     }
     out[idx] = v;
   }
 }
 int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, float* out, int n3, int n7, int n15, int Itot,
-                          int c0, hipStream_t s) {
+                          int c0, int np, hipStream_t s) {
+  KD_REQUIRE(np == 3 || np == 6, "init conv pack: 3 or 6 planes");
+  const int l3 = ic_ldk(3, np), l7 = ic_ldk(7, np);
   float* o3 = out;
-  float* o7 = o3 + (size_t)ic_rows(n3) * IC_K3;
-  float* o15 = o7 + (size_t)ic_rows(n7) * IC_K7;
-  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w3, o3, n3, Itot, c0, 3, IC_RUN3, IC_K3, ic_rows(n3));
-  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w7, o7, n7, Itot, c0, 7, IC_RUN7, IC_K7, ic_rows(n7));
-  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, 15, IC_RUN15, IC_K15,
-                     ic_rows(n15));
+  float* o7 = o3 + (size_t)ic_rows(n3) * l3;
+  float* o15 = o7 + (size_t)ic_rows(n7) * l7;
+  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w3, o3, n3, Itot, c0, np, 3, ic_run(3, np), l3,
+                     ic_rows(n3), 0);
+  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w7, o7, n7, Itot, c0, np, 7, ic_run(7, np), l7,
+                     ic_rows(n7), 0);
+  if (np == 6)
+    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, ic_run(15, 6),
+                       IC_LD15R, 32, 1);
+  else
+    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, IC_RUN15, IC_K15,
+                       ic_rows(n15), 0);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -81,21 +121,48 @@ struct InitConvParams {
   float* y;            // NHWC, row stride ldy, first channel at y
   double* seg;         // GroupNorm partials [B][(n3+n7+n15)/16][S*S/32][2] or nullptr
   int B, S, ldy, n3, n7, n15;
+  const float* sc;     // NP = 6: the self-conditioning planes NCHW [B][3][S][S] (nullptr: zeros)
 };
 
-template <int N3T>   // 32-row tiles of the k = 3 conv (1 or 2)
+template <int N3T, int NP>   // 32-row tiles of the k = 3 conv (1 or 2); input planes per step (3: x, 6: x | self_cond)
 __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr bool RING = NP == 6;   // k = 15 weights streamed through two LDS slots
+  constexpr int RUN3 = ic_run(3, NP), RUN7 = ic_run(7, NP), RUN15 = ic_run(15, NP);
+  constexpr int K3 = ic_ldk(3, NP), K7 = ic_ldk(7, NP), K15 = RING ? IC_LD15R : ic_ldk(15, NP);
+  constexpr int PATCH = ic_patch(NP);
   const int r3 = N3T * 32, r7 = 32, r15 = 32;
   float* W3 = lds;
-  float* W7 = W3 + r3 * IC_K3;
-  float* W15 = W7 + r7 * IC_K7;
-  float* patch = W15 + r15 * IC_K15;
-  float* scratch = patch + IC_PATCH + (threadIdx.x >> 6) * 1024;   // 4 KB per wave (epilogue.h)
+  float* W7 = W3 + r3 * K3;
+  float* W15 = W7 + r7 * K7;   // RING: slot 0 | slot 1
+  float* patch = W15 + (RING ? 2 * IC_CHUNK15 : r15 * K15);
+  float* scratch = patch + PATCH + (threadIdx.x >> 6) * 1024;   // 4 KB per wave (epilogue.h)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nw = (r3 * IC_K3 + r7 * IC_K7 + r15 * IC_K15);
+  // resident weights (RING: + the first kernel row of the k = 15 stream into slot 0)
+  const int nw = RING ? r3 * K3 + r7 * K7 + IC_CHUNK15 : (r3 * K3 + r7 * K7 + r15 * K15);
   for (int i = tid; i < nw; i += 512) lds[i] = p.wp[i];
-  for (int i = tid; i < 8; i += 512) patch[IC_PATCH - 8 + i] = 0.f;
+  for (int i = tid; i < 8; i += 512) patch[PATCH - 8 + i] = 0.f;
+  // RING: chunk c of the stream (kernel row c % 15) lives at wp15 + (c % 15) * IC_CHUNK15; each thread carries its
+  // share of the next chunk in registers (16-byte loads: a chunk is 728 float4)
+  const float* wp15 = p.wp + r3 * K3 + r7 * K7;
+  constexpr int NRV = RING ? (IC_CHUNK15 / 4 + 511) / 512 : 1;
+  f32x4 rv[NRV];
+  auto ring_fetch = [&](int ky) {
+#pragma unroll
+    for (int q = 0; q < NRV; ++q) {
+      const int i = tid + q * 512;
+      if (i < IC_CHUNK15 / 4) rv[q] = *(const f32x4*)(wp15 + (size_t)ky * IC_CHUNK15 + 4 * i);
+    }
+  };
+  auto ring_store = [&](float* slot) {
+#pragma unroll
+    for (int q = 0; q < NRV; ++q) {
+      const int i = tid + q * 512;
+      if (i < IC_CHUNK15 / 4) *(f32x4*)(slot + 4 * i) = rv[q];
+    }
+  };
+  if (RING) ring_fetch(1);
+  int gstep = 0;   // RING: k = 15 kernel rows consumed so far (slot = gstep & 1)
 
   const int S = p.S, tx_n = S / IC_TW, ty_n = S / IC_TH;
   const int ntiles = p.B * tx_n * ty_n;
@@ -103,9 +170,9 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   const int frow = lane & 31, khalf = lane >> 5;
   const int64_t plane = (int64_t)S * S;
 
-  // halo loader: 6 values per thread, fetched into registers one tile ahead (the loads fly during the MFMAs of
+  // halo loader: NP * 2 values per thread, fetched into registers one tile ahead (the loads fly during the MFMAs of
   // the current tile) and written to LDS behind the barrier that ends the current tile's reads
-  constexpr int NPV = (IC_PH * IC_PW * 3 + 511) / 512;
+  constexpr int NPV = (IC_PH * IC_PW * NP + 511) / 512;
   float pv[NPV];
   auto fetch = [&](int tile) {
     const int b = tile / (tx_n * ty_n);
@@ -118,8 +185,12 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
       const int py = r / IC_PW, px = r - py * IC_PW;
       const int iy = y0 - 7 + py, ix = x0 - 7 + px;
       float v = 0.f;
-      if (i < IC_PH * IC_PW * 3 && iy >= 0 && iy < S && ix >= 0 && ix < S)
-        v = p.x[((int64_t)b * 3 + c) * plane + (int64_t)iy * S + ix];
+      if (i < IC_PH * IC_PW * NP && iy >= 0 && iy < S && ix >= 0 && ix < S) {
+        if (NP == 3 || c < 3)
+          v = p.x[((int64_t)b * 3 + c) * plane + (int64_t)iy * S + ix];
+        else if (p.sc)
+          v = p.sc[((int64_t)b * 3 + c - 3) * plane + (int64_t)iy * S + ix];
+      }
       pv[q] = v;
     }
   };
@@ -132,9 +203,9 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
 #pragma unroll
     for (int q = 0; q < NPV; ++q) {
       const int i = tid + q * 512;
-      if (i < IC_PH * IC_PW * 3) {
+      if (i < IC_PH * IC_PW * NP) {
         const int c = i / (IC_PH * IC_PW), r = i - c * (IC_PH * IC_PW);
-        patch[r * 3 + c] = pv[q];
+        patch[r * NP + c] = pv[q];
       }
     }
     __syncthreads();
@@ -187,11 +258,13 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
       };
       // k = 15: window rows row .. row + 14, columns frow .. frow + 14.  Two accumulator chains (even / odd k pairs,
       // added at the end): hipcc sinks every operand read next to its MFMA, and with ONE chain each MFMA also
-      // waits for its predecessor
+      // waits for its predecessor.  RING: every wave walks the kernel rows in step with the others - per row one
+      // barrier (the slot written one row ago has landed; nobody reads the other slot any more), then that other
+      // slot gets the registers' next row and the registers fetch the row after
       auto conv15 = [&]() {
         {
-          const float* pa = patch + (row * IC_PW + frow) * 3 + khalf;
-          const float* pb = W15 + frow * IC_K15 + khalf;
+          const float* pa = patch + (row * IC_PW + frow) * NP + khalf;
+          const float* pb = W15 + frow * K15 + khalf;
           f32x16 a15, b15;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -199,14 +272,21 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
             b15[r] = 0.f;
           }
           for (int ky = 0; ky < 15; ++ky) {
+            if (RING) {
+              __syncthreads();
+              ring_store(W15 + ((gstep + 1) & 1) * IC_CHUNK15);
+              ring_fetch(ky + 2 < 15 ? ky + 2 : ky + 2 - 15);
+              pb = W15 + (gstep & 1) * IC_CHUNK15 + frow * K15 + khalf;
+              ++gstep;
+            }
 #pragma unroll
-            for (int kk = 0; kk + 1 < IC_RUN15 / 2; kk += 2) {
+            for (int kk = 0; kk + 1 < RUN15 / 2; kk += 2) {
               a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk], pb[2 * kk], a15, 0, 0, 0);
               b15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk + 2], pb[2 * kk + 2], b15, 0, 0, 0);
             }
-            a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[IC_RUN15 - 2], pb[IC_RUN15 - 2], a15, 0, 0, 0);
-            pa += IC_PW * 3;
-            pb += IC_RUN15;
+            a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[RUN15 - 2], pb[RUN15 - 2], a15, 0, 0, 0);
+            pa += IC_PW * NP;
+            if (!RING) pb += RUN15;
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) a15[r] += b15[r];
@@ -216,17 +296,17 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
       // k = 7: the centred 7 x 7 window starts 4 rows / 4 columns into the 15 x 15 one
       auto conv7 = [&]() {
         {
-          const float* pa = patch + ((row + 4) * IC_PW + frow + 4) * 3 + khalf;
-          const float* pb = W7 + frow * IC_K7 + khalf;
+          const float* pa = patch + ((row + 4) * IC_PW + frow + 4) * NP + khalf;
+          const float* pb = W7 + frow * K7 + khalf;
           f32x16 a7;
 #pragma unroll
           for (int r = 0; r < 16; ++r) a7[r] = 0.f;
           for (int ky = 0; ky < 7; ++ky) {
 #pragma unroll
-            for (int kk = 0; kk < IC_RUN7 / 2; ++kk)
+            for (int kk = 0; kk < RUN7 / 2; ++kk)
               a7 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk], pb[2 * kk], a7, 0, 0, 0);
-            pa += IC_PW * 3;
-            pb += IC_RUN7;
+            pa += IC_PW * NP;
+            pb += RUN7;
           }
           finish(a7, p.n3, p.n7, rp7);
         }
@@ -235,22 +315,23 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
       auto conv3 = [&]() {
 #pragma unroll
         for (int j = 0; j < N3T; ++j) {
-          const float* pa = patch + ((row + 6) * IC_PW + frow + 6) * 3 + khalf;
-          const float* pb = W3 + (j * 32 + frow) * IC_K3 + khalf;
+          const float* pa = patch + ((row + 6) * IC_PW + frow + 6) * NP + khalf;
+          const float* pb = W3 + (j * 32 + frow) * K3 + khalf;
           f32x16 a3;
 #pragma unroll
           for (int r = 0; r < 16; ++r) a3[r] = 0.f;
 #pragma unroll
           for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int kk = 0; kk < IC_RUN3 / 2; ++kk)
-              a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[ky * IC_PW * 3 + 2 * kk], pb[ky * IC_RUN3 + 2 * kk], a3, 0, 0, 0);
+            for (int kk = 0; kk < RUN3 / 2; ++kk)
+              a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[ky * IC_PW * NP + 2 * kk], pb[ky * RUN3 + 2 * kk], a3, 0, 0, 0);
           finish(a3, j * 32, p.n3 - j * 32, rp3[j]);
         }
       };
       // the two waves of a SIMD (w, w + 4) take the convs in opposite order: one's epilogues (LDS turn, residual
-      // loads, stores, fp64 statistics) run under the other's long k = 15 MFMA chain instead of next to its epilogues
-      if (wave < 4) {
+      // loads, stores, fp64 statistics) run under the other's long k = 15 MFMA chain instead of next to its epilogues.
+      // RING: the k = 15 conv has barriers, so every wave runs it first
+      if (RING || wave < 4) {
         conv15();
         conv7();
         conv3();
@@ -263,14 +344,29 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   }
 }
 
-int launch_init_conv(const float* x, const float* wp, const float* bias, const float* res, float* y, int ldy, double* seg,
-                     int B, int S, int n3, int n7, int n15, hipStream_t s) {
-  KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15), "init conv kernel: image size % 32, weights must fit LDS");
-  KD_REQUIRE(ldy % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0,
+template <int NP>
+static int launch_init_conv_np(const InitConvParams& p, int n3, size_t smem, int grid, hipStream_t s) {
+  if (ic_rows(n3) == 64) {
+    KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<2, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)smem));
+    hipLaunchKernelGGL((init_conv_kernel<2, NP>), dim3(grid), dim3(512), smem, s, p);
+  } else {
+    KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<1, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)smem));
+    hipLaunchKernelGGL((init_conv_kernel<1, NP>), dim3(grid), dim3(512), smem, s, p);
+  }
+  return 0;
+}
+
+int launch_init_conv(const float* x, const float* sc, int np, const float* wp, const float* bias, const float* res, float* y,
+                     int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s) {
+  KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15, np), "init conv kernel: image size % 32, weights must fit LDS");
+  KD_REQUIRE(ldy % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
+                 ((uintptr_t)wp & 15) == 0,
              "init conv kernel: 16-byte aligned output / residual / bias rows");
   KD_REQUIRE(!seg || ((n3 % 16) == 0 && (n7 % 16) == 0 && (n15 % 16) == 0), "init conv partials: 16-channel segments");
-  InitConvParams p{x, wp, bias, res, y, seg, B, S, ldy, n3, n7, n15};
-  const size_t smem = (init_conv_weight_floats(n3, n7, n15) + IC_PATCH + IC_SCRATCH) * sizeof(float);
+  InitConvParams p{x, wp, bias, res, y, seg, B, S, ldy, n3, n7, n15, np == 6 ? sc : nullptr};
+  const size_t smem = init_conv_lds_floats(n3, n7, n15, np) * sizeof(float);
   const int ntiles = B * (S / IC_TW) * (S / IC_TH);
   static int cus = 0;
   if (!cus) {
@@ -281,13 +377,7 @@ int launch_init_conv(const float* x, const float* wp, const float* bias, const f
     cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   const int grid = ntiles < cus ? ntiles : cus;   // persistent: one workgroup per CU keeps the weights in LDS
-  if (ic_rows(n3) == 64) {
-    KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(init_conv_kernel<2>, dim3(grid), dim3(512), smem, s, p);
-  } else {
-    KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(init_conv_kernel<1>, dim3(grid), dim3(512), smem, s, p);
-  }
+  if (np == 6 ? launch_init_conv_np<6>(p, n3, smem, grid, s) : launch_init_conv_np<3>(p, n3, smem, grid, s)) return 1;
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -339,7 +339,7 @@ __global__ void ddpm_update_kernel(float* __restrict__ x, const float* __restric
                                    const float* __restrict__ s_thresh, const float* __restrict__ noise,
                                    int64_t noise_stride, const uint64_t* __restrict__ d_seed, StepTables tb,
                                    const int* __restrict__ d_iter, int R, int dynamic_threshold, int64_t per4,
-                                   int64_t total4) {
+                                   int64_t total4, float* __restrict__ sc_out) {
   const uint64_t seed = *d_seed;  // device-resident: the captured step graph is seed-independent
   const int it = *d_iter;
   const int k = it / R;
@@ -351,23 +351,25 @@ __global__ void ddpm_update_kernel(float* __restrict__ x, const float* __restric
     float s = 1.0f;
     if (dynamic_threshold) s = fmaxf(s_thresh[b], 1.0f);
     f32x4 xv = *(const f32x4*)(x + i * 4), x0v = *(const f32x4*)(x0 + i * 4);
-    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_STEP, it, i), o;
+    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_STEP, it, i), o, xsv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float xs = fminf(fmaxf(x0v[e], -s), s) / s;
+      xsv[e] = xs;
       float mean = alpha_next * (xv[e] * one_minus_c / alpha + c * xs);
       o[e] = mean + ns * z[e];
     }
     *(f32x4*)(x + i * 4) = o;
+    if (sc_out) *(f32x4*)(sc_out + i * 4) = xsv;   // self-conditioning: the next step's UNet reads this x_start
   }
 }
 int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int dynamic_threshold, int B,
-                       int64_t per, hipStream_t s) {
+                       int64_t per, hipStream_t s, float* sc_out) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
   int64_t total4 = (int64_t)B * per / 4;
   hipLaunchKernelGGL(ddpm_update_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, x0, s_thresh, noise,
-                     noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per / 4, total4);
+                     noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per / 4, total4, sc_out);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -510,30 +512,32 @@ __device__ __forceinline__ float edm_thr(float v, float s) { return fminf(fmaxf(
 __global__ void edm_euler_kernel(const float* __restrict__ xh, const float* __restrict__ den,
                                  const float* __restrict__ s_thresh, float* __restrict__ d_out, float* __restrict__ x,
                                  float* __restrict__ net_in, EdmTables tb, const int* __restrict__ d_iter, int R,
-                                 int dynamic_threshold, int64_t per4, int64_t total4) {
+                                 int dynamic_threshold, int64_t per4, int64_t total4, float* __restrict__ sc_out) {
   const int k = *d_iter / R;
   const float sh = tb.sigma_hat[k], step = tb.euler_step[k], c_in = tb.c_in_next[k];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     const float s = dynamic_threshold ? fmaxf(s_thresh[i / per4], 1.0f) : 1.0f;
-    f32x4 hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(den + i * 4), d, xn, ci;
+    f32x4 hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(den + i * 4), d, xn, ci, tv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      d[e] = (hv[e] - edm_thr(dv[e], s)) / sh;
+      tv[e] = edm_thr(dv[e], s);
+      d[e] = (hv[e] - tv[e]) / sh;
       xn[e] = hv[e] + step * d[e];
       ci[e] = c_in * xn[e];
     }
     *(f32x4*)(d_out + i * 4) = d;
     *(f32x4*)(x + i * 4) = xn;
     *(f32x4*)(net_in + i * 4) = ci;
+    if (sc_out) *(f32x4*)(sc_out + i * 4) = tv;   // self-conditioning: the Heun forward (or the next step) reads it
   }
 }
 int launch_edm_euler(const float* xh, const float* den, const float* s_thresh, float* d_out, float* x, float* net_in,
                      const EdmTables& tb, const int* d_iter, int R, int dynamic_threshold, int B, int64_t per,
-                     hipStream_t s) {
+                     hipStream_t s, float* sc_out) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
   const int64_t total4 = (int64_t)B * per / 4;
   hipLaunchKernelGGL(edm_euler_kernel, dim3(grid_for(total4)), dim3(256), 0, s, xh, den, s_thresh, d_out, x, net_in, tb,
-                     d_iter, R, dynamic_threshold, per / 4, total4);
+                     d_iter, R, dynamic_threshold, per / 4, total4, sc_out);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -544,7 +548,7 @@ __global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__
                                 const float* __restrict__ den, const float* __restrict__ s_thresh,
                                 const float* __restrict__ noise, int64_t noise_stride, const uint64_t* __restrict__ d_seed,
                                 EdmTables tb, const int* __restrict__ d_iter, int R, int N, int renoise,
-                                int dynamic_threshold, int64_t per4, int64_t total4) {
+                                int dynamic_threshold, int64_t per4, int64_t total4, float* __restrict__ sc_out) {
   const uint64_t seed = *d_seed;
   const int it = *d_iter;
   const int k = it / R, ri = it - k * R;
@@ -553,12 +557,14 @@ __global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
     const float s = dynamic_threshold ? fmaxf(s_thresh[i / per4], 1.0f) : 1.0f;
     f32x4 xv = *(const f32x4*)(x + i * 4), hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(d_in + i * 4),
-          nv = *(const f32x4*)(den + i * 4), o;
+          nv = *(const f32x4*)(den + i * 4), o, tv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float d2 = (xv[e] - edm_thr(nv[e], s)) / sn;
+      tv[e] = edm_thr(nv[e], s);
+      const float d2 = (xv[e] - tv[e]) / sn;
       o[e] = hv[e] + step * (dv[e] + d2);
     }
+    if (sc_out) *(f32x4*)(sc_out + i * 4) = tv;   // self-conditioning: the next step's first forward reads it
     if (rn) {
       f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_EDM_RENOISE, it, i);
 #pragma unroll
@@ -570,11 +576,11 @@ __global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__
 int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* den, const float* s_thresh,
                     const float* noise, int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb,
                     const int* d_iter, int R, int N, int renoise, int dynamic_threshold, int B, int64_t per,
-                    hipStream_t s) {
+                    hipStream_t s, float* sc_out) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
   const int64_t total4 = (int64_t)B * per / 4;
   hipLaunchKernelGGL(edm_heun_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, xh, d_in, den, s_thresh, noise,
-                     noise_stride, d_seed, tb, d_iter, R, N, renoise, dynamic_threshold, per / 4, total4);
+                     noise_stride, d_seed, tb, d_iter, R, N, renoise, dynamic_threshold, per / 4, total4, sc_out);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -117,8 +117,11 @@ void Builder::build() {
   // (2/3 of its K for the SR UNets) is computed ONCE per sampling call into `init_static` (static_ops)
   // and enters the per-step convolution over x's 3 planes through the residual epilogue.  The sum is
   // the same convolution, only associated differently.
+  // A self-conditioned UNet (u->self_cond) reads x AND the previous step's x0 estimate every step: its per-step planes
+  // are the 6 of cat(x, self_cond), input channels Cc .. Cc + 5 (library order: cond_images | x | self_cond | lowres)
   const int Cc = cfg.cond_images_channels, Cl = cfg.lowres_cond ? 3 : 0;
-  const int init_ch = Cc + 3 + Cl, Cs = Cc + Cl;
+  const int NPs = u->self_cond ? 6 : 3;
+  const int init_ch = Cc + NPs + Cl, Cs = Cc + Cl;
   const bool hoist = Cs > 0;
   const int ks[3] = {3, 7, 15};
   const int ds[3] = {dim / 2, dim / 4, dim - dim / 2 - dim / 4};
@@ -155,7 +158,7 @@ void Builder::build() {
         o.yoff = off;
         o.cin_logical = Cs;
         o.rowrun = true;
-        conv(simg, pack_conv_rowrun_sub(pre + ".weight", ds[i], init_ch, 0, Cc, Cc + 3, Cl, spad, ks[i]),
+        conv(simg, pack_conv_rowrun_sub(pre + ".weight", ds[i], init_ch, 0, Cc, Cc + NPs, Cl, spad, ks[i]),
              P(pre + ".bias", ds[i]), ds[i], ks[i], 1, ks[i] / 2, o);
         off += ds[i];
       }
@@ -173,16 +176,17 @@ void Builder::build() {
     } else {
       xt = alloc(B, S, S, dim);
     }
-    const bool fused_init = init_conv_fused_ok(S, ds[0], ds[1], ds[2]) &&
+    const bool fused_init = init_conv_fused_ok(S, ds[0], ds[1], ds[2], NPs) &&
                             kd_switch("KD_INIT_FUSED", 1) != 0;   // A/B, read per plan
     if (fused_init) {
-      // x's share of the three convs in ONE persistent kernel straight from the NCHW planes (kernels_init.hip)
+      // x's (| self_cond's) share of the three convs in ONE persistent kernel straight from the NCHW planes (kernels_init.hip)
       const float* w3 = raw("init_conv.convs.0.weight", (int64_t)ds[0] * init_ch * 9);
       const float* w7 = raw("init_conv.convs.1.weight", (int64_t)ds[1] * init_ch * 49);
       const float* w15 = raw("init_conv.convs.2.weight", (int64_t)ds[2] * init_ch * 225);
       const int n3 = ds[0], n7 = ds[1], n15 = ds[2], Itot = init_ch, c0 = Cc;
-      float* wp = cached("init_conv_fused", init_conv_weight_floats(n3, n7, n15), [&](float* dst) {
-        KD_THROW_IF(launch_init_conv_pack(w3, w7, w15, dst, n3, n7, n15, Itot, c0, 0));
+      const int np = NPs;
+      float* wp = cached(np == 6 ? "init_conv_fused6" : "init_conv_fused", init_conv_weight_floats(n3, n7, n15, np), [&](float* dst) {
+        KD_THROW_IF(launch_init_conv_pack(w3, w7, w15, dst, n3, n7, n15, Itot, c0, np, 0));
       });
       float* biasp = nullptr;
       if (!hoist) {   // no step-invariant share to carry the biases: one contiguous bias vector
@@ -199,23 +203,27 @@ void Builder::build() {
       const size_t sgo = sg ? add_seg(xt, 0, dim / 16, S * S / 32) : 0;
       const size_t xo = xt.at(), ro = hoist ? init_static.off : 0;
       const int ldy = xt.LD(), Bx = B;
-      const int64_t m = (int64_t)B * S * S * 3 * (9 * n3 + 49 * n7 + 225 * n15);
+      const int64_t m = (int64_t)B * S * S * np * (9 * n3 + 49 * n7 + 225 * n15);
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_init_conv(uu->in_x, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
+        return launch_init_conv(uu->in_x, uu->in_self_cond, np, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
                                 sg ? (double*)uu->P(sgo) : nullptr, Bx, S, n3, n7, n15, s);
-      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim), m);
+      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (np == 6 ? " self-cond" : ""), m);
       u->macs += m;
-      const int64_t issued = (int64_t)B * S * S * (30 * ((n3 + 31) / 32 * 32) + 154 * 32 + 690 * 32);
+      // K runs (3 / 7 / 15 kernel rows of 3k | 6k values, padded to even) x 32-row tiles
+      const int r3 = np == 6 ? 54 : 30, r7 = np == 6 ? 294 : 154, r15 = np == 6 ? 1350 : 690;
+      const int64_t issued = (int64_t)B * S * S * (r3 * ((n3 + 31) / 32 * 32) + r7 * 32 + r15 * 32);
       u->mfma_macs += issued;
       u->op_mfma.back() = issued;
     } else {
-      T img = alloc(B, S, S, 4);  // x's 3 planes + one zero channel
+      const int np = NPs, ipad = np == 6 ? 8 : 4;
+      T img = alloc(B, S, S, ipad);  // x's 3 planes (| self_cond's 3: zeros when it is not given) + zero channels
       size_t yo = img.off;
       int Bx = B, HW = S * S;
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_pack_init(nullptr, 0, uu->in_x, nullptr, 0, uu->P(yo), 4, Bx, HW, s);
+        const float* sc = np == 6 ? uu->in_self_cond : nullptr;
+        return launch_pack_init(nullptr, 0, uu->in_x, sc, sc ? 3 : 0, uu->P(yo), ipad, Bx, HW, s);
       });
       int off = 0;
       for (int i = 0; i < 3; ++i) {
@@ -223,8 +231,8 @@ void Builder::build() {
         ConvOpt o;
         o.dst = &xt;
         o.yoff = off;
-        o.cin_logical = 3;
-        o.rowrun = true;  // K runs over whole kernel rows (ks*4 contiguous floats)
+        o.cin_logical = np;
+        o.rowrun = true;  // K runs over whole kernel rows (ks*ipad contiguous floats)
         o.want_seg = true;  // the three slices fill one partial buffer: GroupNorm of init_resnet_block / the tail
         o.seg_c0 = 0;
         o.seg_cn = dim;
@@ -232,7 +240,7 @@ void Builder::build() {
           o.res = &init_static;
           o.res_coff = off;
         }
-        conv(img, pack_conv_rowrun_sub(pre + ".weight", ds[i], init_ch, Cc, 3, 0, 0, 4, ks[i]),
+        conv(img, pack_conv_rowrun_sub(pre + ".weight", ds[i], init_ch, Cc, np, 0, 0, ipad, ks[i]),
              hoist ? nullptr : P(pre + ".bias", ds[i]), ds[i], ks[i], 1, ks[i] / 2, o);
         off += ds[i];
       }

@@ -118,6 +118,8 @@ SIGNATURES = {
     "kd_unet_hbm_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_create_shared": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
                                         C.POINTER(C.c_void_p)]),
+    "kd_unet_create_self_cond": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
+                                           C.c_int, C.POINTER(C.c_void_p)]),
     "kd_unet_weight_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_macs": (C.c_int64, [C.c_void_p]),
     "kd_unet_mfma_macs": (C.c_int64, [C.c_void_p]),
@@ -130,6 +132,7 @@ SIGNATURES = {
                                     C.c_void_p]),
     "kd_unet_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_void_p]),
     "kd_unet_forward": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8 + [C.c_void_p]),
+    "kd_unet_forward_self_cond": (C.c_int, [C.c_void_p] + [C.c_void_p] * 9 + [C.c_void_p]),
     "kd_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
                                  C.c_void_p]),
     "kd_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
@@ -138,6 +141,7 @@ SIGNATURES = {
                                              C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "kd_sample_finalize": (C.c_int, [C.c_void_p, C.POINTER(kd_sample_args_t), C.c_void_p, C.c_void_p]),
     "kd_sample_last": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "kd_sample_set_self_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kd_edm_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
                                      C.c_void_p]),
     "kd_edm_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
@@ -153,6 +157,8 @@ SIGNATURES = {
     "kd_downsample_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "kd_gn_conv3x3_winograd_fused_nhwc": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "kd_init_conv_nchw": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
+    "kd_init_conv_planes_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6 +
+                                 [C.POINTER(C.c_float), C.c_void_p]),
     "kd_groupnorm_silu_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "kd_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "kd_layernorm_ex": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

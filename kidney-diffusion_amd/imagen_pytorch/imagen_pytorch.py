@@ -270,7 +270,7 @@ class Unet(nn.Module):
         super().__init__()
         self._locals = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
         unsupported = dict(use_linear_attn=use_linear_attn, use_linear_cross_attn=use_linear_cross_attn,
-                           cross_embed_downsample=cross_embed_downsample, self_cond=self_cond)
+                           cross_embed_downsample=cross_embed_downsample)
         bad = [k for k, v in unsupported.items() if (any(v) if isinstance(v, (tuple, list)) else bool(v))]
         required = dict(init_cross_embed=init_cross_embed, scale_skip_connection=scale_skip_connection,
                         final_resnet_block=final_resnet_block, pixel_shuffle_upsample=pixel_shuffle_upsample)
@@ -290,7 +290,10 @@ class Unet(nn.Module):
         self.init_conv_to_final_conv_residual = init_conv_to_final_conv_residual
         self.max_text_len = max_text_len
         self.dim = dim
-        init_channels = channels * (1 + int(lowres_cond)) + cond_images_channels
+        # self_cond: every forward also reads the previous step's thresholded x0 estimate (zeros when not given); the
+        # library's input order is cat(cond_images, x, self_cond, lowres_cond_img)
+        self.self_cond = bool(self_cond)
+        init_channels = channels * (1 + int(lowres_cond) + int(self.self_cond)) + cond_images_channels
 
         self.init_conv = CrossEmbedLayer(init_channels, init_cross_embed_kernel_sizes, dim, stride=1)
         dims = [dim, *[dim * m for m in dim_mults]]
@@ -612,7 +615,8 @@ class Unet(nn.Module):
             handle = C.c_void_p()
             # further plans of this UNet on the same device (other batch / image size) share its packed weights
             share = next((h for k, h in self._engines.items() if k[2] == device.index), None)
-            E.check(lib.kd_unet_create_shared(C.byref(cfg), arr, len(names), share, C.byref(handle)))
+            E.check(lib.kd_unet_create_self_cond(C.byref(cfg), arr, len(names), share, int(self.self_cond),
+                                                 C.byref(handle)))
             del sd
         self._engines[key] = handle
         self._engines_fingerprint = self._weights_fingerprint()
@@ -620,7 +624,8 @@ class Unet(nn.Module):
 
     def forward(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None,
                 cond_images=None, self_cond=None, cond_drop_prob=0.0):
-        """One UNet forward on the engine.  ``time`` is the log-SNR, as in the library."""
+        """One UNet forward on the engine.  ``time`` is the log-SNR, as in the library.  ``self_cond`` [B,3,S,S]
+        (None = zeros) is read by a UNet built with self_cond=True and ignored by any other, as in the library."""
         assert not (self.lowres_cond and not exists(lowres_cond_img)), "low resolution conditioning image must be present"
         assert not (self.lowres_cond and not exists(lowres_noise_times)), "low resolution conditioning noise time must be present"
         assert not (self.has_cond_image ^ exists(cond_images)), \
@@ -631,6 +636,9 @@ class Unet(nn.Module):
         if exists(cond_images):
             assert cond_images.shape[1] == self.cond_images_channels, "invalid number of channels in conditioning image"
             cond_images = resize_image_to(cond_images, s)
+        self_cond = f32(self_cond) if self.self_cond else None
+        if exists(self_cond):
+            assert self_cond.shape == x.shape, "self_cond must have the shape of x"
         x, lowres_cond_img, cond_images = f32(x), f32(lowres_cond_img), f32(cond_images)
         time, lowres_noise_times = f32(time), f32(lowres_noise_times)
         out = torch.empty_like(x)
@@ -641,9 +649,9 @@ class Unet(nn.Module):
             tok = hid = None
             if with_text:
                 tok, hid = self.text_cond(h, text_embeds, text_mask, drop=cond_drop_prob == 1.0, device=x.device)
-            E.check(E.load().kd_unet_forward(h, E.ptr(x), E.ptr(lowres_cond_img), E.ptr(cond_images), E.ptr(time),
-                                             E.ptr(lowres_noise_times), E.ptr(tok), E.ptr(hid), E.ptr(out),
-                                             E.current_stream()))
+            E.check(E.load().kd_unet_forward_self_cond(h, E.ptr(x), E.ptr(self_cond), E.ptr(lowres_cond_img),
+                                                       E.ptr(cond_images), E.ptr(time), E.ptr(lowres_noise_times),
+                                                       E.ptr(tok), E.ptr(hid), E.ptr(out), E.current_stream()))
         return out
 
     def text_cond(self, handle, text_embeds, text_mask, drop, device):
