@@ -38,7 +38,9 @@ const char* kd_last_error(void);
  *   1  rounds 1-3
  *   2  round 4/5: kd_conv3x3_winograd4_nhwc gained `gemm_bf16x3` (before `stream`); kd_unet_config_t gained
  *      `gemm_bf16x3`, `x3_linear` and `wino4_max_images`, kd_sample_args_t `cond_table_max_mb`; kd_unet_cond_table_refused_bytes, kd_linear_bf16x3 (+ _seg_rows), kd_downsample_bf16x3, kd_layernorm_ex and kd_layernorm_linear_bf16x3 added;
- *      kd_unet_cond_table_build_ms takes a non-const handle (it reads the build's events on demand) */
+ *      kd_unet_cond_table_build_ms takes a non-const handle (it reads the build's events on demand); later additions that
+ *      change no existing entry: kd_linear_skinny, kd_global_context_gate, kd_gate_add_nhwc (+ _chunks), kd_gn_fold_seg,
+ *      kd_wf_ab_scale, kd_gn_conv3x3_winograd4_nhwc (the ResnetBlock pieces the plan joins, for unit tests) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -418,6 +420,55 @@ int kd_gn_conv3x3_winograd_fused_nhwc(const float* d_x, const float* d_gamma, co
                                       const float* d_bias, const float* d_res, float* d_y, int B, int H,
                                       int W, int Cin, int Cout, int G, float eps, float* d_out_stats,
                                       int ldx, void* stream);
+
+/* The pieces a ResnetBlock of the plan is joined from, each through the plan's own launches with the plan's argument forms
+ * (engine.hip), so that tests can hold every one against a reference by itself.  All synchronise before returning. */
+/* y[m][:N] (row stride ldy) = act(W f(x[m][:K]) + bias) for the small-M linears (time MLPs, GlobalContext FCs, time-token
+ * projections): x rows of stride ldx, w torch [N][K], bias may be NULL; in_act f / act: 0 none, 1 SiLU, 2 GELU, 3 sigmoid.
+ * The plan's dispatch picks the kernel: VALU where K % 4, ldx % 4 or the alignment of x / w rule out 16-byte loads, else
+ * a GEMV for M = 1 (K <= 16384), else the MFMA kernel with K split over four waves from K >= 512, one wave below. */
+int kd_linear_skinny(const float* d_x, int ldx, const float* d_w, const float* d_bias, float* d_y, int ldy, int M, int K,
+                     int N, int in_act, int act, void* stream);
+/* GlobalContext gate of x NHWC [B][HW][C]: gate [B][C] = sigmoid(W2 SiLU(W0 pooled + b0) + b2) with pooled[b] =
+ * sum_p softmax_p(x[b][p] . wk + bk) x[b][p]; wk [C], bk [1], W0 [hid][C], W2 [C][hid] (torch layouts).  path 0: the
+ * plan's choice (fused where C <= 512, hid <= 256 and B > 1), 1: pooling + two kd_linear_skinny launches, 2: the fused
+ * gate (refused where it does not apply).  d_pooled (may be NULL; not with the fused gate): [B][C], the pooled vector of
+ * path 1.  Needs C % 4 == 0, C <= 2048. */
+int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* d_wk, const float* d_bk, const float* d_w0,
+                           const float* d_b0, int hid, const float* d_w2, const float* d_b2, float* d_gate, float* d_pooled,
+                           int path, void* stream);
+/* y = a * gate[b][c] + r, NHWC [B][HW]: a dense C channels, r / y rows of stride ldr / ldy (0 = C; channel slices of
+ * wider maps), d_gate [B][C] or NULL (1).  d_seg (may be NULL, C % 16 == 0): the GroupNorm partials of y the plan leaves
+ * for the next layer, fp64 [B][C / 16][kd_gate_add_chunks(B, HW)][2] = (sum, sum of squares) per pixel chunk.  Needs
+ * C % 4 == 0, strides multiples of 4 and 16-byte aligned pointers. */
+int kd_gate_add_nhwc(const float* d_a, const float* d_gate, const float* d_r, int ldr, float* d_y, int ldy, double* d_seg,
+                     int B, int HW, int C, void* stream);
+int kd_gate_add_chunks(int B, int HW);
+/* GroupNorm statistics from producers' fp64 segment partials [B][nseg][nchunk][2] (sum, sum of squares per 16-channel
+ * segment and chunk of HW pixels), of up to two sources: source 0 covers channels [0, 16 nseg0), source 1 (d_seg1 may be
+ * NULL) [16 nseg0, C); the GroupNorm sees scale_i * source i, and ab_mul_i goes into the affine's A for its channels (a
+ * consumer that reads the source unscaled).  d_stats (may be NULL): [B][G][2] (mean, rstd).  d_ab (may be NULL): [B][C][2]
+ * the folded affine (A, B) of GroupNorm (gamma, beta) and FiLM (d_scale_shift rows [scale(C) | shift(C)] of stride
+ * ld_ss >= 2 C, may be NULL), times kd_wf_ab_scale() = -log2(e), the form the fused Winograd kernel takes.  Needs
+ * (C / G) % 16 == 0. */
+int kd_gn_fold_seg(const double* d_seg0, int nseg0, int nchunk0, float scale0, float ab_mul0, const double* d_seg1, int nseg1,
+                   int nchunk1, float scale1, float ab_mul1, const float* d_gamma, const float* d_beta,
+                   const float* d_scale_shift, int ld_ss, float* d_ab, float* d_stats, int B, int HW, int C, int G, float eps,
+                   void* stream);
+float kd_wf_ab_scale(void);
+/* One F(4x4,3x3) ResnetBlock conv as the plan runs it (engine.hip wino4_block): y [B][H][W][Cout] = conv3x3(SiLU(FiLM(
+ * GroupNorm_G(x')))) + bias (+ res), x' = x with channels [skip_c0, Cin) times skip_scale (skip_c0 < 0: none) - x itself
+ * is read unscaled, the factor goes into the affine.  x rows of stride ldx (0 = Cin), d_stats [B][G][2] (mean, rstd) of x'
+ * (kd_gn_fold_seg), d_scale_shift (may be NULL) FiLM rows of stride ld_ss, d_res (may be NULL) rows of stride ldres
+ * (0 = Cout).  d_out_seg (may be NULL): the partials of y the plan leaves for the next GroupNorm, fp64
+ * [B][Cout / 16][(H/4) (W/4)][2], one chunk per 4 x 4 tile.  gemm_mode: -1 the 36 position GEMMs on fp32 MFMA, 1 bf16x3 with
+ * V as planes, 2 bf16x3 with V as fp32.  The batch runs in sets of images_per_set images (0 = B), one set of launches after
+ * the other.  Needs H % 4 == 0, W % 4 == 0, images_per_set (H/4) (W/4) % 128 == 0 (% 256 and Cout % 128 == 0 for
+ * bf16x3), Cin % 32 == 0, Cout % 64 == 0. */
+int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats, const float* d_gamma, const float* d_beta,
+                                 const float* d_scale_shift, int ld_ss, int skip_c0, float skip_scale, const float* d_w_oihw,
+                                 const float* d_bias, const float* d_res, int ldres, float* d_y, double* d_out_seg, int B,
+                                 int H, int W, int Cin, int Cout, int G, int gemm_mode, int images_per_set, void* stream);
 
 /* (ldx: row stride of d_x in floats, >= Cin and a multiple of 4, 0 = dense: the plan hands this kernel channel-slice
  * views of wider buffers - a skip tensor living in the concat it will join.) */

@@ -1109,6 +1109,169 @@ int kd_gn_conv3x3_winograd_fused_nhwc(const float* d_x, const float* d_gamma, co
   return 0;
 }
 
+// ---- the pieces of a ResnetBlock the plan joins (engine.hip: skinny, gca, wino4_block, resnet; the gate_add after a
+// GlobalContext gate), one host wrapper each around the plan's own launch_* calls with the plan's argument forms.  Every
+// shape is checked before the first allocation; the buffers live in one holder that frees them on every path.
+namespace {
+struct EntryBufs {
+  std::vector<void*> p;
+  ~EntryBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  int get(void** out, size_t bytes) {
+    KD_HIP_CHECK(hipMalloc(out, bytes));
+    p.push_back(*out);
+    return 0;
+  }
+};
+int entry_finish(int rc, hipStream_t s) {
+  hipError_t e = hipStreamSynchronize(s);
+  if (rc) return rc;
+  KD_HIP_CHECK(e);
+  return 0;
+}
+}  // namespace
+
+int kd_linear_skinny(const float* d_x, int ldx, const float* d_w, const float* d_bias, float* d_y, int ldy, int M, int K,
+                     int N, int in_act, int act, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && d_w && d_y, "kd_linear_skinny: null argument");
+  KD_REQUIRE(M > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N, "kd_linear_skinny needs M, K, N > 0, ldx >= K, ldy >= N");
+  KD_REQUIRE(in_act >= ACT_NONE && in_act <= ACT_SIGMOID && act >= ACT_NONE && act <= ACT_SIGMOID,
+             "kd_linear_skinny: unknown activation");
+  return entry_finish(launch_linear_skinny(d_x, ldx, d_w, d_bias, d_y, ldy, M, K, N, in_act, act, s), s);
+}
+
+int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* d_wk, const float* d_bk, const float* d_w0,
+                           const float* d_b0, int hid, const float* d_w2, const float* d_b2, float* d_gate, float* d_pooled,
+                           int path, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && d_wk && d_bk && d_w0 && d_b0 && d_w2 && d_b2 && d_gate, "kd_global_context_gate: null argument");
+  KD_REQUIRE(B > 0 && HW > 0 && hid > 0 && C % 4 == 0 && C > 0 && C <= 2048,
+             "kd_global_context_gate needs B, HW, hid > 0 and C % 4 == 0, C <= 2048");
+  KD_REQUIRE(path >= 0 && path <= 2, "kd_global_context_gate: path 0 (the plan's choice), 1 (pool + two linears), 2 (fused)");
+  const bool fused_ok = gca_gate_fused_ok(C, hid) && (((uintptr_t)d_w0 | (uintptr_t)d_w2) & 15) == 0;
+  KD_REQUIRE(path != 2 || fused_ok, "kd_global_context_gate: the fused gate needs C <= 512, hid <= 256, 16-byte aligned weights");
+  const bool fused = path == 2 || (path == 0 && gca_gate_fused_ok(C, hid) && B > 1);   // engine.hip gca()
+  KD_REQUIRE(!(fused && d_pooled), "kd_global_context_gate: the fused gate does not leave the pooled vector");
+  EntryBufs bufs;
+  float *scratch = nullptr, *pooled = d_pooled, *hidden = nullptr;
+  if (bufs.get((void**)&scratch, gca_scratch_floats(B, HW, C) * sizeof(float))) return 1;
+  if (fused) return entry_finish(launch_gca_gate(d_x, d_wk, d_bk, scratch, d_w0, d_b0, hid, d_w2, d_b2, d_gate, B, HW, C, s), s);
+  if (!pooled && bufs.get((void**)&pooled, (size_t)B * C * sizeof(float))) return 1;
+  if (bufs.get((void**)&hidden, (size_t)B * hid * sizeof(float))) return 1;
+  int rc = launch_gca_pool(d_x, d_wk, d_bk, nullptr, pooled, scratch, B, HW, C, s);
+  if (!rc) rc = launch_linear_skinny(pooled, C, d_w0, d_b0, hidden, hid, B, C, hid, ACT_NONE, ACT_SILU, s);
+  if (!rc) rc = launch_linear_skinny(hidden, hid, d_w2, d_b2, d_gate, C, B, hid, C, ACT_NONE, ACT_SIGMOID, s);
+  return entry_finish(rc, s);
+}
+
+int kd_gate_add_chunks(int B, int HW) { return B > 0 && HW > 0 ? gate_add_chunks(B, HW) : 0; }
+
+int kd_gate_add_nhwc(const float* d_a, const float* d_gate, const float* d_r, int ldr, float* d_y, int ldy, double* d_seg,
+                     int B, int HW, int C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ldr <= 0) ldr = C;
+  if (ldy <= 0) ldy = C;
+  KD_REQUIRE(d_a && d_r && d_y, "kd_gate_add_nhwc: null argument");
+  KD_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && ldr >= C && ldy >= C && ldr % 4 == 0 && ldy % 4 == 0,
+             "kd_gate_add_nhwc needs C % 4 == 0 and row strides >= C, multiples of 4");
+  KD_REQUIRE((((uintptr_t)d_a | (uintptr_t)d_gate | (uintptr_t)d_r | (uintptr_t)d_y) & 15) == 0,
+             "kd_gate_add_nhwc: 16-byte aligned maps and gate");
+  KD_REQUIRE(!d_seg || C % 16 == 0, "kd_gate_add_nhwc: segment partials need C % 16 == 0");
+  return entry_finish(launch_gate_add(d_a, d_gate, d_r, ldr, d_y, ldy, d_seg, B, HW, C, s), s);
+}
+
+float kd_wf_ab_scale(void) { return WF_AB_SCALE; }
+
+int kd_gn_fold_seg(const double* d_seg0, int nseg0, int nchunk0, float scale0, float ab_mul0, const double* d_seg1, int nseg1,
+                   int nchunk1, float scale1, float ab_mul1, const float* d_gamma, const float* d_beta,
+                   const float* d_scale_shift, int ld_ss, float* d_ab, float* d_stats, int B, int HW, int C, int G, float eps,
+                   void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_seg0 && (d_ab || d_stats), "kd_gn_fold_seg: null argument");
+  KD_REQUIRE(B > 0 && HW > 0 && G > 0 && C % G == 0 && (C / G) % 16 == 0, "kd_gn_fold_seg needs groups of 16 n channels");
+  KD_REQUIRE(nseg0 > 0 && nchunk0 > 0 && (!d_seg1 || (nseg1 > 0 && nchunk1 > 0)) &&
+                 16 * (nseg0 + (d_seg1 ? nseg1 : 0)) == C,
+             "kd_gn_fold_seg: the sources' 16-channel segments must tile the C channels");
+  KD_REQUIRE(!d_ab || (d_gamma && d_beta), "kd_gn_fold_seg: the affine needs gamma and beta");
+  KD_REQUIRE(!d_scale_shift || ld_ss >= 2 * C, "kd_gn_fold_seg: FiLM rows [scale | shift] need ld_ss >= 2 C");
+  SegSrc s0{d_seg0, nseg0, nchunk0, 0, scale0, ab_mul0};
+  SegSrc s1{d_seg1, d_seg1 ? nseg1 : 0, d_seg1 ? nchunk1 : 0, 16 * nseg0, scale1, ab_mul1};
+  return entry_finish(launch_gn_fold_seg(s0, s1, d_gamma, d_beta, d_scale_shift, ld_ss, d_ab, d_stats, B, C, G,
+                                         (double)HW * (C / G), eps, s),
+                      s);
+}
+
+int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats, const float* d_gamma, const float* d_beta,
+                                 const float* d_scale_shift, int ld_ss, int skip_c0, float skip_scale, const float* d_w_oihw,
+                                 const float* d_bias, const float* d_res, int ldres, float* d_y, double* d_out_seg, int B,
+                                 int H, int W, int Cin, int Cout, int G, int gemm_mode, int images_per_set, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ldx <= 0) ldx = Cin;
+  if (ldres <= 0) ldres = Cout;
+  const int Bx = images_per_set > 0 ? images_per_set : B;
+  KD_REQUIRE(d_x && d_stats && d_gamma && d_beta && d_w_oihw && d_bias && d_y, "kd_gn_conv3x3_winograd4_nhwc: null argument");
+  KD_REQUIRE(B > 0 && Bx > 0 && B % Bx == 0, "kd_gn_conv3x3_winograd4_nhwc: images_per_set must divide B");
+  KD_REQUIRE(H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "Winograd F(4x4,3x3) path needs H % 4 == 0 and W % 4 == 0");
+  const int64_t Mt = (int64_t)Bx * (H / 4) * (W / 4);
+  KD_REQUIRE(Mt % 128 == 0 && Cin % 32 == 0 && Cout % 64 == 0 && 36 * Mt < 0x7fffffff &&
+                 (int64_t)36 * Cout * Cin * 4 < 0x7fffffff,
+             "Winograd F(4x4,3x3) path needs images_per_set*H*W/16 % 128 == 0, Cin % 32 == 0, Cout % 64 == 0");
+  KD_REQUIRE(gemm_mode == -1 || gemm_mode == 1 || gemm_mode == 2, "kd_gn_conv3x3_winograd4_nhwc: gemm_mode -1, 1 or 2");
+  KD_REQUIRE(gemm_mode < 0 || gemm_bf16x3_ok(36, Mt, Cout, Cin),
+             "bf16x3 position GEMMs need images_per_set*H*W/16 % 256 == 0, Cout % 128 == 0, Cin % 32 == 0");
+  KD_REQUIRE(G > 0 && Cin % G == 0, "kd_gn_conv3x3_winograd4_nhwc: Cin % G == 0");
+  KD_REQUIRE(ldx >= Cin && ldx % 2 == 0 && ((uintptr_t)d_x & 7) == 0 && (int64_t)Bx * H * W * ldx * 4 < ((int64_t)1 << 32),
+             "kd_gn_conv3x3_winograd4_nhwc: x rows of stride >= Cin, even, 8-byte aligned, one set's map below 4 GB");
+  KD_REQUIRE(skip_c0 < 0 || (skip_c0 <= Cin && skip_c0 % 2 == 0), "kd_gn_conv3x3_winograd4_nhwc: skip_c0 in [0, Cin], even");
+  KD_REQUIRE(!d_scale_shift || ld_ss >= 2 * Cin, "kd_gn_conv3x3_winograd4_nhwc: FiLM rows [scale | shift] need ld_ss >= 2 Cin");
+  KD_REQUIRE(!d_res || (ldres >= Cout && ldres % 2 == 0), "kd_gn_conv3x3_winograd4_nhwc: residual row stride >= Cout, even");
+  KD_REQUIRE((((uintptr_t)d_y | (uintptr_t)d_res | (uintptr_t)d_bias) & 7) == 0,
+             "kd_gn_conv3x3_winograd4_nhwc: 8-byte aligned y, residual and bias");
+  const bool planes = gemm_mode == 1, x3 = gemm_mode > 0;
+  EntryBufs bufs;
+  float *U = nullptr, *D = nullptr;
+  void *V = nullptr, *U3 = nullptr, *ws = nullptr;
+  if (bufs.get((void**)&U, (size_t)36 * Cout * Cin * sizeof(float))) return 1;
+  if (bufs.get(&V, planes ? (size_t)36 * Mt * Cin * 6 : (size_t)36 * Mt * Cin * sizeof(float))) return 1;
+  if (bufs.get((void**)&D, (size_t)36 * Mt * Cout * sizeof(float))) return 1;
+  if (x3 && bufs.get(&U3, ((size_t)36 * Cout * Cin * 3 + 1) / 2 * sizeof(float))) return 1;
+  if (x3 && bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
+  int rc = launch_wino4_pack(d_w_oihw, U, Cout, Cin, s);
+  if (!rc && x3) rc = launch_split3(U, U3, 36, Cout, Cin, s);
+  const int64_t HW = (int64_t)H * W, nchunk = (H / 4) * (W / 4);
+  // the launch sequence of wino4_block (engine.hip), set by set: input transform with the GroupNorm / FiLM / SiLU affine
+  // folded, the 36 position GEMMs (+ the k-cut tiles' sum), output transform with bias, residual and the output partials
+  for (int st = 0; st < B / Bx && !rc; ++st) {
+    const int b0 = st * Bx;
+    const float* xs = d_x + (size_t)b0 * HW * ldx;
+    const float* ss = d_stats + (size_t)b0 * G * 2;
+    const float* ssp = d_scale_shift ? d_scale_shift + (size_t)b0 * ld_ss : nullptr;
+    if (planes)
+      rc = launch_wino4_in3(xs, ldx, ss, d_gamma, d_beta, ssp, ld_ss, V, Bx, H, W, Cin, G, s, skip_c0, skip_scale);
+    else
+      rc = launch_wino4_in(xs, ldx, ss, d_gamma, d_beta, ssp, ld_ss, (float*)V, Bx, H, W, Cin, G, s, skip_c0, skip_scale);
+    if (!rc && x3) {
+      rc = launch_gemm_bf16x3(V, U3, D, 36, (int)Mt, Cout, Cin, ws, s, !planes, false);
+      if (!rc && gemm_bf16x3_needs_sum(36, (int)Mt, Cout, Cin)) rc = launch_gemm_bf16x3_sum(D, 36, (int)Mt, Cout, Cin, ws, s);
+    } else if (!rc) {
+      ConvParams p{};
+      p.x = (const float*)V; p.w = U; p.y = D;
+      p.B = 1; p.Hi = 1; p.Wi = (int)(36 * Mt); p.Cin = Cin; p.ldx = Cin;
+      p.Ho = 1; p.Wo = (int)(36 * Mt); p.Cout = Cout;
+      p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+      p.out_mode = OUT_NHWC; p.ldy = Cout;
+      p.wz_rows = (int)Mt; p.wz_count = 36;
+      rc = launch_conv_igemm(p, s);
+    }
+    if (!rc)
+      rc = launch_wino4_out(D, d_bias, d_res ? d_res + (size_t)b0 * HW * ldres : nullptr, ldres, d_y + (size_t)b0 * HW * Cout,
+                            Cout, d_out_seg ? d_out_seg + (size_t)b0 * (Cout / 16) * nchunk * 2 : nullptr, Bx, H, W, Cout, s);
+  }
+  return entry_finish(rc, s);
+}
+
 // The init cross-embed convs over a 3-plane NCHW image through the plan's fused kernel (kernels_init.hip):
 // y NHWC [B][S][S][n3+n7+n15] = cat(conv3, conv7, conv15)(x) + bias.  d_w*: OIHW [n][3][k][k].
 int kd_init_conv_nchw(const float* d_x, const float* d_w3, const float* d_w7, const float* d_w15, const float* d_bias,

@@ -132,7 +132,9 @@ constexpr int GCA_ROWS = 256;
 static inline int gca_rows(int HW, int B) {
   int r = GCA_ROWS;
   while ((HW + r - 1) / r > 1024) r *= 2;
-  while (r > 32 && (int64_t)((HW + r - 1) / r) * B < 1024) r /= 2;
+  // (never past the 1024 chunks the merge kernels' LDS holds: a batch-1 map of 131073 .. 262143 pixels - 384 x 384 - has
+  // fewer than 1024 chunks of 256 pixels and more than 1024 of 128)
+  while (r > 32 && (int64_t)((HW + r - 1) / r) * B < 1024 && (HW + r / 2 - 1) / (r / 2) <= 1024) r /= 2;
   return r;
 }
 constexpr int GCA_MAXT = 8;     // float4 slices per lane: C <= 2048
