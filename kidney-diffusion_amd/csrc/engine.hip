@@ -385,7 +385,6 @@ struct Builder {
   }
   // ---- GroupNorm partials handed from the kernel that writes a map to the layer that normalises it (SegSrc,
   // common.h): per tensor (keyed by its workspace offset) up to two channel ranges with their partial buffers.
-  // KD_SEG_STATS=0 keeps the separate statistics passes (A/B, read per plan).
   struct SegPart {
     size_t off = 0;   // partial buffer [B][nseg][nchunk][2] doubles
     int nseg = 0, nchunk = 0, c0 = 0;
@@ -397,7 +396,6 @@ struct Builder {
     std::vector<SegPart> parts;
   };
   std::unordered_map<size_t, SegList> seg_of;   // key: T::at() - a slice and its buffer have different keys
-  const bool seg_on = kd_switch("KD_SEG_STATS", 1) != 0;
   const bool x3_planes_on = kd_switch("KD_X3_PLANES", 1) != 0;   // LayerNorm outputs read by one bf16x3 GEMM: in plane form
   void drop_seg_block(size_t block) {
     for (auto it = seg_of.begin(); it != seg_of.end();) {
@@ -447,7 +445,7 @@ struct Builder {
   // the sources covering ALL C channels of x in order (at most two), or false
   bool seg_sources(const T& x, SegPart (&out)[2], int& n) const {
     n = 0;
-    if (!seg_on || x.C % cfg.resnet_groups || (x.C / cfg.resnet_groups) % 16) return false;
+    if (x.C % cfg.resnet_groups || (x.C / cfg.resnet_groups) % 16) return false;
     auto it = seg_of.find(x.at());
     if (it == seg_of.end()) return false;
     std::vector<SegPart> v = it->second.parts;
@@ -629,7 +627,7 @@ struct Builder {
     // shuffled channels): several launches filling slices of one tensor (init conv) share the chunk count
     size_t sego = 0;
     int seg_nseg = 0, seg_c0 = 0, seg_nchunk = 0;
-    if (o.want_seg && seg_on && !ext && !to_text && !to_static && !to_cond) {
+    if (o.want_seg && !ext && !to_text && !to_static && !to_cond) {
       const int cw = o.out_mode == OUT_PIXSHUF ? Cout / 4 : Cout;
       seg_c0 = o.seg_c0 >= 0 ? o.seg_c0 : o.yoff;   // in channels of the tensor y (a slice counts from its own first)
       const int span = o.seg_c0 >= 0 ? o.seg_cn : cw;
@@ -808,7 +806,7 @@ struct Builder {
     int rows = (int)x.rows(), C = x.C, ldx = x.LD(), ldres = res ? res->LD() : 0;
     // the output feeds a GroupNorm (the ResnetBlock's block2 behind its cross-attention): one chunk of partials per pixel
     const int hw = x.HW();
-    const bool sg = want_seg && seg_on && !to_cond && !to_text && !to_static && C % 16 == 0 && C <= 4096 && x.B * hw == rows;
+    const bool sg = want_seg && !to_cond && !to_text && !to_static && C % 16 == 0 && C <= 4096 && x.B * hw == rows;
     const size_t sgo = sg ? add_seg(y, 0, C / 16, hw) : 0;
     kd_unet* uu = u;
     emit([=](hipStream_t s) {
@@ -1056,24 +1054,49 @@ struct Builder {
     return gate;
   }
 
-  // ---- Winograd F(2x2,3x3) for the `Block` = GroupNorm -> [FiLM] -> SiLU -> conv3x3 of deep layers
-  // (kernels_wino.hip).  Worth it where the 2.25x smaller GEMM outweighs moving 4x the map through
-  // the transforms: measured on MI355X, Cin >= 256 wins and Cin = 128 loses (profiles/README.md).
-  // cfg.conv_algo: 0 auto, 1 never, >= 32 explicit Cin threshold (experiments, tests).
-  bool wino_ok(const T& x, int cout) const {
-    if (cfg.conv_algo == 1 || cfg.conv_algo == 4) return false;
-    const int min_cin = cfg.conv_algo >= 32 ? cfg.conv_algo : 256;
-    // the fused kernel (fwino_ok) takes every layer whose map it can tile and whose launch fills the chip, up to the
-    // Cin its affine table holds.  Measured on the 64->256 UNet, ms/step with the hand-over at Cin <= 0 / 256 / 512 /
-    // 1024 / all: 48.1 / 44.8 / 44.5 / 45.1 / 45.3 with the eight-wave kernel of round 1 (its Cin = 1024 launches lost
-    // to the batched GEMMs), 37.59 / 37.36 / 37.40 at <= 512 / 1024 / 2048 with the persistent sixteen-wave kernel
-    // (300 us against 265 + 40 + 21 for GEMM + transforms).  KD_FWINO_MAX_CIN moves it for experiments, read per plan
-    const int fw_max = kd_switch("KD_FWINO_MAX_CIN", 2048);
-    if (wino4_ok(x, cout)) return false;
-    if (cfg.conv_algo < 32 && x.C <= fw_max && fwino_ok(x, cout)) return false;
-    if ((x.H & 1) || (x.W & 1) || x.C < min_cin || x.C % 32 || cout <= 32 || cout % 4) return false;
-    const int64_t Mt = (int64_t)x.B * (x.H / 2) * (x.W / 2);
-    return Mt % 256 == 0 && 16 * Mt < 0x7fffffff && (int64_t)16 * cout * x.C * 4 < 0x7fffffff;
+  // ---- The path of a ResnetBlock 3x3 conv, the `Block` = GroupNorm -> [FiLM] -> SiLU -> conv3x3 (gn_conv3x3): Winograd
+  // F(4x4,3x3) as 36 batched GEMMs (wino4_block), F(2x2,3x3) as 16 batched GEMMs (wino_block), the fused F(2x2,3x3) kernel
+  // with the GroupNorm folded in (fwino_gn_conv), or gn_silu + the direct conv.  Decided here alone: resnet() dispatches on
+  // it, and add_skip (unet_build.inc) asks it whether the layer takes a skip concat's 2^-1/2 itself - Wino4 through its
+  // input transform's affine, WinoFused through the GroupNorm partials' ab_mul (SegPart); the other two read the skip half
+  // scaled in memory.
+  enum class Conv3x3 { Wino4, WinoGemm, WinoFused, Direct };
+  struct Conv3x3Choice { Conv3x3 algo; int images; };   // images: Wino4's images per launch set (wino4_images)
+  Conv3x3Choice conv3x3_choice(const T& x, int cout) const {
+    const int images = wino4_images(x, cout);
+    if (images > 0) return {Conv3x3::Wino4, images};
+    const bool fused = fwino_ok(x, cout);
+    // Winograd F(2x2,3x3) as batched GEMMs (kernels_wino.hip).  Worth it where the 2.25x smaller GEMM outweighs moving 4x
+    // the map through the transforms: measured on MI355X, Cin >= 256 wins and Cin = 128 loses (profiles/README.md).
+    // cfg.conv_algo: 0 auto, 1 never, >= 32 explicit Cin threshold (experiments, tests).
+    auto gemm_ok = [&] {
+      if (cfg.conv_algo == 1 || cfg.conv_algo == 4) return false;
+      const int min_cin = cfg.conv_algo >= 32 ? cfg.conv_algo : 256;
+      // the fused kernel (fwino_ok) takes every layer whose map it can tile and whose launch fills the chip, up to the
+      // Cin its affine table holds.  Measured on the 64->256 UNet, ms/step with the hand-over at Cin <= 0 / 256 / 512 /
+      // 1024 / all: 48.1 / 44.8 / 44.5 / 45.1 / 45.3 with the eight-wave kernel of round 1 (its Cin = 1024 launches lost
+      // to the batched GEMMs), 37.59 / 37.36 / 37.40 at <= 512 / 1024 / 2048 with the persistent sixteen-wave kernel
+      // (300 us against 265 + 40 + 21 for GEMM + transforms).
+      if (cfg.conv_algo < 32 && fused) return false;
+      if ((x.H & 1) || (x.W & 1) || x.C < min_cin || x.C % 32 || cout <= 32 || cout % 4) return false;
+      const int64_t Mt = (int64_t)x.B * (x.H / 2) * (x.W / 2);
+      return Mt % 256 == 0 && 16 * Mt < 0x7fffffff && (int64_t)16 * cout * x.C * 4 < 0x7fffffff;
+    };
+    if (gemm_ok()) return {Conv3x3::WinoGemm, 0};
+    // the fused kernel with the GroupNorm folded in: the per-image affine table sits in LDS, one image's map under 2^31 bytes
+    if (fused && x.C <= wino_fused_gn_max_cin() && x.C % cfg.resnet_groups == 0 && (int64_t)x.H * x.W * x.LD() * 4 < 0x7fffffff)
+      return {Conv3x3::WinoFused, 0};
+    return {Conv3x3::Direct, 0};
+  }
+  // ---- fused Winograd F(2x2,3x3) + GroupNorm / FiLM / SiLU (kernels_wino_fused128.hip): every ResnetBlock 3x3 conv
+  // whose map the kernel can tile (H % 8, W % 16, Cout % 128: all reference configs; a reduced-width model's narrow
+  // levels take the batched-GEMM or the direct path).  cfg.conv_algo 0: wherever the shape fits and the launch fills
+  // the chip; 1 and 2: never (2 = the batched-GEMM Winograd path only); 3: wherever the shape fits (tests).
+  bool fwino_ok(const T& x, int cout) const {
+    if (cfg.conv_algo == 1 || cfg.conv_algo == 2) return false;
+    if (x.C < 32 || !wino_fused128_ok(x.B, x.H, x.W, x.C, cout)) return false;
+    if (cfg.conv_algo == 3) return true;
+    return (int64_t)x.B * (x.H / 16) * (x.W / 16) * (cout / 64) >= 256;  // one workgroup per CU and round
   }
   // ---- Winograd F(4x4,3x3) (kernels_wino4.hip): 36 batched GEMMs over tiles of 4x4 outputs, 4x fewer MFMA issues than
   // the direct conv and 1.78x fewer than F(2x2,3x3), for V / D transform buffers of 2.25x the map.  cfg.conv_algo 0:
@@ -1099,7 +1122,6 @@ struct Builder {
     }
     return 0;
   }
-  bool wino4_ok(const T& x, int cout) const { return wino4_images(x, cout) > 0; }
   bool wino4_whole_ok(const T& x, int cout) const {
     if (cfg.conv_algo != 0 && cfg.conv_algo != 4) return false;
     if (cfg.wino43_min_cin < 0 && cfg.conv_algo == 0) return false;
@@ -1129,13 +1151,12 @@ struct Builder {
     if (cfg.wino43_min_cin == 0 && cfg.gemm_bf16x3 >= 0 && gemm_bf16x3_ok(36, Mt, cout, x.C)) thr = 128;
     return x.C >= thr;
   }
+  // Bx images per set of launches (wino4_images): V and D are one set's, the sets run one after the other.
   // skip_c0 >= 0: channels [skip_c0, ..) of x hold an unscaled skip tensor the layer must see times skip_scale: the input
   // transform folds the factor into its affine (the statistics come from partials that carry the scale: add_skip)
-  T wino4_block(const T& x, const std::string& gn_prefix, int ss_col, const std::string& conv_prefix, int Cout,
-                const T* res, int skip_c0 = -1, float skip_scale = 1.0f) {
-    const int Cin = x.C, G = cfg.resnet_groups, H = x.H, W = x.W, HW = x.HW();
-    // Bx images per set of launches (wino4_images): V and D are one set's, the sets run one after the other
-    const int Bs_ = wino4_images(x, Cout), Bx = Bs_ > 0 ? Bs_ : x.B, nset = x.B / Bx;
+  T wino4_block(const T& x, int Bx, const std::string& gn_prefix, int ss_col, const std::string& conv_prefix, int Cout,
+                const T* res, int skip_c0, float skip_scale) {
+    const int Cin = x.C, G = cfg.resnet_groups, H = x.H, W = x.W, HW = x.HW(), nset = x.B / Bx;
     const int64_t Mt = (int64_t)Bx * (H / 4) * (W / 4);
     const float* gamma = P(gn_prefix + ".weight", Cin);
     const float* beta = P(gn_prefix + ".bias", Cin);
@@ -1164,7 +1185,7 @@ struct Builder {
     const std::string shape = " M" + std::to_string((int64_t)Bx * HW) + " Cin" + std::to_string(Cin) + " Cout" +
                               std::to_string(Cout);
     kd_unet* uu = u;
-    const bool sg = seg_on && Cout % 64 == 0;   // GroupNorm partials of y for whichever layer normalises it next
+    const bool sg = Cout % 64 == 0;   // GroupNorm partials of y for whichever layer normalises it next
     const size_t sgo_all = sg ? add_seg(y, 0, Cout / 16, (H / 4) * (W / 4)) : 0;
     for (int st = 0; st < nset; ++st) {
       const int b0 = st * Bx;   // first image of the set
@@ -1244,7 +1265,7 @@ struct Builder {
     T D = alloc(1, 1, (int)(16 * nt_slice), Cout);
     T y = alloc(Bx, H, W, Cout);
     // GroupNorm partials of y from the output transform (one chunk per 2x2 tile) for whichever layer normalises it next
-    const bool sg = seg_on && Cout % 16 == 0;
+    const bool sg = Cout % 16 == 0;
     const size_t sgo = sg ? add_seg(y, 0, Cout / 16, (H / 2) * (W / 2)) : 0;
     const std::string shape = " M" + std::to_string((int64_t)Bx * HW) + " Cin" + std::to_string(Cin) + " Cout" +
                               std::to_string(Cout);
@@ -1285,25 +1306,9 @@ struct Builder {
     return y;
   }
 
-  // ---- fused Winograd F(2x2,3x3) + GroupNorm / FiLM / SiLU (kernels_wino_fused128.hip): every ResnetBlock 3x3 conv
-  // whose map the kernel can tile (H % 8, W % 16, Cout % 128: all reference configs; a reduced-width model's narrow
-  // levels take the batched-GEMM or the direct path).  cfg.conv_algo 0: wherever the shape fits and the launch fills
-  // the chip; 1 and 2: never (2 = the batched-GEMM Winograd path only); 3: wherever the shape fits (tests).
-  bool fwino_ok(const T& x, int cout) const {
-    if (cfg.conv_algo == 1 || cfg.conv_algo == 2) return false;
-    if (x.C < 32 || !wino_fused128_ok(x.B, x.H, x.W, x.C, cout)) return false;
-    if (cfg.conv_algo == 3) return true;
-    return (int64_t)x.B * (x.H / 16) * (x.W / 16) * (cout / 64) >= 256;  // one workgroup per CU and round
-  }
-  // The same layer straight from the un-normalised block input: GroupNorm statistics, the per-(image, channel)
+  // The fused F(2x2,3x3) layer straight from the un-normalised block input: GroupNorm statistics, the per-(image, channel)
   // affine fold, and the fused kernel that applies GroupNorm / FiLM / SiLU to the raw patch in LDS
-  // (wino_fused_gn_kernel): the activated map is never written.  KD_FWINO_GN=0 keeps the separate
-  // gn_apply_silu pass (A/B, read per plan).
-  bool fwino_gn_ok(const T& x, int cout) const {
-    const bool on = kd_switch("KD_FWINO_GN", 1) != 0;
-    return on && x.C <= wino_fused_gn_max_cin() && x.C % cfg.resnet_groups == 0 && fwino_ok(x, cout) &&
-           (int64_t)x.H * x.W * x.LD() * 4 < 0x7fffffff;
-  }
+  // (wino_fused_gn_kernel): the activated map is never written.
   T fwino_gn_conv(const T& x, const std::string& gn_prefix, int ss_col, const std::string& conv_prefix, int Cout,
                   const T* res) {
     const int Cin = x.C, G = cfg.resnet_groups, Bx = x.B, H = x.H, W = x.W;
@@ -1326,7 +1331,7 @@ struct Builder {
       }, "gn fold C" + std::to_string(Cin));
     }
     // the epilogue leaves the partials of y for whichever GroupNorm reads it next (block2, or the next block)
-    const bool so_ = seg_on && Cout % 16 == 0 && kd_switch("KD_FWINO_STATS", 1) != 0;
+    const bool so_ = Cout % 16 == 0;
     const size_t pout = so_ ? add_seg(y, 0, Cout / 16, (int)wino_fused_out_stats_chunks(H, W, Cout, Cout / 16)) : 0;
     size_t xo = x.at(), yo = y.off, ro = res ? res->at() : 0, abo = ab.off;
     const bool hr = res != nullptr;
@@ -1351,6 +1356,34 @@ struct Builder {
     return y;
   }
 
+  // The `Block` `pre` (.groupnorm, .project) of a ResnetBlock on the path conv3x3_choice picks.  free_x: x dies here, released
+  // once the layer has read it.  skip_c0 / skip_scale: see resnet() (Wino4 takes them; WinoFused has them in the partials).
+  T gn_conv3x3(const T& x, bool free_x, const std::string& pre, int ss_col, int Cout, const T* res, int skip_c0 = -1,
+               float skip_scale = 1.0f) {
+    const Conv3x3Choice c = conv3x3_choice(x, Cout);
+    if (skip_c0 >= 0 && c.algo != Conv3x3::Wino4 && c.algo != Conv3x3::WinoFused)
+      throw std::runtime_error("plan: folded skip scale on a conv path that cannot apply it: " + pre);
+    const std::string gn = pre + ".groupnorm", cv = pre + ".project";
+    T y;
+    switch (c.algo) {
+      case Conv3x3::Wino4: y = wino4_block(x, c.images, gn, ss_col, cv, Cout, res, skip_c0, skip_scale); break;
+      case Conv3x3::WinoGemm: y = wino_block(x, gn, ss_col, cv, Cout, res); break;
+      case Conv3x3::WinoFused: y = fwino_gn_conv(x, gn, ss_col, cv, Cout, res); break;
+      case Conv3x3::Direct: {
+        T a = gn_silu(x, gn, ss_col);
+        if (free_x) free(x);   // before the conv allocates its output, which may take x's place
+        ConvOpt o;
+        o.res = res;          // y + res folded into the conv epilogue
+        o.want_seg = true;    // the next GroupNorm reads y (block1 behind a cross-attention: none does, harmless)
+        y = conv(a, pack_conv(cv + ".weight", Cout, a.C, a.C, 3), P(cv + ".bias", Cout), Cout, 3, 1, 1, o);
+        free(a);
+        return y;
+      }
+    }
+    if (free_x) free(x);
+    return y;
+  }
+
   // ResnetBlock.  Does NOT free x.
   // ct: the buffer of the skip concat that follows this block ([B,H,W,dim_out + skip channels]); when the
   // block ends in its 1x1 skip conv, that conv writes the block output straight into the first dim_out
@@ -1365,21 +1398,7 @@ struct Builder {
     bool has_cross = has(pre + ".cross_attn.to_q.weight");
     if (has_cross && !ctx) throw std::runtime_error("cross-attention block without conditioning tokens: " + pre);
     int dim_in = x.C;
-    T h;
-    if (wino4_ok(x, dim_out)) {
-      h = wino4_block(x, pre + ".block1.groupnorm", -1, pre + ".block1.project", dim_out, nullptr, skip_c0, skip_scale);
-    } else if (wino_ok(x, dim_out)) {
-      h = wino_block(x, pre + ".block1.groupnorm", -1, pre + ".block1.project", dim_out, nullptr);
-    } else if (fwino_gn_ok(x, dim_out)) {
-      h = fwino_gn_conv(x, pre + ".block1.groupnorm", -1, pre + ".block1.project", dim_out, nullptr);
-    } else {
-      T y1 = gn_silu(x, pre + ".block1.groupnorm", -1);
-      ConvOpt o1;
-      o1.want_seg = true;   // block2's GroupNorm (or the cross-attention's input has none: harmless) reads h next
-      h = conv(y1, pack_conv(pre + ".block1.project.weight", dim_out, dim_in, dim_in, 3),
-               P(pre + ".block1.project.bias", dim_out), dim_out, 3, 1, 1, o1);
-      free(y1);
-    }
+    T h = gn_conv3x3(x, false, pre + ".block1", -1, dim_out, nullptr, skip_c0, skip_scale);
     if (has_cross) {
       T h2 = cross_attn(h, pre + ".cross_attn", *ctx);
       free(h);
@@ -1388,29 +1407,7 @@ struct Builder {
     auto it = tmlp_off.find(pre);
     int ss_col = it != tmlp_off.end() ? it->second : -1;
     bool has_res_conv = has(pre + ".res_conv.weight");
-    T h2;
-    if (wino4_ok(h, dim_out)) {
-      h2 = wino4_block(h, pre + ".block2.groupnorm", ss_col, pre + ".block2.project", dim_out,
-                       (!use_gca && !has_res_conv) ? &x : nullptr);
-      free(h);
-    } else if (wino_ok(h, dim_out)) {
-      h2 = wino_block(h, pre + ".block2.groupnorm", ss_col, pre + ".block2.project", dim_out,
-                      (!use_gca && !has_res_conv) ? &x : nullptr);
-      free(h);
-    } else if (fwino_gn_ok(h, dim_out)) {
-      h2 = fwino_gn_conv(h, pre + ".block2.groupnorm", ss_col, pre + ".block2.project", dim_out,
-                         (!use_gca && !has_res_conv) ? &x : nullptr);
-      free(h);
-    } else {
-      T y2 = gn_silu(h, pre + ".block2.groupnorm", ss_col);
-      ConvOpt o2;
-      if (!use_gca && !has_res_conv) o2.res = &x;  // h2 + x folded into the conv epilogue
-      o2.want_seg = true;
-      free(h);
-      h2 = conv(y2, pack_conv(pre + ".block2.project.weight", dim_out, dim_out, dim_out, 3),
-                P(pre + ".block2.project.bias", dim_out), dim_out, 3, 1, 1, o2);
-      free(y2);
-    }
+    T h2 = gn_conv3x3(h, true, pre + ".block2", ss_col, dim_out, (!use_gca && !has_res_conv) ? &x : nullptr);
     if (!use_gca && !has_res_conv) return h2;
     if (skip_c0 >= 0 && !has_res_conv) throw std::runtime_error("plan: folded skip scale without a skip conv: " + pre);
     const float* w_res = nullptr;
@@ -1440,7 +1437,7 @@ struct Builder {
         if (out.C != dim_out) throw std::runtime_error("plan: output slot of the wrong width: " + pre);
         size_t ao = h2.off, go = gate.off, ro = x.at(), yo = out.at();
         int Bx = x.B, HW = x.HW(), ldr = x.LD(), ldy = out.LD();
-        const bool sg = seg_on && dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
+        const bool sg = dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
         const size_t sgo = sg ? add_seg(out, 0, dim_out / 16, gate_add_chunks(Bx, HW)) : 0;
         kd_unet* uu = u;
         emit([=](hipStream_t s) {
@@ -1501,7 +1498,7 @@ struct Builder {
     T y = alloc(x.B, Ho, Wo, Cout);
     const X3Epi base = downsample_x3_epi(x, Cout);
     // the output feeds the GroupNorm of the level's first ResnetBlock: partials from the epilogue
-    const bool sg = seg_on && Cout % 16 == 0 && (Ho * Wo) % 32 == 0;
+    const bool sg = Cout % 16 == 0 && (Ho * Wo) % 32 == 0;
     const int seg_rows = gemm_bf16x3_seg_rows((int)M, Cout, K);
     const size_t sgo = sg ? add_seg(y, 0, Cout / 16, Ho * Wo / seg_rows) : 0;
     const size_t xo = x.at(), yo = y.off;

@@ -20,7 +20,7 @@
 // 1/24, so fp32 re-association costs more than in F(2x2,3x3): relative L2 against an fp64 convolution 3-4e-6 at
 // Cin = 512 .. 2048 (F(2x2,3x3): 5e-7, direct fp32 chain: 2.5e-7; scratch/wino43_accuracy.py), inside the 2e-5 the
 // UNet forward is held to (tests/test_fullsize_gpu.py).  The plan uses it where the 4x-smaller GEMM outweighs the
-// transform passes: Cin >= 512 (Builder::wino4_ok).
+// transform passes: Cin >= 512 (Builder::wino4_whole_ok).
 #include "common.h"
 
 namespace kd {

@@ -199,7 +199,7 @@ void Builder::build() {
           }
         });
       }
-      const bool sg = seg_on && dim % 16 == 0 && ds[0] % 16 == 0 && ds[1] % 16 == 0 && ds[2] % 16 == 0;
+      const bool sg = dim % 16 == 0 && ds[0] % 16 == 0 && ds[1] % 16 == 0 && ds[2] % 16 == 0;
       const size_t sgo = sg ? add_seg(xt, 0, dim / 16, S * S / 32) : 0;
       const size_t xo = xt.at(), ro = hoist ? init_static.off : 0;
       const int ldy = xt.LD(), Bx = B;
@@ -392,14 +392,14 @@ void Builder::build() {
       have_ct = false;
       x = full;   // the reference the skip stack held is x's now
       // scale 2^-1/2 of the skip half: folded into the consumer where it reads statistics and weights that can
-      // carry it (fused GroupNorm conv + 1x1 skip conv), else applied in place
+      // carry it (block1's 3x3 conv on the paths conv3x3_choice names + the 1x1 skip conv), else applied in place
       move_seg(skip, full, Ca, skip_scale, skip_scale);
       SegPart sp[2];
       int nsp = 0;
       // (round 5: the F(4x4,3x3) layers too - their input transform takes the factor into its affine; nine in-place scale
       // passes of the 64 x 64 .. 16 x 16 levels gone at batch 16)
-      const bool w4ok = wino4_ok(full, dim_out), w4 = w4ok && kd_switch("KD_W4_SKIPSCALE", 1) != 0;
-      if ((w4 || (!w4ok && fwino_gn_ok(full, dim_out) && !wino_ok(full, dim_out))) && seg_sources(full, sp, nsp)) return Ca;
+      const Conv3x3 algo = conv3x3_choice(full, dim_out).algo;
+      if ((algo == Conv3x3::Wino4 || algo == Conv3x3::WinoFused) && seg_sources(full, sp, nsp)) return Ca;
       scale_slice(full, Ca, skip.C, skip_scale);
       auto it = seg_of.find(full.at());
       if (it != seg_of.end())
