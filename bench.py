@@ -17,8 +17,13 @@ the data path); rank 0 prints ONE JSON line.
                                           # sample_ultra_res.py:235-240) before any GPU call and relays the line
 
 The line of the headline workload also carries `rccl_ranks` (an all-reduce of ones over the process group: the
-number of ranks the collective library saw) and a nested `grid` object: patches/s of the 8x8 ultra-res grid
-(BASELINE configs[4], the >= 6x scaling target) for 1 and 3 canvases in flight, measured by the same command.
+number of ranks the collective library saw) and the whole step's roofline.  A plain run does nothing else: set-up,
+warm-up, the timed steps, --dump-outputs, the line.  `--full` adds, after the timed steps, what takes runs of its own:
+the per-launch kernel classes, the conditioning-table build, a nested `grid` object (patches/s of the 8x8 ultra-res grid,
+BASELINE configs[4], the >= 6x scaling target, for 1 and 3 canvases in flight), `other_configs`, the CPU baseline and
+the parity check against it.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
 """
 import argparse
 import ctypes as C
@@ -710,10 +715,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="sr: after the timed steps also run the per-launch profile, the conditioning-table build, the nested "
+                         "grid, other_configs, the CPU baseline and the parity check (the --no-* options below leave parts out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline and parity check")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-kernel-classes", action="store_true",
-                    help="skip the per-launch profile after the timed region (rocprofv3 runs: keeps only the steps in the trace)")
+                    help="--full: skip the per-launch profile after the timed region (rocprofv3 runs: keeps only the steps in the trace)")
     ap.add_argument("--workload", choices=("sr", "grid"), default="sr",
                     help="sr: the headline metric (default); grid: ultra-res patch grid, patches/s")
     ap.add_argument("--grid-n", type=int, default=8)
@@ -746,10 +754,10 @@ def main():
                     help="sr: Unet.x3_linear (0 = the plan's default: token GEMMs / 1x1 convs with K >= 512 on the bf16x3 kernel; "
                          "-1 = on conv_buf_kernel, fp32 MFMA; n = K >= n)")
     ap.add_argument("--no-line-grid", action="store_true",
-                    help="sr: leave the nested `grid` object (8x8 grid patches/s for 1 and 3 canvases) out of the line")
+                    help="sr --full: leave the nested `grid` object (8x8 grid patches/s for 1 and 3 canvases) out of the line")
     ap.add_argument("--line-grid-steps", type=int, default=8, help="timesteps per stage of the nested grid runs")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="sr: leave `other_configs` (one forward of configs[0], [1] and unet3 at batch 8) out of the line")
+                    help="sr --full: leave `other_configs` (one forward of configs[0], [1] and unet3 at batch 8) out of the line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="sr: after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy: "
                          "x_prev, pred, x0, thresholds (float32, 38 MB); the inputs depend on the arguments only")
@@ -869,9 +877,9 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, lib, handle, x)
 
-    # what the conditioning table costs a cold 250-step sample(): all T rows rebuilt, device time by HIP events
+    # --full: what the conditioning table costs a cold 250-step sample(): all T rows rebuilt, device time by HIP events
     cond_build = None
-    if not args.no_cond_table:
+    if args.full and not args.no_cond_table:
         built, rows, runs = C.c_int(0), C.c_int(0), C.c_int(0)
         E.check(lib.kd_sample_build_cond_table(handle, C.byref(sc), C.byref(sa), 0, T_SCHED, 1, C.byref(built), E.current_stream()))
         ms = float(lib.kd_unet_cond_table_build_ms(handle, C.byref(rows), C.byref(runs)))
@@ -881,15 +889,15 @@ def main():
                       # timed steps computed their conditioning themselves
                       "refused_bytes": int(lib.kd_unet_cond_table_refused_bytes(handle))}
 
-    # the >= 6x target of BASELINE.json is patch throughput of the 8x8 grid: measured by the same command, after the
-    # timed region of the headline metric, on every rank (collective inside); 1 canvas (dependency bound 4.27x at 8
+    # the >= 6x target of BASELINE.json is patch throughput of the 8x8 grid: measured by the same command with --full, after
+    # the timed region of the headline metric, on every rank (collective inside); 1 canvas (dependency bound 4.27x at 8
     # ranks) and 3 canvases in flight (bound 6.2x)
     grid_res = None
-    if not args.no_line_grid:
+    if args.full and not args.no_line_grid:
         grid_res = grid_workload(args, world, rank, device, distributed, barrier, [1, 3], args.line_grid_steps, 1, 1)
 
     others = None
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         others = other_configs(device, lib)
 
     if rank == 0:
@@ -900,7 +908,7 @@ def main():
         # share of the step's time the matrix pipe would be busy at its nominal rates: fp32 MFMA work + bf16 MFMA work
         step_pipe_frac = step_issued / FP32_PEAK_TFLOPS + step_issued_bf16 / BF16_PEAK_TFLOPS
         step_direct = flop_per_step / (dev_ms_per_step * 1e-3) / 1e12
-        kernels = kernel_classes(lib, handle) if world == 1 and not args.no_kernel_classes else None
+        kernels = kernel_classes(lib, handle) if args.full and world == 1 and not args.no_kernel_classes else None
         # the dominant kernel: whichever of the ResnetBlock 3x3-conv kernels takes most of the step in this plan (since the end
         # of round 5 the bf16x3 position GEMMs of F(4x4,3x3); the fused F(2x2,3x3) kernel where the plan keeps layers on it)
         dom = max((k for k in (kernels or []) if k["kernel"] in (DOMINANT, X3_ALL)), key=lambda k: k["ms"], default=None)
@@ -947,7 +955,7 @@ def main():
                 rocprof_avg_launch_us=prof.get("dominant_avg_us") if same else None,
                 traffic=prof.get("dominant_bytes_per_launch") if same else None,
                 traffic_source=("profile-derived, not measured in this run: " + prof["source"]) if prof.get("source") and same else None)
-        else:  # multi-GPU runs / --no-kernel-classes: no per-launch profile, whole-step pipe utilisation instead
+        else:  # plain and multi-GPU runs / --no-kernel-classes: no per-launch profile, whole-step pipe utilisation instead
             # (nearly all matrix work of the plan is bf16 MFMA now: the step's bf16 rate against the bf16 peak, per GPU; the
             # fp32-pipe share and the combined busy fraction are in roofline.step)
             if step_issued_bf16 / BF16_PEAK_TFLOPS >= step_issued / FP32_PEAK_TFLOPS:
@@ -1009,7 +1017,7 @@ def main():
                     "mfma_frac_per_gpu": r["roofline"]["frac"]} for r in grid_res}}
         if others:
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, first = cpu_baseline(unet)
             out["cpu_baseline"] = cpu
             out.update(engine_parity(unet, first, device, lib))

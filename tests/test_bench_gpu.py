@@ -1,8 +1,9 @@
 """bench.py as the driver calls it for N > 1: `python bench.py --gpus N` WITHOUT a launcher must start its own ranks
 (one process per GPU through torch.distributed.run, as the reference spawns its workers, sample_ultra_res.py:235-240), run the
 headline workload on every rank and print ONE JSON line on rank 0 that also carries the number of ranks the collective
-library connected and the patch throughput of the ultra-res grid.  A one-GPU box cannot hold two RCCL ranks, so the
-rehearsal runs the ranks over gloo on the one card (`KD_BENCH_BACKEND=gloo`); the RCCL run is the driver's."""
+library connected and, with --full, the patch throughput of the ultra-res grid.  A one-GPU box cannot hold two RCCL ranks,
+so the rehearsal runs the ranks over gloo on the one card (`KD_BENCH_BACKEND=gloo`); the RCCL run is the driver's.
+Without --full a run does only what the headline figure needs."""
 import json
 import os
 import subprocess
@@ -21,8 +22,8 @@ def test_bench_self_launch_two_ranks_over_gloo(device, tmp_path):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     dump = tmp_path / "outputs"
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--line-grid-steps", "1", "--grid-n", "2", "--dump-outputs", str(dump)]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--line-grid-steps", "1", "--grid-n", "2", "--dump-outputs", str(dump)]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -44,3 +45,24 @@ def test_bench_self_launch_two_ranks_over_gloo(device, tmp_path):
         assert g[key]["patches"] == 4 * ncan and g[key]["patches_per_s"] > 0
         assert g[key]["schedule_slots"] <= 4 * ncan      # two ranks share the waves of a 2x2 grid
     assert g["canvases_3"]["schedule_slots"] < 3 * g["canvases_1"]["schedule_slots"] or g["canvases_1"]["schedule_slots"] == 3
+
+
+def test_bench_plain_run_measures_the_headline_only(device):
+    """`python bench.py --gpus 1 --steps K --warmup W`: the headline fields, and none of what --full adds after the timed
+    steps (per-launch profile, conditioning-table build, nested grid, other configs, CPU baseline, parity)."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "denoising-steps/sec (64->256 SR UNet, bs16)" and d["unit"] == "denoising-steps/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 1 and d["rccl_ranks"] == 1
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6
+    assert d["roofline"]["step"]["device_ms"] > 0 and d["roofline"]["kernels"] is None
+    assert d["config"]["cond_table_build_ms"] is None
+    assert not {"grid", "other_configs", "cpu_baseline", "parity_pred_rel_l2"} & set(d)
