@@ -40,7 +40,9 @@ const char* kd_last_error(void);
  *      `gemm_bf16x3`, `x3_linear` and `wino4_max_images`, kd_sample_args_t `cond_table_max_mb`; kd_unet_cond_table_refused_bytes, kd_linear_bf16x3 (+ _seg_rows), kd_downsample_bf16x3, kd_layernorm_ex and kd_layernorm_linear_bf16x3 added;
  *      kd_unet_cond_table_build_ms takes a non-const handle (it reads the build's events on demand); later additions that
  *      change no existing entry: kd_linear_skinny, kd_global_context_gate, kd_gate_add_nhwc (+ _chunks), kd_gn_fold_seg,
- *      kd_wf_ab_scale, kd_gn_conv3x3_winograd4_nhwc (the ResnetBlock pieces the plan joins, for unit tests) */
+ *      kd_wf_ab_scale, kd_gn_conv3x3_winograd4_nhwc (the ResnetBlock pieces the plan joins, for unit tests); kd_unet_create_ext
+ *      with its struct kd_unet_ext_t for linear attention, kd_linattn_chunk_tokens, kd_linattn_dwconv_nhwc, kd_linattn_context,
+ *      kd_linattn_apply */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -153,6 +155,19 @@ int kd_unet_create_shared(const kd_unet_config_t* cfg, const kd_param_t* params,
  * the thresholded x0 estimate of each step into the next forward.  share_with must have the same self_cond. */
 int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
                              const kd_unet_t* share_with, int self_cond, kd_unet_t** out);
+/* Structural options beyond kd_unet_config_t, for kd_unet_create_ext: library kwargs the first plans did not have.
+ * use_linear_attn[l]: level l's attention slot (downs.l.3 / the matching ups.j.2) holds a LinearAttentionTransformerBlock
+ * where layer_attns[l] is 0 (full attention wins); use_linear_cross_attn[l]: the level's first ResnetBlock on each path
+ * (downs.l.1, ups.j.0) has cross-attention, and it is a LinearCrossAttention.  Entries from num_levels on are ignored. */
+typedef struct kd_unet_ext {
+  int self_cond;   /* as kd_unet_create_self_cond */
+  int use_linear_attn[KD_MAX_LEVELS];
+  int use_linear_cross_attn[KD_MAX_LEVELS];
+} kd_unet_ext_t;
+/* kd_unet_create_self_cond with the options of `ext` (NULL = all zero: the plan of kd_unet_create_shared).  An ext with
+ * every linear flag zero gives the same plan - the same launches and the same bits - as kd_unet_create_self_cond. */
+int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                       const kd_unet_ext_t* ext, kd_unet_t** out);
 void kd_unet_destroy(kd_unet_t* u);
 /* bytes of HBM held (weights + workspace) and algorithmic MACs of one forward (whole batch) */
 int64_t kd_unet_hbm_bytes(const kd_unet_t* u);
@@ -444,6 +459,20 @@ int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* 
 int kd_gate_add_nhwc(const float* d_a, const float* d_gate, const float* d_r, int ldr, float* d_y, int ldy, double* d_seg,
                      int B, int HW, int C, void* stream);
 int kd_gate_add_chunks(int B, int HW);
+/* Linear attention (dim_head 64), the kernels the plan runs, for unit tests.  kd_linattn_dwconv_nhwc: y = depthwise 3x3
+ * (zero padding) of x, both [B][H][W][3 heads 64] (q | k | v), weights the library's to_{q,k,v}.2.weight [heads 64][1][3][3];
+ * d_part [B][ceil(H W / kd_linattn_chunk_tokens())][heads 64][2] = (max, sum of exp(k - max)) of k per chunk of tokens.
+ * kd_linattn_context: d_ctx [B][heads][64][64] = softmax_n(k)^T v over the HW tokens (k / v rows of stride ld, d_part as
+ * the conv leaves it) then the null key / value [64] (or NULL) then m context tokens (d_ck / d_cv [B][m] rows of stride
+ * ldc).  kd_linattn_apply: out[b][n][h 64 + e] = [SiLU](softmax_d(q) scale . ctx[b][h]). */
+int kd_linattn_chunk_tokens(void);
+int kd_linattn_dwconv_nhwc(const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, float* d_y,
+                           float* d_part, int B, int H, int W, int heads, void* stream);
+int kd_linattn_context(const float* d_k, const float* d_v, int ld, const float* d_part, int HW, const float* d_ck,
+                       const float* d_cv, int ldc, int m, const float* d_null_k, const float* d_null_v, float* d_ctx, int B,
+                       int heads, void* stream);
+int kd_linattn_apply(const float* d_q, int ldq, const float* d_ctx, float* d_out, int ldo, int B, int N, int heads,
+                     float scale, int silu, void* stream);
 /* GroupNorm statistics from producers' fp64 segment partials [B][nseg][nchunk][2] (sum, sum of squares per 16-channel
  * segment and chunk of HW pixels), of up to two sources: source 0 covers channels [0, 16 nseg0), source 1 (d_seg1 may be
  * NULL) [16 nseg0, C); the GroupNorm sees scale_i * source i, and ab_mul_i goes into the affine's A for its channels (a

@@ -545,6 +545,15 @@ int kd_unet_create_shared(const kd_unet_config_t* cfg, const kd_param_t* params,
 
 int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params,
                              const kd_unet_t* share_with, int self_cond, kd_unet_t** out) {
+  kd_unet_ext_t ext;
+  memset(&ext, 0, sizeof ext);
+  ext.self_cond = self_cond;
+  return kd_unet_create_ext(cfg, params, n_params, share_with, &ext, out);
+}
+
+int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                       const kd_unet_ext_t* ext, kd_unet_t** out) {
+  const int self_cond = ext ? ext->self_cond : 0;
   if (!cfg || !params || !out) {
     set_error("kd_unet_create: null argument");
     return 1;
@@ -561,6 +570,11 @@ int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* para
   kd_unet* u = new kd_unet();
   u->cfg = *cfg;
   u->self_cond = self_cond != 0;
+  if (ext)
+    for (int l = 0; l < KD_MAX_LEVELS; ++l) {
+      u->lin_attn[l] = l < cfg->num_levels && ext->use_linear_attn[l] != 0;
+      u->lin_cross[l] = l < cfg->num_levels && ext->use_linear_cross_attn[l] != 0;
+    }
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   try {
@@ -1140,6 +1154,41 @@ int kd_linear_skinny(const float* d_x, int ldx, const float* d_w, const float* d
   KD_REQUIRE(in_act >= ACT_NONE && in_act <= ACT_SIGMOID && act >= ACT_NONE && act <= ACT_SIGMOID,
              "kd_linear_skinny: unknown activation");
   return entry_finish(launch_linear_skinny(d_x, ldx, d_w, d_bias, d_y, ldy, M, K, N, in_act, act, s), s);
+}
+
+int kd_linattn_chunk_tokens(void) { return LA_CHUNK; }
+
+int kd_linattn_dwconv_nhwc(const float* d_x, const float* d_wq, const float* d_wk, const float* d_wv, float* d_y,
+                           float* d_part, int B, int H, int W, int heads, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && d_wq && d_wk && d_wv && d_y && d_part, "kd_linattn_dwconv_nhwc: null argument");
+  KD_REQUIRE(B > 0 && H > 0 && W > 0 && heads > 0, "kd_linattn_dwconv_nhwc needs B, H, W, heads > 0");
+  const int inner = heads * 64;
+  EntryBufs bufs;
+  float* w = nullptr;
+  if (bufs.get((void**)&w, (size_t)27 * inner * sizeof(float))) return 1;
+  int rc = launch_linattn_pack_dw(d_wq, d_wk, d_wv, w, inner, s);
+  if (!rc) rc = launch_linattn_dwconv(d_x, w, d_y, d_part, B, H, W, inner, s);
+  return entry_finish(rc, s);
+}
+
+int kd_linattn_context(const float* d_k, const float* d_v, int ld, const float* d_part, int HW, const float* d_ck,
+                       const float* d_cv, int ldc, int m, const float* d_null_k, const float* d_null_v, float* d_ctx, int B,
+                       int heads, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_ctx && B > 0 && heads > 0 && HW >= 0 && m >= 0, "kd_linattn_context: null output or bad sizes");
+  EntryBufs bufs;
+  float* ws = nullptr;
+  if (HW > 0 && bufs.get((void**)&ws, linattn_ws_floats(B, heads, HW) * sizeof(float))) return 1;
+  return entry_finish(launch_linattn_context(d_k, d_v, ld, d_part, HW, d_ck, d_cv, ldc, m, d_null_k, d_null_v, ws, d_ctx, B,
+                                             heads, s), s);
+}
+
+int kd_linattn_apply(const float* d_q, int ldq, const float* d_ctx, float* d_out, int ldo, int B, int N, int heads,
+                     float scale, int silu, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_q && d_ctx && d_out, "kd_linattn_apply: null argument");
+  return entry_finish(launch_linattn_apply(d_q, ldq, d_ctx, d_out, ldo, B, N, heads, scale, silu, s), s);
 }
 
 int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* d_wk, const float* d_bk, const float* d_w0,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <algorithm>
 #include <string>
 
 // Experiment switches of the A/B measurements logged in profiles/README.md.  The product build compiles every switch
@@ -305,6 +306,27 @@ int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, fl
 // nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
 int launch_init_conv(const float* x_nchw, const float* sc_nchw, int np, const float* wp, const float* bias, const float* res,
                      float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
+
+// ---- linear attention, dim_head = 64 (kernels_linattn.hip).  q | k | v are column slices of one [B][H][W][3 inner] map
+constexpr int LA_CHUNK = 64;   // tokens per chunk of the k-softmax partials
+int linattn_chunks(int HW);
+int linattn_splits(int B, int heads, int HW);   // token splits per (image, head) of the context reduction (0 when HW == 0)
+size_t linattn_ws_floats(int B, int heads, int HW);
+// [9][3 inner] tap-major depthwise weights from to_q.2 / to_k.2 / to_v.2 ([inner][1][3][3] each)
+int launch_linattn_pack_dw(const float* wq, const float* wk, const float* wv, float* dst, int inner, hipStream_t s);
+// y = depthwise 3x3 (zero padding) of x, both dense [B][H][W][3 inner]; part [B][linattn_chunks(HW)][inner] float2 =
+// (max, sum of exp(k - max)) of k's channels over each chunk of LA_CHUNK tokens
+int launch_linattn_dwconv(const float* x, const float* w, float* y, float* part, int B, int H, int W, int inner,
+                          hipStream_t s);
+// ctx [B][heads][64][64] = softmax_n(k)^T v per (image, head) over the HW tokens of k / v (rows of stride ld, image stride
+// HW ld; part as launch_linattn_dwconv leaves it) followed by the shared null key / value (nk / nv [64], or nullptr) and
+// m context tokens (ck / cv [B][m] rows of stride ldc).  ws: linattn_ws_floats(B, heads, HW) floats (nullptr when HW == 0)
+int launch_linattn_context(const float* k, const float* v, int ld, const float* part, int HW, const float* ck,
+                           const float* cv, int ldc, int m, const float* nk, const float* nv, float* ws, float* ctx, int B,
+                           int heads, hipStream_t s);
+// out[b][n][h 64 + e] = act(softmax_d(q[b][n][h 64 + d]) scale . ctx[b][h][d][e]), act = SiLU when silu != 0
+int launch_linattn_apply(const float* q, int ldq, const float* ctx, float* out, int ldo, int B, int N, int heads,
+                         float scale, int silu, hipStream_t s);
 
 // ---- final conv to 3 channels (kernels_final.hip)
 int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, hipStream_t s);

@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/kd_engine.h"
@@ -152,6 +153,10 @@ struct kd_unet {
   int64_t mfma_bf16_macs = 0;  // ... bf16 MACs of the bf16x3 GEMMs (six per fp32 MAC; not part of mfma_macs)
   int time_cond_dim = 0;
   int self_cond = 0;   // Unet(self_cond=True): the init conv also reads in_self_cond (kd_unet_create_self_cond)
+  // per level: LinearAttentionTransformerBlock at the attention slot where layer_attns is 0 (use_linear_attn); the level's
+  // first ResnetBlocks' cross-attention is LinearCrossAttention (use_linear_cross_attn) - kd_unet_create_ext
+  int lin_attn[KD_MAX_LEVELS] = {0};
+  int lin_cross[KD_MAX_LEVELS] = {0};
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
@@ -1400,7 +1405,7 @@ struct Builder {
     int dim_in = x.C;
     T h = gn_conv3x3(x, false, pre + ".block1", -1, dim_out, nullptr, skip_c0, skip_scale);
     if (has_cross) {
-      T h2 = cross_attn(h, pre + ".cross_attn", *ctx);
+      T h2 = lin_cross_pre.count(pre) ? linear_cross_attn(h, pre + ".cross_attn", *ctx) : cross_attn(h, pre + ".cross_attn", *ctx);
       free(h);
       h = h2;
     }
@@ -1664,6 +1669,11 @@ struct Builder {
            tcd, tcd, ACT_NONE, ACT_NONE);
   }
 
+  // linear attention (linattn_build.inc): the ResnetBlocks whose cross-attention is LinearCrossAttention, by prefix
+  std::unordered_set<std::string> lin_cross_pre;
+  T linear_attn_block(const T& x, const std::string& pre, const T* ctx, const T* dst = nullptr);
+  T linear_cross_attn(const T& x, const std::string& pre, const T& c);
+  T feed_forward_tail(const T& x, const T& proj, const std::string& g_out, const std::string& f, const T* dst);
   void build();
   void build_text();
 };
@@ -1671,6 +1681,7 @@ struct Builder {
 }  // namespace kd
 
 #include "unet_build.inc"  // Builder::build(): the walk over the module tree
+#include "linattn_build.inc"  // Builder: LinearAttentionTransformerBlock and LinearCrossAttention
 #include "text_build.inc"  // Builder::build_text(): step-invariant text conditioning
 #include "api.inc"         // sampler loop + extern "C" entry points
 

@@ -17,6 +17,12 @@ void Builder::build() {
   if (dim % 32) throw std::runtime_error("dim must be a multiple of 32 (GroupNorm(8) over dim/8 channels, 16-B loads)");
 
   collect_time_mlps();
+  // use_linear_cross_attn: the level's first ResnetBlock on each path gets (linear) cross-attention
+  for (int l = 0; l < L; ++l)
+    if (u->lin_cross[l]) {
+      lin_cross_pre.insert("downs." + std::to_string(l) + ".1");
+      lin_cross_pre.insert("ups." + std::to_string(L - 1 - l) + ".0");
+    }
   // Skip tensors live in the buffer of the concat they will later be part of (KD_CONCAT_SLOT=0: copied at the
   // concat as before; A/B, read per plan)
   const bool slot_on = kd_switch("KD_CONCAT_SLOT", 1) != 0;
@@ -271,7 +277,7 @@ void Builder::build() {
       step(downsample(x, pre + ".0", dim_out));
       cur = dim_out;
     }
-    step(resnet(x, pre + ".1", cur, cfg.layer_cross_attns[l] ? &c : nullptr, false));
+    step(resnet(x, pre + ".1", cur, cfg.layer_cross_attns[l] || u->lin_cross[l] ? &c : nullptr, false));
     // every hidden of this level is later concatenated behind dim_out channels of the up path: its producer
     // writes it into channels [dim_out, dim_out + cur) of that buffer
     auto make_slot = [&]() {
@@ -298,6 +304,12 @@ void Builder::build() {
       T slot;
       if (slot_on) slot = make_slot();
       take(transformer(x, pre + ".3", &c, slot_on ? &slot : nullptr), slot, slot_on);
+      retain(x);
+      hiddens.push_back(x);
+    } else if (u->lin_attn[l]) {   // LinearAttentionTransformerBlock: where full attention is off
+      T slot;
+      if (slot_on) slot = make_slot();
+      take(linear_attn_block(x, pre + ".3", &c, slot_on ? &slot : nullptr), slot, slot_on);
       retain(x);
       hiddens.push_back(x);
     } else if (x.ld != 0) {
@@ -429,17 +441,19 @@ void Builder::build() {
     const bool is_last = i == L - 1;
     const int nb = cfg.num_resnet_blocks[l];
     const bool attn = cfg.layer_attns[l] != 0;
+    const bool lin = !attn && u->lin_attn[l] != 0;
     const bool ups = !is_last || cfg.memory_efficient;
     int sc0 = add_skip(dim_out);
-    step(resnet(x, pre + ".0", dim_out, cfg.layer_cross_attns[l] ? &c : nullptr, false,
+    step(resnet(x, pre + ".0", dim_out, cfg.layer_cross_attns[l] || u->lin_cross[l] ? &c : nullptr, false,
                 nb > 0 ? offer_ct(x.B, x.H, x.W, dim_out) : nullptr, nullptr, sc0, skip_scale));
     for (int n = 0; n < nb; ++n) {
       sc0 = add_skip(dim_out);
-      const bool next_is_skip = n + 1 < nb || (!attn && !ups && !is_last);
+      const bool next_is_skip = n + 1 < nb || (!attn && !lin && !ups && !is_last);
       step(resnet(x, pre + ".1." + std::to_string(n), dim_out, nullptr, cfg.use_gca != 0,
                   next_is_skip ? offer_ct(x.B, x.H, x.W, dim_out) : nullptr, nullptr, sc0, skip_scale));
     }
     if (attn) step(transformer(x, pre + ".2", &c));
+    if (lin) step(linear_attn_block(x, pre + ".2", &c));
     if (ups) {
       const T* target = nullptr;
       T fin;

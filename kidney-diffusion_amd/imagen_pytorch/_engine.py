@@ -107,6 +107,11 @@ class kd_edm_schedule_t(C.Structure):
                   "c_skip_hat", "c_out_hat", "c_noise_hat", "c_in_next", "c_skip_next", "c_out_next", "c_noise_next")
     ]
 
+class kd_unet_ext_t(C.Structure):
+    _fields_ = [("self_cond", C.c_int), ("use_linear_attn", C.c_int * KD_MAX_LEVELS),
+                ("use_linear_cross_attn", C.c_int * KD_MAX_LEVELS)]
+
+
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
 SIGNATURES = {
     "kd_last_error": (C.c_char_p, []),
@@ -120,6 +125,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_void_p)]),
     "kd_unet_create_self_cond": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
                                            C.c_int, C.POINTER(C.c_void_p)]),
+    "kd_unet_create_ext": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
+                                     C.POINTER(kd_unet_ext_t), C.POINTER(C.c_void_p)]),
     "kd_unet_weight_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_macs": (C.c_int64, [C.c_void_p]),
     "kd_unet_mfma_macs": (C.c_int64, [C.c_void_p]),
@@ -156,6 +163,12 @@ SIGNATURES = {
     "kd_linear_bf16x3_seg_rows": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "kd_downsample_bf16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "kd_gn_conv3x3_winograd_fused_nhwc": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "kd_linattn_chunk_tokens": (C.c_int, []),
+    "kd_linattn_dwconv_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "kd_linattn_context": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "kd_linattn_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_float, C.c_int, C.c_void_p]),
     "kd_linear_skinny": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "kd_global_context_gate": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 +
                                [C.c_int, C.c_void_p]),

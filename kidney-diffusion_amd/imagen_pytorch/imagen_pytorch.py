@@ -152,6 +152,49 @@ class CrossAttention(_Decl, _QKNorm):
         self.to_out = nn.Sequential(nn.Linear(inner, dim, bias=False), LayerNorm(dim))
 
 
+class LinearCrossAttention(CrossAttention):
+    """The library's linear-attention form of CrossAttention: the same parameters and keys (q_scale / k_scale of the
+    learned-qk-norm fork load with it and are not used by the linear form)."""
+
+
+class ChanLayerNorm(_Decl):  # gain-only, over the channels of an NCHW map
+    def __init__(self, dim):
+        super().__init__()
+        self.g = nn.Parameter(torch.ones(1, dim, 1, 1))
+
+
+class LinearAttention(_Decl):
+    """q / k / v: (Dropout, 1x1 conv, depthwise 3x3 conv), no biases; to_context: LayerNorm + Linear without bias."""
+
+    def __init__(self, dim, *, dim_head, heads, context_dim=None):
+        super().__init__()
+        inner = dim_head * heads
+        self.norm = ChanLayerNorm(dim)
+
+        def proj():
+            return nn.Sequential(_Stateless(), nn.Conv2d(dim, inner, 1, bias=False),
+                                 nn.Conv2d(inner, inner, 3, bias=False, padding=1, groups=inner))
+
+        self.to_q, self.to_k, self.to_v = proj(), proj(), proj()
+        self.to_context = (nn.Sequential(nn.LayerNorm(context_dim), nn.Linear(context_dim, inner * 2, bias=False))
+                           if exists(context_dim) else None)
+        self.to_out = nn.Sequential(nn.Conv2d(inner, dim, 1, bias=False), ChanLayerNorm(dim))
+
+
+def _chan_feed_forward(dim, mult):
+    hidden = int(dim * mult)
+    return nn.Sequential(ChanLayerNorm(dim), nn.Conv2d(dim, hidden, 1, bias=False), _Stateless(), ChanLayerNorm(hidden),
+                         nn.Conv2d(hidden, dim, 1, bias=False))
+
+
+class LinearAttentionTransformerBlock(_Decl):
+    def __init__(self, dim, *, depth, heads, dim_head, ff_mult, context_dim=None):
+        super().__init__()
+        self.layers = nn.ModuleList([
+            nn.ModuleList([LinearAttention(dim, dim_head=dim_head, heads=heads, context_dim=context_dim),
+                           _chan_feed_forward(dim, ff_mult)]) for _ in range(depth)])
+
+
 def _feed_forward(dim, mult):
     hidden = int(dim * mult)
     return nn.Sequential(LayerNorm(dim), nn.Linear(dim, hidden, bias=False), _Stateless(), LayerNorm(hidden),
@@ -225,12 +268,13 @@ class Block(_Decl):
 
 class ResnetBlock(_Decl):
     def __init__(self, dim, dim_out, *, cond_dim=None, time_cond_dim=None, groups=8, use_gca=False, heads=8,
-                 dim_head=64):
+                 dim_head=64, linear_attn=False):
         super().__init__()
         if exists(time_cond_dim):
             self.time_mlp = nn.Sequential(_Stateless(), nn.Linear(time_cond_dim, dim_out * 2))
         if exists(cond_dim):
-            self.cross_attn = CrossAttention(dim_out, context_dim=cond_dim, dim_head=dim_head, heads=heads)
+            klass = LinearCrossAttention if linear_attn else CrossAttention
+            self.cross_attn = klass(dim_out, context_dim=cond_dim, dim_head=dim_head, heads=heads)
         self.block1 = Block(dim, dim_out, groups)
         self.block2 = Block(dim_out, dim_out, groups)
         if use_gca:
@@ -269,8 +313,7 @@ class Unet(nn.Module):
         when the incoming keys contain `q_scale` - so the first real checkpoint decides the variant."""
         super().__init__()
         self._locals = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
-        unsupported = dict(use_linear_attn=use_linear_attn, use_linear_cross_attn=use_linear_cross_attn,
-                           cross_embed_downsample=cross_embed_downsample)
+        unsupported = dict(cross_embed_downsample=cross_embed_downsample)
         bad = [k for k, v in unsupported.items() if (any(v) if isinstance(v, (tuple, list)) else bool(v))]
         required = dict(init_cross_embed=init_cross_embed, scale_skip_connection=scale_skip_connection,
                         final_resnet_block=final_resnet_block, pixel_shuffle_upsample=pixel_shuffle_upsample)
@@ -331,9 +374,14 @@ class Unet(nn.Module):
         groups = cast_tuple(resnet_groups, L)
         attns = cast_tuple(layer_attns, L)
         cross = cast_tuple(layer_cross_attns, L)
+        # use_linear_attn: a LinearAttentionTransformerBlock at the levels without full attention; use_linear_cross_attn:
+        # the level's first ResnetBlocks get cross-attention, in its linear form
+        lin = cast_tuple(use_linear_attn, L)
+        lcross = cast_tuple(use_linear_cross_attn, L)
         assert len(set(groups)) == 1, "per-level resnet_groups are not planned by the engine"
         self._plan = dict(dim=dim, dim_mults=tuple(dim_mults), num_resnet_blocks=nrb, layer_attns=attns,
-                          layer_cross_attns=cross, attn_heads=attn_heads, attn_dim_head=attn_dim_head,
+                          layer_cross_attns=cross, use_linear_attn=lin, use_linear_cross_attn=lcross,
+                          attn_heads=attn_heads, attn_dim_head=attn_dim_head,
                           ff_mult=ff_mult, num_time_tokens=num_time_tokens, sinu_dim=learned_sinu_pos_emb_dim,
                           groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn)
 
@@ -342,7 +390,15 @@ class Unet(nn.Module):
         self.downs = nn.ModuleList([])
         self.ups = nn.ModuleList([])
         skip_dims = []
-        for ind, ((d_in, d_out), n, g, la, lc) in enumerate(zip(in_out, nrb, groups, attns, cross)):
+
+        def attn_block(d, la, ll):   # full attention wins over linear attention
+            if la:
+                return TransformerBlock(d, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak)
+            if ll:
+                return LinearAttentionTransformerBlock(d, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak)
+            return _Stateless()
+
+        for ind, ((d_in, d_out), n, g, la, lc, ll, lx) in enumerate(zip(in_out, nrb, groups, attns, cross, lin, lcross)):
             is_last = ind >= L - 1
             cur = d_in
             pre = None
@@ -356,10 +412,11 @@ class Unet(nn.Module):
                     nn.Conv2d(d_in, d_out, 3, padding=1), nn.Conv2d(d_in, d_out, 1))
             self.downs.append(nn.ModuleList([
                 pre,
-                ResnetBlock(cur, cur, cond_dim=cond_dim if lc else None, time_cond_dim=tcd, groups=g, **ak),
+                ResnetBlock(cur, cur, cond_dim=cond_dim if lc or lx else None, time_cond_dim=tcd, groups=g,
+                            linear_attn=bool(lx), **ak),
                 nn.ModuleList([ResnetBlock(cur, cur, time_cond_dim=tcd, groups=g, use_gca=use_global_context_attn)
                                for _ in range(n)]),
-                TransformerBlock(cur, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak) if la else _Stateless(),
+                attn_block(cur, la, ll),
                 post,
             ]))
         mid = dims[-1]
@@ -372,15 +429,17 @@ class Unet(nn.Module):
             self.mid_attn = TransformerBlock(mid, depth=1, ff_mult=2, **ak) if mid_attn_form == "transformer" \
                 else ResidualAttentionBlock(mid, **ak)
         self.mid_block2 = ResnetBlock(mid, mid, cond_dim=cond_dim, time_cond_dim=tcd, groups=groups[-1], **ak)
-        for ind, ((d_in, d_out), n, g, la, lc) in enumerate(
-                zip(reversed(in_out), reversed(nrb), reversed(groups), reversed(attns), reversed(cross))):
+        for ind, ((d_in, d_out), n, g, la, lc, ll, lx) in enumerate(
+                zip(reversed(in_out), reversed(nrb), reversed(groups), reversed(attns), reversed(cross), reversed(lin),
+                    reversed(lcross))):
             is_last = ind == L - 1
             sd = skip_dims.pop()
             self.ups.append(nn.ModuleList([
-                ResnetBlock(d_out + sd, d_out, cond_dim=cond_dim if lc else None, time_cond_dim=tcd, groups=g, **ak),
+                ResnetBlock(d_out + sd, d_out, cond_dim=cond_dim if lc or lx else None, time_cond_dim=tcd, groups=g,
+                            linear_attn=bool(lx), **ak),
                 nn.ModuleList([ResnetBlock(d_out + sd, d_out, time_cond_dim=tcd, groups=g,
                                            use_gca=use_global_context_attn) for _ in range(n)]),
-                TransformerBlock(d_out, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak) if la else _Stateless(),
+                attn_block(d_out, la, ll),
                 PixelShuffleUpsample(d_out, d_in) if (not is_last or memory_efficient) else _Stateless(),
             ]))
         fin = dim + (dim if init_conv_to_final_conv_residual else 0)
@@ -615,8 +674,12 @@ class Unet(nn.Module):
             handle = C.c_void_p()
             # further plans of this UNet on the same device (other batch / image size) share its packed weights
             share = next((h for k, h in self._engines.items() if k[2] == device.index), None)
-            E.check(lib.kd_unet_create_self_cond(C.byref(cfg), arr, len(names), share, int(self.self_cond),
-                                                 C.byref(handle)))
+            ext = E.kd_unet_ext_t()
+            ext.self_cond = int(self.self_cond)
+            for i in range(L):
+                ext.use_linear_attn[i] = int(bool(p["use_linear_attn"][i]))
+                ext.use_linear_cross_attn[i] = int(bool(p["use_linear_cross_attn"][i]))
+            E.check(lib.kd_unet_create_ext(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(handle)))
             del sd
         self._engines[key] = handle
         self._engines_fingerprint = self._weights_fingerprint()
