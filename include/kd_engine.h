@@ -42,7 +42,8 @@ const char* kd_last_error(void);
  *      change no existing entry: kd_linear_skinny, kd_global_context_gate, kd_gate_add_nhwc (+ _chunks), kd_gn_fold_seg,
  *      kd_wf_ab_scale, kd_gn_conv3x3_winograd4_nhwc (the ResnetBlock pieces the plan joins, for unit tests); kd_unet_create_ext
  *      with its struct kd_unet_ext_t for linear attention, kd_linattn_chunk_tokens, kd_linattn_dwconv_nhwc, kd_linattn_context,
- *      kd_linattn_apply */
+ *      kd_linattn_apply; kd_attention_ex and kd_l2norm_heads (the attention core and the qk-norm with the plan's argument
+ *      forms, for unit tests) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -540,6 +541,19 @@ int kd_layernorm_linear_bf16x3(const float* d_x, const float* d_g, const float* 
  * Hkv in {1,H}; out [B,Nq,H,D].  D must be 64. */
 int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_out,
                  int B, int Nq, int Nk, int H, int Hkv, int D, void* stream);
+/* The same core with every argument the plan's launches pass (engine.hip transformer() / cross_attn(), text_build.inc), a
+ * straight pass-through for unit tests: out[b][i][h 64 + d] (row stride ldo) = softmax_j(scale q[b][i][h] . K[j]) V[j] over the
+ * key list cat(null key, segment 0, segment 1).  q rows of stride ldq; d_null_kv [2][64] = (key, value) shared by all heads, or
+ * NULL; segment s: k / v [B][n_s] rows of stride ld_s holding Hkv heads of 64 (Hkv = 1: one head shared by all H); a segment
+ * with n = 0 may have NULL pointers.  Strides are multiples of 4, pointers 16-byte aligned.  Which of the two kernels runs is
+ * the launch's own choice (matrix cores from Nq >= 128 and 16 blocks of 128 queries).  Synchronises before returning. */
+int kd_attention_ex(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
+                    const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
+                    float scale, void* stream);
+/* The qk-norm of kd_unet_config_t::attn_qk_norm, in place: each of the `heads` 64-wide segments at the start of every row
+ * (stride ld >= heads 64) becomes x / max(||x||, 1e-12) (* d_scale_vec [64], may be NULL); columns past the segments are
+ * not touched.  Synchronises before returning. */
+int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_scale_vec, void* stream);
 /* Per-sample linear-interpolated quantile of |x| over n values (torch.quantile semantics). */
 int kd_quantile_abs(const float* d_x, float* d_out, int B, int64_t n, float q, void* d_workspace,
                     size_t workspace_bytes, void* stream);

@@ -1432,6 +1432,28 @@ int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_
                           (hipStream_t)stream);
 }
 
+// launch_attention with every argument the plan passes it (engine.hip transformer() / cross_attn(), text_build.inc):
+// learned null key / value, two K/V segments with their own row strides, q / out row strides, scale
+int kd_attention_ex(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
+                    const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
+                    float scale, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_q && d_out && B > 0 && H > 0 && n0 >= 0 && n1 >= 0, "kd_attention_ex: null argument or bad sizes");
+  KD_REQUIRE((n0 == 0 || (d_k0 && d_v0)) && (n1 == 0 || (d_k1 && d_v1)), "kd_attention_ex: a segment with keys needs k and v");
+  KD_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_null_kv | (uintptr_t)d_k0 | (uintptr_t)d_v0 | (uintptr_t)d_k1 | (uintptr_t)d_v1 |
+               (uintptr_t)d_out) & 15) == 0, "kd_attention_ex: 16-byte aligned pointers");
+  KVSeg s0{d_k0, d_v0, ld0, n0};
+  KVSeg s1{d_k1, d_v1, ld1, n1};
+  return entry_finish(launch_attention(d_q, ldq, d_null_kv, d_null_kv ? d_null_kv + 64 : nullptr, s0, s1, d_out, ldo, B,
+                                       Nq, H, Hkv, scale, s), s);
+}
+
+int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_scale_vec, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && rows >= 0 && heads > 0 && ld >= heads * 64, "kd_l2norm_heads: null argument or ld < heads * 64");
+  return entry_finish(launch_l2norm_heads(d_x, ld, rows, heads, d_scale_vec, s), s);
+}
+
 size_t kd_quantile_workspace_bytes(int B) { return quantile_ws_bytes(B); }
 int kd_quantile_abs(const float* d_x, float* d_out, int B, int64_t n, float q, void* d_workspace,
                     size_t workspace_bytes, void* stream) {
