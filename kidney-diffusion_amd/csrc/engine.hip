@@ -134,6 +134,119 @@ struct T {  // NHWC tensor in the workspace, or a channel slice of one (a skip t
   bool dense() const { return LD() == C; }
 };
 
+// ------------------------------------------------------------------------------ sampler state (sampler.inc)
+// Device buffers that die with their owner: the sampler's scratch, the temporaries of a test entry point (api.inc)
+struct DevBufs {
+  std::vector<void*> p;
+  ~DevBufs() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <class P>
+  int get(P** out, size_t bytes) {
+    KD_HIP_CHECK(hipMalloc((void**)out, bytes));
+    p.push_back(*out);
+    return 0;
+  }
+};
+
+// A device table keyed on its CONTENT: a sampling call with the schedule of the previous one (every patch of a grid,
+// every k-range of a traced run) uploads nothing.  Changed content goes through a pinned staging buffer with ONE
+// asynchronous copy on the caller's stream, so it is ordered behind the launches already queued there that still read
+// the old content.  A table that grows moves: captured iterations carry its address in their key.
+struct DeviceTable {
+  float* dev = nullptr;
+  float* pinned = nullptr;   // staging for the asynchronous upload
+  size_t cap = 0;            // floats, of both
+  std::vector<float> host;   // what `dev` holds
+  hipEvent_t ev = nullptr;   // recorded behind the last upload from the staging buffer
+  ~DeviceTable() {
+    release();
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  void release() {
+    if (dev) (void)hipFree(dev);
+    if (pinned) (void)hipHostFree(pinned);
+    dev = pinned = nullptr;
+    cap = 0;
+    host.clear();
+  }
+  int upload(std::vector<float>&& h, hipStream_t s) {
+    if (h == host) return 0;
+    // the previous upload may still be reading the staging buffer - on WHICHEVER stream it was issued (the grid
+    // scheduler alternates one plan between the caller's stream and its side stream): wait for its event, not for `s`
+    if (ev) KD_HIP_CHECK(hipEventSynchronize(ev));
+    const size_t bytes = h.size() * sizeof(float);
+    if (cap < h.size()) {
+      KD_HIP_CHECK(hipStreamSynchronize(s));   // replays on `s` may still read the old table
+      release();
+      KD_HIP_CHECK(hipMalloc((void**)&dev, bytes));
+      KD_HIP_CHECK(hipHostMalloc((void**)&pinned, bytes, hipHostMallocDefault));
+      cap = h.size();
+    }
+    memcpy(pinned, h.data(), bytes);
+    KD_HIP_CHECK(hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, s));
+    if (!ev) KD_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    KD_HIP_CHECK(hipEventRecord(ev, s));
+    host = std::move(h);
+    return 0;
+  }
+};
+
+// One captured sampler iteration and what it was captured for (sampler.inc: replay_or_capture)
+struct StepGraph {
+  hipGraphExec_t exec = nullptr;
+  std::vector<uint64_t> key;
+  ~StepGraph() { drop(); }
+  void drop() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    exec = nullptr;
+  }
+};
+
+// The per-schedule conditioning table (sampler.inc: sampler_cond_table) of the plan's cond region
+struct CondTable {
+  char* tab = nullptr;   // [T][cond_bytes]
+  size_t bytes = 0;
+  std::vector<float> sched;   // the schedule tables' content the rows were built for
+  int T = 0;
+  float lowres = 0.f;
+  std::vector<char> row_ok;   // [T]: rows are built on demand, for the steps a call walks
+  float build_ms = -1.f;      // device time and row count of the last build (kd_unet_cond_table_build_ms)
+  int build_rows = 0, build_runs = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last build; read lazily (ev_pending)
+  bool ev_pending = false;
+  int64_t refused_bytes = 0;   // > 0: the last sampling call wanted a table of this size and the cap / allocator refused
+  ~CondTable() {
+    if (tab) (void)hipFree(tab);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+};
+
+struct Sampler {
+  // scratch, allocated on first use at addresses that stay (the captured iterations hold them): UNet output, the
+  // guidance forward's, x0 estimate, per-sample thresholds and times; EDM: x_hat, d and the UNet input of the step
+  float *pred = nullptr, *pred_null = nullptr, *x0 = nullptr, *thresh = nullptr, *time = nullptr;
+  float *xhat = nullptr, *d = nullptr, *net_in = nullptr;
+  float* self_cond = nullptr;   // self_cond plans: the thresholded x0 estimate carried to the next forward [B,3,S,S]
+  int* iter = nullptr;
+  uint64_t* seed = nullptr;   // Philox key, device-resident so the step graph does not depend on it
+  void* qws = nullptr;
+  DevBufs mem;
+  DeviceTable ddpm_tab;   // 9 x T (kd_schedule_t)
+  DeviceTable edm_tab;    // 15 x N (kd_edm_schedule_t), then S_noise
+  hipStream_t cap_stream = nullptr;
+  StepGraph ddpm_graph, edm_graph[2];   // EDM: one per step kind (0: with the Heun correction, 1: without)
+  CondTable cond;
+  void drop_graphs() {   // the conditioning table moved: every captured iteration holds its address
+    ddpm_graph.drop();
+    for (auto& g : edm_graph) g.drop();
+  }
+  ~Sampler() {
+    if (cap_stream) (void)hipStreamDestroy(cap_stream);
+  }
+};
+
 }  // namespace kd
 
 using namespace kd;
@@ -171,82 +284,27 @@ struct kd_unet {
   const float *in_text_embeds = nullptr, *in_text_mask = nullptr;
   int in_text_len = 0, in_text_drop = 0;
   float *out_text_tokens = nullptr, *out_text_hiddens = nullptr;
-  float* s_pred_null = nullptr;  // classifier-free guidance: second forward's output
-  // sampler scratch (allocated on first use)
-  float *s_pred = nullptr, *s_x0 = nullptr, *s_thresh = nullptr, *s_time = nullptr, *s_tables = nullptr;
-  int* s_iter = nullptr;
-  // self_cond plans: the thresholded x0 estimate the sampler carries to the next forward [B,3,S,S], at a fixed address
-  // (the captured step reads and writes it)
-  float* s_sc = nullptr;
-  uint64_t* s_seed = nullptr;  // Philox key, device-resident so the step graph does not depend on it
-  void* s_qws = nullptr;
-  int s_tables_cap = 0;
-  std::vector<float> s_tables_host;  // what s_tables holds (9 x T): an unchanged schedule is not uploaded again
-  float* s_tables_pinned = nullptr;  // staging for the asynchronous upload
-  size_t s_tables_pinned_floats = 0;
-  hipEvent_t s_tables_ev = nullptr;  // recorded behind the last upload from the staging buffer (whatever stream it ran on)
-  // cached graph of one iteration
-  hipGraphExec_t graph_exec = nullptr;
-  hipStream_t cap_stream = nullptr;
-  std::vector<uint64_t> graph_key;
-  // EDM sampler (kd_edm_sample_*): x_hat, d and the UNet input of the step, its per-step tables (16 x N, stride N,
-  // content-keyed like s_tables) and one captured iteration per step kind (0: with the Heun correction, 1: without)
-  float *e_xhat = nullptr, *e_d = nullptr, *e_in = nullptr, *e_tables = nullptr;
-  int e_tables_cap = 0;   // floats
-  std::vector<float> e_tables_host;
-  float* e_tables_pinned = nullptr;
-  hipEvent_t e_tables_ev = nullptr;
-  hipGraphExec_t e_graph[2] = {nullptr, nullptr};
-  std::vector<uint64_t> e_graph_key[2];
-  void drop_graphs() {   // every captured graph: they hold the addresses of the tables / buffers being replaced
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    graph_exec = nullptr;
-    for (auto& g : e_graph) {
-      if (g) (void)hipGraphExecDestroy(g);
-      g = nullptr;
-    }
-  }
+  kd::Sampler smp;   // sampler scratch, schedule tables, captured iterations, conditioning table (sampler.inc)
 
   // ---- step-invariant-per-schedule-index conditioning (time embeddings, FiLM scale / shift, time tokens and their
   // cross-attention K / V): ops flagged op_is_cond write only into the `cond_ws` region (offsets carry COND_FLAG); the
-  // sampler can run them once per schedule step into `cond_tab` and replay a step with one gather instead
+  // sampler can run them once per schedule step into `smp.cond` and replay a step with one gather instead
   static constexpr size_t COND_FLAG = size_t(1) << 62;
   std::vector<char> op_is_cond;
   char* cond_ws = nullptr;
   size_t cond_bytes = 0;
-  char* cond_tab = nullptr;        // [T][cond_bytes]
-  size_t cond_tab_bytes = 0;
-  std::vector<float> cond_tab_sched;   // the schedule (9 x T) the table was built for
-  int cond_tab_T = 0;
-  float cond_tab_lowres = 0.f;
-  bool cond_tab_valid = false;
   // the tensors of the cond region (every one batch-major: the table is then built B schedule steps per run)
   std::vector<kd::CondSeg> cond_segs;
   bool cond_rows_ok = true;
   kd::CondSeg* d_cond_segs = nullptr;
   uint32_t cond_row_total = 0;
-  std::vector<char> cond_tab_row_ok;   // [T]: rows are built on demand, for the steps a call walks
-  float cond_tab_build_ms = -1.f;    // device time and row count of the last build (kd_unet_cond_table_build_ms)
-  int cond_tab_build_rows = 0, cond_tab_build_runs = 0;
-  hipEvent_t cond_ev0 = nullptr, cond_ev1 = nullptr;   // around the last build; read lazily (cond_ev_pending)
-  bool cond_ev_pending = false;
-  int64_t cond_tab_refused_bytes = 0;   // > 0: the last sampling call wanted a table of this size and the cap / allocator refused
   void* x3_ws = nullptr;   // slabs of the bf16x3 GEMMs' left-over tiles (launch_gemm_bf16x3), allocated with the first such layer
 
   float* P(size_t off) const { return (float*)((off & COND_FLAG) ? cond_ws + (off & ~COND_FLAG) : ws + off); }
   ~kd_unet() {
-    drop_graphs();
-    if (cap_stream) (void)hipStreamDestroy(cap_stream);
-    void* frees[] = {ws, s_pred, s_x0, s_thresh, s_time, s_tables, s_iter, s_seed, s_qws, s_pred_null, cond_ws, cond_tab,
-                     d_cond_segs, x3_ws, e_xhat, e_d, e_in, e_tables, s_sc};
-    for (void* p : frees)
+    smp.drop_graphs();   // before the buffers they point into
+    for (void* p : {(void*)ws, (void*)cond_ws, (void*)d_cond_segs, x3_ws})
       if (p) (void)hipFree(p);
-    if (s_tables_pinned) (void)hipHostFree(s_tables_pinned);
-    if (s_tables_ev) (void)hipEventDestroy(s_tables_ev);
-    if (e_tables_pinned) (void)hipHostFree(e_tables_pinned);
-    if (e_tables_ev) (void)hipEventDestroy(e_tables_ev);
-    if (cond_ev0) (void)hipEventDestroy(cond_ev0);
-    if (cond_ev1) (void)hipEventDestroy(cond_ev1);
   }
 };
 
@@ -331,7 +389,7 @@ struct Builder {
   // ---- activations
   // to_cond: the ops being emitted compute conditioning that depends on the inputs log_snr / lowres_log_snr / text only
   // (never on x): they are flagged, and everything they allocate lives in the permanent cond region (bump-allocated,
-  // never reused), so the sampler can snapshot / restore that region per schedule step (kd_unet::cond_tab)
+  // never reused), so the sampler can snapshot / restore that region per schedule step (kd::CondTable)
   bool to_cond = false;
   size_t cond_end = 0;
   size_t cond_alloc(size_t bytes) {
@@ -1683,5 +1741,6 @@ struct Builder {
 #include "unet_build.inc"  // Builder::build(): the walk over the module tree
 #include "linattn_build.inc"  // Builder: LinearAttentionTransformerBlock and LinearCrossAttention
 #include "text_build.inc"  // Builder::build_text(): step-invariant text conditioning
-#include "api.inc"         // sampler loop + extern "C" entry points
+#include "sampler.inc"     // DDPM and EDM sampler loops
+#include "api.inc"         // extern "C" entry points
 

@@ -121,6 +121,43 @@ def test_graph_replay_equals_eager_and_cond_table_on_equals_off(device):
     assert torch.equal(again, base)
 
 
+@pytest.mark.parametrize("sampler", ["ddpm", "edm"])
+def test_schedule_length_changing_on_a_live_plan_equals_a_fresh_plan(device, sampler):
+    """One SR UNet, one plan, sampled with 3, then 5, then 3 steps through two sampler objects that share the UNet: the
+    schedule tables on the device regrow and shrink, the captured iteration and the conditioning table are rebuilt.  Each
+    result must be bit-equal to the same call on a plan made fresh by invalidate_engine(): same kernels, same inputs,
+    same order."""
+    import imagen_pytorch as ip
+
+    pu = H.product_unet_like(H.oracle_unet("small2", lowres_cond=True, seed=5)).to(device)
+
+    def make(steps):
+        if sampler == "ddpm":
+            return ip.Imagen([ip.NullUnet(), pu], image_sizes=(16, 32), timesteps=(steps, steps), pred_objectives=("noise", "v"),
+                             condition_on_text=False).to(device)
+        return ip.ElucidatedImagen([ip.NullUnet(), pu], image_sizes=(16, 32), num_sample_steps=steps, sigma_max=(80, 320),
+                                   condition_on_text=False).to(device)
+
+    ims = {3: make(3), 5: make(5)}   # (made before the first call: .to() drops the plans)
+    g = torch.Generator().manual_seed(14)
+    low = torch.rand(2, 3, 16, 16, generator=g).to(device)
+    cond = torch.rand(2, 3, 32, 32, generator=g).to(device)
+    nf = RS.generator_noise_fn(31)
+
+    def run(steps):
+        return ims[steps].sample(noise_fn=nf, batch_size=2, start_at_unet_number=2, start_image_or_video=low, cond_images=cond,
+                                 use_graph=True, device=device)
+
+    lengths = (3, 5, 3)
+    live = [run(n) for n in lengths]
+    assert len(pu._engines) == 1, "the three calls must share one plan"
+    for i, n in enumerate(lengths):
+        pu.invalidate_engine()
+        fresh = run(n)
+        assert torch.isfinite(fresh).all() and torch.equal(live[i], fresh), (i, n, float((live[i] - fresh).abs().max()))
+    assert not torch.equal(live[0], live[1]), "the schedule length must matter"
+
+
 def test_seeded_sampling_is_reproducible_and_in_range(device):
     _, pim = _base(device, N=3)
     a = pim.sample(batch_size=2, seed=1234, device=device)
