@@ -43,7 +43,8 @@ const char* kd_last_error(void);
  *      kd_wf_ab_scale, kd_gn_conv3x3_winograd4_nhwc (the ResnetBlock pieces the plan joins, for unit tests); kd_unet_create_ext
  *      with its struct kd_unet_ext_t for linear attention, kd_linattn_chunk_tokens, kd_linattn_dwconv_nhwc, kd_linattn_context,
  *      kd_linattn_apply; kd_attention_ex and kd_l2norm_heads (the attention core and the qk-norm with the plan's argument
- *      forms, for unit tests) */
+ *      forms, for unit tests); kd_text_select, kd_add_rows_bcast, kd_mean_rows and kd_copy_rows (the text plan's small kernels,
+ *      for unit tests); kd_unet_text_cond accepts d_text_mask = NULL (text_mask = None) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -197,7 +198,8 @@ int64_t kd_unet_cond_table_refused_bytes(const kd_unet_t* u);
 /* Step-invariant text conditioning (the text branch of Unet.forward; reached by the
  * reference through sample_cond.py:36-48 / sample.py:51-60): text_to_cond, null-embedding select,
  * PerceiverResampler pooling, to_text_non_attn_cond.  Run once per sample call.
- *   d_text_embeds [B,L,text_embed_dim], d_text_mask [B,L] as 0/1 floats, L <= max_text_len;
+ *   d_text_embeds [B,L,text_embed_dim], d_text_mask [B,L] as floats (!= 0 keeps the token), L <= max_text_len;
+ *   d_text_mask = NULL is the library's text_mask = None: all L tokens kept, the rows L .. max_text_len stay the zero padding;
  *   drop = 1 gives the null conditioning (cond_drop_prob = 1, used for classifier-free guidance);
  *   out: d_text_tokens [B,text_tokens,cond_dim], d_text_hiddens [B,time_cond_dim]. */
 int kd_unet_text_cond(kd_unet_t* u, const float* d_text_embeds, const float* d_text_mask, int L, int drop,
@@ -554,6 +556,21 @@ int kd_attention_ex(const float* d_q, int ldq, const float* d_null_kv, const flo
  * (stride ld >= heads 64) becomes x / max(||x||, 1e-12) (* d_scale_vec [64], may be NULL); columns past the segments are
  * not touched.  Synchronises before returning. */
 int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_scale_vec, void* stream);
+/* The small kernels of the text-conditioning plan (text_build.inc) with the plan's argument forms, straight pass-throughs for
+ * unit tests; each synchronises before returning.
+ *   kd_text_select:    out [B][P][C]: row p = tok[b][p] where p < L, mask[b][p] != 0 and !drop, else null_embed[p].  tok [B][L][C]
+ *                      (no rows past L), mask [B][L] floats, null_embed [P][C], 1 <= L <= P.  d_mask == NULL (text_mask = None):
+ *                      every row p < L is kept and the rows p >= L are zero; drop still gives null_embed everywhere.
+ *   kd_add_rows_bcast: y[b][r][:] = x[b][r][:] + add[r][:], x / y [B][R][C], add [R][C].
+ *   kd_mean_rows:      y[b][:] = mean over r of x[b][r][:], x [B][R][C], y [B][C]; summed in row order in fp32.
+ *   kd_copy_rows:      dst[b dst_bstride + r ld_dst + c] = src[b src_bstride + r ld_src + c] for b < B, r < rows, c < C
+ *                      (strides in floats; src_bstride = 0 broadcasts one block of rows to every batch element). */
+int kd_text_select(const float* d_tok, const float* d_mask, const float* d_null_embed, float* d_out, int B, int L, int P, int C,
+                   int drop, void* stream);
+int kd_add_rows_bcast(const float* d_x, const float* d_add, float* d_y, int B, int R, int C, void* stream);
+int kd_mean_rows(const float* d_x, float* d_y, int B, int R, int C, void* stream);
+int kd_copy_rows(const float* d_src, int64_t src_bstride, int ld_src, float* d_dst, int64_t dst_bstride, int ld_dst, int rows,
+                 int C, int B, void* stream);
 /* Per-sample linear-interpolated quantile of |x| over n values (torch.quantile semantics). */
 int kd_quantile_abs(const float* d_x, float* d_out, int B, int64_t n, float q, void* d_workspace,
                     size_t workspace_bytes, void* stream);

@@ -839,6 +839,36 @@ int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_
   return entry_finish(launch_l2norm_heads(d_x, ld, rows, heads, d_scale_vec, s), s);
 }
 
+// ---- the small kernels of the text-conditioning plan (text_build.inc), one pass-through each with the plan's argument forms
+int kd_text_select(const float* d_tok, const float* d_mask, const float* d_null_embed, float* d_out, int B, int L, int P, int C,
+                   int drop, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_tok && d_null_embed && d_out, "kd_text_select: null argument");
+  KD_REQUIRE(B > 0 && C > 0 && L >= 1 && L <= P, "kd_text_select needs B, C > 0 and 1 <= L <= P");
+  return entry_finish(launch_text_select(d_tok, d_mask, d_null_embed, d_out, B, L, P, C, drop != 0, s), s);
+}
+
+int kd_add_rows_bcast(const float* d_x, const float* d_add, float* d_y, int B, int R, int C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && d_add && d_y && B > 0 && R > 0 && C > 0, "kd_add_rows_bcast: null argument or empty shape");
+  return entry_finish(launch_add_rows_bcast(d_x, d_add, d_y, B, R, C, s), s);
+}
+
+int kd_mean_rows(const float* d_x, float* d_y, int B, int R, int C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_x && d_y && B > 0 && R > 0 && C > 0, "kd_mean_rows: null argument or empty shape");
+  KD_REQUIRE((int64_t)B * C < 0x7fffffff, "kd_mean_rows: B * C must stay below 2^31 (one thread per output, int index)");
+  return entry_finish(launch_mean_rows(d_x, d_y, B, R, C, s), s);
+}
+
+int kd_copy_rows(const float* d_src, int64_t src_bstride, int ld_src, float* d_dst, int64_t dst_bstride, int ld_dst, int rows,
+                 int C, int B, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_src && d_dst && rows >= 0 && C >= 0 && B >= 0, "kd_copy_rows: null argument or negative size");
+  KD_REQUIRE(ld_src >= C && ld_dst >= C && src_bstride >= 0 && dst_bstride >= 0, "kd_copy_rows needs row strides >= C, batch strides >= 0");
+  return entry_finish(launch_copy_rows(d_src, src_bstride, ld_src, d_dst, dst_bstride, ld_dst, rows, C, B, s), s);
+}
+
 size_t kd_quantile_workspace_bytes(int B) { return quantile_ws_bytes(B); }
 int kd_quantile_abs(const float* d_x, float* d_out, int B, int64_t n, float q, void* d_workspace,
                     size_t workspace_bytes, void* stream) {

@@ -232,9 +232,6 @@ int launch_layernorm(const float* x, int ldx, const float* g, const float* beta,
 // dst[row][0..C) = src[row][0..C) * scale, row strides ld_src / ld_dst (dst may be src)
 int launch_copy_scale_rows(const float* src, int ld_src, float* dst, int ld_dst, int C, float scale, int64_t rows,
                            hipStream_t s);
-// y[row] = [a[row] | b[row] * scale_b]; a == nullptr: only the b half is written (a's producer wrote in place)
-int launch_concat2(const float* a, int Ca, const float* b, int Cb, float scale_b, float* y, int64_t rows,
-                   hipStream_t s);
 // y = a*gate[b][c] + r   (NHWC; a dense, r / y with row strides ldr / ldy); seg: optional segment partials of y,
 // [B][C/16][gate_add_chunks(B, HW)][2] doubles (SegSrc below)
 int launch_gate_add(const float* a, const float* gate, const float* r, int ldr, float* y, int ldy, double* seg, int B,

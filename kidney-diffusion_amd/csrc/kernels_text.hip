@@ -10,6 +10,8 @@ static inline int grid_for(int64_t n) {
 }
 
 // out[b][p][:] = (p < L && mask[b][p] != 0 && !drop) ? tok[b][p][:] : null_embed[p][:]      p < P (= max_text_len)
+// mask == nullptr is the library's text_mask = None: every token p < L is kept and the rows p >= L keep the zeros the
+// library pads the tokens with (no mask, nothing to select against); drop still gives null_embed everywhere
 __global__ void text_select_kernel(const float* __restrict__ tok, const float* __restrict__ mask,
                                    const float* __restrict__ null_embed, float* __restrict__ out, int L, int P, int C,
                                    int drop, int64_t total) {
@@ -19,8 +21,9 @@ __global__ void text_select_kernel(const float* __restrict__ tok, const float* _
     int64_t t = idx / C;
     int p = (int)(t % P);
     int64_t b = t / P;
-    bool keep = !drop && p < L && mask[b * L + p] != 0.f;
-    out[idx] = keep ? tok[(b * L + p) * C + c] : null_embed[(int64_t)p * C + c];
+    bool keep = !drop && p < L && (!mask || mask[b * L + p] != 0.f);
+    bool zero_pad = !drop && !mask && p >= L;
+    out[idx] = keep ? tok[(b * L + p) * C + c] : zero_pad ? 0.f : null_embed[(int64_t)p * C + c];
   }
 }
 int launch_text_select(const float* tok, const float* mask, const float* null_embed, float* out, int B, int L, int P,

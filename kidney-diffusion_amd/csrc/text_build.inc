@@ -3,6 +3,7 @@
 // reference reaches it through sample_cond.py:36-48 / sample.py:51-60 with the seg-cond UNet of
 // train.py:30-39 (text_embed_dim 3, one "token" [0.0, 0.5, 0.2], cond_dim 512).
 //   tokens  = where(mask & keep, text_to_cond(text_embeds) padded to max_text_len, null_text_embed)
+//             (no mask: the padded tokens as they are, where(keep, ., null_text_embed))
 //   tokens  = PerceiverResampler(tokens)            (4 mean-pooled + 32 learned latents, depth 2)
 //   hiddens = where(keep, to_text_non_attn_cond(mean(tokens)), null_text_hidden)
 namespace kd {
@@ -30,8 +31,8 @@ void Builder::build_text() {
     int Bx = B;
     emit([=](hipStream_t s) {
       const int L = uu->in_text_len;
-      if (L < 1 || L > P || !uu->in_text_embeds || !uu->in_text_mask) {
-        set_error("text conditioning: text_embeds [B,L<=max_text_len,text_embed_dim] and mask are required");
+      if (L < 1 || L > P || !uu->in_text_embeds) {   // (in_text_mask == nullptr: the library's text_mask = None)
+        set_error("text conditioning: text_embeds [B,L<=max_text_len,text_embed_dim] are required");
         return 1;
       }
       if (launch_linear_skinny(uu->in_text_embeds, ted, w, bias, uu->P(to), cd, Bx * L, ted, cd, ACT_NONE, ACT_NONE, s))

@@ -723,8 +723,10 @@ class Unet(nn.Module):
         f32 = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
         text_embeds = f32(text_embeds)[:, : self.max_text_len].contiguous()
         b, L, _ = text_embeds.shape
-        mask = torch.ones(b, L, device=device) if text_mask is None else f32(text_mask)[:, : self.max_text_len]
-        mask = mask.contiguous()  # named tensors: they must outlive the asynchronous launches below
+        # text_mask = None: no mask reaches the engine, which then keeps the library's zero padding of the rows L .. max_text_len
+        # (a mask of ones would select null_text_embed there)
+        mask = None if text_mask is None else f32(text_mask)[:, : self.max_text_len].contiguous()
+        # named tensors: they must outlive the asynchronous launches below
         tok = torch.empty(b, self.n_text_tokens, self.cond_dim, device=device)
         hid = torch.empty(b, self.time_cond_dim, device=device)
         E.check(E.load().kd_unet_text_cond(handle, E.ptr(text_embeds), E.ptr(mask), L, int(bool(drop)), E.ptr(tok),

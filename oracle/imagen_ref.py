@@ -192,6 +192,12 @@ class _QKNorm:
         return q * self.q_scale, k * self.k_scale, 8.0
 
 
+def _softmax_dtype(sim):
+    """The library's `softmax(dtype=torch.float32)`: half-precision logits are raised to fp32.  A `.double()` copy of a
+    module (the tests' fp64 reference) keeps its fp64 - for fp32 logits this is the library's call unchanged."""
+    return torch.promote_types(sim.dtype, torch.float32)
+
+
 class Attention(nn.Module, _QKNorm):
     """Multi-query self attention (one shared k/v head) with learned null k/v and
     optional context k/v."""
@@ -228,7 +234,7 @@ class Attention(nn.Module, _QKNorm):
             v = torch.cat((cv, v), dim=-2)
         q, k, sim_scale = self.similarity_inputs(q, k)
         sim = torch.einsum("bhid,bjd->bhij", q, k) * sim_scale
-        attn = sim.softmax(dim=-1, dtype=torch.float32)
+        attn = sim.softmax(dim=-1, dtype=_softmax_dtype(sim))
         out = torch.einsum("bhij,bjd->bhid", attn, v)
         out = out.permute(0, 2, 1, 3).reshape(b, n, -1)
         return self.to_out(out)
@@ -262,7 +268,7 @@ class CrossAttention(nn.Module, _QKNorm):
         v = torch.cat((nv.expand(b, h, 1, -1), v), dim=-2)
         q, k, sim_scale = self.similarity_inputs(q, k)
         sim = torch.einsum("bhid,bhjd->bhij", q, k) * sim_scale
-        attn = sim.softmax(dim=-1, dtype=torch.float32)
+        attn = sim.softmax(dim=-1, dtype=_softmax_dtype(sim))
         out = torch.einsum("bhij,bhjd->bhid", attn, v)
         out = out.permute(0, 2, 1, 3).reshape(b, n, -1)
         return self.to_out(out)
@@ -346,7 +352,7 @@ class PerceiverAttention(nn.Module, _QKNorm):
         q, k, v = split(q), split(k), split(v)
         q, k, sim_scale = self.similarity_inputs(q, k)
         sim = torch.einsum("bhid,bhjd->bhij", q, k) * sim_scale
-        attn = sim.softmax(dim=-1, dtype=torch.float32)
+        attn = sim.softmax(dim=-1, dtype=_softmax_dtype(sim))
         out = torch.einsum("bhij,bhjd->bhid", attn, v)
         out = out.permute(0, 2, 1, 3).reshape(b, q.shape[2], -1)
         return self.to_out(out)

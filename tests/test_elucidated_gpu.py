@@ -74,13 +74,19 @@ SEG_KW = dict(dim=32, dim_mults=(1, 2, 3, 4), cond_dim=64, text_embed_dim=3, num
               cond_images_channels=4)   # train.py:30-39 at reduced dim
 
 
-@pytest.mark.parametrize("cond_scale", [1.0, 3.0])
-def test_text_conditioned_sampling_with_guidance_matches_the_restatement(device, cond_scale):
+@pytest.mark.parametrize("cond_scale,tokens", [pytest.param(1.0, 1, id="1.0"), pytest.param(3.0, 1, id="3.0"),
+                                               pytest.param(2.5, 3, id="2.5-three-tokens")])
+def test_text_conditioned_sampling_with_guidance_matches_the_restatement(device, cond_scale, tokens):
+    """tokens = 3: three embedding rows per sample, the middle one all zero (a false entry in sample()'s default mask): the
+    conditioning table and the replayed graphs carry K / V of more than one text token."""
     ou = H.randomize_(R.Unet(**SEG_KW, cond_on_text=True), 17)
     oim, pim = _pair(device, [ou], (16,), text_embed_dim=3, num_sample_steps=3)
     B = 2
     g = torch.Generator().manual_seed(3)
     text = torch.tensor([0.0, 0.5, 0.2]).reshape(1, 1, 3).repeat_interleave(B, dim=0)
+    if tokens == 3:
+        text = torch.cat((text, torch.zeros(B, 1, 3), torch.tensor([[[0.3, -0.2, 1.0]], [[-0.6, 0.1, 0.4]]])), dim=1)
+        assert torch.any(text != 0.0, dim=-1).tolist() == [[True, False, True]] * B
     labels = torch.nn.functional.one_hot(torch.randint(0, 4, (B, 16, 16), generator=g), 4).permute(0, 3, 1, 2).float()
     nf = RS.generator_noise_fn(5)
     ref = oim.sample(noise_fn=nf, text_embeds=text, cond_images=labels, cond_scale=cond_scale)

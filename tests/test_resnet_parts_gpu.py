@@ -68,6 +68,12 @@ SKINNY = [
     pytest.param(16, 1024, 512, 0, 0, 0, 0, 1, id="c3-gca-fc1"),
     pytest.param(16, 512, 1024, 0, 0, 0, 0, 3, id="c3-gca-fc2"),
     pytest.param(16, 1024, "c3", 0, 0, 0, 1, 0, id="c3-stacked-time-mlps"),
+    # text_to_cond (text_build.inc), the one launch whose row count grows with the input: M = B L tokens, K = text_embed_dim,
+    # N = cond_dim.  K = 3 runs on the VALU kernel, K = 16 and 768 on the matrix cores with 8 and 16 row tiles
+    pytest.param(231, 3, 64, 0, 0, 0, 0, 0, id="text-to-cond-M231-K3"),
+    pytest.param(512, 3, 512, 0, 0, 0, 0, 0, id="text-to-cond-M512-K3"),
+    pytest.param(231, 768, 64, 0, 0, 0, 0, 0, id="text-to-cond-M231-K768"),
+    pytest.param(512, 16, 512, 0, 0, 0, 0, 0, id="text-to-cond-M512-K16"),
 ]
 
 

@@ -487,11 +487,11 @@ SEG_KW = dict(dim=32, dim_mults=(1, 2, 3, 4), cond_dim=64, text_embed_dim=3, num
               cond_images_channels=4)  # train.py:30-39 at reduced dim
 
 
-def _seg_pair(device, seed=17, T=4):
+def _seg_pair(device, seed=17, T=4, **unet_kw):
     import imagen_pytorch as ip
     from oracle import imagen_ref as R
 
-    ou = H.randomize_(R.Unet(**SEG_KW, cond_on_text=True), seed)
+    ou = H.randomize_(R.Unet(**{**SEG_KW, **unet_kw}, cond_on_text=True), seed)
     oim = RS.Imagen([ou], image_sizes=(16,), timesteps=(T,), pred_objectives=("noise",), text_embed_dim=3)
     pim = ip.Imagen([ip.Unet(**oim.unets[0]._locals)], image_sizes=(16,), timesteps=(T,), pred_objectives=("noise",),
                     text_embed_dim=3)
@@ -517,15 +517,31 @@ def test_text_conditioned_unet_forward_matches_oracle(device):
             ref = ou(x, t, text_embeds=text, text_mask=mask, cond_images=labels, cond_drop_prob=drop)
         got = pu(dv(x), dv(t), text_embeds=dv(text), text_mask=dv(mask), cond_images=dv(labels), cond_drop_prob=drop)
         assert H.rel_l2(got, ref) < FWD_REL_L2, (drop, H.rel_l2(got, ref))
+    # three tokens of max_text_len 8 with the ragged mask [3, 1, 0] (the last sample keeps nothing), and no mask at all
+    oim, pim = _seg_pair(device, max_text_len=8)
+    ou, pu = oim.unets[0], pim.unets[0]
+    text = torch.randn(B, 3, 3, generator=g)
+    ragged = torch.tensor([[True, True, True], [True, False, False], [False, False, False]])
+    for mask, drop in ((ragged, 0.0), (ragged, 1.0), (None, 0.0)):
+        with torch.no_grad():
+            ref = ou(x, t, text_embeds=text, text_mask=mask, cond_images=labels, cond_drop_prob=drop)
+        got = pu(dv(x), dv(t), text_embeds=dv(text), text_mask=None if mask is None else dv(mask), cond_images=dv(labels),
+                 cond_drop_prob=drop)
+        assert H.rel_l2(got, ref) < FWD_REL_L2, (mask is None, drop, H.rel_l2(got, ref))
 
 
-@pytest.mark.parametrize("cond_scale", [1.0, 2.5])
-def test_text_conditioned_sampling_with_guidance_matches_oracle(device, cond_scale):
-    """BASELINE config 2 shape (seg-cond base UNet) at reduced dim/T; cond_scale as sample.py:55-59."""
+@pytest.mark.parametrize("cond_scale,tokens", [pytest.param(1.0, 1, id="1.0"), pytest.param(2.5, 1, id="2.5"),
+                                               pytest.param(2.5, 3, id="2.5-three-tokens")])
+def test_text_conditioned_sampling_with_guidance_matches_oracle(device, cond_scale, tokens):
+    """BASELINE config 2 shape (seg-cond base UNet) at reduced dim/T; cond_scale as sample.py:55-59.  tokens = 3: three
+    embedding rows per sample, one of them all zero, so that sample()'s default mask any(text != 0) has a false entry."""
     oim, pim = _seg_pair(device, T=4)
     B = 2
     g = torch.Generator().manual_seed(3)
     text = torch.tensor([0.0, 0.5, 0.2]).reshape(1, 1, 3).repeat_interleave(B, dim=0)
+    if tokens == 3:
+        text = torch.cat((text, torch.zeros(B, 1, 3), torch.tensor([[[0.3, -0.2, 1.0]], [[-0.6, 0.1, 0.4]]])), dim=1)
+        assert torch.any(text != 0.0, dim=-1).tolist() == [[True, False, True]] * B
     labels = torch.nn.functional.one_hot(torch.randint(0, 4, (B, 16, 16), generator=g), 4).permute(0, 3, 1, 2).float()
     nf = RS.generator_noise_fn(5)
     ref = oim.sample(noise_fn=nf, text_embeds=text, cond_images=labels, cond_scale=cond_scale)
