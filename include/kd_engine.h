@@ -64,7 +64,7 @@ typedef struct kd_unet_config {
   int layer_attns[KD_MAX_LEVELS];
   int layer_cross_attns[KD_MAX_LEVELS];
   int cond_dim;               /* already defaulted to dim by the host */
-  int channels;               /* 3 */
+  int channels;               /* image channels of x, self_cond, lowres and the output: 1 .. 4 (RGB: 3) */
   int cond_images_channels;   /* 0 / 3 / 4 / 6 */
   int lowres_cond;            /* set by Imagen for unets after the first */
   int memory_efficient;
@@ -519,6 +519,19 @@ int kd_init_conv_nchw(const float* d_x, const float* d_w3, const float* d_w7, co
 int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
                              const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
                              int S, int n3, int n7, int n15, int iters, float* ms, void* stream);
+/* The same for images of `channels` = 1 .. 4 planes (kd_init_conv_planes_nchw == this with channels = 3): d_x and
+ * d_self_cond are [B][channels][S][S], the per-step planes input channels c0 .. c0 + channels - 1 (x) and, with
+ * d_self_cond != NULL, the `channels` after them.  Fails where the kernel's 160 KB of LDS do not hold the shape (8 planes
+ * at n3 = 64: the plan runs its generic three-conv path there). */
+int kd_init_conv_planes_c_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
+                               const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
+                               int S, int n3, int n7, int n15, int iters, float* ms, int channels, void* stream);
+/* The UNet's final 3x3 conv to the image's `channels` = 1 .. 4 planes through the plan's launches (kernels_final.hip):
+ * out NCHW [B][channels][H][W] = conv3x3(cat(feat, lowres)) + bias with d_feat NHWC [B][H][W][Cfeat], d_w_oihw
+ * [channels][Cfeat + Cl][3][3] (Cl = channels when d_lowres is given, else 0), d_lowres NCHW [B][channels][H][W] or
+ * NULL.  Needs Cfeat % 4 == 0. */
+int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                       int B, int H, int W, int Cfeat, int channels, void* stream);
 /* GroupNorm(G) + optional FiLM (scale+1, shift: [B,2C] = [scale | shift]) + SiLU, NHWC. */
 int kd_groupnorm_silu_nhwc(const float* d_x, const float* d_gamma, const float* d_beta,
                            const float* d_scale_shift, float* d_y, int B, int HW, int C, int G,

@@ -256,7 +256,7 @@ int kd_sample_loop(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_arg
 }
 
 // What the last executed denoising iteration left in the sampler's scratch: which = 0 the UNet output (eps-hat /
-// v-hat, after guidance) [B,3,S,S]; 1 the x0 estimate BEFORE the threshold clamp [B,3,S,S]; 2 the per-sample
+// v-hat, after guidance) [B,C,S,S]; 1 the x0 estimate BEFORE the threshold clamp [B,C,S,S]; 2 the per-sample
 // dynamic thresholds max(1, quantile) [B].  Stream-ordered device-to-device copy (parity checks: bench.py, tests).
 int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream) {
   if (!u || !d_out) {
@@ -272,12 +272,12 @@ int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream) {
   const int B = u->cfg.batch, S = u->cfg.image_size;
   const float* src = which == 0 ? m.pred : which == 1 ? m.x0 : which == 2 ? m.thresh : which == 3 ? m.xhat
                    : which == 4 ? m.d : m.self_cond;
-  const size_t bytes = (which == 2 ? (size_t)B : (size_t)B * 3 * S * S) * sizeof(float);
+  const size_t bytes = (which == 2 ? (size_t)B : (size_t)B * u->cfg.channels * S * S) * sizeof(float);
   KD_HIP_CHECK(hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 
-// Seeds the self-conditioning estimate a self_cond plan carries (d_x_start [B,3,S,S], NULL = zeros), so that
+// Seeds the self-conditioning estimate a self_cond plan carries (d_x_start [B,C,S,S], NULL = zeros), so that
 // kd_sample_steps / kd_edm_sample_steps with k_begin > 0 continue from a chosen state.  Stream-ordered.
 int kd_sample_set_self_cond(kd_unet_t* u, const float* d_x_start, void* stream) {
   if (!u) {
@@ -299,7 +299,7 @@ int kd_sample_finalize(kd_unet_t* u, const kd_sample_args_t* args, float* d_img,
     set_error("kd_sample_finalize: null argument");
     return 1;
   }
-  return launch_finalize(d_img, args->d_inpaint_images, args->d_inpaint_masks, u->cfg.batch, 3,
+  return launch_finalize(d_img, args->d_inpaint_images, args->d_inpaint_masks, u->cfg.batch, u->cfg.channels,
                          (int64_t)u->cfg.image_size * u->cfg.image_size, (hipStream_t)stream);
 }
 
@@ -729,9 +729,18 @@ int kd_init_conv_nchw(const float* d_x, const float* d_w3, const float* d_w7, co
 int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
                              const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
                              int S, int n3, int n7, int n15, int iters, float* ms, void* stream) {
+  return kd_init_conv_planes_c_nchw(d_x, d_self_cond, d_w3, d_w7, d_w15, Itot, c0, d_bias, d_res, d_y, B, S, n3, n7, n15, iters,
+                                    ms, 3, stream);
+}
+
+int kd_init_conv_planes_c_nchw(const float* d_x, const float* d_self_cond, const float* d_w3, const float* d_w7,
+                               const float* d_w15, int Itot, int c0, const float* d_bias, const float* d_res, float* d_y, int B,
+                               int S, int n3, int n7, int n15, int iters, float* ms, int channels, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int np = d_self_cond ? 6 : 3;
+  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_init_conv_planes_c_nchw: 1 to 4 image channels");
+  const int np = d_self_cond ? 2 * channels : channels;
   KD_REQUIRE(d_x && d_w3 && d_w7 && d_w15 && d_y && iters >= 1, "kd_init_conv_planes_nchw: null argument or iters < 1");
+  KD_REQUIRE(B >= 1 && S >= 1, "kd_init_conv_planes_nchw: empty shape");
   KD_REQUIRE(c0 >= 0 && c0 + np <= Itot, "kd_init_conv_planes_nchw: input channels c0 .. c0 + planes - 1 out of range");
   KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15, np), "init conv kernel: S % 32 == 0 and the weights must fit LDS");
   EntryBufs bufs;
@@ -744,7 +753,7 @@ int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const f
     if (rc) set_error("kd_init_conv_planes_nchw: event setup failed");
   }
   for (int i = 0; i < iters && !rc; ++i)
-    rc = launch_init_conv(d_x, d_self_cond, np, wp, d_bias, d_res, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, s);
+    rc = launch_init_conv(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, s);
   if (!rc && ms && hipEventRecord(e1, s) != hipSuccess) {
     set_error("kd_init_conv_planes_nchw: event record failed");
     rc = 1;
@@ -760,6 +769,35 @@ int kd_init_conv_planes_nchw(const float* d_x, const float* d_self_cond, const f
   if (rc) return rc;
   KD_HIP_CHECK(e);
   return 0;
+}
+
+// The final 3x3 conv to the image's channels as the plan runs it (unet_build.inc tail, kernels_final.hip): weight pack,
+// the 1x1 GEMM to the (output, tap) columns, the low-res planes' step-invariant share when d_lowres is given, the gather
+int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                       int B, int H, int W, int Cfeat, int channels, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_feat && d_w_oihw && d_bias && d_out, "kd_final_conv_nchw: null argument");
+  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_final_conv_nchw: 1 to 4 image channels");
+  KD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cfeat >= 4 && Cfeat % 4 == 0 && (int64_t)B * H * W < 0x7fffffff / 48,
+             "kd_final_conv_nchw needs a non-empty map below 2^31 / 48 pixels and Cfeat % 4 == 0");
+  const int Ctot = Cfeat + (d_lowres ? channels : 0), nf = final_gemm_cols(channels);
+  EntryBufs bufs;
+  float *wp = nullptr, *pm = nullptr, *stat = nullptr;
+  if (bufs.get(&wp, (size_t)nf * Cfeat * sizeof(float)) || bufs.get(&pm, (size_t)B * H * W * nf * sizeof(float))) return 1;
+  if (d_lowres && bufs.get(&stat, (size_t)B * channels * H * W * sizeof(float))) return 1;
+  int rc = launch_pack_final(d_w_oihw, wp, Ctot, Cfeat, channels, s);
+  if (!rc && d_lowres) rc = launch_final_static(d_lowres, d_w_oihw, d_bias, stat, Ctot, Cfeat, channels, B, H, W, s);
+  if (!rc) {
+    ConvParams p{};
+    p.x = d_feat; p.w = wp; p.y = pm;
+    p.B = B; p.Hi = H; p.Wi = W; p.Cin = Cfeat; p.ldx = Cfeat;
+    p.Ho = H; p.Wo = W; p.Cout = nf;
+    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+    p.out_mode = OUT_NHWC; p.ldy = nf;
+    rc = launch_conv_igemm(p, s);
+  }
+  if (!rc) rc = launch_final_gather(pm, stat, d_bias, d_out, channels, B, H, W, s);
+  return entry_finish(rc, s);
 }
 
 int kd_groupnorm_silu_nhwc(const float* d_x, const float* d_gamma, const float* d_beta, const float* d_scale_shift,

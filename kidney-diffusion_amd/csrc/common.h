@@ -253,8 +253,8 @@ int launch_gn_fold_seg(SegSrc s0, SegSrc s1, const float* gamma, const float* be
                        float* ab, float* stats, int B, int C, int G, double count, float eps, hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);
 int launch_act(const float* a, float* y, int64_t n, int act, hipStream_t s);
-// init image assembly: NCHW planes -> NHWC [B][H][W][Cpad] with channel order cond | x | lowres, zero pad
-int launch_pack_init(const float* cond, int Cc, const float* x, const float* lowres, int Cl, float* y, int Cpad,
+// init image assembly: NCHW planes -> NHWC [B][H][W][Cpad] with channel order cond | x (Cx planes) | lowres, zero pad
+int launch_pack_init(const float* cond, int Cc, const float* x, int Cx, const float* lowres, int Cl, float* y, int Cpad,
                      int B, int HW, hipStream_t s);
 // y[b][r][:] rows copy helper for building key/value buffers: dst[b][row_off + r][c] = src[b][r][c]
 int launch_copy_rows(const float* src, int64_t src_bstride, int ld_src, float* dst, int64_t dst_bstride,
@@ -292,16 +292,16 @@ int launch_gca_gate(const float* x, const float* wk, const float* bk, float* scr
 // time embedding: out[b][0]=t, [1..h]=sin(t*w*2pi), [h+1..2h]=cos
 int launch_sinu_emb(const float* t, const float* w, float* out, int B, int half, hipStream_t s);
 
-// ---- the init cross-embed convs over the per-step planes in one kernel (kernels_init.hip): np = 3 (x) or 6 (x | the
-// self-conditioning image)
+// ---- the init cross-embed convs over the per-step planes in one kernel (kernels_init.hip): np = cx (x's channels:
+// 1 .. 4) or 2 cx (x | the self-conditioning image); false where the kernel's LDS does not hold the shape
 bool init_conv_fused_ok(int S, int n3, int n7, int n15, int np);
 size_t init_conv_weight_floats(int n3, int n7, int n15, int np);
 // w3 / w7 / w15: OIHW weights over Itot input channels, of which c0 .. c0 + np - 1 are the per-step planes
 int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, float* out, int n3, int n7, int n15, int Itot,
                           int c0, int np, hipStream_t s);
-// y[b][py][px][0 .. n3+n7+n15) (row stride ldy) = cat(conv3, conv7, conv15)(x | sc) + (bias | res); sc (np = 6 only,
-// nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
-int launch_init_conv(const float* x_nchw, const float* sc_nchw, int np, const float* wp, const float* bias, const float* res,
+// y[b][py][px][0 .. n3+n7+n15) (row stride ldy) = cat(conv3, conv7, conv15)(x | sc) + (bias | res); x, sc: cx planes
+// each; sc (np = 2 cx only, nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
+int launch_init_conv(const float* x_nchw, const float* sc_nchw, int cx, int np, const float* wp, const float* bias, const float* res,
                      float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
 
 // ---- linear attention, dim_head = 64 (kernels_linattn.hip).  q | k | v are column slices of one [B][H][W][3 inner] map
@@ -325,11 +325,12 @@ int launch_linattn_context(const float* k, const float* v, int ld, const float* 
 int launch_linattn_apply(const float* q, int ldq, const float* ctx, float* out, int ldo, int B, int N, int heads,
                          float scale, int silu, hipStream_t s);
 
-// ---- final conv to 3 channels (kernels_final.hip)
-int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, hipStream_t s);
+// ---- final conv to the image's `ch` = 1 .. 4 channels (kernels_final.hip)
+int final_gemm_cols(int ch);   // width of P: the 9 ch (output, tap) columns padded for the 1x1 GEMM (32; 48 at ch = 4)
+int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, hipStream_t s);
 int launch_final_static(const float* lowres, const float* w_oihw, const float* bias, float* stat, int Ctot, int c0,
-                        int B, int H, int W, hipStream_t s);
-int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int B, int H, int W,
+                        int ch, int B, int H, int W, hipStream_t s);
+int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int ch, int B, int H, int W,
                         hipStream_t s);
 
 // ---- text conditioning helpers (kernels_text.hip)

@@ -24,6 +24,16 @@
 // the k = 3 / 7 weights stay resident and the k = 15 weights STREAM through a two-slot LDS ring, one kernel row
 // (32 rows x 90 values, 11.4 KiB) per slot: all eight waves run the k = 15 conv in lockstep, one barrier per kernel
 // row, the next row's weights loaded into registers under the current row's MFMAs.
+//
+// Images of C = 1, 2 or 4 channels (Unet(channels=C)) give NP = C planes per step, 2 C with self-conditioning: the
+// kernel is built for NP = 1, 2, 3, 4, 6, 8.  Resident weights or the ring is decided from the LDS bytes (ic_ring): every
+// weight group is padded to at least 32 rows, so the resident form fits 160 KiB for NP <= 3 and for no NP >= 4 (NP = 4,
+// 32 | 32 | 32 rows: 190 KiB; dim 128: 194 KiB resident, 97 KiB as a ring), and the ring form fits for all but NP = 8 at
+// dim 128 (161.3 KiB: init_conv_fused_ok refuses it and the plan takes the generic three-conv path).  The pixel stride in
+// the patch stays NP floats, so that the K run of a kernel row stays contiguous: an odd NP reads the A operand free of
+// bank conflicts (ds_read_b32: 32 banks per 32-lane half), NP = 2 | 6 two-way, NP = 4 four-way, NP = 8 eight-way.
+// Padding the stride to NP + 1 would buy the conflicts off with (NP + 1) / NP times the MFMAs (zero columns in every
+// run); the cost of the conflicts at even NP is unmeasured.
 #include "common.h"
 #include "epilogue.h"
 
@@ -42,32 +52,58 @@ __host__ __device__ constexpr int ic_patch(int np) { return IC_PH * IC_PW * np +
 // K run of one kernel row ((k | NP) values, padded to even) and the odd row stride of a resident weight group
 __host__ __device__ constexpr int ic_run(int k, int np) { return (k * np + 1) / 2 * 2; }
 __host__ __device__ constexpr int ic_ldk(int k, int np) { return k * ic_run(k, np) + 1; }
-constexpr int IC_RUN15 = ic_run(15, 3);   // 46
-constexpr int IC_K15 = ic_ldk(15, 3), IC_K7 = ic_ldk(7, 3), IC_K3 = ic_ldk(3, 3);                // odd row strides
-// NP = 6: the k = 15 weights as 15 kernel-row chunks [ky][32 rows][IC_LD15R] (odd stride); two chunks in LDS at a time
-constexpr int IC_LD15R = ic_run(15, 6) + 1, IC_CHUNK15 = 32 * IC_LD15R;   // 91, 2912 floats
+// ring form: the k = 15 weights as 15 kernel-row chunks [ky][32 rows][ic_ld15r] (odd stride); two chunks in LDS at a time
+__host__ __device__ constexpr int ic_ld15r(int np) { return ic_run(15, np) + 1; }          // NP = 6: 91
+__host__ __device__ constexpr int ic_chunk15(int np) { return 32 * ic_ld15r(np); }         // NP = 6: 2912 floats
+constexpr int IC_LDS_BYTES = 160 * 1024;
 
 // floats of LDS for the packed weights of (n3, n7, n15) output channels, each padded to a multiple of 32 rows
 __host__ __device__ constexpr int ic_rows(int n) { return (n + 31) / 32 * 32; }
-size_t init_conv_weight_floats(int n3, int n7, int n15, int np) {
-  if (np == 6) return (size_t)ic_rows(n3) * ic_ldk(3, 6) + (size_t)ic_rows(n7) * ic_ldk(7, 6) + (size_t)15 * IC_CHUNK15;
-  return (size_t)ic_rows(n3) * IC_K3 + (size_t)ic_rows(n7) * IC_K7 + (size_t)ic_rows(n15) * IC_K15;
+__host__ __device__ constexpr int ic_resident_floats(int r3, int r7, int r15, int np) {   // all three groups in LDS
+  return r3 * ic_ldk(3, np) + r7 * ic_ldk(7, np) + r15 * ic_ldk(15, np);
 }
-// LDS of the kernel: resident weights (NP = 6: + the two ring slots) + patch + epilogue scratch
+// Resident weights or the k = 15 ring, from the LDS bytes: the kernel takes at most 64 | 32 | 32 and (rows are padded)
+// at least 32 | 32 | 32 weight rows, and for every NP either the largest set fits resident or the smallest does not -
+// so the form is a function of NP (the static_asserts below hold the argument)
+__host__ __device__ constexpr bool ic_ring(int np) {
+  return (ic_resident_floats(32, 32, 32, np) + ic_patch(np) + IC_SCRATCH) * (int)sizeof(float) > IC_LDS_BYTES;
+}
+template <int NP>
+constexpr bool ic_form_decided() {
+  return ic_ring(NP) || (ic_resident_floats(64, 32, 32, NP) + ic_patch(NP) + IC_SCRATCH) * (int)sizeof(float) <= IC_LDS_BYTES;
+}
+static_assert(ic_form_decided<1>() && ic_form_decided<2>() && ic_form_decided<3>() && ic_form_decided<4>() &&
+                  ic_form_decided<6>() && ic_form_decided<8>(),
+              "an NP whose resident weights fit for some widths only needs a kernel of either form");
+static_assert(!ic_ring(3) && ic_ring(6), "3 planes: resident weights; 6 planes: the ring");
+// whether ANY shape with 64 rows of k = 3 weights fits the LDS at np planes (else the two-tile kernel is not instantiated)
+__host__ __device__ constexpr bool ic_two_tiles_fit(int np) {
+  return !ic_ring(np) || (64 * ic_ldk(3, np) + 32 * ic_ldk(7, np) + 2 * ic_chunk15(np) + ic_patch(np) + IC_SCRATCH) *
+                                 (int)sizeof(float) <= IC_LDS_BYTES;
+}
+static_assert(ic_two_tiles_fit(6) && !ic_two_tiles_fit(8), "6 planes run at dim 128, 8 planes up to dim 64");
+static bool ic_np_ok(int np) { return np == 1 || np == 2 || np == 3 || np == 4 || np == 6 || np == 8; }
+size_t init_conv_weight_floats(int n3, int n7, int n15, int np) {
+  if (ic_ring(np))
+    return (size_t)ic_rows(n3) * ic_ldk(3, np) + (size_t)ic_rows(n7) * ic_ldk(7, np) + (size_t)15 * ic_chunk15(np);
+  return (size_t)ic_resident_floats(ic_rows(n3), ic_rows(n7), ic_rows(n15), np);
+}
+// LDS of the kernel: resident weights (ring form: k = 3 / 7 + the two ring slots) + patch + epilogue scratch
 static size_t init_conv_lds_floats(int n3, int n7, int n15, int np) {
-  const size_t w = np == 6 ? (size_t)ic_rows(n3) * ic_ldk(3, 6) + (size_t)ic_rows(n7) * ic_ldk(7, 6) + 2 * IC_CHUNK15
-                           : init_conv_weight_floats(n3, n7, n15, 3);
+  const size_t w = ic_ring(np)
+                       ? (size_t)ic_rows(n3) * ic_ldk(3, np) + (size_t)ic_rows(n7) * ic_ldk(7, np) + 2 * ic_chunk15(np)
+                       : init_conv_weight_floats(n3, n7, n15, np);
   return w + ic_patch(np) + IC_SCRATCH;
 }
 bool init_conv_fused_ok(int S, int n3, int n7, int n15, int np) {
-  if (np != 3 && np != 6) return false;
+  if (!ic_np_ok(np) || n3 < 1 || n7 < 1 || n15 < 1) return false;
   const size_t lds = init_conv_lds_floats(n3, n7, n15, np) * sizeof(float);
-  return S % IC_TW == 0 && S % IC_TH == 0 && lds <= 160 * 1024 && ic_rows(n3) <= 64 && ic_rows(n7) <= 32 &&
+  return S % IC_TW == 0 && S % IC_TH == 0 && lds <= (size_t)IC_LDS_BYTES && ic_rows(n3) <= 64 && ic_rows(n7) <= 32 &&
          ic_rows(n15) <= 32 && n3 % 4 == 0 && n7 % 4 == 0 && n15 % 4 == 0;
 }
 
 // OIHW [n][Itot][k][k] -> rows [n][ky][kx*np + c] over input channels c0..c0+np-1, runs padded to `run`, rows to `ldk`
-// (zeros), n padded to a multiple of 32 rows (zeros).  chunked: [ky][n][r] with row stride ldk (the NP = 6 k = 15 ring)
+// (zeros), n padded to a multiple of 32 rows (zeros).  chunked: [ky][n][r] with row stride ldk (the k = 15 ring)
 __global__ void init_conv_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int n_real, int Itot, int c0,
                                       int np, int k, int run, int ldk, int rows, int chunked) {
   const int total = chunked ? k * rows * ldk : rows * ldk;
@@ -94,7 +130,7 @@ __global__ void init_conv_pack_kernel(const float* __restrict__ w, float* __rest
 }
 int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, float* out, int n3, int n7, int n15, int Itot,
                           int c0, int np, hipStream_t s) {
-  KD_REQUIRE(np == 3 || np == 6, "init conv pack: 3 or 6 planes");
+  KD_REQUIRE(ic_np_ok(np), "init conv pack: 1, 2, 3, 4, 6 or 8 planes");
   const int l3 = ic_ldk(3, np), l7 = ic_ldk(7, np);
   float* o3 = out;
   float* o7 = o3 + (size_t)ic_rows(n3) * l3;
@@ -103,31 +139,33 @@ int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, fl
                      ic_rows(n3), 0);
   hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w7, o7, n7, Itot, c0, np, 7, ic_run(7, np), l7,
                      ic_rows(n7), 0);
-  if (np == 6)
-    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, ic_run(15, 6),
-                       IC_LD15R, 32, 1);
+  if (ic_ring(np))
+    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, ic_run(15, np),
+                       ic_ld15r(np), 32, 1);
   else
-    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, IC_RUN15, IC_K15,
-                       ic_rows(n15), 0);
+    hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w15, o15, n15, Itot, c0, np, 15, ic_run(15, np),
+                       ic_ldk(15, np), ic_rows(n15), 0);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 struct InitConvParams {
-  const float* x;      // NCHW [B][3][S][S]
+  const float* x;      // NCHW [B][cx][S][S]
   const float* wp;     // init_conv_weight_floats packed weights
   const float* bias;   // [n3 + n7 + n15] or nullptr (then `res` carries it)
   const float* res;    // dense NHWC [B][S][S][n3+n7+n15] step-invariant share, or nullptr
   float* y;            // NHWC, row stride ldy, first channel at y
   double* seg;         // GroupNorm partials [B][(n3+n7+n15)/16][S*S/32][2] or nullptr
   int B, S, ldy, n3, n7, n15;
-  const float* sc;     // NP = 6: the self-conditioning planes NCHW [B][3][S][S] (nullptr: zeros)
+  const float* sc;     // NP = 2 cx: the self-conditioning planes NCHW [B][cx][S][S] (nullptr: zeros)
+  int cx;              // image channels: NP = cx (x) or 2 cx (x | self_cond)
 };
 
-template <int N3T, int NP>   // 32-row tiles of the k = 3 conv (1 or 2); input planes per step (3: x, 6: x | self_cond)
+template <int N3T, int NP>   // 32-row tiles of the k = 3 conv (1 or 2); input planes per step (C: x, 2 C: x | self_cond)
 __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr bool RING = NP == 6;   // k = 15 weights streamed through two LDS slots
+  constexpr bool RING = ic_ring(NP);   // k = 15 weights streamed through two LDS slots
+  constexpr int IC_LD15R = ic_ld15r(NP), IC_CHUNK15 = ic_chunk15(NP);
   constexpr int RUN3 = ic_run(3, NP), RUN7 = ic_run(7, NP), RUN15 = ic_run(15, NP);
   constexpr int K3 = ic_ldk(3, NP), K7 = ic_ldk(7, NP), K15 = RING ? IC_LD15R : ic_ldk(15, NP);
   constexpr int PATCH = ic_patch(NP);
@@ -143,7 +181,7 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   for (int i = tid; i < nw; i += 512) lds[i] = p.wp[i];
   for (int i = tid; i < 8; i += 512) patch[PATCH - 8 + i] = 0.f;
   // RING: chunk c of the stream (kernel row c % 15) lives at wp15 + (c % 15) * IC_CHUNK15; each thread carries its
-  // share of the next chunk in registers (16-byte loads: a chunk is 728 float4)
+  // share of the next chunk in registers (16-byte loads: a chunk is 728 float4 at NP = 6)
   const float* wp15 = p.wp + r3 * K3 + r7 * K7;
   constexpr int NRV = RING ? (IC_CHUNK15 / 4 + 511) / 512 : 1;
   f32x4 rv[NRV];
@@ -169,6 +207,8 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
   const int C = p.n3 + p.n7 + p.n15;
   const int frow = lane & 31, khalf = lane >> 5;
   const int64_t plane = (int64_t)S * S;
+  // image channels: fixed by NP where only one channel count gives it (1, 3: x alone; 6, 8: x | self_cond)
+  const int cx = (NP & 1) ? NP : NP == 6 ? 3 : NP == 8 ? 4 : p.cx;
 
   // halo loader: NP * 2 values per thread, fetched into registers one tile ahead (the loads fly during the MFMAs of
   // the current tile) and written to LDS behind the barrier that ends the current tile's reads
@@ -186,10 +226,10 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
       const int iy = y0 - 7 + py, ix = x0 - 7 + px;
       float v = 0.f;
       if (i < IC_PH * IC_PW * NP && iy >= 0 && iy < S && ix >= 0 && ix < S) {
-        if (NP == 3 || c < 3)
-          v = p.x[((int64_t)b * 3 + c) * plane + (int64_t)iy * S + ix];
+        if ((NP & 1) || c < cx)
+          v = p.x[((int64_t)b * cx + c) * plane + (int64_t)iy * S + ix];
         else if (p.sc)
-          v = p.sc[((int64_t)b * 3 + c - 3) * plane + (int64_t)iy * S + ix];
+          v = p.sc[((int64_t)b * cx + c - cx) * plane + (int64_t)iy * S + ix];
       }
       pv[q] = v;
     }
@@ -284,7 +324,8 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
               a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk], pb[2 * kk], a15, 0, 0, 0);
               b15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * kk + 2], pb[2 * kk + 2], b15, 0, 0, 0);
             }
-            a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[RUN15 - 2], pb[RUN15 - 2], a15, 0, 0, 0);
+            if ((RUN15 / 2) & 1)   // an odd number of k pairs (NP = 2, 3, 6): the last one
+              a15 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[RUN15 - 2], pb[RUN15 - 2], a15, 0, 0, 0);
             pa += IC_PW * NP;
             if (!RING) pb += RUN15;
           }
@@ -347,9 +388,14 @@ __global__ __launch_bounds__(512, 1) void init_conv_kernel(InitConvParams p) {
 template <int NP>
 static int launch_init_conv_np(const InitConvParams& p, int n3, size_t smem, int grid, hipStream_t s) {
   if (ic_rows(n3) == 64) {
-    KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<2, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem));
-    hipLaunchKernelGGL((init_conv_kernel<2, NP>), dim3(grid), dim3(512), smem, s, p);
+    // (8 planes: no shape with two k = 3 tiles fits the LDS - init_conv_fused_ok - so that kernel is not built)
+    if constexpr (ic_two_tiles_fit(NP)) {
+      KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<2, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)smem));
+      hipLaunchKernelGGL((init_conv_kernel<2, NP>), dim3(grid), dim3(512), smem, s, p);
+    } else {
+      KD_REQUIRE(false, "init conv kernel: two k = 3 tiles of this many planes do not fit LDS");
+    }
   } else {
     KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_conv_kernel<1, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)smem));
@@ -358,14 +404,15 @@ static int launch_init_conv_np(const InitConvParams& p, int n3, size_t smem, int
   return 0;
 }
 
-int launch_init_conv(const float* x, const float* sc, int np, const float* wp, const float* bias, const float* res, float* y,
+int launch_init_conv(const float* x, const float* sc, int cx, int np, const float* wp, const float* bias, const float* res, float* y,
                      int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s) {
   KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15, np), "init conv kernel: image size % 32, weights must fit LDS");
   KD_REQUIRE(ldy % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
                  ((uintptr_t)wp & 15) == 0,
              "init conv kernel: 16-byte aligned output / residual / bias rows");
   KD_REQUIRE(!seg || ((n3 % 16) == 0 && (n7 % 16) == 0 && (n15 % 16) == 0), "init conv partials: 16-channel segments");
-  InitConvParams p{x, wp, bias, res, y, seg, B, S, ldy, n3, n7, n15, np == 6 ? sc : nullptr};
+  KD_REQUIRE(cx >= 1 && (np == cx || np == 2 * cx), "init conv kernel: planes = channels (x) or 2 channels (x | self_cond)");
+  InitConvParams p{x, wp, bias, res, y, seg, B, S, ldy, n3, n7, n15, np == 2 * cx ? sc : nullptr, cx};
   const size_t smem = init_conv_lds_floats(n3, n7, n15, np) * sizeof(float);
   const int ntiles = B * (S / IC_TW) * (S / IC_TH);
   static int cus = 0;
@@ -377,7 +424,16 @@ int launch_init_conv(const float* x, const float* sc, int np, const float* wp, c
     cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   const int grid = ntiles < cus ? ntiles : cus;   // persistent: one workgroup per CU keeps the weights in LDS
-  if (np == 6 ? launch_init_conv_np<6>(p, n3, smem, grid, s) : launch_init_conv_np<3>(p, n3, smem, grid, s)) return 1;
+  int rc = 1;
+  switch (np) {
+    case 1: rc = launch_init_conv_np<1>(p, n3, smem, grid, s); break;
+    case 2: rc = launch_init_conv_np<2>(p, n3, smem, grid, s); break;
+    case 3: rc = launch_init_conv_np<3>(p, n3, smem, grid, s); break;
+    case 4: rc = launch_init_conv_np<4>(p, n3, smem, grid, s); break;
+    case 6: rc = launch_init_conv_np<6>(p, n3, smem, grid, s); break;
+    case 8: rc = launch_init_conv_np<8>(p, n3, smem, grid, s); break;
+  }
+  if (rc) return 1;
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -667,7 +667,7 @@ int launch_act(const float* a, float* y, int64_t n, int act, hipStream_t s) {
 // ------------------------------------------------------------------------- init image assembly
 // NCHW planes (cond | x | lowres) -> NHWC [B][HW][Cpad], zero padded.  Channel order follows
 // Unet.forward: x = cat(x, lowres); x = cat(cond_images, x)   (SURVEY A.1 / §3.2).
-__global__ void pack_init_kernel(const float* __restrict__ cond, int Cc, const float* __restrict__ x,
+__global__ void pack_init_kernel(const float* __restrict__ cond, int Cc, const float* __restrict__ x, int Cx,
                                  const float* __restrict__ lowres, int Cl, float* __restrict__ y, int Cpad,
                                  int64_t HW, int64_t total) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -678,15 +678,16 @@ __global__ void pack_init_kernel(const float* __restrict__ cond, int Cc, const f
     int c = 0;
     for (int i = 0; i < Cc; ++i) o[c++] = cond[(b * Cc + i) * HW + p];
     if (x)  // x == nullptr: only the step-invariant planes (cond | lowres) are packed
-      for (int i = 0; i < 3; ++i) o[c++] = x[(b * 3 + i) * HW + p];
+      for (int i = 0; i < Cx; ++i) o[c++] = x[(b * Cx + i) * HW + p];
     for (int i = 0; i < Cl; ++i) o[c++] = lowres[(b * Cl + i) * HW + p];
     for (; c < Cpad; ++c) o[c] = 0.f;
   }
 }
-int launch_pack_init(const float* cond, int Cc, const float* x, const float* lowres, int Cl, float* y, int Cpad,
+int launch_pack_init(const float* cond, int Cc, const float* x, int Cx, const float* lowres, int Cl, float* y, int Cpad,
                      int B, int HW, hipStream_t s) {
+  KD_REQUIRE(Cc + (x ? Cx : 0) + Cl <= Cpad, "pack init: the planes do not fit the padded pixel");
   int64_t total = (int64_t)B * HW;
-  hipLaunchKernelGGL(pack_init_kernel, dim3(grid_for(total)), dim3(256), 0, s, cond, Cc, x, lowres, Cl, y, Cpad,
+  hipLaunchKernelGGL(pack_init_kernel, dim3(grid_for(total)), dim3(256), 0, s, cond, Cc, x, Cx, lowres, Cl, y, Cpad,
                      (int64_t)HW, total);
   KD_HIP_CHECK(hipGetLastError());
   return 0;

@@ -27,7 +27,7 @@ static int run_static(kd_unet* u, hipStream_t s) {
 static inline bool cfg_on(const kd_sample_args_t* a) { return a->cond_scale != 0.0f && a->cond_scale != 1.0f; }
 
 static inline size_t image_bytes(const kd_unet* u) {
-  return (size_t)u->cfg.batch * 3 * u->cfg.image_size * u->cfg.image_size * sizeof(float);
+  return (size_t)u->cfg.batch * u->cfg.channels * u->cfg.image_size * u->cfg.image_size * sizeof(float);
 }
 
 struct SamplerCtx {
@@ -242,12 +242,12 @@ static int guided_forward(kd_unet* u, const SamplerCtx& ctx, const kd_sample_arg
 
 static int emit_iteration(kd_unet* u, const SamplerCtx& ctx, const kd_sample_args_t* a, float* d_img, hipStream_t s) {
   Sampler& m = u->smp;
-  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R;
-  const int64_t hw = (int64_t)S * S, per = 3 * hw;
+  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, Ci = u->cfg.channels;
+  const int64_t hw = (int64_t)S * S, per = Ci * hw;
   const bool inpaint = a->d_inpaint_images != nullptr;
   if (inpaint)
     if (launch_inpaint_mix(d_img, a->d_inpaint_images, a->d_inpaint_masks, a->d_noise_inpaint, B * per, m.seed, ctx.tb,
-                           m.iter, R, B, 3, hw, s))
+                           m.iter, R, B, Ci, hw, s))
       return 1;
   if (launch_fill_time(ctx.tb.log_snr, m.iter, R, m.time, B, s)) return 1;
   if (guided_forward(u, ctx, a, d_img, m.cond.tab, s)) return 1;
@@ -355,7 +355,7 @@ static int edm_forward(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, c
                        int j, hipStream_t s) {
   Sampler& m = u->smp;
   const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, N = ctx.T / 2;
-  const int64_t per = (int64_t)3 * S * S;
+  const int64_t per = (int64_t)u->cfg.channels * S * S;
   if (launch_fill_time(j ? tb.c_noise_next : tb.c_noise_hat, m.iter, R, m.time, B, s)) return 1;
   // table rows [0, N): time input at sigma_hat, [N, 2N): at sigma_next
   const char* rows = ctx.cond_tab ? m.cond.tab + (size_t)j * N * u->cond_bytes : nullptr;
@@ -374,11 +374,11 @@ static int edm_forward(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, c
 static int emit_edm_iteration(kd_unet* u, const SamplerCtx& ctx, const EdmTables& tb, float s_noise,
                               const kd_sample_args_t* a, float* d_img, bool heun, hipStream_t s) {
   Sampler& m = u->smp;
-  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, N = ctx.T / 2;
-  const int64_t hw = (int64_t)S * S, per = 3 * hw;
+  const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, N = ctx.T / 2, Ci = u->cfg.channels;
+  const int64_t hw = (int64_t)S * S, per = Ci * hw;
   const bool inpaint = a->d_inpaint_images != nullptr;
   if (launch_edm_churn(d_img, m.xhat, m.net_in, a->d_inpaint_images, a->d_inpaint_masks, a->d_noise_step, B * per, m.seed, tb,
-                       s_noise, m.iter, R, B, 3, hw, s))
+                       s_noise, m.iter, R, B, Ci, hw, s))
     return 1;
   if (edm_forward(u, ctx, tb, a, m.xhat, 0, s)) return 1;
   // self_cond: Euler leaves the first forward's thresholded estimate for the Heun forward (and, on the last step, for

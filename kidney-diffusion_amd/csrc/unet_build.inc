@@ -9,7 +9,8 @@ void Builder::build() {
   const int tcd = dim * 4 * (cfg.lowres_cond ? 2 : 1);
   u->time_cond_dim = tcd;
   if (L < 1 || L > KD_MAX_LEVELS) throw std::runtime_error("num_levels out of range");
-  if (cfg.channels != 3) throw std::runtime_error("only 3-channel images are supported");
+  if (cfg.channels < 1 || cfg.channels > 4) throw std::runtime_error("images of 1 to 4 channels are supported");
+  const int Ci = cfg.channels;   // image channels: x, the self-conditioning image, the low-res image and the output
   if (cfg.attn_dim_head != 64) throw std::runtime_error("attention kernel is built for dim_head = 64");
   if (B < 1 || S < 1) throw std::runtime_error("batch and image_size must be positive");
   const int n_down = cfg.memory_efficient ? L : L - 1;
@@ -47,16 +48,16 @@ void Builder::build() {
 
   // Buffers that are written once per sampling call (static_ops) and read by every step are allocated
   // FIRST and stay live to the end of the build, so the arena can never hand their space to a per-step tensor.
-  const int fin_c = dim + (cfg.lowres_cond ? 3 : 0);
-  const float* wfin = P("final_conv.weight", (int64_t)3 * fin_c * 9);
-  const float* bfin = P("final_conv.bias", 3);
-  float* wfin_p = cached("final_conv_gemm", (size_t)32 * dim,
-                         [&](float* dst) { KD_THROW_IF(launch_pack_final(wfin, dst, fin_c, dim, 0)); });
+  const int fin_c = dim + (cfg.lowres_cond ? Ci : 0), fin_n = final_gemm_cols(Ci);
+  const float* wfin = P("final_conv.weight", (int64_t)Ci * fin_c * 9);
+  const float* bfin = P("final_conv.bias", Ci);
+  float* wfin_p = cached("final_conv_gemm", (size_t)fin_n * dim,
+                         [&](float* dst) { KD_THROW_IF(launch_pack_final(wfin, dst, fin_c, dim, Ci, 0)); });
   T fin_static;
   const bool fin_has_static = cfg.lowres_cond != 0;
   if (fin_has_static) {
     to_static = true;
-    fin_static = alloc(B, 3, S, S);
+    fin_static = alloc(B, Ci, S, S);
     size_t so = fin_static.off;
     int Bx = B;
     kd_unet* uu = u;
@@ -65,7 +66,7 @@ void Builder::build() {
         set_error("lowres_cond_img must be given iff the UNet has lowres_cond");
         return 1;
       }
-      return launch_final_static(uu->in_lowres, wfin, bfin, uu->P(so), fin_c, dim, Bx, S, S, s);
+      return launch_final_static(uu->in_lowres, wfin, bfin, uu->P(so), fin_c, dim, Ci, Bx, S, S, s);
     });
     to_static = false;
   }
@@ -121,12 +122,12 @@ void Builder::build() {
   // ---- initial cross-embed convolution (k = 3, 7, 15) over cond | x | lowres.
   // The cond / low-res planes do not change during a sampling loop: their share of the convolution
   // (2/3 of its K for the SR UNets) is computed ONCE per sampling call into `init_static` (static_ops)
-  // and enters the per-step convolution over x's 3 planes through the residual epilogue.  The sum is
+  // and enters the per-step convolution over x's planes through the residual epilogue.  The sum is
   // the same convolution, only associated differently.
   // A self-conditioned UNet (u->self_cond) reads x AND the previous step's x0 estimate every step: its per-step planes
-  // are the 6 of cat(x, self_cond), input channels Cc .. Cc + 5 (library order: cond_images | x | self_cond | lowres)
-  const int Cc = cfg.cond_images_channels, Cl = cfg.lowres_cond ? 3 : 0;
-  const int NPs = u->self_cond ? 6 : 3;
+  // are the 2 C of cat(x, self_cond), input channels Cc .. Cc + 2 C - 1 (library order: cond_images | x | self_cond | lowres)
+  const int Cc = cfg.cond_images_channels, Cl = cfg.lowres_cond ? Ci : 0;
+  const int NPs = u->self_cond ? 2 * Ci : Ci;
   const int init_ch = Cc + NPs + Cl, Cs = Cc + Cl;
   const bool hoist = Cs > 0;
   const int ks[3] = {3, 7, 15};
@@ -153,7 +154,7 @@ void Builder::build() {
       int Bx = B, HW = S * S;
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_pack_init(uu->in_cond, Cc, nullptr, uu->in_lowres, Cl, uu->P(so), spad, Bx, HW, s);
+        return launch_pack_init(uu->in_cond, Cc, nullptr, 0, uu->in_lowres, Cl, uu->P(so), spad, Bx, HW, s);
       });
       init_static = alloc(B, S, S, dim);
       int off = 0;
@@ -191,7 +192,7 @@ void Builder::build() {
       const float* w15 = raw("init_conv.convs.2.weight", (int64_t)ds[2] * init_ch * 225);
       const int n3 = ds[0], n7 = ds[1], n15 = ds[2], Itot = init_ch, c0 = Cc;
       const int np = NPs;
-      float* wp = cached(np == 6 ? "init_conv_fused6" : "init_conv_fused", init_conv_weight_floats(n3, n7, n15, np), [&](float* dst) {
+      float* wp = cached(uu->self_cond ? "init_conv_fused6" : "init_conv_fused", init_conv_weight_floats(n3, n7, n15, np), [&](float* dst) {
         KD_THROW_IF(launch_init_conv_pack(w3, w7, w15, dst, n3, n7, n15, Itot, c0, np, 0));
       });
       float* biasp = nullptr;
@@ -212,24 +213,24 @@ void Builder::build() {
       const int64_t m = (int64_t)B * S * S * np * (9 * n3 + 49 * n7 + 225 * n15);
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_init_conv(uu->in_x, uu->in_self_cond, np, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
+        return launch_init_conv(uu->in_x, uu->in_self_cond, Ci, np, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
                                 sg ? (double*)uu->P(sgo) : nullptr, Bx, S, n3, n7, n15, s);
-      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (np == 6 ? " self-cond" : ""), m);
+      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (uu->self_cond ? " self-cond" : ""), m);
       u->macs += m;
-      // K runs (3 / 7 / 15 kernel rows of 3k | 6k values, padded to even) x 32-row tiles
-      const int r3 = np == 6 ? 54 : 30, r7 = np == 6 ? 294 : 154, r15 = np == 6 ? 1350 : 690;
+      // K runs (3 / 7 / 15 kernel rows of np k values, padded to even) x 32-row tiles
+      const int r3 = 3 * (((3 * np + 1) / 2) * 2), r7 = 7 * (((7 * np + 1) / 2) * 2), r15 = 15 * (((15 * np + 1) / 2) * 2);
       const int64_t issued = (int64_t)B * S * S * (r3 * ((n3 + 31) / 32 * 32) + r7 * 32 + r15 * 32);
       u->mfma_macs += issued;
       u->op_mfma.back() = issued;
     } else {
-      const int np = NPs, ipad = np == 6 ? 8 : 4;
-      T img = alloc(B, S, S, ipad);  // x's 3 planes (| self_cond's 3: zeros when it is not given) + zero channels
+      const int np = NPs, ipad = (np + 3) & ~3;
+      T img = alloc(B, S, S, ipad);  // x's planes (| self_cond's: zeros when it is not given) + zero channels
       size_t yo = img.off;
       int Bx = B, HW = S * S;
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        const float* sc = np == 6 ? uu->in_self_cond : nullptr;
-        return launch_pack_init(nullptr, 0, uu->in_x, sc, sc ? 3 : 0, uu->P(yo), ipad, Bx, HW, s);
+        const float* sc = uu->self_cond ? uu->in_self_cond : nullptr;
+        return launch_pack_init(nullptr, 0, uu->in_x, Ci, sc, sc ? Ci : 0, uu->P(yo), ipad, Bx, HW, s);
       });
       int off = 0;
       for (int i = 0; i < 3; ++i) {
@@ -489,18 +490,18 @@ void Builder::build() {
   free(c);
   if (tmlp_total > 0) free(t_ss);
 
-  // ---- final conv over cat(x, lowres_cond_img) to 3 channels (kernels_final.hip): a 1x1 GEMM to the
-  // 27 (output, tap) columns on the matrix cores + a 9-tap gather; the low-res planes' share is
+  // ---- final conv over cat(x, lowres_cond_img) to the image's channels (kernels_final.hip): a 1x1 GEMM to the
+  // 9 C (output, tap) columns on the matrix cores + a 9-tap gather; the low-res planes' share is
   // step-invariant and computed once per sampling call.
   {
     ConvOpt o;
-    o.macs_override = (int64_t)B * S * S * 3 * fin_c * 9;
-    T pm = conv(x, wfin_p, nullptr, 32, 1, 1, 0, o);
+    o.macs_override = (int64_t)B * S * S * Ci * fin_c * 9;
+    T pm = conv(x, wfin_p, nullptr, fin_n, 1, 1, 0, o);
     size_t po = pm.off, so = fin_has_static ? fin_static.off : 0;
     int Bx = B;
     kd_unet* uu = u;
     emit([=](hipStream_t s) {
-      return launch_final_gather(uu->P(po), fin_has_static ? uu->P(so) : nullptr, bfin, uu->out, Bx, S, S, s);
+      return launch_final_gather(uu->P(po), fin_has_static ? uu->P(so) : nullptr, bfin, uu->out, Ci, Bx, S, S, s);
     }, "final gather");
     free(pm);
   }

@@ -183,6 +183,9 @@ SIGNATURES = {
     "kd_init_conv_nchw": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_void_p]),
     "kd_init_conv_planes_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6 +
                                  [C.POINTER(C.c_float), C.c_void_p]),
+    "kd_init_conv_planes_c_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6 +
+                                   [C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "kd_final_conv_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "kd_groupnorm_silu_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "kd_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "kd_layernorm_ex": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -319,9 +319,11 @@ class Unet(nn.Module):
                         final_resnet_block=final_resnet_block, pixel_shuffle_upsample=pixel_shuffle_upsample)
         bad += [k for k, v in required.items() if not v]
         if bad or final_conv_kernel_size != 3 or tuple(init_cross_embed_kernel_sizes) != (3, 7, 15) \
-                or layer_attns_depth != 1 or attn_dim_head != 64 or channels != 3:
+                or layer_attns_depth != 1 or attn_dim_head != 64 or channels not in (1, 2, 3, 4):
             raise NotImplementedError(
                 f"Unet option outside what the reference's configs use and the HIP engine plans: {bad or 'see kwargs'}")
+        if channels != 3 and channels_out is not None and channels_out != channels:
+            raise NotImplementedError("channels_out must equal channels: the engine's final conv writes the image's channels")
 
         self.channels = channels
         self.channels_out = default(channels_out, channels)
@@ -687,14 +689,15 @@ class Unet(nn.Module):
 
     def forward(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None,
                 cond_images=None, self_cond=None, cond_drop_prob=0.0):
-        """One UNet forward on the engine.  ``time`` is the log-SNR, as in the library.  ``self_cond`` [B,3,S,S]
+        """One UNet forward on the engine.  ``time`` is the log-SNR, as in the library.  ``self_cond`` [B,C,S,S]
         (None = zeros) is read by a UNet built with self_cond=True and ignored by any other, as in the library."""
         assert not (self.lowres_cond and not exists(lowres_cond_img)), "low resolution conditioning image must be present"
         assert not (self.lowres_cond and not exists(lowres_noise_times)), "low resolution conditioning noise time must be present"
         assert not (self.has_cond_image ^ exists(cond_images)), \
             "you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa"
         E.require_gpu()
-        b, _, s, _ = x.shape
+        b, c, s, _ = x.shape
+        assert c == self.channels, f"x has {c} channels, the UNet was built with channels={self.channels}"
         f32 = lambda t: None if t is None else t.to(device=x.device, dtype=torch.float32).contiguous()
         if exists(cond_images):
             assert cond_images.shape[1] == self.cond_images_channels, "invalid number of channels in conditioning image"
@@ -958,9 +961,12 @@ class Imagen(nn.Module):
         if not return_pil_images:
             return out
         from PIL import Image  # noqa: local import, PIL only needed for this branch
-        # the library maps T.ToPILImage() over the images: float -> mul(255).byte(), i.e. truncation
-        to_pil = lambda t: [Image.fromarray(i.clamp(0, 1).mul(255).to(torch.uint8).permute(1, 2, 0).cpu().numpy())
-                            for i in t]
+        # the library maps T.ToPILImage() over the images: float -> mul(255).byte(), i.e. truncation; mode by channel
+        # count: L (one channel: a 2-D array), LA, RGB, RGBA
+        def to_pil(t):
+            arrs = [i.clamp(0, 1).mul(255).to(torch.uint8).permute(1, 2, 0).cpu().numpy() for i in t]
+            return [Image.fromarray(a[:, :, 0] if a.shape[2] == 1 else a) for a in arrs]
+
         return [to_pil(o) for o in out] if return_all_unet_outputs else to_pil(out)
 
     def _p_sample_loop(self, unet, stage, size, sched, objective, dynamic_threshold, batch, device, prev_img,
