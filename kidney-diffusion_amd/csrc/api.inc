@@ -48,6 +48,7 @@ int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, in
     }
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
+  u->cus = gemm_bf16x3_device_cus();   // read once: every plan-time question and every launch shape of this plan uses it
   try {
     Builder b(u);
     for (int i = 0; i < n_params; ++i) {
@@ -59,8 +60,7 @@ int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, in
     if (cfg->cond_on_text && cfg->text_tokens > 0) {  // step-invariant text conditioning, same workspace
       Builder bt(u);
       bt.params = b.params;
-      bt.to_text = true;
-      bt.cond_hoist = false;
+      bt.phase = Builder::Phase::Text;
       bt.build_text();
       u->ws_bytes = std::max(u->ws_bytes, bt.arena.peak);
     }
@@ -313,6 +313,8 @@ int entry_finish(int rc, hipStream_t s) {
   KD_HIP_CHECK(e);
   return 0;
 }
+// the launch shape of a bf16x3 GEMM of a test entry point: one per call, for the device that is current
+X3Shape entry_x3_shape(int G, int64_t M, int N, int K) { return gemm_bf16x3_shape(G, (int)M, N, K, gemm_bf16x3_device_cus()); }
 }  // namespace
 
 // act bit 8 (0x100) selects the row-run K layout used for the small-Cin init convs
@@ -414,7 +416,7 @@ int kd_conv3x3_winograd4_nhwc(const float* d_x, const float* d_w_oihw, const flo
     rc = launch_split3(U, U3, 36, Cout, Cin, s);
     if (!rc && gemm_bf16x3 == 1) rc = launch_wino4_in3(d_x, Cin, nullptr, nullptr, nullptr, nullptr, 0, V, B, H, W, Cin, 1, s);
     if (!rc && gemm_bf16x3 != 1) rc = launch_wino4_in(d_x, Cin, nullptr, nullptr, nullptr, nullptr, 0, V, B, H, W, Cin, 1, s);
-    if (!rc) rc = launch_gemm_bf16x3(V, U3, D, 36, (int)Mt, Cout, Cin, x3ws, s, gemm_bf16x3 != 1);
+    if (!rc) rc = launch_gemm_bf16x3(V, U3, D, 36, (int)Mt, Cout, Cin, entry_x3_shape(36, Mt, Cout, Cin), x3ws, s, gemm_bf16x3 != 1);
   }
   if (!rc && !gemm_bf16x3) rc = launch_wino4_in(d_x, Cin, nullptr, nullptr, nullptr, nullptr, 0, V, B, H, W, Cin, 1, s);
   if (!rc && !gemm_bf16x3) {
@@ -443,7 +445,7 @@ int kd_gemm_bf16x3(const float* d_a, const float* d_b, float* d_c, int G, int M,
   if (bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;   // slabs of the left-over tiles' k-parts
   int rc = a_planes ? launch_split3(d_a, A3, G, M, K, s) : 0;
   if (!rc) rc = launch_split3(d_b, B3, G, N, K, s);
-  if (!rc) rc = launch_gemm_bf16x3(a_planes ? A3 : (const void*)d_a, B3, d_c, G, M, N, K, ws, s, !a_planes);
+  if (!rc) rc = launch_gemm_bf16x3(a_planes ? A3 : (const void*)d_a, B3, d_c, G, M, N, K, entry_x3_shape(G, M, N, K), ws, s, !a_planes);
   return entry_finish(rc, s);
 }
 
@@ -462,7 +464,8 @@ int kd_downsample_bf16x3(const float* d_x, int ldx, const float* d_w, const floa
   e.hw = (H / 2) * (W / 2);
   e.seg = d_seg;
   e.seg_nseg = d_seg ? O / 16 : 0;
-  KD_REQUIRE(H > 0 && W > 0 && !(H & 1) && !(W & 1) && M < 0x7fffffff && gemm_bf16x3_epi_ok(M, O, K, e),
+  const X3Shape sh = entry_x3_shape(1, M, O, K);
+  KD_REQUIRE(H > 0 && W > 0 && !(H & 1) && !(W & 1) && M < 0x7fffffff && gemm_bf16x3_epi_ok(M, O, K, e, sh),
              "kd_downsample_bf16x3 needs even map sides, C % 16 == 0, B (H/2) (W/2) % 256 == 0, O % 128 == 0");
   // torch weight [O][4 C] with k = c 4 + tap  ->  [tap][O][C] (launch_pack_unshuffle)  ->  [O][tap C + c]  ->  planes
   EntryBufs bufs;
@@ -474,11 +477,11 @@ int kd_downsample_bf16x3(const float* d_x, int ldx, const float* d_w, const floa
   int rc = launch_pack_unshuffle(d_w, wt, O, C, s);
   for (int t = 0; t < 4 && !rc; ++t) rc = launch_copy_scale_rows(wt + (size_t)t * O * C, C, wk + (size_t)t * C, K, C, 1.0f, O, s);
   if (!rc) rc = launch_split3(wk, W3, 1, O, K, s);
-  if (!rc) rc = launch_gemm_bf16x3(d_x, W3, d_y, 1, (int)M, O, K, ws, s, true, true, &e);
+  if (!rc) rc = launch_gemm_bf16x3(d_x, W3, d_y, 1, (int)M, O, K, sh, ws, s, true, true, &e);
   return entry_finish(rc, s);
 }
 
-int kd_linear_bf16x3_seg_rows(int M, int N, int K) { return gemm_bf16x3_ok(1, M, N, K) ? gemm_bf16x3_seg_rows(M, N, K) : 0; }
+int kd_linear_bf16x3_seg_rows(int M, int N, int K) { return gemm_bf16x3_ok(1, M, N, K) ? entry_x3_shape(1, M, N, K).seg_rows() : 0; }
 
 int kd_linear_bf16x3(const float* d_x, int ldx, const float* d_w, const float* d_bias, const float* d_res, int ldres,
                      const float* d_gate_src, int ldgs, const float* d_gate, int hw, float* d_y, int ldy, int M, int N, int K,
@@ -498,13 +501,14 @@ int kd_linear_bf16x3(const float* d_x, int ldx, const float* d_w, const float* d
   e.hw = hw;
   e.ldy = ldy > 0 ? ldy : (pixshuf_wo ? N / 4 : N);
   e.lda = ldx > 0 ? ldx : K;
-  KD_REQUIRE(gemm_bf16x3_epi_ok(M, N, K, e), "kd_linear_bf16x3 needs M % 256 == 0, N % 128 == 0, K % 32 == 0, row strides >= the "
+  const X3Shape sh = entry_x3_shape(1, M, N, K);
+  KD_REQUIRE(gemm_bf16x3_epi_ok(M, N, K, e, sh), "kd_linear_bf16x3 needs M % 256 == 0, N % 128 == 0, K % 32 == 0, row strides >= the "
                                              "rows, hw % 256 == 0 under a gate");
   EntryBufs bufs;
   void *W3 = nullptr, *ws = nullptr;
   if (bufs.get(&W3, (size_t)N * K * 6) || bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
   int rc = launch_split3(d_w, W3, 1, N, K, s);
-  if (!rc) rc = launch_gemm_bf16x3(d_x, W3, d_y, 1, M, N, K, ws, s, true, true, &e);
+  if (!rc) rc = launch_gemm_bf16x3(d_x, W3, d_y, 1, M, N, K, sh, ws, s, true, true, &e);
   return entry_finish(rc, s);
 }
 
@@ -676,6 +680,7 @@ int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats
   KD_REQUIRE((((uintptr_t)d_y | (uintptr_t)d_res | (uintptr_t)d_bias) & 7) == 0,
              "kd_gn_conv3x3_winograd4_nhwc: 8-byte aligned y, residual and bias");
   const bool planes = gemm_mode == 1, x3 = gemm_mode > 0;
+  const X3Shape sh = entry_x3_shape(36, Mt, Cout, Cin);
   EntryBufs bufs;
   float *U = nullptr, *D = nullptr;
   void *V = nullptr, *U3 = nullptr, *ws = nullptr;
@@ -699,8 +704,7 @@ int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats
     else
       rc = launch_wino4_in(xs, ldx, ss, d_gamma, d_beta, ssp, ld_ss, (float*)V, Bx, H, W, Cin, G, s, skip_c0, skip_scale);
     if (!rc && x3) {
-      rc = launch_gemm_bf16x3(V, U3, D, 36, (int)Mt, Cout, Cin, ws, s, !planes, false);
-      if (!rc && gemm_bf16x3_needs_sum(36, (int)Mt, Cout, Cin)) rc = launch_gemm_bf16x3_sum(D, 36, (int)Mt, Cout, Cin, ws, s);
+      rc = launch_gemm_bf16x3(V, U3, D, 36, (int)Mt, Cout, Cin, sh, ws, s, !planes);
     } else if (!rc) {
       ConvParams p{};
       p.x = (const float*)V; p.w = U; p.y = D;
@@ -836,13 +840,14 @@ int kd_layernorm_linear_bf16x3(const float* d_x, const float* d_g, const float* 
   e.hw = rows;
   e.ldy = ldy > 0 ? ldy : N;
   e.lda = C;
-  KD_REQUIRE(gemm_bf16x3_epi_ok(rows, N, C, e), "kd_layernorm_linear_bf16x3 needs rows % 256 == 0, N % 128 == 0, C % 32 == 0");
+  const X3Shape sh = entry_x3_shape(1, rows, N, C);
+  KD_REQUIRE(gemm_bf16x3_epi_ok(rows, N, C, e, sh), "kd_layernorm_linear_bf16x3 needs rows % 256 == 0, N % 128 == 0, C % 32 == 0");
   EntryBufs bufs;
   void *W3 = nullptr, *ws = nullptr;
   if (bufs.get(&W3, (size_t)N * C * 6) || bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
   int rc = launch_split3(d_w, W3, 1, N, C, s);
   if (!rc) rc = launch_layernorm(d_x, C, d_g, d_beta, nullptr, 0, (float*)d_planes, rows, C, eps, s, in_act, nullptr, nullptr, nullptr, 0, 1);
-  if (!rc) rc = launch_gemm_bf16x3(d_planes, W3, d_y, 1, rows, N, C, ws, s, false, true, &e);
+  if (!rc) rc = launch_gemm_bf16x3(d_planes, W3, d_y, 1, rows, N, C, sh, ws, s, false, true, &e);
   return entry_finish(rc, s);
 }
 

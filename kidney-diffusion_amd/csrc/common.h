@@ -162,28 +162,35 @@ struct X3Epi {
   // pixel, k = tap a_tap_c + c the channel c of its input pixel (2 oy + tap / 2, 2 ox + tap % 2); K = 4 a_tap_c
   int a_tap_c = 0, a_wi = 0, a_hi = 0;
   // GroupNorm partials of y for the layer that normalises it (SegSrc): [images][seg_nseg][hw / rows][2] doubles with rows =
-  // gemm_bf16x3_seg_rows(M, N, K) (32, or 8 where the tiles are cut in k and the summing launch leaves them), segment
+  // X3Shape::seg_rows() (32, or 8 where the tiles are cut in k and the summing launch leaves them), segment
   // (n + seg_coff) / 16 of column n; needs hw % 32 == 0
   double* seg = nullptr;
   int seg_nseg = 0, seg_coff = 0;
-  int seg_rows8 = 0;             // set by launch_gemm_bf16x3: chunks of 8 rows (gemm_bf16x3_seg_rows == 8)
+  int seg_rows8 = 0;             // set by launch_gemm_bf16x3: chunks of 8 rows (X3Shape::seg_rows() == 8)
   int wide = 0;                  // set by launch_gemm_bf16x3: 16-byte epilogue accesses (every row 16-byte aligned)
   int act = ACT_NONE;            // applied to acc + bias, before the added maps
   // > 0: PixelShuffle(2) output (upsample convs, weight rows packed n' = q N/4 + c): the width Wo of the INPUT map; y is
   // [4 M][ldy] rows of N / 4 channels; statistics chunks as conv_buf_kernel's: 4 (32-row block of the image) + q
   int pixshuf_wo = 0;
 };
-bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e);
+// The shape of a launch: P persistent workgroups; the R tiles left over after their whole rounds - all tiles when there are
+// fewer than CUs - start at tile `first` and are cut in k into S parts.  A value: whoever emits a launch (a plan, with the CU
+// count it read once at its build; a test entry point, once per call) decides it and every question and launch uses that one
+struct X3Shape {
+  int P, R, S, first;
+  bool needs_sum() const { return R && S > 1; }      // the parts' accumulators are added by launch_gemm_bf16x3_sum
+  int seg_rows() const { return needs_sum() ? 8 : 32; }   // rows per chunk of the GroupNorm partials the launch leaves (X3Epi::seg)
+};
+// a pure function of its arguments; {0, 0, 1, 0} (no launch) for dimensions without a whole tile or cus <= 0.  The launches
+// take a shape made from THEIR G, M, N, K and refuse one that does not fit them
+X3Shape gemm_bf16x3_shape(int G, int M, int N, int K, int cus);
+int gemm_bf16x3_device_cus();   // CUs of the current device (256 where it cannot be asked)
+bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e, const X3Shape& sh);
 // a_f32: A is plain fp32 rows, split into its planes by the kernel's loader waves on the way into LDS
-// The tiles left over after the whole rounds of the persistent kernel - all tiles when there are fewer than CUs - are cut
-// in k; their parts' accumulators are added (and the epilogue applied) by a second launch (launch_gemm_bf16x3_sum;
-// with_sum = true: launched here)
-int launch_gemm_bf16x3(const void* A3, const void* B3, float* C, int G, int M, int N, int K, void* ws, hipStream_t s,
+// with_sum = true: the summing launch (and with it the epilogue of the cut tiles) is launched here as well
+int launch_gemm_bf16x3(const void* A3, const void* B3, float* C, int G, int M, int N, int K, const X3Shape& sh, void* ws, hipStream_t s,
                        bool a_f32 = false, bool with_sum = true, const X3Epi* epi = nullptr);
-bool gemm_bf16x3_needs_sum(int G, int M, int N, int K);
-int gemm_bf16x3_seg_rows(int M, int N, int K);
-int launch_gemm_bf16x3_sum(float* C, int G, int M, int N, int K, const void* ws, hipStream_t s, const X3Epi* epi = nullptr);
-int gemm_bf16x3_workgroups(int G, int M, int N, int K);
+int launch_gemm_bf16x3_sum(float* C, int G, int M, int N, int K, const X3Shape& sh, const void* ws, hipStream_t s, const X3Epi* epi = nullptr);
 // launch_wino4_in writing V as the three planes the bf16x3 GEMM reads ([3][36][C/16][Mt][16] bf16; Mt % 8 == 0, C % 16 == 0)
 int launch_wino4_in3(const float* x, int ldx, const float* stats, const float* gamma, const float* beta,
                      const float* scale_shift, int ld_ss, void* V3, int B, int H, int W, int C, int G, hipStream_t s,

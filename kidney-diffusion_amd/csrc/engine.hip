@@ -8,11 +8,13 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -298,7 +300,8 @@ struct kd_unet {
   bool cond_rows_ok = true;
   kd::CondSeg* d_cond_segs = nullptr;
   uint32_t cond_row_total = 0;
-  void* x3_ws = nullptr;   // slabs of the bf16x3 GEMMs' left-over tiles (launch_gemm_bf16x3), allocated with the first such layer
+  void* x3_ws = nullptr;   // slabs of the bf16x3 GEMMs' left-over tiles, allocated with the first such layer (emit_x3_gemm)
+  int cus = 0;   // CUs of the device the plan was built on: every launch shape of its bf16x3 GEMMs (X3Shape) comes from this
 
   float* P(size_t off) const { return (float*)((off & COND_FLAG) ? cond_ws + (off & ~COND_FLAG) : ws + off); }
   ~kd_unet() {
@@ -386,11 +389,35 @@ struct Builder {
     });
   }
 
+  // ---- where the ops being emitted go
+  // Step: an ordinary per-step op (u->ops).
+  // Cond: conditioning that depends on the inputs log_snr / lowres_log_snr / text only (never on x): in u->ops too, but
+  //   flagged, and everything it allocates lives in the permanent cond region (bump-allocated, never reused), so the
+  //   sampler can snapshot / restore that region per schedule step (kd::CondTable).
+  // Static: step-invariant work, run once per sampling call (u->static_ops).
+  // Text: the text-conditioning sub-plan (u->text_ops).
+  enum class Phase { Step, Cond, Static, Text };
+  Phase phase = Phase::Step;
+  bool step_op() const { return phase == Phase::Step; }
+  bool recorded() const { return phase == Phase::Step || phase == Phase::Cond; }   // in u->ops: a row of the profile
+  struct PhaseScope {   // enters a phase; the previous one is back, once, when exit() is called or the scope ends (also by a throw)
+    Builder& b;
+    const Phase prev;
+    bool exited = false;
+    PhaseScope(Builder& b_, Phase p) : b(b_), prev(b_.phase) { b.phase = p; }
+    PhaseScope(const PhaseScope&) = delete;
+    void exit() {
+      if (!exited) b.phase = prev;
+      exited = true;
+    }
+    ~PhaseScope() { exit(); }
+  };
+  PhaseScope scope(Phase p) { return PhaseScope(*this, p); }
+  // for what is a function of the conditioning tokens alone (their K / V): hoisted into the cond region, but for the text
+  // sub-plan, which has none
+  PhaseScope cond_scope() { return PhaseScope(*this, phase == Phase::Text ? Phase::Text : Phase::Cond); }
+
   // ---- activations
-  // to_cond: the ops being emitted compute conditioning that depends on the inputs log_snr / lowres_log_snr / text only
-  // (never on x): they are flagged, and everything they allocate lives in the permanent cond region (bump-allocated,
-  // never reused), so the sampler can snapshot / restore that region per schedule step (kd::CondTable)
-  bool to_cond = false;
   size_t cond_end = 0;
   size_t cond_alloc(size_t bytes) {
     bytes = (bytes + 255) & ~size_t(255);
@@ -403,7 +430,7 @@ struct Builder {
     T t;
     t.B = b; t.H = h; t.W = w; t.C = c;
     const size_t bytes = (size_t)b * h * w * c * sizeof(float);
-    if (to_cond) {
+    if (phase == Phase::Cond) {
       t.off = cond_alloc(bytes);
       // batch-major: [B][...] as allocated, or a linear()'s flattened [1][1][B x tokens][N] (the batch still outermost)
       const size_t total = (size_t)b * h * w * c, row = total / (size_t)B;
@@ -420,7 +447,7 @@ struct Builder {
   T alloc_bytes(size_t bytes) {
     T t;
     t.B = 1; t.H = 1; t.W = 1; t.C = (int)((bytes + 3) / 4);
-    if (to_cond) {
+    if (phase == Phase::Cond) {
       t.off = cond_alloc(bytes);
       u->cond_rows_ok = false;   // a cond tensor without batch rows: the table is built step by step
       return t;
@@ -551,24 +578,26 @@ struct Builder {
     }, "gn stats HW" + std::to_string(HW) + " C" + std::to_string(C));
     return false;
   }
-  bool cond_hoist = true;  // (false inside the text sub-plan)
-  bool to_text = false;    // building the text-conditioning sub-plan: ops go to u->text_ops
-  bool to_static = false;  // emitting step-invariant work (run once per sampling call): u->static_ops
   const float* P_(const std::string& n) { return P(n); }
   void emit(std::function<int(hipStream_t)> f, std::string label = "op", int64_t macs = 0) {
-    if (to_text) {
-      u->text_ops.push_back(std::move(f));
-      return;
-    }
-    if (to_static) {
-      u->static_ops.push_back(std::move(f));
+    if (!recorded()) {
+      (phase == Phase::Text ? u->text_ops : u->static_ops).push_back(std::move(f));
       return;
     }
     u->ops.push_back(std::move(f));
     u->op_label.push_back(std::move(label));
     u->op_macs.push_back(macs);
     u->op_mfma.push_back(0);
-    u->op_is_cond.push_back(to_cond ? 1 : 0);
+    u->op_is_cond.push_back(phase == Phase::Cond ? 1 : 0);
+  }
+  // the MACs of the op just emitted: m as the reference computes it (the text sub-plan's are not the UNet's; the step-invariant
+  // share of the init conv counts although it runs once per sampling call), `issued` on the matrix cores per step
+  void count_macs(int64_t m, int64_t issued) {
+    if (phase != Phase::Text) u->macs += m;
+    if (recorded()) {
+      u->mfma_macs += issued;
+      u->op_mfma.back() = issued;
+    }
   }
 
   // ---- conv / GEMM emission
@@ -591,23 +620,28 @@ struct Builder {
     int seg_c0 = -1, seg_cn = 0;  // channel range of y the partial buffer spans (default: this launch's own range);
                                   // launches filling slices of one tensor name the same span and share the buffer
   };
-  // a 1x1 conv / token GEMM that runs on the bf16x3 kernel's epilogue form (kernels_gemm_bf16x3.hip)
-  bool x3_linear_ok(const T& x, int Cout, int K, int stride, int pad, const ConvOpt& o) const {
-    if (cfg.gemm_bf16x3 < 0 || cfg.conv_algo != 0 || cfg.x3_linear < 0 || to_text || to_static || to_cond) return false;
-    if (K != 1 || stride != 1 || pad != 0 || o.rowrun || o.wz_rows || o.out_external) return false;
-    if (o.out_mode != OUT_NHWC && o.out_mode != OUT_PIXSHUF) return false;
-    if (o.gate_src && o.res) return false;
+  // What every layer on the bf16x3 kernel's epilogue form (kernels_gemm_bf16x3.hip) must pass: a default-algorithm plan's
+  // ordinary step op, whole tiles and at least 64 of them, K of at least min_k where the launch runs whole rounds, and the
+  // epilogue's own conditions for the launch shape this plan will use
+  bool x3_epi_layer_ok(int64_t M, int Cout, int K, int min_k, const X3Epi& e) const {
+    if (cfg.gemm_bf16x3 < 0 || cfg.conv_algo != 0 || cfg.x3_linear < 0 || !step_op()) return false;
+    if (Cout % 128 || M % 256 || (M / 256) * (Cout / 128) < 64) return false;   // below 64 tiles the k-parts get too short
     // measured per launch against conv_buf_kernel at batch 16 (profiles/README.md, round 5): K >= 256 wins wherever the
     // launch runs whole rounds (256 -> 128 on the 256 x 256 map 748 -> 645 us); with fewer tiles than CUs every tile is cut
     // in k and a second launch adds the parts (10-15 us): K = 512 then only draws level (45.5 against 45.7 us), K >= 1024 wins
     // (K = 128 where the launch runs whole rounds: the 128 -> 512 upsample conv of the 128 x 128 map 455 -> 388 us)
-    if (x.C % 32 || Cout % 128) return false;
-    const int64_t M = x.rows();
-    if (M % 256 || (M / 256) * (Cout / 128) < 64) return false;   // below 64 tiles the k-parts get too short
-    const bool cut = gemm_bf16x3_needs_sum(1, (int)M, Cout, x.C);
-    const int min_k = cfg.x3_linear > 0 ? cfg.x3_linear : cut ? 256 : 128;
-    if (x.C < min_k) return false;
-    if (cfg.x3_linear == 0 && x.C < 1024 && cut) return false;
+    const X3Shape sh = gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus);
+    const bool cut = sh.needs_sum();
+    if (K < (cfg.x3_linear > 0 ? cfg.x3_linear : cut ? 256 : min_k)) return false;
+    if (cfg.x3_linear == 0 && K < 1024 && cut) return false;
+    return gemm_bf16x3_epi_ok(M, Cout, K, e, sh);
+  }
+  // a 1x1 conv / token GEMM that runs on it
+  bool x3_linear_ok(const T& x, int Cout, int K, int stride, int pad, const ConvOpt& o) const {
+    if (K != 1 || stride != 1 || pad != 0 || o.rowrun || o.wz_rows || o.out_external) return false;
+    if (o.out_mode != OUT_NHWC && o.out_mode != OUT_PIXSHUF) return false;
+    if (o.gate_src && o.res) return false;
+    if (x.C % 32 || (x.coff & 3)) return false;   // (the launch wants 16-byte aligned rows of A)
     X3Epi e;
     e.lda = x.LD();
     if (x.x3p && (!x.dense() || x.coff)) return false;
@@ -620,7 +654,7 @@ struct Builder {
     e.hw = x.H * x.W;
     e.act = o.act;
     e.pixshuf_wo = o.out_mode == OUT_PIXSHUF ? x.W : 0;
-    return gemm_bf16x3_epi_ok(M, Cout, x.C, e);
+    return x3_epi_layer_ok(x.rows(), Cout, x.C, 128, e);
   }
   // images per launch of a 1x1 conv on the bf16x3 kernel: the whole batch, or - where the maps of the whole batch pass the
   // 2 GB its 32-bit offsets span (unet3's outer levels at batch 8) - the largest divisor of the batch that fits; 0 = not on it
@@ -637,6 +671,35 @@ struct Builder {
       if (xs.B <= cap && x3_linear_ok(xs, Cout, K, stride, pad, o)) return xs.B;
     }
     return whole ? x.B : 0;
+  }
+  // One bf16x3 GEMM of the plan, C[G][M][N] = A[G][M][K] W3[G][N][K]^T at byte offsets a_off / c_off of the workspace: the
+  // slabs of the k-parts (with the first such layer), the launch with the shape this plan's CU count gives, its MACs
+  // (`macs` algorithmic, 6 G M N K bf16 issued), and the launch that adds the k-parts where that shape cuts tiles (its own
+  // op: the whole chip adds them).  epi_of: yields the X3Epi at run time (the epilogue form, G = 1; applied by the summing
+  // launch where there is one), or nullptr.  Rows of the profile: `stem` x3 (without an epilogue: `stem` gemm bf16x3) and
+  // `stem` x3 sum, each followed by `shape`
+  template <class EpiOf>
+  void emit_x3_gemm(size_t a_off, const void* W3, size_t c_off, int G, int64_t M, int N, int K, bool a_f32, EpiOf epi_of,
+                    const std::string& stem, const std::string& shape, int64_t macs) {
+    constexpr bool has_epi = !std::is_same<EpiOf, std::nullptr_t>::value;
+    if (!u->x3_ws) KD_HIP_THROW(hipMalloc(&u->x3_ws, gemm_bf16x3_workspace_bytes()));
+    const X3Shape sh = gemm_bf16x3_shape(G, (int)M, N, K, u->cus);
+    kd_unet* uu = u;
+    auto launch = [=](hipStream_t s, bool sum) {   // the GEMM, or the launch that adds its k-parts
+      X3Epi e;
+      const X3Epi* ep = nullptr;
+      if constexpr (has_epi) {
+        e = epi_of();
+        ep = &e;
+      }
+      if (sum) return launch_gemm_bf16x3_sum(uu->P(c_off), G, (int)M, N, K, sh, uu->x3_ws, s, ep);
+      return launch_gemm_bf16x3(uu->P(a_off), W3, uu->P(c_off), G, (int)M, N, K, sh, uu->x3_ws, s, a_f32, false, ep);
+    };
+    emit([=](hipStream_t s) { return launch(s, false); }, stem + (has_epi ? " x3" : " gemm bf16x3") + shape, macs);
+    u->macs += macs;
+    u->op_mfma.back() = 6 * G * M * N * K;   // bf16 MACs
+    u->mfma_bf16_macs += u->op_mfma.back();
+    if (sh.needs_sum()) emit([=](hipStream_t s) { return launch(s, true); }, stem + " x3 sum" + shape);
   }
   T conv(const T& x, const float* w, const float* bias, int Cout, int K, int stride, int pad, const ConvOpt& o) {
     if (x.x3p && !x3_linear_ok(x, Cout, K, stride, pad, o))
@@ -680,17 +743,15 @@ struct Builder {
     const int ks = conv_ksplit(p);
     T part;
     if (ks > 1) {   // (scratch of this launch pair, not conditioning state: never in the cond region / table)
-      const bool tc = to_cond;
-      to_cond = false;
+      auto ph = scope(phase == Phase::Cond ? Phase::Step : phase);
       part = alloc_bytes((size_t)ks * x.B * Ho * Wo * Cout * sizeof(float));
-      to_cond = tc;
     }
     const size_t parto = part.off;
     // GroupNorm partials of the output, left by the epilogue (channels [yoff, yoff + Cout) of y, or the Cout / 4
     // shuffled channels): several launches filling slices of one tensor (init conv) share the chunk count
     size_t sego = 0;
     int seg_nseg = 0, seg_c0 = 0, seg_nchunk = 0;
-    if (o.want_seg && !ext && !to_text && !to_static && !to_cond) {
+    if (o.want_seg && !ext && step_op()) {
       const int cw = o.out_mode == OUT_PIXSHUF ? Cout / 4 : Cout;
       seg_c0 = o.seg_c0 >= 0 ? o.seg_c0 : o.yoff;   // in channels of the tensor y (a slice counts from its own first)
       const int span = o.seg_c0 >= 0 ? o.seg_cn : cw;
@@ -704,7 +765,7 @@ struct Builder {
       const int lin3_b = x3_linear_images(x, Cout, K, stride, pad, o);
       const bool lin3 = lin3_b > 0;
       int nchunk = conv_seg_chunks(probe) > 0 && lin3 && o.out_mode == OUT_NHWC
-                       ? Ho * Wo / gemm_bf16x3_seg_rows(lin3_b * Ho * Wo, Cout, x.C)
+                       ? Ho * Wo / gemm_bf16x3_shape(1, lin3_b * Ho * Wo, Cout, x.C, u->cus).seg_rows()
                        : conv_seg_chunks(probe);
       // (the bf16x3 PixelShuffle epilogue takes maps 16 pixels wide - conv_buf_kernel's wants 32 - with the same chunks: four
       // sub-positions per 32 input pixels)
@@ -731,7 +792,6 @@ struct Builder {
       const float* W3 = cached("x3lin:" + std::to_string((uintptr_t)w) + ":" + std::to_string(Cout) + "x" + std::to_string(Cin),
                                ((size_t)Cout * Cin * 3 + 1) / 2,
                                [&](float* dst) { KD_THROW_IF(launch_split3(w, dst, 1, Cout, Cin, 0)); });
-      if (!u->x3_ws) KD_HIP_THROW(hipMalloc(&u->x3_ws, gemm_bf16x3_workspace_bytes()));
       X3Epi base;
       base.bias = bias;
       base.ldres = p.ldres;
@@ -764,19 +824,8 @@ struct Builder {
         };
         const std::string shape = " M" + std::to_string(M) + " Cin" + std::to_string(Cin) + " Cout" + std::to_string(Cout);
         const int64_t m = o.macs_override >= 0 ? o.macs_override : M * Cout * Cin;
-        const bool a_f32 = !x.x3p;   // (planes: written by the LayerNorm in front, the loader waves only move them)
-        emit([=](hipStream_t s) {
-          const X3Epi e = epi_of();
-          return launch_gemm_bf16x3(uu->P(xo_s), W3, uu->P(yo_s) + yoff, 1, (int)M, Cout, Cin, uu->x3_ws, s, a_f32, false, &e);
-        }, "conv k1 x3" + shape, m);
-        u->macs += m;
-        u->op_mfma.back() = 6 * M * Cout * Cin;   // bf16 MACs
-        u->mfma_bf16_macs += u->op_mfma.back();
-        if (gemm_bf16x3_needs_sum(1, (int)M, Cout, Cin))   // every tile cut in k (fewer tiles than CUs): the parts are added, and the epilogue applied, here
-          emit([=](hipStream_t s) {
-            const X3Epi e = epi_of();
-            return launch_gemm_bf16x3_sum(uu->P(yo_s) + yoff, 1, (int)M, Cout, Cin, uu->x3_ws, s, &e);
-          }, "conv k1 x3 sum" + shape);
+        // (planes: written by the LayerNorm in front, the loader waves only move them)
+        emit_x3_gemm(xo_s, W3, yo_s + (size_t)yoff * sizeof(float), 1, M, Cout, Cin, !x.x3p, epi_of, "conv k1", shape, m);
       }   // sets of images
       if (ks > 1) free(part);
       return y;
@@ -799,42 +848,43 @@ struct Builder {
     if (ks > 1) free(part);
     int cin = o.cin_logical > 0 ? o.cin_logical : x.C;
     int64_t m = o.macs_override >= 0 ? o.macs_override : (int64_t)x.B * Ho * Wo * Cout * cin * K * K;
-    if (!to_text && !to_static) {
+    if (recorded()) {
       u->op_label.back() = "conv k" + std::to_string(K) + " s" + std::to_string(stride) + " M" +
                            std::to_string((int64_t)x.B * Ho * Wo) + " Cin" + std::to_string(x.C) + " Cout" +
                            std::to_string(Cout);
       u->op_macs.back() = m;
     }
-    // algorithmic MACs of one forward as the reference computes it: the step-invariant part of the
-    // init conv is counted even though the engine runs it once per sampling call instead of per step
-    if (!to_text) u->macs += m;
-    if (!to_text && !to_static) {
-      const int64_t issued = (int64_t)x.B * Ho * Wo * Cout * p.Cin * p.KH * p.KW;
-      u->mfma_macs += issued;
-      u->op_mfma.back() = issued;
-    }
+    count_macs(m, (int64_t)x.B * Ho * Wo * Cout * p.Cin * p.KH * p.KW);
     return y;
   }
+  // x, res and dst of a token GEMM as the [1][1][rows][C] maps conv() and x3_linear_ok() take (`o` points into this)
+  struct FlatLinear {
+    T x, res, dst;
+    ConvOpt o;
+    static T flat(const T& t) {
+      T f = t;
+      f.B = 1; f.H = 1; f.W = (int)t.rows();
+      return f;
+    }
+    FlatLinear(const T& x_, const T* res_, const T* dst_, int act) : x(flat(x_)) {
+      o.act = act;
+      if (res_) {
+        res = flat(*res_);
+        o.res = &res;
+      }
+      if (dst_) {
+        dst = flat(*dst_);
+        o.dst = &dst;
+      }
+    }
+    FlatLinear(const FlatLinear&) = delete;
+  };
   // token GEMM y[M,N] = x[M,K] @ w[N,K]^T
   // `dst`: write into this tensor (a slice of a wider buffer: a skip tensor in its concat slot) instead of a new one
   T linear(const T& x, const float* w, const float* bias, int N, int act = ACT_NONE, const T* res = nullptr,
            const T* dst = nullptr) {
-    T xf = x;
-    xf.B = 1; xf.H = 1; xf.W = (int)x.rows();
-    ConvOpt o;
-    o.act = act;
-    T rf, df;
-    if (res) {
-      rf = *res;
-      rf.B = 1; rf.H = 1; rf.W = (int)res->rows();
-      o.res = &rf;
-    }
-    if (dst) {
-      df = *dst;
-      df.B = 1; df.H = 1; df.W = (int)dst->rows();
-      o.dst = &df;
-    }
-    T y = conv(xf, w, bias, N, 1, 1, 0, o);
+    const FlatLinear f(x, res, dst, act);
+    T y = conv(f.x, w, bias, N, 1, 1, 0, f.o);
     y.B = x.B; y.H = x.H; y.W = x.W;
     return y;
   }
@@ -845,7 +895,7 @@ struct Builder {
     emit([=](hipStream_t s) {
       return launch_linear_skinny(uu->P(x_off), ldx, w, bias, uu->P(y_off), ldy, M, K, N, in_act, act, s);
     }, "skinny M" + std::to_string(M) + " K" + std::to_string(K) + " N" + std::to_string(N), (int64_t)M * K * N);
-    if (!to_text) u->macs += (int64_t)M * K * N;
+    if (phase != Phase::Text) u->macs += (int64_t)M * K * N;
   }
 
   // in_act: applied to x on the way in (ACT_GELU: the feed-forward's GELU when its GEMM stores the raw product);
@@ -853,7 +903,7 @@ struct Builder {
   // planes & 1 / & 2: y / y2 is read by one bf16x3 GEMM and nothing else - left as that kernel's three bf16 planes
   T layernorm(const T& x, const float* g, const float* beta, const T* res = nullptr, int in_act = ACT_NONE,
               const float* g2 = nullptr, T* y2 = nullptr, bool want_seg = false, int planes = 0) {
-    if (!x3_planes_on || x.C % 16 || x.C > 4096 || to_cond || to_text || to_static) planes = 0;
+    if (!x3_planes_on || x.C % 16 || x.C > 4096 || !step_op()) planes = 0;
     auto alloc_out = [&](bool pl) {
       if (!pl) return alloc(x.B, x.H, x.W, x.C);
       T t = alloc_bytes((size_t)x.rows() * x.C * 6);
@@ -869,7 +919,7 @@ struct Builder {
     int rows = (int)x.rows(), C = x.C, ldx = x.LD(), ldres = res ? res->LD() : 0;
     // the output feeds a GroupNorm (the ResnetBlock's block2 behind its cross-attention): one chunk of partials per pixel
     const int hw = x.HW();
-    const bool sg = want_seg && !to_cond && !to_text && !to_static && C % 16 == 0 && C <= 4096 && x.B * hw == rows;
+    const bool sg = want_seg && step_op() && C % 16 == 0 && C <= 4096 && x.B * hw == rows;
     const size_t sgo = sg ? add_seg(y, 0, C / 16, hw) : 0;
     kd_unet* uu = u;
     emit([=](hipStream_t s) {
@@ -881,22 +931,9 @@ struct Builder {
   // would linear(x, .., N) run on the bf16x3 kernel (x3_linear_ok on the flattened rows)?
   // (x stands for a dense tensor of its shape: the LayerNorm output the GEMM will read)
   bool linear_is_x3(const T& x, int N, const T* res = nullptr, const T* dst = nullptr) const {
-    T xf = x;
-    xf.B = 1; xf.H = 1; xf.W = (int)x.rows();
-    xf.ld = 0; xf.coff = 0;
-    ConvOpt o;
-    T rf, df;
-    if (res) {
-      rf = *res;
-      rf.B = 1; rf.H = 1; rf.W = (int)res->rows();
-      o.res = &rf;
-    }
-    if (dst) {
-      df = *dst;
-      df.B = 1; df.H = 1; df.W = (int)dst->rows();
-      o.dst = &df;
-    }
-    return x3_linear_ok(xf, N, 1, 1, 0, o);
+    FlatLinear f(x, res, dst, ACT_NONE);
+    f.x.ld = 0; f.x.coff = 0;
+    return x3_linear_ok(f.x, N, 1, 1, 0, f.o);
   }
 
   // GroupNorm -> [FiLM: scale/shift rows of t_ss at column ss_col] -> SiLU as its own pass (layers the fused conv
@@ -950,12 +987,12 @@ struct Builder {
     T xn = layernorm(x, P(pre + ".norm.g", dim), nullptr);
     T q = linear(xn, P(pre + ".to_q.weight", (int64_t)inner * dim), nullptr, inner);
     free(xn);
-    // K / V of the conditioning tokens: a function of c alone (cond region, see to_cond)
-    const bool was_cond = to_cond;
-    to_cond = cond_hoist;
-    T kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
-    if (cfg.attn_qk_norm) qk_norm(kv, 2 * inner, H, k_scale_of(pre));
-    to_cond = was_cond;
+    T kv;
+    {   // K / V of the conditioning tokens: a function of c alone (cond region, see Phase::Cond)
+      auto ph = cond_scope();
+      kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
+      if (cfg.attn_qk_norm) qk_norm(kv, 2 * inner, H, k_scale_of(pre));
+    }
     const float* nkv = null_kv_of(pre);
     if (cfg.attn_qk_norm) qk_norm(q, inner, H, q_scale_of(pre));
     T o = alloc(x.B, x.H, x.W, inner);
@@ -1013,14 +1050,12 @@ struct Builder {
     T ckv;
     bool has_ctx = ctx != nullptr;
     if (has_ctx) {   // K / V of the context tokens: a function of c alone (cond region)
-      const bool was_cond = to_cond;
-      to_cond = cond_hoist;
+      auto ph = cond_scope();
       T cn = layernorm(*ctx, P(a + ".to_context.0.weight", ctx->C), P(a + ".to_context.0.bias", ctx->C));
       ckv = linear(cn, P(a + ".to_context.1.weight", (int64_t)2 * D * ctx->C), P(a + ".to_context.1.bias", 2 * D),
                    2 * D);
       free(cn);
       if (cfg.attn_qk_norm) qk_norm(ckv, 2 * D, 1, k_scale_of(a));
-      to_cond = was_cond;
     }
     const float* nkv = null_kv_of(a);
     if (cfg.attn_qk_norm) {
@@ -1172,7 +1207,7 @@ struct Builder {
   int wino4_images(const T& x, int cout) const {
     const int cap = cfg.wino4_max_images > 0 ? cfg.wino4_max_images : x.B;
     if (cap >= x.B && wino4_whole_ok(x, cout)) return x.B;
-    if (cap >= x.B && (cfg.conv_algo != 0 || cfg.wino43_min_cin != 0 || cfg.gemm_bf16x3 < 0 || to_text || to_static)) return 0;
+    if (cap >= x.B && (cfg.conv_algo != 0 || cfg.wino43_min_cin != 0 || cfg.gemm_bf16x3 < 0 || !recorded())) return 0;
     if (cap < x.B && !wino4_whole_ok(x, cout)) return 0;   // (the test knob cuts layers the plan takes, nothing else)
     for (int ns = 2; ns <= x.B; ++ns) {
       if (x.B % ns) continue;
@@ -1229,7 +1264,7 @@ struct Builder {
                       [&](float* dst) { KD_THROW_IF(launch_wino4_pack(wsrc, dst, Cout, Cin, 0)); });
     emit_gn_stats(x, gamma, beta, ss_col, nullptr);
     // the 36 GEMMs as fp32-class products on the bf16 matrix pipe (kernels_gemm_bf16x3.hip) where the shape fits its tile
-    const bool x3 = cfg.gemm_bf16x3 >= 0 && !to_text && !to_static && gemm_bf16x3_ok(36, Mt, Cout, Cin);
+    const bool x3 = cfg.gemm_bf16x3 >= 0 && recorded() && gemm_bf16x3_ok(36, Mt, Cout, Cin);
     // V written as planes by the input transform, or as fp32, split by the GEMM's loader waves on the way into LDS: the
     // transform then writes a third less and is that much faster, but the loaders' vector work beside the MFMA waves costs a
     // GEMM that is bound by the matrix pipe 10-15 %.  Per layer (same box, batch 16, transform + GEMM in us, planes / fp32;
@@ -1266,17 +1301,8 @@ struct Builder {
       if (x3) {
         const float* U3 = cached("wino4x3:" + conv_prefix, ((size_t)36 * Cout * Cin * 3 + 1) / 2,
                                  [&](float* dst) { KD_THROW_IF(launch_split3(U, dst, 36, Cout, Cin, 0)); });
-        const size_t vo = V.off, d_o = D.off;
-        const int64_t macs = (int64_t)Bx * HW * Cout * Cin * 9;   // the algorithmic MACs of the 3x3 conv it replaces
-        if (!u->x3_ws) KD_HIP_THROW(hipMalloc(&u->x3_ws, gemm_bf16x3_workspace_bytes()));
-        emit([=](hipStream_t s) { return launch_gemm_bf16x3(uu->P(vo), U3, uu->P(d_o), 36, (int)Mt, Cout, Cin, uu->x3_ws, s, !x3_planes, false); },
-             "wino4 gemm bf16x3" + shape, macs);
-        u->macs += macs;
-        u->op_mfma.back() = 6 * 36 * Mt * Cout * Cin;   // bf16 MACs
-        u->mfma_bf16_macs += u->op_mfma.back();
-        if (gemm_bf16x3_needs_sum(36, (int)Mt, Cout, Cin))   // the left-over tiles' k-parts (its own launch: the whole chip adds them)
-          emit([=](hipStream_t s) { return launch_gemm_bf16x3_sum(uu->P(d_o), 36, (int)Mt, Cout, Cin, uu->x3_ws, s); },
-               "wino4 x3 sum" + shape);
+        // (the algorithmic MACs of the 3x3 conv it replaces)
+        emit_x3_gemm(V.off, U3, D.off, 36, Mt, Cout, Cin, !x3_planes, nullptr, "wino4", shape, (int64_t)Bx * HW * Cout * Cin * 9);
       } else {
         ConvOpt o;
         o.wz_rows = (int)Mt;
@@ -1284,7 +1310,7 @@ struct Builder {
         o.dst = &D;
         o.macs_override = (int64_t)Bx * HW * Cout * Cin * 9;   // the algorithmic MACs of the 3x3 conv it replaces
         conv(V, U, nullptr, Cout, 1, 1, 0, o);
-        if (!to_text && !to_static) u->op_label.back() = "wino4 gemm" + shape;
+        if (recorded()) u->op_label.back() = "wino4 gemm" + shape;
       }
       {
         const size_t sgo = sgo_all + (size_t)b0 * (Cout / 16) * ((H / 4) * (W / 4)) * 2 * sizeof(double);
@@ -1352,7 +1378,7 @@ struct Builder {
       o.dst = &Ds;
       o.macs_override = nt * 4 * Cout * Cin * 9;  // algorithmic MACs of the share of the 3x3 conv it replaces
       conv(Vs, U, nullptr, Cout, 1, 1, 0, o);
-      if (!to_text && !to_static) u->op_label.back() = "wino gemm" + shape;
+      if (recorded()) u->op_label.back() = "wino gemm" + shape;
       {
         size_t d_o = D.off, yo = y.off, ro = res ? res->at() : 0;
         bool hr = res != nullptr;
@@ -1410,12 +1436,7 @@ struct Builder {
     }, "wino fused M" + std::to_string((int64_t)Bx * H * W) + " Cin" + std::to_string(Cin) + " Cout" +
            std::to_string(Cout), m);
     free(ab);
-    if (!to_text) u->macs += m;
-    if (!to_text && !to_static) {
-      const int64_t issued = (int64_t)Bx * H * W * 4 * Cout * ((Cin / 4 + 3) / 4 * 16);
-      u->mfma_macs += issued;
-      u->op_mfma.back() = issued;
-    }
+    count_macs(m, (int64_t)Bx * H * W * 4 * Cout * ((Cin / 4 + 3) / 4 * 16));
     return y;
   }
 
@@ -1533,13 +1554,8 @@ struct Builder {
     return e;
   }
   bool downsample_x3_ok(const T& x, int Cout) const {
-    if (cfg.gemm_bf16x3 < 0 || cfg.conv_algo != 0 || cfg.x3_linear < 0 || to_text || to_static || to_cond) return false;
-    if ((x.H & 1) || (x.W & 1) || x.C % 16 || Cout % 128) return false;
-    const int K = 4 * x.C;
-    const int64_t M = (int64_t)x.B * (x.H / 2) * (x.W / 2);
-    if (K < (cfg.x3_linear > 0 ? cfg.x3_linear : 256) || M % 256 || (M / 256) * (Cout / 128) < 64) return false;
-    if (cfg.x3_linear == 0 && K < 1024 && gemm_bf16x3_needs_sum(1, (int)M, Cout, K)) return false;
-    return gemm_bf16x3_epi_ok(M, Cout, K, downsample_x3_epi(x, Cout));
+    if ((x.H & 1) || (x.W & 1) || x.C % 16) return false;
+    return x3_epi_layer_ok((int64_t)x.B * (x.H / 2) * (x.W / 2), Cout, 4 * x.C, 256, downsample_x3_epi(x, Cout));
   }
   T downsample_x3(const T& x, const std::string& pre, const float* w_taps /*[tap][O][C]*/, const float* bias, int Cout) {
     const int C = x.C, K = 4 * C, Ho = x.H / 2, Wo = x.W / 2;
@@ -1557,14 +1573,11 @@ struct Builder {
       KD_THROW_IF(rc);
       KD_HIP_THROW(er);
     });
-    if (!u->x3_ws) KD_HIP_THROW(hipMalloc(&u->x3_ws, gemm_bf16x3_workspace_bytes()));
     T y = alloc(x.B, Ho, Wo, Cout);
     const X3Epi base = downsample_x3_epi(x, Cout);
     // the output feeds the GroupNorm of the level's first ResnetBlock: partials from the epilogue
     const bool sg = Cout % 16 == 0 && (Ho * Wo) % 32 == 0;
-    const int seg_rows = gemm_bf16x3_seg_rows((int)M, Cout, K);
-    const size_t sgo = sg ? add_seg(y, 0, Cout / 16, Ho * Wo / seg_rows) : 0;
-    const size_t xo = x.at(), yo = y.off;
+    const size_t sgo = sg ? add_seg(y, 0, Cout / 16, Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows()) : 0;
     kd_unet* uu = u;
     auto epi_of = [=]() {
       X3Epi e = base;
@@ -1576,19 +1589,7 @@ struct Builder {
       return e;
     };
     const std::string shape = " M" + std::to_string(M) + " Cin" + std::to_string(C) + " Cout" + std::to_string(Cout);
-    const int64_t m = M * Cout * K;
-    emit([=](hipStream_t s) {
-      const X3Epi e = epi_of();
-      return launch_gemm_bf16x3(uu->P(xo), W3, uu->P(yo), 1, (int)M, Cout, K, uu->x3_ws, s, true, false, &e);
-    }, "conv k2 x3" + shape, m);
-    u->macs += m;
-    u->op_mfma.back() = 6 * m;   // bf16 MACs
-    u->mfma_bf16_macs += 6 * m;
-    if (gemm_bf16x3_needs_sum(1, (int)M, Cout, K))
-      emit([=](hipStream_t s) {
-        const X3Epi e = epi_of();
-        return launch_gemm_bf16x3_sum(uu->P(yo), 1, (int)M, Cout, K, uu->x3_ws, s, &e);
-      }, "conv k2 x3 sum" + shape);
+    emit_x3_gemm(x.at(), W3, y.off, 1, M, Cout, K, true, epi_of, "conv k2", shape, M * Cout * K);
     return y;
   }
   T downsample(const T& x, const std::string& pre, int dim_out) {  // pixel-unshuffle + conv1x1 == 2x2/s2 conv

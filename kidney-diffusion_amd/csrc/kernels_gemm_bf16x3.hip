@@ -782,23 +782,21 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(const float* __restrict_
   for (int k = 0; k < 4; ++k) c[(int64_t)k * N] = v[k];
 }
 
-static int x3_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    cus = n;
-  }
-  return cus;
+// CUs of the current device: what a plan (kd_unet::cus) or a test entry point reads ONCE and hands to gemm_bf16x3_shape
+int gemm_bf16x3_device_cus() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+    n = 256;
+  return n;
 }
 
 // Shape of a launch: P persistent workgroups; `rounds` whole rounds of P tiles; the R tiles left over (the first is tile
 // `first`) are cut in k into S parts of an equal, even number of at least eight stages (S = 1: not cut), one part per
 // workgroup q < S R.  With fewer tiles than CUs (token GEMMs of the 16 x 16 level: 64-128 tiles) there is no whole round:
 // every tile is cut and P = S R <= CUs.
-static void x3_shape(int G, int M, int N, int K, int* P, int* R, int* S, int* first) {
-  const int tiles = (M / BM) * (N / BN) * G, nk = K / BK, cus = x3_cus();
+X3Shape gemm_bf16x3_shape(int G, int M, int N, int K, int cus) {
+  const int tiles = (M / BM) * (N / BN) * G, nk = K / BK;
+  if (tiles <= 0 || cus <= 0) return X3Shape{0, 0, 1, 0};   // (no launch: gemm_bf16x3_ok refuses the shape)
   auto split_of = [&](int r, int p) {
     int s = p / r;
     if (s > X3_MAX_SPLIT) s = X3_MAX_SPLIT;
@@ -807,51 +805,40 @@ static void x3_shape(int G, int M, int N, int K, int* P, int* R, int* S, int* fi
     return s < 1 ? 1 : s;
   };
   if (tiles < cus) {
-    *R = tiles;
-    *first = 0;
-    *S = split_of(tiles, cus);
-    *P = tiles * *S;
-    return;
+    const int S = split_of(tiles, cus);
+    return X3Shape{tiles * S, tiles, S, 0};
   }
-  *P = cus;
-  *R = tiles % cus;
-  *first = tiles - *R;
-  *S = *R ? split_of(*R, cus) : 1;
+  const int R = tiles % cus;
+  return X3Shape{cus, R, R ? split_of(R, cus) : 1, tiles - R};
 }
 
-// workgroups of the launch
-int gemm_bf16x3_workgroups(int G, int M, int N, int K) {
-  int P, R, S, first;
-  x3_shape(G, M, N, K, &P, &R, &S, &first);
-  return P;
+// is `sh` a shape of these dimensions (the GEMM and the summing launch must agree on the left-over tiles, and every part
+// needs its slab)?  What gemm_bf16x3_shape gives for any CU count up to X3_MAX_WG passes
+static bool x3_shape_fits(const X3Shape& sh, int G, int M, int N) {
+  const int tiles = (M / BM) * (N / BN) * G;
+  if (sh.P <= 0 || sh.P > X3_MAX_WG || sh.R < 0 || sh.S < 1 || sh.S > X3_MAX_SPLIT || sh.first + sh.R != tiles) return false;
+  return sh.first == 0 ? sh.P == sh.R * sh.S : sh.first % sh.P == 0 && sh.R * sh.S <= sh.P;
 }
+
 size_t gemm_bf16x3_workspace_bytes() {   // a slab per workgroup
   return (size_t)X3_MAX_WG * BM * BN * sizeof(float);
 }
 
-// rows per chunk of the GroupNorm partials a launch leaves (X3Epi::seg): 32 from the kernel's epilogue, 8 from the summing launch
-int gemm_bf16x3_seg_rows(int M, int N, int K) { return gemm_bf16x3_needs_sum(1, M, N, K) ? 8 : 32; }
-bool gemm_bf16x3_needs_sum(int G, int M, int N, int K) {
-  int P, R, S, first;
-  x3_shape(G, M, N, K, &P, &R, &S, &first);
-  return R && S > 1;
-}
-int launch_gemm_bf16x3_sum(float* C, int G, int M, int N, int K, const void* ws, hipStream_t s, const X3Epi* epi) {
-  int P, R, S, first;
-  x3_shape(G, M, N, K, &P, &R, &S, &first);
-  if (!(R && S > 1)) return 0;
+int launch_gemm_bf16x3_sum(float* C, int G, int M, int N, int K, const X3Shape& sh, const void* ws, hipStream_t s, const X3Epi* epi) {
+  if (!sh.needs_sum()) return 0;
+  KD_REQUIRE(x3_shape_fits(sh, G, M, N), "bf16x3 GEMM: the launch shape is not one of these dimensions");
+  const dim3 grid((unsigned)(sh.R * 32));
   if (epi)
-    hipLaunchKernelGGL(sum_slabs_kernel<true>, dim3((unsigned)(R * 32)), dim3(256), 0, s, (const float*)ws, C, G, M, N, S, first, *epi);
+    hipLaunchKernelGGL(sum_slabs_kernel<true>, grid, dim3(256), 0, s, (const float*)ws, C, G, M, N, sh.S, sh.first, *epi);
   else
-    hipLaunchKernelGGL(sum_slabs_kernel<false>, dim3((unsigned)(R * 32)), dim3(256), 0, s, (const float*)ws, C, G, M, N, S, first,
-                       X3Epi{});
+    hipLaunchKernelGGL(sum_slabs_kernel<false>, grid, dim3(256), 0, s, (const float*)ws, C, G, M, N, sh.S, sh.first, X3Epi{});
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // the epilogue form's extra conditions (G = 1): row strides that keep every byte offset below 2^31, one image per tile
 // where a per-image gate is applied, 4-byte aligned maps
-bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e) {
+bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e, const X3Shape& sh) {
   if (!gemm_bf16x3_ok(1, M, N, K)) return false;
   if ((e.a_tap_c ? e.lda < e.a_tap_c : e.lda < K) || (e.ldy < N && !e.pixshuf_wo) || (e.lda & 3)) return false;
   // gather form (2 x 2 / stride-2 conv): four taps of C channels, whole stage units per tap, even map sides, whole images
@@ -862,11 +849,11 @@ bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e) {
   if (e.res && (e.ldres < N || M * (int64_t)e.ldres * 4 >= ((int64_t)1 << 31))) return false;
   if (e.gate_src && (!e.gate || e.ldgs < N || e.hw <= 0 || e.hw % BM || M * (int64_t)e.ldgs * 4 >= ((int64_t)1 << 31))) return false;
   // output statistics: whole 32-row blocks per image, segments of 16 channels (a launch whose tiles are cut in k leaves
-  // them from its summing launch, one chunk per 8 rows: gemm_bf16x3_seg_rows)
+  // them from its summing launch, one chunk per 8 rows: X3Shape::seg_rows)
   if (e.seg && (e.hw <= 0 || e.hw % 32 || M % e.hw || (e.seg_coff & 15) || e.seg_nseg <= 0)) return false;
   // PixelShuffle(2) output: whole 16-pixel runs of an image row and 32-channel runs of a sub-position per accumulator block;
   // the kernel's epilogue only (no tile cut in k), no added maps
-  if (e.pixshuf_wo && (e.pixshuf_wo % 16 || M % e.pixshuf_wo || (N & 127) || e.res || e.gate_src || gemm_bf16x3_needs_sum(1, (int)M, N, K) ||
+  if (e.pixshuf_wo && (e.pixshuf_wo % 16 || M % e.pixshuf_wo || (N & 127) || e.res || e.gate_src || sh.needs_sum() ||
                        4 * M * (int64_t)e.ldy >= ((int64_t)1 << 29) || e.ldy < N / 4))
     return false;
   if (e.act < ACT_NONE || e.act > ACT_SIGMOID) return false;
@@ -876,20 +863,20 @@ bool gemm_bf16x3_epi_ok(int64_t M, int N, int K, const X3Epi& e) {
 // ws: gemm_bf16x3_workspace_bytes() bytes (the slabs of the left-over tiles' parts); one per stream of launches (a plan's
 // launches are ordered on its stream)
 // a_f32: A is plain fp32 [G][M][K] (split by the kernel's loader waves) instead of three planes
-// with_sum = false: the caller launches launch_gemm_bf16x3_sum behind it (where gemm_bf16x3_needs_sum)
+// sh: gemm_bf16x3_shape(G, M, N, K, CUs) as its caller decided it (a plan: once, at plan build)
+// with_sum = false: the caller launches launch_gemm_bf16x3_sum behind it (where sh.needs_sum())
 // epi != nullptr: the token-GEMM / 1x1-conv form (G = 1; gemm_bf16x3_epi_ok)
-int launch_gemm_bf16x3(const void* A3, const void* B3, float* C, int G, int M, int N, int K, void* ws, hipStream_t s, bool a_f32,
-                       bool with_sum, const X3Epi* epi) {
+int launch_gemm_bf16x3(const void* A3, const void* B3, float* C, int G, int M, int N, int K, const X3Shape& sh, void* ws, hipStream_t s,
+                       bool a_f32, bool with_sum, const X3Epi* epi) {
   KD_REQUIRE(gemm_bf16x3_ok(G, M, N, K), "bf16x3 GEMM needs M % 256 == 0, N % 128 == 0, K % 32 == 0 and operand planes < 4 GB");
   KD_REQUIRE((((uintptr_t)A3 | (uintptr_t)B3 | (uintptr_t)ws) & 15) == 0 && ws, "bf16x3 GEMM needs 16-byte aligned operand planes and a workspace");
-  KD_REQUIRE(!epi || (G == 1 && gemm_bf16x3_epi_ok(M, N, K, *epi) && (a_f32 || (epi->lda == K && !epi->a_tap_c))),
+  KD_REQUIRE(!epi || (G == 1 && gemm_bf16x3_epi_ok(M, N, K, *epi, sh) && (a_f32 || (epi->lda == K && !epi->a_tap_c))),
              "bf16x3 GEMM, epilogue form: G = 1, row strides >= the row, byte offsets < 2^31, one image per 256-row tile under a gate");
-  int P, R, S, first;
-  x3_shape(G, M, N, K, &P, &R, &S, &first);
-  KD_REQUIRE(P <= X3_MAX_WG, "bf16x3 GEMM: more workgroups than the workspace holds");
+  const int P = sh.P, S = sh.S;
+  KD_REQUIRE(x3_shape_fits(sh, G, M, N), "bf16x3 GEMM: the launch shape is not one of these dimensions, or has more workgroups than the workspace holds");
   float* slab = (float*)ws;
   X3Epi e = epi ? *epi : X3Epi{};
-  e.seg_rows8 = R && S > 1;
+  e.seg_rows8 = sh.needs_sum();
   // 16-byte epilogue accesses: every row of y and of the added maps 16-byte aligned
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   // The plain form (Winograd position GEMMs, G > 1) stores its tiles through kind 1's 16-byte path too - nothing added, rows
@@ -921,7 +908,7 @@ int launch_gemm_bf16x3(const void* A3, const void* B3, float* C, int G, int M, i
   }
 #undef KD_X3
   KD_HIP_CHECK(hipGetLastError());
-  if (with_sum && R && S > 1) return launch_gemm_bf16x3_sum(C, G, M, N, K, ws, s, epi);
+  if (with_sum) return launch_gemm_bf16x3_sum(C, G, M, N, K, sh, ws, s, epi);
   return 0;
 }
 

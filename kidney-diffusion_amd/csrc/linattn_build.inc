@@ -48,12 +48,10 @@ T Builder::linear_attn_block(const T& x, const std::string& pre, const T* ctx, c
   T ckv;
   const bool has_ctx = ctx != nullptr;
   if (has_ctx) {
-    const bool was_cond = to_cond;
-    to_cond = cond_hoist;
+    auto ph = cond_scope();
     T cn = layernorm(*ctx, P(a + ".to_context.0.weight", ctx->C), P(a + ".to_context.0.bias", ctx->C));
     ckv = linear(cn, P(a + ".to_context.1.weight", (int64_t)2 * inner * ctx->C), nullptr, 2 * inner);
     free(cn);
-    to_cond = was_cond;
   }
   const int Bx = x.B, Hh = x.H, Ww = x.W, HW = x.HW(), nchunk = linattn_chunks(HW);
   const int m = has_ctx ? ctx->HW() : 0;
@@ -112,20 +110,19 @@ T Builder::linear_cross_attn(const T& x, const std::string& pre, const T& c) {
   const float* nkv = P(pre + ".null_kv", 2 * D);
   const int Bx = x.B, m = c.HW();
   kd_unet* uu = u;
-  const bool was_cond = to_cond;
-  to_cond = cond_hoist;
-  T kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
-  T ctxm = alloc(Bx, H, D, D);
-  {
+  T ctxm;
+  {   // a function of c alone (cond region)
+    auto ph = cond_scope();
+    T kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
+    ctxm = alloc(Bx, H, D, D);
     const size_t kvo = kv.off, co = ctxm.off;
     emit([=](hipStream_t s) {
       return launch_linattn_context(nullptr, nullptr, 0, nullptr, 0, uu->P(kvo), uu->P(kvo) + inner, 2 * inner, m, nkv,
                                     nkv + D, nullptr, uu->P(co), Bx, H, s);
     }, "linattn xcontext m" + std::to_string(m + 1), (int64_t)Bx * H * (m + 1) * D * D);
-    if (!to_text) u->macs += (int64_t)Bx * H * (m + 1) * D * D;
+    if (phase != Phase::Text) u->macs += (int64_t)Bx * H * (m + 1) * D * D;
+    free(kv);
   }
-  free(kv);
-  to_cond = was_cond;
   T o = alloc(Bx, x.H, x.W, inner);
   {
     const size_t qo = q.off, co = ctxm.off, oo = o.off;

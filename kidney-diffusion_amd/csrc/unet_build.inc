@@ -56,7 +56,7 @@ void Builder::build() {
   T fin_static;
   const bool fin_has_static = cfg.lowres_cond != 0;
   if (fin_has_static) {
-    to_static = true;
+    auto ph = scope(Phase::Static);
     fin_static = alloc(B, Ci, S, S);
     size_t so = fin_static.off;
     int Bx = B;
@@ -68,13 +68,12 @@ void Builder::build() {
       }
       return launch_final_static(uu->in_lowres, wfin, bfin, uu->P(so), fin_c, dim, Ci, Bx, S, S, s);
     });
-    to_static = false;
   }
 
   // ---- conditioning: time (+ low-res time) embeddings, tokens, batched FiLM scale/shift
   const int n_time_tok = cfg.num_time_tokens * (cfg.lowres_cond ? 2 : 1);
   const int ntok = n_time_tok + cfg.text_tokens;
-  to_cond = true;   // everything down to t_ss: functions of (log_snr, lowres_log_snr, text) only
+  auto cond_ph = scope(Phase::Cond);   // everything down to t_ss: functions of (log_snr, lowres_log_snr, text) only
   T c_raw = alloc(B, 1, ntok, cd);
   T t_emb = alloc(B, 1, 1, tcd);
   {
@@ -117,7 +116,7 @@ void Builder::build() {
     skinny(t_emb.off, tcd, tmlp_w, tmlp_b, t_ss.off, tmlp_total, B, tcd, tmlp_total, ACT_SILU, ACT_NONE);
   }
   free(t_emb);
-  to_cond = false;
+  cond_ph.exit();
 
   // ---- initial cross-embed convolution (k = 3, 7, 15) over cond | x | lowres.
   // The cond / low-res planes do not change during a sampling loop: their share of the convolution
@@ -148,7 +147,7 @@ void Builder::build() {
     };
     if (hoist) {
       const int spad = (Cs + 3) & ~3;
-      to_static = true;
+      auto ph = scope(Phase::Static);
       T simg = alloc(B, S, S, spad);
       size_t so = simg.off;
       int Bx = B, HW = S * S;
@@ -170,7 +169,6 @@ void Builder::build() {
         off += ds[i];
       }
       free(simg);
-      to_static = false;
     }
     // init_conv_to_final_conv_residual: the init conv's output is the second half of the concat in front of
     // final_res_block, so it is written there from the start (a channel slice of that buffer): no copy later
@@ -216,12 +214,9 @@ void Builder::build() {
         return launch_init_conv(uu->in_x, uu->in_self_cond, Ci, np, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
                                 sg ? (double*)uu->P(sgo) : nullptr, Bx, S, n3, n7, n15, s);
       }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (uu->self_cond ? " self-cond" : ""), m);
-      u->macs += m;
       // K runs (3 / 7 / 15 kernel rows of np k values, padded to even) x 32-row tiles
       const int r3 = 3 * (((3 * np + 1) / 2) * 2), r7 = 7 * (((7 * np + 1) / 2) * 2), r15 = 15 * (((15 * np + 1) / 2) * 2);
-      const int64_t issued = (int64_t)B * S * S * (r3 * ((n3 + 31) / 32 * 32) + r7 * 32 + r15 * 32);
-      u->mfma_macs += issued;
-      u->op_mfma.back() = issued;
+      count_macs(m, (int64_t)B * S * S * (r3 * ((n3 + 31) / 32 * 32) + r7 * 32 + r15 * 32));
     } else {
       const int np = NPs, ipad = (np + 3) & ~3;
       T img = alloc(B, S, S, ipad);  // x's planes (| self_cond's: zeros when it is not given) + zero channels

@@ -138,6 +138,85 @@ def test_unet_forward_with_winograd_f4_levels_matches_oracle(device):
         assert H.rel_l2(got, outs[4]) < 2e-6 and H.rel_l2(got, ref) < FWD_REL_L2, (H.rel_l2(got, outs[4]), H.rel_l2(got, ref))
 
 
+def test_bf16x3_gemms_of_a_plan_carry_their_sums_and_macs(device):
+    """Every bf16x3 GEMM of a plan comes from one emitter (Builder::emit_x3_gemm): where the plan's launch shape cuts tiles in
+    k, the launch that adds the k-parts follows the GEMM directly, and the GEMM row carries the bf16 MACs.  dim 128 with
+    dim_mults (1, 2, 4), batch 8 at 64 x 64, attention on the 16 x 16 level, x3_linear = 128 - on 256 CUs: the 128 -> 128
+    ResnetBlock convs are F(4x4,3x3) with 36 (2048 / 256) = 288 tiles, a whole round and 32 tiles left over whose K = 128 is
+    too short to cut (no sum); the 256 -> 128 ones of the up path cut those 32 in two (wino4 x3 sum); the 512 -> 1024
+    feed-forward GEMM has 8 x 8 = 64 tiles, fewer than CUs, every one cut in four (conv k1 x3 sum).  (Batch 4 has no
+    F(4x4,3x3) layer with a sum: 144 tiles, one part each.)"""
+    import ctypes as C
+    import re
+
+    import imagen_pytorch as ip
+    from imagen_pytorch import _engine as E
+    from oracle import imagen_ref as R
+
+    kw = dict(dim=128, dim_mults=(1, 2, 4), num_resnet_blocks=1, layer_attns=(False, False, True),
+              layer_cross_attns=(False, False, True))
+    B, S = 8, 64
+    ou = H.randomize_(R.Unet(**kw, cond_on_text=False, text_embed_dim=None), 29).eval()
+    g = torch.Generator().manual_seed(4)
+    x, t = torch.randn(B, 3, S, S, generator=g), torch.randn(B, generator=g) * 3
+    with torch.no_grad():
+        ref = ou(x, t)
+    pu = H.product_unet_like(ou).to(device)
+    pu.x3_linear = 128
+    got = pu(x.to(device), t.to(device)).clone()
+    lib, h = E.load(), pu.engine(B, S, device, with_text=False)
+    buf = C.create_string_buffer(1 << 20)
+    E.check(lib.kd_unet_profile(h, 1, buf, len(buf), E.current_stream()))
+    rows = [l.split(",") for l in buf.value.decode().strip().split("\n")[1:]]   # index, label, macs, avg_us, mfma_macs
+    labels = [r[1] for r in rows]
+    is_gemm = lambda l: re.match(r"(wino4 gemm bf16x3|conv k[12] x3) M", l) is not None
+    is_sum = lambda l: re.match(r"(wino4 x3|conv k[12] x3) sum M", l) is not None
+    suffix = lambda l: l[l.index(" M"):]
+    stem = lambda l: "wino4" if l.startswith("wino4") else l[:7]
+    print("\n".join(l for l in labels if is_gemm(l) or is_sum(l)))
+    # a launch of P <= CUs workgroups whose left-over tiles (all, below CUs) can be cut in k: the rule of gemm_bf16x3_shape,
+    # restated with its constants of kernels_gemm_bf16x3.hip - tiles of BM x BN = 256 x 128, stages of BK = 16, at most
+    # X3_MAX_SPLIT = 8 parts of at least 8 stages (a change of those constants has to be made here as well)
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+
+    def cut(label):
+        M, K, N = (int(v) for v in re.search(r" M(\d+) Cin(\d+) Cout(\d+)", label).groups())
+        G = 36 if label.startswith("wino4") else 1
+        if label.startswith("wino4"):
+            M //= 16          # rows of a position GEMM: the 4 x 4 output tiles
+        if label.startswith("conv k2"):
+            K *= 4            # the four taps
+        tiles, nk = (M // 256) * (N // 128) * G, K // 16
+        r = tiles if tiles < cus else tiles % cus
+        if r == 0:
+            return False
+        s = min(cus // r, 8, nk // 8)
+        while s > 1 and nk % (2 * s):
+            s -= 1
+        return s > 1
+
+    for i, l in enumerate(labels):
+        if is_sum(l):
+            assert i > 0 and is_gemm(labels[i - 1]) and stem(labels[i - 1]) == stem(l) and suffix(labels[i - 1]) == suffix(l), \
+                (labels[i - 1], l)
+        if is_gemm(l):
+            has_sum = i + 1 < len(labels) and is_sum(labels[i + 1])
+            assert has_sum == cut(l), (l, has_sum)
+    summed = [labels[i - 1] for i, l in enumerate(labels) if is_sum(l)]
+    assert any(l.startswith("wino4 gemm bf16x3") for l in summed), "no F(4x4,3x3) position GEMM with its sum in the plan"
+    assert any(l.startswith("conv k1 x3") for l in summed), "no token GEMM / 1x1 conv with its sum in the plan"
+    assert any(is_gemm(l) and l not in summed for l in labels), "no bf16x3 launch without a sum in the plan"
+    bf16 = sum(int(r[4]) for r in rows if is_gemm(r[1]))
+    other = sum(int(r[4]) for r in rows if not is_gemm(r[1]))
+    print(f"mfma_macs column: bf16x3 rows {bf16} (kd_unet_mfma_bf16_macs {lib.kd_unet_mfma_bf16_macs(h)}), other rows {other} "
+          f"(kd_unet_mfma_macs {lib.kd_unet_mfma_macs(h)})")
+    assert bf16 == lib.kd_unet_mfma_bf16_macs(h) and bf16 > 0
+    assert other == lib.kd_unet_mfma_macs(h)
+    err = H.rel_l2(got, ref)
+    print(f"rel-L2 vs oracle {err:.2e}")
+    assert err < FWD_REL_L2, f"rel-L2 {err:.3e}"
+
+
 def test_conditioning_table_gives_bit_identical_samples(device):
     """The time conditioning of a step (embeddings, FiLM scale / shift, time tokens, their cross-attention K / V) depends
     on the schedule index alone when there is no text: the sampler computes it once per schedule into a table and an
