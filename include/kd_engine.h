@@ -44,7 +44,8 @@ const char* kd_last_error(void);
  *      with its struct kd_unet_ext_t for linear attention, kd_linattn_chunk_tokens, kd_linattn_dwconv_nhwc, kd_linattn_context,
  *      kd_linattn_apply; kd_attention_ex and kd_l2norm_heads (the attention core and the qk-norm with the plan's argument
  *      forms, for unit tests); kd_text_select, kd_add_rows_bcast, kd_mean_rows and kd_copy_rows (the text plan's small kernels,
- *      for unit tests); kd_unet_text_cond accepts d_text_mask = NULL (text_mask = None) */
+ *      for unit tests); kd_unet_text_cond accepts d_text_mask = NULL (text_mask = None); kd_unet_ext_t gained `cross_embed_downsample`
+ *      and `upsample_nearest` at its end (zero = the plans of before); kd_upsample_nearest_conv3x3_nhwc added */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -165,6 +166,13 @@ typedef struct kd_unet_ext {
   int self_cond;   /* as kd_unet_create_self_cond */
   int use_linear_attn[KD_MAX_LEVELS];
   int use_linear_cross_attn[KD_MAX_LEVELS];
+  /* The library's other resampling layers.  cross_embed_downsample = 1 (`Unet(cross_embed_downsample=True)`, kernel sizes
+   * (2, 4)): every Downsample is a CrossEmbedLayer, cat(Conv2d(d, d_out / 2, 2, stride 2), Conv2d(d, d_out - d_out / 2, 4,
+   * stride 2, pad 1)) with parameters `<pre>.convs.{0,1}.{weight,bias}`; d_out must be even.  upsample_nearest = 1
+   * (`Unet(pixel_shuffle_upsample=False)`): every Upsample is nn.Upsample(2, nearest) -> Conv2d(d, d_out, 3, padding 1),
+   * parameters `<pre>.1.{weight,bias}`, no activation; needs d % 8 == 0 and d_out % 32 == 0 (refused at build otherwise). */
+  int cross_embed_downsample;
+  int upsample_nearest;
 } kd_unet_ext_t;
 /* kd_unet_create_self_cond with the options of `ext` (NULL = all zero: the plan of kd_unet_create_shared).  An ext with
  * every linear flag zero gives the same plan - the same launches and the same bits - as kd_unet_create_self_cond. */
@@ -385,6 +393,13 @@ int kd_edm_sample_steps(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_s
 int kd_conv2d_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias, float* d_y,
                    int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad,
                    int act, void* stream);
+/* nn.Upsample(scale_factor 2, nearest) followed by Conv2d(Cin, Cout, 3, padding 1) in one kernel (kernels_resample.hip): four
+ * phase GEMMs with K = 4 Cin over the low-res map, the 3x3 taps that fall on one input pixel summed; the upsampled map is
+ * never written.  x: NHWC [B,H,W,Cin] dense; w: torch OIHW [Cout,Cin,3,3] (packed into the sixteen summed tap matrices on
+ * each call of this test entry); y: NHWC [B,2H,2W] rows of stride ldy (0 = Cout), the result in channels [yoff, yoff + Cout)
+ * and nothing else touched.  Needs Cin % 8 == 0, Cout % 32 == 0, ldy % 4 == 0, yoff % 4 == 0. */
+int kd_upsample_nearest_conv3x3_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias, float* d_y, int ldy, int yoff,
+                                     int B, int H, int W, int Cin, int Cout, void* stream);
 /* The same 3x3 / stride-1 / pad-1 convolution through the plan's Winograd F(2x2,3x3) path (used for
  * the deep ResnetBlock convs): fp32, differs from kd_conv2d_nhwc by re-association
  * only.  Needs even H, W; B*H*W/4 % 256 == 0; Cin % 32 == 0; Cout > 32. */

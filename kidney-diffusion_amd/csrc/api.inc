@@ -46,6 +46,10 @@ int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, in
       u->lin_attn[l] = l < cfg->num_levels && ext->use_linear_attn[l] != 0;
       u->lin_cross[l] = l < cfg->num_levels && ext->use_linear_cross_attn[l] != 0;
     }
+  if (ext) {
+    u->cross_embed_downsample = ext->cross_embed_downsample != 0;
+    u->upsample_nearest = ext->upsample_nearest != 0;
+  }
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   u->cus = gemm_bf16x3_device_cus();   // read once: every plan-time question and every launch shape of this plan uses it
@@ -355,6 +359,24 @@ int kd_conv2d_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias,
     p.partial = part;
     if (!rc) rc = launch_conv_igemm(p, s);
   }
+  return entry_finish(rc, s);
+}
+
+// nn.Upsample(2, nearest) -> Conv2d(Cin, Cout, 3, padding 1) through the plan's launches (kernels_resample.hip): the pack of
+// the sixteen summed tap matrices, then the four phase GEMMs
+int kd_upsample_nearest_conv3x3_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias, float* d_y, int ldy, int yoff,
+                                     int B, int H, int W, int Cin, int Cout, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ldy == 0) ldy = Cout;
+  if (const char* why = upsample_nearest_refusal(Cin, ldy, yoff, B, H, W, Cin, Cout)) {
+    set_error(why);
+    return 1;
+  }
+  EntryBufs bufs;
+  float* wp = nullptr;
+  if (bufs.get(&wp, upsample_nearest_weight_floats(Cin, Cout) * sizeof(float))) return 1;
+  int rc = launch_upsample_nearest_pack(d_w_oihw, wp, Cout, Cin, s);
+  if (!rc) rc = launch_upsample_nearest_conv3x3(d_x, Cin, wp, d_bias, d_y, ldy, yoff, B, H, W, Cin, Cout, s);
   return entry_finish(rc, s);
 }
 

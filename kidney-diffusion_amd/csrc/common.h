@@ -332,6 +332,15 @@ int launch_linattn_context(const float* k, const float* v, int ld, const float* 
 int launch_linattn_apply(const float* q, int ldq, const float* ctx, float* out, int ldo, int B, int N, int heads,
                          float scale, int silu, hipStream_t s);
 
+// ---- nearest x2 upsample + 3x3 conv as four phase GEMMs over the low-res map (kernels_resample.hip)
+// nullptr where the kernel takes the shape, else the condition it misses (Cin % 8, Cout % 32, strides / offset % 4)
+const char* upsample_nearest_refusal(int ldx, int ldy, int yoff, int B, int H, int W, int Cin, int Cout);
+size_t upsample_nearest_weight_floats(int Cin, int Cout);   // the sixteen summed tap matrices [16][Cout][Cin]
+int launch_upsample_nearest_pack(const float* w_oihw, float* wp, int O, int I, hipStream_t s);
+// y[b][2 y + p][2 x + q][yoff + n] (row stride ldy) = conv3x3(nearest_x2(x))[..] + bias; x [B][H][W] rows of stride ldx
+int launch_upsample_nearest_conv3x3(const float* x, int ldx, const float* wp, const float* bias, float* y, int ldy, int yoff, int B,
+                                    int H, int W, int Cin, int Cout, hipStream_t s);
+
 // ---- final conv to the image's `ch` = 1 .. 4 channels (kernels_final.hip)
 int final_gemm_cols(int ch);   // width of P: the 9 ch (output, tap) columns padded for the 1x1 GEMM (32; 48 at ch = 4)
 int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, hipStream_t s);

@@ -272,6 +272,9 @@ struct kd_unet {
   // first ResnetBlocks' cross-attention is LinearCrossAttention (use_linear_cross_attn) - kd_unet_create_ext
   int lin_attn[KD_MAX_LEVELS] = {0};
   int lin_cross[KD_MAX_LEVELS] = {0};
+  // the library's other resampling forms (kd_unet_ext_t): Downsample slots hold a CrossEmbedLayer (kernel sizes 2 and 4);
+  // Upsample slots hold nearest x2 + conv3x3 instead of conv1x1 -> SiLU -> PixelShuffle
+  int cross_embed_downsample = 0, upsample_nearest = 0;
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
@@ -701,6 +704,7 @@ struct Builder {
     u->mfma_bf16_macs += u->op_mfma.back();
     if (sh.needs_sum()) emit([=](hipStream_t s) { return launch(s, true); }, stem + " x3 sum" + shape);
   }
+  int last_seg_nchunk = 0;   // chunks per image of the GroupNorm partials the last conv() / downsample_x3() leaves, 0 = none
   T conv(const T& x, const float* w, const float* bias, int Cout, int K, int stride, int pad, const ConvOpt& o) {
     if (x.x3p && !x3_linear_ok(x, Cout, K, stride, pad, o))
       throw std::runtime_error("plan: a tensor in plane form reached a layer that is not a bf16x3 GEMM");
@@ -782,6 +786,7 @@ struct Builder {
         sego = have ? have->off : add_seg(y, seg_c0, seg_nseg, nchunk);
       }
     }
+    last_seg_nchunk = seg_nseg ? seg_nchunk : 0;
     // ---- token GEMMs / 1x1 convs with K >= 512 as fp32 products on the bf16 matrix pipe (kernels_gemm_bf16x3.hip,
     // epilogue form: bias / residual / gate, strided rows; weights split into planes once per plan, the fp32 activations by
     // the kernel's loader waves; GroupNorm partials of the output where no tile is cut in k).  Layers with an activation
@@ -1543,21 +1548,25 @@ struct Builder {
 
   // the Downsample (pixel-unshuffle + conv1x1 = a 2 x 2 / stride-2 conv) on the bf16x3 kernel: its fp32-A loader gathers the
   // four input pixels of an output pixel (X3Epi::a_tap_c), K = 4 C
-  X3Epi downsample_x3_epi(const T& x, int Cout) const {
+  X3Epi downsample_x3_epi(const T& x, int ldy) const {
     X3Epi e;
     e.lda = x.LD();
-    e.ldy = Cout;
+    e.ldy = ldy;
     e.a_tap_c = x.C;
     e.a_wi = x.W;
     e.a_hi = x.H;
     e.hw = (x.H / 2) * (x.W / 2);
     return e;
   }
-  bool downsample_x3_ok(const T& x, int Cout) const {
+  // ldy: row stride of the output (0 = Cout; a CrossEmbedLayer's 2 x 2 half fills a channel slice of the level's map)
+  bool downsample_x3_ok(const T& x, int Cout, int ldy = 0) const {
     if ((x.H & 1) || (x.W & 1) || x.C % 16) return false;
-    return x3_epi_layer_ok((int64_t)x.B * (x.H / 2) * (x.W / 2), Cout, 4 * x.C, 256, downsample_x3_epi(x, Cout));
+    return x3_epi_layer_ok((int64_t)x.B * (x.H / 2) * (x.W / 2), Cout, 4 * x.C, 256, downsample_x3_epi(x, ldy ? ldy : Cout));
   }
-  T downsample_x3(const T& x, const std::string& pre, const float* w_taps /*[tap][O][C]*/, const float* bias, int Cout) {
+  // dst: write channels [0, Cout) of this map (of dst->C >= Cout channels, whose GroupNorm partials the launch's buffer then
+  // spans: the launches filling the other channels find it under the same span) instead of a new one
+  T downsample_x3(const T& x, const std::string& pre, const float* w_taps /*[tap][O][C]*/, const float* bias, int Cout,
+                  const T* dst = nullptr) {
     const int C = x.C, K = 4 * C, Ho = x.H / 2, Wo = x.W / 2;
     const int64_t M = (int64_t)x.B * Ho * Wo;
     // B operand [O][K] with k = tap C + c, then its three planes
@@ -1573,18 +1582,20 @@ struct Builder {
       KD_THROW_IF(rc);
       KD_HIP_THROW(er);
     });
-    T y = alloc(x.B, Ho, Wo, Cout);
-    const X3Epi base = downsample_x3_epi(x, Cout);
+    T y = dst ? *dst : alloc(x.B, Ho, Wo, Cout);
+    const X3Epi base = downsample_x3_epi(x, y.LD());
     // the output feeds the GroupNorm of the level's first ResnetBlock: partials from the epilogue
-    const bool sg = Cout % 16 == 0 && (Ho * Wo) % 32 == 0;
-    const size_t sgo = sg ? add_seg(y, 0, Cout / 16, Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows()) : 0;
+    const int span = y.C;   // channels the partial buffer covers
+    const bool sg = Cout % 16 == 0 && span % 16 == 0 && (Ho * Wo) % 32 == 0;
+    last_seg_nchunk = sg ? Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows() : 0;
+    const size_t sgo = sg ? add_seg(y, 0, span / 16, last_seg_nchunk) : 0;
     kd_unet* uu = u;
     auto epi_of = [=]() {
       X3Epi e = base;
       e.bias = bias;
       if (sg) {
         e.seg = (double*)uu->P(sgo);
-        e.seg_nseg = Cout / 16;
+        e.seg_nseg = span / 16;
       }
       return e;
     };
@@ -1593,6 +1604,7 @@ struct Builder {
     return y;
   }
   T downsample(const T& x, const std::string& pre, int dim_out) {  // pixel-unshuffle + conv1x1 == 2x2/s2 conv
+    if (u->cross_embed_downsample) return cross_embed_downsample(x, pre, dim_out);
     if (cfg.downsample_conv4) {   // earlier library versions: Conv2d(dim, dim_out, 4, stride 2, pad 1)
       ConvOpt o4;
       o4.want_seg = true;
@@ -1607,7 +1619,72 @@ struct Builder {
     o.want_seg = true;   // feeds the GroupNorm of the level's first ResnetBlock
     return conv(x, w, P(pre + ".1.bias", dim_out), dim_out, 2, 2, 0, o);
   }
+  // `Unet(cross_embed_downsample=True)`: CrossEmbedLayer(d, (2, 4), dim_out, stride 2) = cat(Conv2d(d, dim_out / 2, 2, stride 2),
+  // Conv2d(d, dim_out - dim_out / 2, 4, stride 2, pad 1)): two launches into the channel halves of one map - the 2 x 2 half
+  // on the path downsample() picks for that Cout, the 4 x 4 half on the generic conv as the downsample_conv4 fork - that
+  // share one buffer of GroupNorm partials where their chunks agree (else the first ResnetBlock takes its statistics itself)
+  T cross_embed_downsample(const T& x, const std::string& pre, int dim_out) {
+    if (dim_out & 1) throw std::runtime_error("cross_embed_downsample: odd dim_out " + std::to_string(dim_out) + " at " + pre);
+    if ((x.H & 1) || (x.W & 1)) throw std::runtime_error("cross_embed_downsample: odd map at " + pre);
+    const int d2 = dim_out / 2, d4 = dim_out - d2, C = x.C;
+    const float* w2 = pack_conv(pre + ".convs.0.weight", d2, C, C, 2);   // [tap = kh 2 + kw][O][C]: downsample()'s tap layout
+    const float* b2 = P(pre + ".convs.0.bias", d2);
+    T y = alloc(x.B, x.H / 2, x.W / 2, dim_out);
+    if (downsample_x3_ok(x, d2, dim_out)) {
+      downsample_x3(x, pre + ".convs.0", w2, b2, d2, &y);
+    } else {
+      ConvOpt o2;
+      o2.dst = &y;
+      o2.want_seg = true;
+      o2.seg_c0 = 0;
+      o2.seg_cn = dim_out;
+      conv(x, w2, b2, d2, 2, 2, 0, o2);
+    }
+    const int chunks2 = last_seg_nchunk;
+    ConvOpt o4;
+    o4.dst = &y;
+    o4.yoff = d2;
+    o4.want_seg = true;
+    o4.seg_c0 = 0;
+    o4.seg_cn = dim_out;
+    conv(x, pack_conv(pre + ".convs.1.weight", d4, C, C, 4), P(pre + ".convs.1.bias", d4), d4, 4, 2, 1, o4);
+    // one buffer over all dim_out channels, filled by both launches - or none
+    auto it = seg_of.find(y.at());
+    if (it != seg_of.end() && (it->second.parts.size() != 1 || chunks2 == 0 || chunks2 != last_seg_nchunk)) {
+      for (auto& sp : it->second.parts)
+        if (sp.owned) arena.release(sp.off);
+      seg_of.erase(it);
+    }
+    return y;
+  }
+  // `Unet(pixel_shuffle_upsample=False)`: nn.Upsample(scale 2, nearest) -> Conv2d(d, dim_out, 3, padding 1), no activation, as
+  // four phase GEMMs over the low-res map (kernels_resample.hip).  ct as upsample().  The kernel leaves no GroupNorm
+  // partials: the next ResnetBlock takes its statistics with the launch it uses for any producer without them.  A shape
+  // the kernel does not take is refused here, at build, with the condition it misses.
+  T upsample_nearest(const T& x, const std::string& pre, int dim_out, const T* ct = nullptr) {
+    const int C = x.C;
+    const float* wsrc = raw(pre + ".1.weight", (int64_t)dim_out * C * 9);
+    const float* b = P(pre + ".1.bias", dim_out);
+    T y = ct ? *ct : alloc(x.B, 2 * x.H, 2 * x.W, dim_out);
+    if (y.B != x.B || y.H != 2 * x.H || y.W != 2 * x.W) throw std::runtime_error("plan: upsample target of the wrong shape");
+    if (const char* why = upsample_nearest_refusal(x.LD(), y.LD(), y.coff, x.B, x.H, x.W, C, dim_out))
+      throw std::runtime_error(std::string(why) + " (" + pre + ": Cin " + std::to_string(C) + ", Cout " + std::to_string(dim_out) + ")");
+    if ((x.coff & 3)) throw std::runtime_error("upsample_nearest_conv3x3: input channel offset must be a multiple of 4 (" + pre + ")");
+    const float* wp = cached("upnearest_w:" + pre, upsample_nearest_weight_floats(C, dim_out),
+                             [&](float* dst) { KD_THROW_IF(launch_upsample_nearest_pack(wsrc, dst, dim_out, C, 0)); });
+    const size_t xo = x.at(), yo = y.off;
+    const int ldx = x.LD(), ldy = y.LD(), yoff = y.coff, Bx = x.B, H = x.H, W = x.W;
+    kd_unet* uu = u;
+    const int64_t M = (int64_t)Bx * H * W;
+    const int64_t m = 4 * M * dim_out * C * 9;
+    emit([=](hipStream_t s) {
+      return launch_upsample_nearest_conv3x3(uu->P(xo), ldx, wp, b, uu->P(yo), ldy, yoff, Bx, H, W, C, dim_out, s);
+    }, "upsample nearest conv3 M" + std::to_string(M) + " Cin" + std::to_string(C) + " Cout" + std::to_string(dim_out), m);
+    count_macs(m, 4 * M * dim_out * 4 * C);
+    return y;
+  }
   T upsample(const T& x, const std::string& pre, int dim_out, const T* ct = nullptr) {  // conv1x1 -> SiLU -> PixelShuffle(2)
+    if (u->upsample_nearest) return upsample_nearest(x, pre, dim_out, ct);
     const float* wsrc = raw(pre + ".net.0.weight", (int64_t)4 * dim_out * x.C);
     const float* bsrc = raw(pre + ".net.0.bias", 4 * dim_out);
     const int C = x.C;

@@ -109,7 +109,8 @@ class kd_edm_schedule_t(C.Structure):
 
 class kd_unet_ext_t(C.Structure):
     _fields_ = [("self_cond", C.c_int), ("use_linear_attn", C.c_int * KD_MAX_LEVELS),
-                ("use_linear_cross_attn", C.c_int * KD_MAX_LEVELS)]
+                ("use_linear_cross_attn", C.c_int * KD_MAX_LEVELS),
+                ("cross_embed_downsample", C.c_int), ("upsample_nearest", C.c_int)]
 
 
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
@@ -154,6 +155,7 @@ SIGNATURES = {
     "kd_edm_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
                                       C.c_int, C.c_int, C.c_void_p]),
     "kd_conv2d_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
+    "kd_upsample_nearest_conv3x3_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "kd_conv3x3_winograd_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "kd_conv3x3_winograd4_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "kd_gemm_bf16x3": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),

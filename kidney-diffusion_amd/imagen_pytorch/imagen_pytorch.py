@@ -299,6 +299,7 @@ class Unet(nn.Module):
         layer_attns_depth=1, attend_at_middle=True, layer_cross_attns=True, use_linear_attn=False,
         use_linear_cross_attn=False, cond_on_text=True, max_text_len=256, resnet_groups=8,
         init_cross_embed=True, init_cross_embed_kernel_sizes=(3, 7, 15), cross_embed_downsample=False,
+        cross_embed_downsample_kernel_sizes=(2, 4),
         attn_pool_text=True, attn_pool_num_latents=32, dropout=0.0, memory_efficient=False,
         init_conv_to_final_conv_residual=False, use_global_context_attn=True, scale_skip_connection=True,
         final_resnet_block=True, final_conv_kernel_size=3, self_cond=False, pixel_shuffle_upsample=True,
@@ -313,11 +314,11 @@ class Unet(nn.Module):
         when the incoming keys contain `q_scale` - so the first real checkpoint decides the variant."""
         super().__init__()
         self._locals = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
-        unsupported = dict(cross_embed_downsample=cross_embed_downsample)
-        bad = [k for k, v in unsupported.items() if (any(v) if isinstance(v, (tuple, list)) else bool(v))]
         required = dict(init_cross_embed=init_cross_embed, scale_skip_connection=scale_skip_connection,
-                        final_resnet_block=final_resnet_block, pixel_shuffle_upsample=pixel_shuffle_upsample)
-        bad += [k for k, v in required.items() if not v]
+                        final_resnet_block=final_resnet_block)
+        bad = [k for k, v in required.items() if not v]
+        if tuple(cross_embed_downsample_kernel_sizes) != (2, 4):
+            raise NotImplementedError("cross_embed_downsample_kernel_sizes: the engine plans the library's default (2, 4) only")
         if bad or final_conv_kernel_size != 3 or tuple(init_cross_embed_kernel_sizes) != (3, 7, 15) \
                 or layer_attns_depth != 1 or attn_dim_head != 64 or channels not in (1, 2, 3, 4):
             raise NotImplementedError(
@@ -333,6 +334,10 @@ class Unet(nn.Module):
         self.has_cond_image = cond_images_channels > 0
         self.memory_efficient = memory_efficient
         self.init_conv_to_final_conv_residual = init_conv_to_final_conv_residual
+        # the library's other resampling layers: a CrossEmbedLayer (kernel sizes 2 and 4, stride 2) in every Downsample slot;
+        # nearest x2 + conv3x3 instead of the PixelShuffleUpsample
+        self.cross_embed_downsample = bool(cross_embed_downsample)
+        self.pixel_shuffle_upsample = bool(pixel_shuffle_upsample)
         self.max_text_len = max_text_len
         self.dim = dim
         # self_cond: every forward also reads the previous step's thresholded x0 estimate (zeros when not given); the
@@ -385,7 +390,9 @@ class Unet(nn.Module):
                           layer_cross_attns=cross, use_linear_attn=lin, use_linear_cross_attn=lcross,
                           attn_heads=attn_heads, attn_dim_head=attn_dim_head,
                           ff_mult=ff_mult, num_time_tokens=num_time_tokens, sinu_dim=learned_sinu_pos_emb_dim,
-                          groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn)
+                          groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn,
+                          cross_embed_downsample=self.cross_embed_downsample,
+                          upsample_nearest=not self.pixel_shuffle_upsample)
 
         self.init_resnet_block = ResnetBlock(dim, dim, time_cond_dim=tcd, groups=groups[0],
                                              use_gca=use_global_context_attn, **ak) if memory_efficient else None
@@ -400,17 +407,27 @@ class Unet(nn.Module):
                 return LinearAttentionTransformerBlock(d, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak)
             return _Stateless()
 
+        def down(d, d_out):
+            if self.cross_embed_downsample:
+                return CrossEmbedLayer(d, cross_embed_downsample_kernel_sizes, d_out, stride=2)
+            return _downsample(d, d_out, downsample_form)
+
+        def up(d, d_out):
+            if self.pixel_shuffle_upsample:
+                return PixelShuffleUpsample(d, d_out)
+            return nn.Sequential(_Stateless(), nn.Conv2d(d, d_out, 3, padding=1))   # nn.Upsample(2, nearest), conv
+
         for ind, ((d_in, d_out), n, g, la, lc, ll, lx) in enumerate(zip(in_out, nrb, groups, attns, cross, lin, lcross)):
             is_last = ind >= L - 1
             cur = d_in
             pre = None
             if memory_efficient:
-                pre = _downsample(d_in, d_out, downsample_form)
+                pre = down(d_in, d_out)
                 cur = d_out
             skip_dims.append(cur)
             post = None
             if not memory_efficient:
-                post = _downsample(cur, d_out, downsample_form) if not is_last else Parallel(
+                post = down(cur, d_out) if not is_last else Parallel(
                     nn.Conv2d(d_in, d_out, 3, padding=1), nn.Conv2d(d_in, d_out, 1))
             self.downs.append(nn.ModuleList([
                 pre,
@@ -442,7 +459,7 @@ class Unet(nn.Module):
                 nn.ModuleList([ResnetBlock(d_out + sd, d_out, time_cond_dim=tcd, groups=g,
                                            use_gca=use_global_context_attn) for _ in range(n)]),
                 attn_block(d_out, la, ll),
-                PixelShuffleUpsample(d_out, d_in) if (not is_last or memory_efficient) else _Stateless(),
+                up(d_out, d_in) if (not is_last or memory_efficient) else _Stateless(),
             ]))
         fin = dim + (dim if init_conv_to_final_conv_residual else 0)
         self.final_res_block = ResnetBlock(fin, dim, time_cond_dim=tcd, groups=groups[0], use_gca=True)
@@ -476,7 +493,8 @@ class Unet(nn.Module):
         build those after loading, as ImagenTrainer.load does."""
         ref = self.final_conv.weight
         changed = False
-        if downsample_form is not None and downsample_form != self.downsample_form:
+        # (a Unet built with cross_embed_downsample=True has no such fork: its Downsample slots hold CrossEmbedLayers)
+        if downsample_form is not None and downsample_form != self.downsample_form and not self.cross_embed_downsample:
             for l, lvl in enumerate(self.downs):
                 for slot in (0, 4):
                     if isinstance(lvl[slot], (nn.Sequential, nn.Conv2d)):   # (not the last level's Parallel, not None)
@@ -505,6 +523,8 @@ class Unet(nn.Module):
                         for k, v in state_dict.items())
             plain = any(k.startswith(prefix + "mid_attn.fn.") for k in state_dict)
             want = ("conv4x4" if conv4 else "unshuffle", "residual_attention" if plain else "transformer")
+            if self.cross_embed_downsample:   # `downs.L.{0,4}.convs.K.*`: neither form of the fork, nothing to follow
+                want = (self.downsample_form, want[1])
             if want != (self.downsample_form, self.mid_attn_form):
                 print(f"imagen_pytorch: checkpoint keys name the library fork downsample={want[0]}, mid_attn={want[1]} "
                       "-> module tree and engine plan follow it")
@@ -681,6 +701,8 @@ class Unet(nn.Module):
             for i in range(L):
                 ext.use_linear_attn[i] = int(bool(p["use_linear_attn"][i]))
                 ext.use_linear_cross_attn[i] = int(bool(p["use_linear_cross_attn"][i]))
+            ext.cross_embed_downsample = int(p["cross_embed_downsample"])
+            ext.upsample_nearest = int(p["upsample_nearest"])
             E.check(lib.kd_unet_create_ext(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(handle)))
             del sd
         self._engines[key] = handle
