@@ -316,6 +316,18 @@ struct kd_unet {
 
 namespace kd {
 
+// An address in the plan's workspace or cond region: known as a byte offset at build (the ops are emitted before either
+// exists), a pointer once the op runs.  The null Ref (an absent residual, gate, partial buffer, FiLM row) yields nullptr.
+struct Ref {
+  const kd_unet* u = nullptr;
+  size_t off = 0;   // as kd_unet::P takes it (COND_FLAG included)
+  explicit operator bool() const { return u != nullptr; }
+  float* f() const { return u ? u->P(off) : nullptr; }
+  double* d() const { return (double*)f(); }
+  Ref floats(int64_t n) const { return u ? Ref{u, off + (size_t)n * sizeof(float)} : Ref(); }   // moved on by n floats
+  Ref doubles(int64_t n) const { return u ? Ref{u, off + (size_t)n * sizeof(double)} : Ref(); }
+};
+
 // ------------------------------------------------------------------------------ plan builder
 struct Builder {
   kd_unet* u;
@@ -476,6 +488,19 @@ struct Builder {
       drop_seg_block(t.off);
     }
   }
+  // ---- the addresses an op captures (Ref).  at: (row 0, channel 0) of t, the first channel of a slice; base: row 0 of the
+  // block t lives in, for launches that take the channel offset on its own; a nullptr tensor gives the null Ref
+  Ref at(const T& t) const { return Ref{u, t.at()}; }
+  Ref base(const T& t) const { return Ref{u, t.off}; }
+  Ref at(const T* t) const { return t ? at(*t) : Ref(); }
+  // image b0 of the map t (a launch over a set of images starts at the set's first)
+  Ref image(const T& t, int b0) const { return at(t).floats((int64_t)b0 * t.HW() * t.LD()); }
+  Ref image(const T* t, int b0) const { return t ? image(*t, b0) : Ref(); }
+  // image b0's FiLM scale | shift row of t_ss from column ss_col on (ss_col < 0: no FiLM, the null Ref) and t_ss's row stride
+  struct Film { Ref row; int ld; };
+  Film film(int ss_col, int b0 = 0) const { return {ss_col >= 0 ? at(t_ss).floats((int64_t)b0 * tmlp_total + ss_col) : Ref(), tmlp_total}; }
+  // image b0's share of a partial buffer add_seg() reserved at workspace offset `off`: [B][nseg][nchunk][2] doubles
+  Ref seg_at(size_t off, int nseg = 0, int nchunk = 0, int b0 = 0) const { return Ref{u, off}.doubles((int64_t)b0 * nseg * nchunk * 2); }
   // ---- GroupNorm partials handed from the kernel that writes a map to the layer that normalises it (SegSrc,
   // common.h): per tensor (keyed by its workspace offset) up to two channel ranges with their partial buffers.
   struct SegPart {
@@ -557,27 +582,23 @@ struct Builder {
     const int G = cfg.resnet_groups, Bx = x.B, HW = x.HW(), C = x.C;
     SegPart sp[2];
     int n = 0;
-    kd_unet* uu = u;
-    const size_t so = gn_stats_t.off, sso = t_ss.off;
-    const int ld = tmlp_total;
+    const Ref st = at(gn_stats_t);
     if (seg_sources(x, sp, n)) {
       const SegPart a = sp[0], b2 = n > 1 ? sp[1] : SegPart();
-      const bool two = n > 1, has_ab = ab != nullptr;
-      const size_t abo = has_ab ? ab->off : 0;
+      const Ref pa = seg_at(a.off), pb = n > 1 ? seg_at(b2.off) : Ref(), abr = at(ab);
+      const Film ss = film(ss_col);
       emit([=](hipStream_t s) {
-        SegSrc s0{(const double*)uu->P(a.off), a.nseg, a.nchunk, a.c0, a.scale, a.ab_mul};
-        SegSrc s1{two ? (const double*)uu->P(b2.off) : nullptr, b2.nseg, b2.nchunk, b2.c0, b2.scale, b2.ab_mul};
-        const float* ssp = ss_col >= 0 ? uu->P(sso) + ss_col : nullptr;
-        return launch_gn_fold_seg(s0, s1, gamma, beta, ssp, ld, has_ab ? uu->P(abo) : nullptr, uu->P(so), Bx, C, G,
-                                  (double)HW * (C / G), 1e-5f, s);
+        SegSrc s0{pa.d(), a.nseg, a.nchunk, a.c0, a.scale, a.ab_mul};
+        SegSrc s1{pb.d(), b2.nseg, b2.nchunk, b2.c0, b2.scale, b2.ab_mul};
+        return launch_gn_fold_seg(s0, s1, gamma, beta, ss.row.f(), ss.ld, abr.f(), st.f(), Bx, C, G, (double)HW * (C / G), 1e-5f, s);
       }, "gn fold seg HW" + std::to_string(HW) + " C" + std::to_string(C));
-      return has_ab;
+      return ab != nullptr;
     }
     if (gn_partial_bytes(Bx, HW, C, G) > gn_partial_max) throw std::runtime_error("gn partial scratch too small");
-    const size_t xo = x.at(), po = gn_partial_t.off;
+    const Ref xr = at(x), part = at(gn_partial_t);
     const int ldx = x.LD();
     emit([=](hipStream_t s) {
-      return launch_gn_stats(uu->P(xo), ldx, uu->P(so), (double*)uu->P(po), Bx, HW, C, G, 1e-5f, s);
+      return launch_gn_stats(xr.f(), ldx, st.f(), part.d(), Bx, HW, C, G, 1e-5f, s);
     }, "gn stats HW" + std::to_string(HW) + " C" + std::to_string(C));
     return false;
   }
@@ -675,19 +696,19 @@ struct Builder {
     }
     return whole ? x.B : 0;
   }
-  // One bf16x3 GEMM of the plan, C[G][M][N] = A[G][M][K] W3[G][N][K]^T at byte offsets a_off / c_off of the workspace: the
+  // One bf16x3 GEMM of the plan, C[G][M][N] = A[G][M][K] W3[G][N][K]^T with A at `a` and C at `c` of the workspace: the
   // slabs of the k-parts (with the first such layer), the launch with the shape this plan's CU count gives, its MACs
   // (`macs` algorithmic, 6 G M N K bf16 issued), and the launch that adds the k-parts where that shape cuts tiles (its own
   // op: the whole chip adds them).  epi_of: yields the X3Epi at run time (the epilogue form, G = 1; applied by the summing
   // launch where there is one), or nullptr.  Rows of the profile: `stem` x3 (without an epilogue: `stem` gemm bf16x3) and
   // `stem` x3 sum, each followed by `shape`
   template <class EpiOf>
-  void emit_x3_gemm(size_t a_off, const void* W3, size_t c_off, int G, int64_t M, int N, int K, bool a_f32, EpiOf epi_of,
+  void emit_x3_gemm(Ref a, const void* W3, Ref c, int G, int64_t M, int N, int K, bool a_f32, EpiOf epi_of,
                     const std::string& stem, const std::string& shape, int64_t macs) {
     constexpr bool has_epi = !std::is_same<EpiOf, std::nullptr_t>::value;
     if (!u->x3_ws) KD_HIP_THROW(hipMalloc(&u->x3_ws, gemm_bf16x3_workspace_bytes()));
     const X3Shape sh = gemm_bf16x3_shape(G, (int)M, N, K, u->cus);
-    kd_unet* uu = u;
+    void* const x3_ws = u->x3_ws;   // (allocated once per plan, above: the address stays)
     auto launch = [=](hipStream_t s, bool sum) {   // the GEMM, or the launch that adds its k-parts
       X3Epi e;
       const X3Epi* ep = nullptr;
@@ -695,8 +716,8 @@ struct Builder {
         e = epi_of();
         ep = &e;
       }
-      if (sum) return launch_gemm_bf16x3_sum(uu->P(c_off), G, (int)M, N, K, sh, uu->x3_ws, s, ep);
-      return launch_gemm_bf16x3(uu->P(a_off), W3, uu->P(c_off), G, (int)M, N, K, sh, uu->x3_ws, s, a_f32, false, ep);
+      if (sum) return launch_gemm_bf16x3_sum(c.f(), G, (int)M, N, K, sh, x3_ws, s, ep);
+      return launch_gemm_bf16x3(a.f(), W3, c.f(), G, (int)M, N, K, sh, x3_ws, s, a_f32, false, ep);
     };
     emit([=](hipStream_t s) { return launch(s, false); }, stem + (has_epi ? " x3" : " gemm bf16x3") + shape, macs);
     u->macs += macs;
@@ -737,11 +758,9 @@ struct Builder {
     p.yoff = y.coff + o.yoff;   // (a slice destination: channels count from the slice's first)
     p.ldres = o.res ? o.res->LD() : 0;
     p.ldgs = o.gate_src ? o.gate_src->LD() : 0;
-    size_t xo = x.at(), yo = y.off;
-    bool has_res = o.res != nullptr, has_gs = o.gate_src != nullptr, ext = o.out_external;
-    size_t ro = has_res ? o.res->at() : 0, gso = has_gs ? o.gate_src->at() : 0, go = has_gs ? o.gate->off : 0;
-    kd_unet* uu = u;
+    const bool ext = o.out_external;
     const int res_coff = o.res_coff, o_yoff = o.yoff;
+    const int Bset = x3_linear_images(x, Cout, K, stride, pad, o);   // > 0: on the bf16x3 kernel, this many images per launch
     // small-M layers (batch-1 patches): split-K scratch, released right after the launch is recorded
     // (one in-order stream: the next op that reuses the block runs after the reduction)
     const int ks = conv_ksplit(p);
@@ -750,7 +769,7 @@ struct Builder {
       auto ph = scope(phase == Phase::Cond ? Phase::Step : phase);
       part = alloc_bytes((size_t)ks * x.B * Ho * Wo * Cout * sizeof(float));
     }
-    const size_t parto = part.off;
+    const Ref partial = ks > 1 ? at(part) : Ref();
     // GroupNorm partials of the output, left by the epilogue (channels [yoff, yoff + Cout) of y, or the Cout / 4
     // shuffled channels): several launches filling slices of one tensor (init conv) share the chunk count
     size_t sego = 0;
@@ -761,15 +780,14 @@ struct Builder {
       const int span = o.seg_c0 >= 0 ? o.seg_cn : cw;
       ConvParams probe = p;
       // (the residual's channel offset decides the alignment of its rows: checked here, at plan time)
-      probe.res = has_res ? (const float*)(uintptr_t)(4096 + (o.res->at() % 4096) + (size_t)res_coff * sizeof(float)) : nullptr;
-      probe.gate_src = has_gs ? (const float*)16 : nullptr;
+      probe.res = o.res ? (const float*)(uintptr_t)(4096 + (o.res->at() % 4096) + (size_t)res_coff * sizeof(float)) : nullptr;
+      probe.gate_src = o.gate_src ? (const float*)16 : nullptr;
       probe.seg_c0 = y.coff + seg_c0;
       probe.partial = ks > 1 ? (float*)16 : nullptr;   // split-K: statistics from the reduction kernel, one chunk per pixel
       // (the bf16x3 form of a 1x1 conv whose tiles are cut in k leaves its partials from the summing launch, a chunk per 8 rows)
-      const int lin3_b = x3_linear_images(x, Cout, K, stride, pad, o);
-      const bool lin3 = lin3_b > 0;
+      const bool lin3 = Bset > 0;
       int nchunk = conv_seg_chunks(probe) > 0 && lin3 && o.out_mode == OUT_NHWC
-                       ? Ho * Wo / gemm_bf16x3_shape(1, lin3_b * Ho * Wo, Cout, x.C, u->cus).seg_rows()
+                       ? Ho * Wo / gemm_bf16x3_shape(1, Bset * Ho * Wo, Cout, x.C, u->cus).seg_rows()
                        : conv_seg_chunks(probe);
       // (the bf16x3 PixelShuffle epilogue takes maps 16 pixels wide - conv_buf_kernel's wants 32 - with the same chunks: four
       // sub-positions per 32 input pixels)
@@ -791,7 +809,7 @@ struct Builder {
     // epilogue form: bias / residual / gate, strided rows; weights split into planes once per plan, the fp32 activations by
     // the kernel's loader waves; GroupNorm partials of the output where no tile is cut in k).  Layers with an activation
     // stay on conv_buf_kernel; cfg.conv_algo != 0 (the direct-convolution plans of the tests) too
-    if (const int Bset = x3_linear_images(x, Cout, K, stride, pad, o)) {
+    if (Bset > 0) {
       const int64_t M = (int64_t)Bset * Ho * Wo;   // rows of one launch: Bset images (the whole batch but for maps past 2 GB)
       const int Cin = x.C;
       const float* W3 = cached("x3lin:" + std::to_string((uintptr_t)w) + ":" + std::to_string(Cout) + "x" + std::to_string(Cin),
@@ -806,22 +824,18 @@ struct Builder {
       base.lda = p.ldx;
       base.act = o.act;
       base.pixshuf_wo = o.out_mode == OUT_PIXSHUF ? Wo : 0;
-      const int yoff = p.yoff;
       const int seg_coff = o_yoff - seg_c0;
-      const int64_t seg_per_image = (int64_t)seg_nseg * seg_nchunk * 2;   // doubles: [image][segment][chunk][2]
-      const int64_t y_per_image = (int64_t)(o.out_mode == OUT_PIXSHUF ? 4 : 1) * Ho * Wo * p.ldy;   // floats
       for (int b0 = 0; b0 < x.B; b0 += Bset) {
-        // (every per-image pointer moved on by the set's first image)
-        const size_t xo_s = xo + (size_t)b0 * x.H * x.W * p.ldx * sizeof(float), yo_s = yo + (size_t)b0 * y_per_image * sizeof(float);
-        const size_t ro_s = ro + (size_t)b0 * Ho * Wo * p.ldres * sizeof(float), gso_s = gso + (size_t)b0 * Ho * Wo * p.ldgs * sizeof(float);
-        const size_t go_s = go + (size_t)b0 * Cout * sizeof(float), sego_s = sego + (size_t)b0 * seg_per_image * sizeof(double);
+        // (every per-image address is that of the set's first image)
+        const Ref res = image(o.res, b0).floats(res_coff), gs = image(o.gate_src, b0), gate = image(o.gate, b0);
+        const Ref seg = seg_nseg ? seg_at(sego, seg_nseg, seg_nchunk, b0) : Ref();
         auto epi_of = [=]() {
           X3Epi e = base;
-          e.res = has_res ? uu->P(ro_s) + res_coff : nullptr;
-          e.gate_src = has_gs ? uu->P(gso_s) : nullptr;
-          e.gate = has_gs ? uu->P(go_s) : nullptr;
-          if (seg_nseg) {   // the output feeds a GroupNorm: its partials from the epilogue (of the summing launch where tiles are cut in k)
-            e.seg = (double*)uu->P(sego_s);
+          e.res = res.f();
+          e.gate_src = gs.f();
+          e.gate = gate.f();
+          if (seg) {   // the output feeds a GroupNorm: its partials from the epilogue (of the summing launch where tiles are cut in k)
+            e.seg = seg.d();
             e.seg_nseg = seg_nseg;
             e.seg_coff = seg_coff;
           }
@@ -830,21 +844,24 @@ struct Builder {
         const std::string shape = " M" + std::to_string(M) + " Cin" + std::to_string(Cin) + " Cout" + std::to_string(Cout);
         const int64_t m = o.macs_override >= 0 ? o.macs_override : M * Cout * Cin;
         // (planes: written by the LayerNorm in front, the loader waves only move them)
-        emit_x3_gemm(xo_s, W3, yo_s + (size_t)yoff * sizeof(float), 1, M, Cout, Cin, !x.x3p, epi_of, "conv k1", shape, m);
+        emit_x3_gemm(image(x, b0), W3, image(y, b0).floats(o_yoff), 1, M, Cout, Cin, !x.x3p, epi_of, "conv k1", shape, m);
       }   // sets of images
       if (ks > 1) free(part);
       return y;
     }
+    const Ref xr = at(x), yr = base(y), res = at(o.res).floats(res_coff), gs = at(o.gate_src), gate = at(o.gate);
+    const Ref seg = seg_nseg ? seg_at(sego) : Ref();
+    const kd_unet* io = u;   // the plan's output buffer is a per-call argument, read when the op runs
     emit([=](hipStream_t s) {
       ConvParams q = p;
-      q.x = uu->P(xo);
-      q.y = ext ? uu->out : uu->P(yo);
-      q.res = has_res ? uu->P(ro) + res_coff : nullptr;
-      q.gate_src = has_gs ? uu->P(gso) : nullptr;
-      q.gate = has_gs ? uu->P(go) : nullptr;
-      q.partial = ks > 1 ? uu->P(parto) : nullptr;
-      if (seg_nseg) {
-        q.seg_partial = (double*)uu->P(sego);
+      q.x = xr.f();
+      q.y = ext ? io->out : yr.f();
+      q.res = res.f();
+      q.gate_src = gs.f();
+      q.gate = gate.f();
+      q.partial = partial.f();
+      if (seg) {
+        q.seg_partial = seg.d();
         q.seg_nseg = seg_nseg;
         q.seg_c0 = p.yoff - o_yoff + seg_c0;   // block channel of the partial buffer's segment 0
       }
@@ -893,12 +910,10 @@ struct Builder {
     y.B = x.B; y.H = x.H; y.W = x.W;
     return y;
   }
-  // small-M linear on [M,K] rows living at workspace offset (row stride ldx) -> [M,N] (row stride ldy)
-  void skinny(size_t x_off, int ldx, const float* w, const float* bias, size_t y_off, int ldy, int M, int K, int N,
-              int in_act, int act) {
-    kd_unet* uu = u;
+  // small-M linear on [M,K] rows living at x of the workspace (row stride ldx) -> [M,N] at y (row stride ldy)
+  void skinny(Ref x, int ldx, const float* w, const float* bias, Ref y, int ldy, int M, int K, int N, int in_act, int act) {
     emit([=](hipStream_t s) {
-      return launch_linear_skinny(uu->P(x_off), ldx, w, bias, uu->P(y_off), ldy, M, K, N, in_act, act, s);
+      return launch_linear_skinny(x.f(), ldx, w, bias, y.f(), ldy, M, K, N, in_act, act, s);
     }, "skinny M" + std::to_string(M) + " K" + std::to_string(K) + " N" + std::to_string(N), (int64_t)M * K * N);
     if (phase != Phase::Text) u->macs += (int64_t)M * K * N;
   }
@@ -919,17 +934,14 @@ struct Builder {
     if ((planes & 1) && want_seg) throw std::runtime_error("plan: GroupNorm partials of a LayerNorm output in plane form");
     T y = alloc_out(planes & 1);
     if (g2) *y2 = alloc_out(planes & 2);
-    size_t xo = x.at(), yo = y.off, ro = res ? res->at() : 0, y2o = g2 ? y2->off : 0;
-    bool hr = res != nullptr;
     int rows = (int)x.rows(), C = x.C, ldx = x.LD(), ldres = res ? res->LD() : 0;
     // the output feeds a GroupNorm (the ResnetBlock's block2 behind its cross-attention): one chunk of partials per pixel
     const int hw = x.HW();
     const bool sg = want_seg && step_op() && C % 16 == 0 && C <= 4096 && x.B * hw == rows;
-    const size_t sgo = sg ? add_seg(y, 0, C / 16, hw) : 0;
-    kd_unet* uu = u;
+    const Ref seg = sg ? seg_at(add_seg(y, 0, C / 16, hw)) : Ref();
+    const Ref xr = at(x), yr = at(y), rr = at(res), y2r = g2 ? at(*y2) : Ref();
     emit([=](hipStream_t s) {
-      return launch_layernorm(uu->P(xo), ldx, g, beta, hr ? uu->P(ro) : nullptr, ldres, uu->P(yo), rows, C, 1e-5f, s, in_act, g2,
-                              g2 ? uu->P(y2o) : nullptr, sg ? (double*)uu->P(sgo) : nullptr, hw, planes);
+      return launch_layernorm(xr.f(), ldx, g, beta, rr.f(), ldres, yr.f(), rows, C, 1e-5f, s, in_act, g2, y2r.f(), seg.d(), hw, planes);
     }, std::string(g2 ? "ln x2 rows" : "ln rows") + std::to_string(rows) + " C" + std::to_string(C) + (planes ? " planes" : ""));
     return y;
   }
@@ -949,12 +961,11 @@ struct Builder {
     int G = cfg.resnet_groups;
     T y = alloc(x.B, x.H, x.W, x.C);
     emit_gn_stats(x, gamma, beta, ss_col, nullptr);
-    size_t xo = x.at(), yo = y.off, so = gn_stats_t.off, sso = t_ss.off;
-    int Bx = x.B, HW = x.HW(), C = x.C, ld = tmlp_total, ldx = x.LD();
-    kd_unet* uu = u;
+    const Ref xr = at(x), yr = at(y), st = at(gn_stats_t);
+    const Film ss = film(ss_col);
+    int Bx = x.B, HW = x.HW(), C = x.C, ldx = x.LD();
     emit([=](hipStream_t s) {
-      const float* ssp = ss_col >= 0 ? uu->P(sso) + ss_col : nullptr;
-      return launch_gn_apply_silu(uu->P(xo), ldx, uu->P(so), gamma, beta, ssp, ld, uu->P(yo), Bx, HW, C, G, s);
+      return launch_gn_apply_silu(xr.f(), ldx, st.f(), gamma, beta, ss.row.f(), ss.ld, yr.f(), Bx, HW, C, G, s);
     }, "gn apply HW" + std::to_string(HW) + " C" + std::to_string(C));
     return y;
   }
@@ -965,10 +976,9 @@ struct Builder {
   }
   // in place on a workspace tensor: normalise (and scale) the `heads` 64-wide segments at the start of each row
   void qk_norm(const T& t, int ld, int heads, const float* scale_vec) {
-    size_t off = t.at();   // (a column slice of a wider buffer: the fused q / kv projection)
+    const Ref tr = at(t);   // (a column slice of a wider buffer: the fused q / kv projection)
     int64_t rows = t.rows();
-    kd_unet* uu = u;
-    emit([=](hipStream_t s) { return launch_l2norm_heads(uu->P(off), ld, rows, heads, scale_vec, s); },
+    emit([=](hipStream_t s) { return launch_l2norm_heads(tr.f(), ld, rows, heads, scale_vec, s); },
          "qk l2norm rows" + std::to_string(rows) + " heads" + std::to_string(heads));
   }
   const float* q_scale_of(const std::string& pre) { return cfg.attn_qk_norm == 2 ? P(pre + ".q_scale", cfg.attn_dim_head) : nullptr; }
@@ -1002,14 +1012,13 @@ struct Builder {
     if (cfg.attn_qk_norm) qk_norm(q, inner, H, q_scale_of(pre));
     T o = alloc(x.B, x.H, x.W, inner);
     {
-      size_t qo = q.off, kvo = kv.off, oo = o.off;
+      const Ref qr = at(q), kr = at(kv), vr = kr.floats(inner), outr = at(o);
       int Bx = x.B, Nq = x.HW(), Nc = c.HW();
       float scale = attn_scale();
-      kd_unet* uu = u;
       emit([=](hipStream_t s) {
-        KVSeg s0{uu->P(kvo), uu->P(kvo) + inner, 2 * inner, Nc};
+        KVSeg s0{kr.f(), vr.f(), 2 * inner, Nc};
         KVSeg s1{nullptr, nullptr, 0, 0};
-        return launch_attention(uu->P(qo), inner, nkv, nkv + D, s0, s1, uu->P(oo), inner, Bx, Nq, H, H, scale, s);
+        return launch_attention(qr.f(), inner, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, Nq, H, H, scale, s);
       }, "xattn Nq" + std::to_string(Nq) + " Nk" + std::to_string(Nc + 1));
       u->macs += (int64_t)Bx * H * Nq * (Nc + 1) * D * 2;
     }
@@ -1069,16 +1078,15 @@ struct Builder {
     }
     T o = alloc(x.B, x.H, x.W, inner);
     {
-      size_t qo = q.at(), kvo = kv.at(), oo = o.off, co = has_ctx ? ckv.off : 0;
+      const Ref qr = at(q), kr = at(kv), outr = at(o), ck = has_ctx ? at(ckv) : Ref();
       int Bx = x.B, N = x.HW(), Nc = has_ctx ? ctx->HW() : 0;
       const int ldq = q.LD(), ldkv = kv.LD();
       float scale = attn_scale();
-      kd_unet* uu = u;
       emit([=](hipStream_t s) {
         KVSeg s0{nullptr, nullptr, 0, 0};
-        if (has_ctx) s0 = KVSeg{uu->P(co), uu->P(co) + D, 2 * D, Nc};
-        KVSeg s1{uu->P(kvo), uu->P(kvo) + D, ldkv, N};
-        return launch_attention(uu->P(qo), ldq, nkv, nkv + D, s0, s1, uu->P(oo), inner, Bx, N, H, 1, scale, s);
+        if (ck) s0 = KVSeg{ck.f(), ck.floats(D).f(), 2 * D, Nc};
+        KVSeg s1{kr.f(), kr.floats(D).f(), ldkv, N};
+        return launch_attention(qr.f(), ldq, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, N, H, 1, scale, s);
       }, "attn N" + std::to_string(N));
       u->macs += (int64_t)Bx * H * N * (N + Nc + 1) * D * 2;
     }
@@ -1126,13 +1134,13 @@ struct Builder {
     const float* w2 = P(pre + ".net.2.weight", (int64_t)C * hid);
     const float* b2 = P(pre + ".net.2.bias", C);
     int Bx = h.B, HW = h.HW();
-    kd_unet* uu = u;
+    const Ref hr = at(h);
     if (gca_gate_fused_ok(C, hid) && h.B > 1 && kd_switch("KD_GCA_FUSED", 1)) {   // (a batch-1 patch: one workgroup would stream the weights alone)
       T scratch = alloc_bytes(gca_scratch_floats(h.B, h.HW(), C) * sizeof(float));
       T gate = alloc(h.B, 1, 1, C);
-      size_t ho = h.off, so = scratch.off, go = gate.off;
+      const Ref sr = at(scratch), gr = at(gate);
       emit([=](hipStream_t s) {
-        return launch_gca_gate(uu->P(ho), wk, bk, uu->P(so), w0, b0, hid, w2, b2, uu->P(go), Bx, HW, C, s);
+        return launch_gca_gate(hr.f(), wk, bk, sr.f(), w0, b0, hid, w2, b2, gr.f(), Bx, HW, C, s);
       }, "gca_gate HW" + std::to_string(HW) + " C" + std::to_string(C));
       u->macs += (int64_t)Bx * HW * C * 2 + (int64_t)Bx * C * hid * 2;
       free(scratch);
@@ -1141,18 +1149,18 @@ struct Builder {
     T logits = alloc(h.B, h.H, h.W, 1);
     T pooled = alloc(h.B, 1, 1, C);
     T scratch = alloc_bytes(gca_scratch_floats(h.B, h.HW(), C) * sizeof(float));
-    size_t ho = h.off, lo = logits.off, po = pooled.off, so = scratch.off;
+    const Ref lr = at(logits), pr = at(pooled), sr = at(scratch);
     emit([=](hipStream_t s) {
-      return launch_gca_pool(uu->P(ho), wk, bk, uu->P(lo), uu->P(po), uu->P(so), Bx, HW, C, s);
+      return launch_gca_pool(hr.f(), wk, bk, lr.f(), pr.f(), sr.f(), Bx, HW, C, s);
     }, "gca_pool HW" + std::to_string(HW) + " C" + std::to_string(C));
     u->macs += (int64_t)Bx * HW * C * 2;
     free(logits);
     free(scratch);
     T hidden = alloc(h.B, 1, 1, hid);
-    skinny(pooled.off, C, w0, b0, hidden.off, hid, h.B, C, hid, ACT_NONE, ACT_SILU);
+    skinny(at(pooled), C, w0, b0, at(hidden), hid, h.B, C, hid, ACT_NONE, ACT_SILU);
     free(pooled);
     T gate = alloc(h.B, 1, 1, C);
-    skinny(hidden.off, hid, w2, b2, gate.off, C, h.B, hid, C, ACT_NONE, ACT_SIGMOID);
+    skinny(at(hidden), hid, w2, b2, at(gate), C, h.B, hid, C, ACT_NONE, ACT_SIGMOID);
     free(hidden);
     return gate;
   }
@@ -1287,27 +1295,27 @@ struct Builder {
     T y = alloc(x.B, H, W, Cout);
     const std::string shape = " M" + std::to_string((int64_t)Bx * HW) + " Cin" + std::to_string(Cin) + " Cout" +
                               std::to_string(Cout);
-    kd_unet* uu = u;
     const bool sg = Cout % 64 == 0;   // GroupNorm partials of y for whichever layer normalises it next
-    const size_t sgo_all = sg ? add_seg(y, 0, Cout / 16, (H / 4) * (W / 4)) : 0;
+    const int seg_nchunk = (H / 4) * (W / 4);
+    const size_t sgo_all = sg ? add_seg(y, 0, Cout / 16, seg_nchunk) : 0;
+    const Ref vr = at(V), dr = at(D);
     for (int st = 0; st < nset; ++st) {
       const int b0 = st * Bx;   // first image of the set
       {
-        size_t xo = x.at() + (size_t)b0 * HW * x.LD() * sizeof(float), vo = V.off;
-        size_t so = gn_stats_t.off + (size_t)b0 * G * 2 * sizeof(float), sso = t_ss.off + (size_t)b0 * tmlp_total * sizeof(float);
-        const int ld = tmlp_total, ldx = x.LD();
+        const Ref xr = image(x, b0), sr = at(gn_stats_t).floats((int64_t)b0 * G * 2);
+        const Film ss = film(ss_col, b0);
+        const int ldx = x.LD();
         emit([=](hipStream_t s) {
-          const float* ssp = ss_col >= 0 ? uu->P(sso) + ss_col : nullptr;
           if (x3_planes)
-            return launch_wino4_in3(uu->P(xo), ldx, uu->P(so), gamma, beta, ssp, ld, uu->P(vo), Bx, H, W, Cin, G, s, skip_c0, skip_scale);
-          return launch_wino4_in(uu->P(xo), ldx, uu->P(so), gamma, beta, ssp, ld, uu->P(vo), Bx, H, W, Cin, G, s, skip_c0, skip_scale);
+            return launch_wino4_in3(xr.f(), ldx, sr.f(), gamma, beta, ss.row.f(), ss.ld, vr.f(), Bx, H, W, Cin, G, s, skip_c0, skip_scale);
+          return launch_wino4_in(xr.f(), ldx, sr.f(), gamma, beta, ss.row.f(), ss.ld, vr.f(), Bx, H, W, Cin, G, s, skip_c0, skip_scale);
         }, (x3_planes ? "wino4_in3" : "wino4_in") + shape);
       }
       if (x3) {
         const float* U3 = cached("wino4x3:" + conv_prefix, ((size_t)36 * Cout * Cin * 3 + 1) / 2,
                                  [&](float* dst) { KD_THROW_IF(launch_split3(U, dst, 36, Cout, Cin, 0)); });
         // (the algorithmic MACs of the 3x3 conv it replaces)
-        emit_x3_gemm(V.off, U3, D.off, 36, Mt, Cout, Cin, !x3_planes, nullptr, "wino4", shape, (int64_t)Bx * HW * Cout * Cin * 9);
+        emit_x3_gemm(vr, U3, dr, 36, Mt, Cout, Cin, !x3_planes, nullptr, "wino4", shape, (int64_t)Bx * HW * Cout * Cin * 9);
       } else {
         ConvOpt o;
         o.wz_rows = (int)Mt;
@@ -1318,14 +1326,10 @@ struct Builder {
         if (recorded()) u->op_label.back() = "wino4 gemm" + shape;
       }
       {
-        const size_t sgo = sgo_all + (size_t)b0 * (Cout / 16) * ((H / 4) * (W / 4)) * 2 * sizeof(double);
-        size_t d_o = D.off, yo = y.off + (size_t)b0 * HW * Cout * sizeof(float);
-        const bool hr = res != nullptr;
+        const Ref seg = sg ? seg_at(sgo_all, Cout / 16, seg_nchunk, b0) : Ref(), yr = image(y, b0), rr = image(res, b0);
         const int ldres = res ? res->LD() : 0;
-        size_t ro = res ? res->at() + (size_t)b0 * HW * ldres * sizeof(float) : 0;
         emit([=](hipStream_t s) {
-          return launch_wino4_out(uu->P(d_o), bias, hr ? uu->P(ro) : nullptr, ldres, uu->P(yo), Cout,
-                                  sg ? (double*)uu->P(sgo) : nullptr, Bx, H, W, Cout, s);
+          return launch_wino4_out(dr.f(), bias, rr.f(), ldres, yr.f(), Cout, seg.d(), Bx, H, W, Cout, s);
         }, "wino4_out" + shape);
       }
     }   // sets
@@ -1360,21 +1364,17 @@ struct Builder {
     T y = alloc(Bx, H, W, Cout);
     // GroupNorm partials of y from the output transform (one chunk per 2x2 tile) for whichever layer normalises it next
     const bool sg = Cout % 16 == 0;
-    const size_t sgo = sg ? add_seg(y, 0, Cout / 16, (H / 2) * (W / 2)) : 0;
+    const Ref seg = sg ? seg_at(add_seg(y, 0, Cout / 16, (H / 2) * (W / 2))) : Ref();
     const std::string shape = " M" + std::to_string((int64_t)Bx * HW) + " Cin" + std::to_string(Cin) + " Cout" +
                               std::to_string(Cout);
+    const Ref xr = at(x), vr = at(V), dr = at(D), yr = at(y), rr = at(res), st = at(gn_stats_t);
+    const Film ss = film(ss_col);
+    const int ldx = x.LD(), ldres = res ? res->LD() : 0;
     for (int64_t t0 = 0; t0 < Mt; t0 += nt_slice) {
       const int64_t nt = std::min(nt_slice, Mt - t0);
-      {
-        size_t xo = x.at(), vo = V.off, so = gn_stats_t.off, sso = t_ss.off;
-        int ld = tmlp_total, ldx = x.LD();
-        kd_unet* uu = u;
-        emit([=](hipStream_t s) {
-          const float* ssp = ss_col >= 0 ? uu->P(sso) + ss_col : nullptr;
-          return launch_wino_in(uu->P(xo), ldx, uu->P(so), gamma, beta, ssp, ld, uu->P(vo), Bx, H, W, Cin, G, t0, nt,
-                                s);
-        }, "wino_in" + shape);
-      }
+      emit([=](hipStream_t s) {
+        return launch_wino_in(xr.f(), ldx, st.f(), gamma, beta, ss.row.f(), ss.ld, vr.f(), Bx, H, W, Cin, G, t0, nt, s);
+      }, "wino_in" + shape);
       T Vs = V, Ds = D;
       Vs.W = (int)(16 * nt);
       Ds.W = (int)(16 * nt);
@@ -1384,16 +1384,9 @@ struct Builder {
       o.macs_override = nt * 4 * Cout * Cin * 9;  // algorithmic MACs of the share of the 3x3 conv it replaces
       conv(Vs, U, nullptr, Cout, 1, 1, 0, o);
       if (recorded()) u->op_label.back() = "wino gemm" + shape;
-      {
-        size_t d_o = D.off, yo = y.off, ro = res ? res->at() : 0;
-        bool hr = res != nullptr;
-        int ldres = res ? res->LD() : 0;
-        kd_unet* uu = u;
-        emit([=](hipStream_t s) {
-          return launch_wino_out(uu->P(d_o), bias, hr ? uu->P(ro) : nullptr, ldres, uu->P(yo), Bx, H, W, Cout, t0, nt,
-                                 s, sg ? (double*)uu->P(sgo) : nullptr);
-        }, "wino_out" + shape);
-      }
+      emit([=](hipStream_t s) {
+        return launch_wino_out(dr.f(), bias, rr.f(), ldres, yr.f(), Bx, H, W, Cout, t0, nt, s, seg.d());
+      }, "wino_out" + shape);
     }
     free(V);
     free(D);
@@ -1414,21 +1407,18 @@ struct Builder {
                       [&](float* dst) { KD_THROW_IF(launch_wino_fused128_pack(wsrc, dst, Cout, Cin, 0, WF_U_SCALE)); });
     T ab = alloc_bytes((size_t)Bx * Cin * 2 * sizeof(float));
     T y = alloc(Bx, H, W, Cout);
-    kd_unet* uu = u;
+    const Ref abr = at(ab);
     // statistics: from the partials x's producer left (one launch gives the folded affine too), else a pass over x
     if (!emit_gn_stats(x, gamma, beta, ss_col, &ab)) {
-      size_t so = gn_stats_t.off, sso = t_ss.off, abo = ab.off;
-      const int ld = tmlp_total;
-      emit([=](hipStream_t s) {
-        const float* ssp = ss_col >= 0 ? uu->P(sso) + ss_col : nullptr;
-        return launch_gn_fold(uu->P(so), gamma, beta, ssp, ld, uu->P(abo), Bx, Cin, G, s);
-      }, "gn fold C" + std::to_string(Cin));
+      const Ref st = at(gn_stats_t);
+      const Film ss = film(ss_col);
+      emit([=](hipStream_t s) { return launch_gn_fold(st.f(), gamma, beta, ss.row.f(), ss.ld, abr.f(), Bx, Cin, G, s); },
+           "gn fold C" + std::to_string(Cin));
     }
     // the epilogue leaves the partials of y for whichever GroupNorm reads it next (block2, or the next block)
     const bool so_ = Cout % 16 == 0;
-    const size_t pout = so_ ? add_seg(y, 0, Cout / 16, (int)wino_fused_out_stats_chunks(H, W, Cout, Cout / 16)) : 0;
-    size_t xo = x.at(), yo = y.off, ro = res ? res->at() : 0, abo = ab.off;
-    const bool hr = res != nullptr;
+    const Ref seg = so_ ? seg_at(add_seg(y, 0, Cout / 16, (int)wino_fused_out_stats_chunks(H, W, Cout, Cout / 16))) : Ref();
+    const Ref xr = at(x), yr = at(y), rr = at(res);
     const int ldres = res ? res->LD() : 0, ldx = x.LD();
     const int64_t m = (int64_t)Bx * H * W * Cout * Cin * 9;
     // id -> (image, y0, x0, slab) of the kernel's work items: one table per map shape, shared by the layers
@@ -1436,8 +1426,8 @@ struct Builder {
     const float* items = cached("winof128_items:" + shape_key, wino_fused128_items_count(Bx, H, W, Cout) * 4,
                                 [&](float* dst) { KD_THROW_IF(launch_wino_fused128_items(dst, Bx, H, W, Cout, 0)); });
     emit([=](hipStream_t s) {
-      return launch_wino_fused_gn128(uu->P(xo), ldx, uu->P(abo), U, bias, hr ? uu->P(ro) : nullptr, ldres, uu->P(yo), Bx, H,
-                                     W, Cin, Cout, so_ ? (double*)uu->P(pout) : nullptr, so_ ? Cout / 16 : 0, items, s);
+      return launch_wino_fused_gn128(xr.f(), ldx, abr.f(), U, bias, rr.f(), ldres, yr.f(), Bx, H, W, Cin, Cout, seg.d(),
+                                     so_ ? Cout / 16 : 0, items, s);
     }, "wino fused M" + std::to_string((int64_t)Bx * H * W) + " Cin" + std::to_string(Cin) + " Cout" +
            std::to_string(Cout), m);
     free(ab);
@@ -1524,14 +1514,12 @@ struct Builder {
       } else {
         out = out_slot ? *out_slot : alloc(x.B, x.H, x.W, dim_out);
         if (out.C != dim_out) throw std::runtime_error("plan: output slot of the wrong width: " + pre);
-        size_t ao = h2.off, go = gate.off, ro = x.at(), yo = out.at();
+        const Ref ar = at(h2), gr = at(gate), rr = at(x), yr = at(out);
         int Bx = x.B, HW = x.HW(), ldr = x.LD(), ldy = out.LD();
         const bool sg = dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
-        const size_t sgo = sg ? add_seg(out, 0, dim_out / 16, gate_add_chunks(Bx, HW)) : 0;
-        kd_unet* uu = u;
+        const Ref seg = sg ? seg_at(add_seg(out, 0, dim_out / 16, gate_add_chunks(Bx, HW))) : Ref();
         emit([=](hipStream_t s) {
-          return launch_gate_add(uu->P(ao), uu->P(go), uu->P(ro), ldr, uu->P(yo), ldy,
-                                 sg ? (double*)uu->P(sgo) : nullptr, Bx, HW, dim_out, s);
+          return launch_gate_add(ar.f(), gr.f(), rr.f(), ldr, yr.f(), ldy, seg.d(), Bx, HW, dim_out, s);
         }, "gate_add HW" + std::to_string(HW) + " C" + std::to_string(dim_out));
       }
       free(gate);
@@ -1588,19 +1576,18 @@ struct Builder {
     const int span = y.C;   // channels the partial buffer covers
     const bool sg = Cout % 16 == 0 && span % 16 == 0 && (Ho * Wo) % 32 == 0;
     last_seg_nchunk = sg ? Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows() : 0;
-    const size_t sgo = sg ? add_seg(y, 0, span / 16, last_seg_nchunk) : 0;
-    kd_unet* uu = u;
+    const Ref seg = sg ? seg_at(add_seg(y, 0, span / 16, last_seg_nchunk)) : Ref();
     auto epi_of = [=]() {
       X3Epi e = base;
       e.bias = bias;
-      if (sg) {
-        e.seg = (double*)uu->P(sgo);
+      if (seg) {
+        e.seg = seg.d();
         e.seg_nseg = span / 16;
       }
       return e;
     };
     const std::string shape = " M" + std::to_string(M) + " Cin" + std::to_string(C) + " Cout" + std::to_string(Cout);
-    emit_x3_gemm(x.at(), W3, y.off, 1, M, Cout, K, true, epi_of, "conv k2", shape, M * Cout * K);
+    emit_x3_gemm(at(x), W3, at(y), 1, M, Cout, K, true, epi_of, "conv k2", shape, M * Cout * K);
     return y;
   }
   T downsample(const T& x, const std::string& pre, int dim_out) {  // pixel-unshuffle + conv1x1 == 2x2/s2 conv
@@ -1672,13 +1659,12 @@ struct Builder {
     if ((x.coff & 3)) throw std::runtime_error("upsample_nearest_conv3x3: input channel offset must be a multiple of 4 (" + pre + ")");
     const float* wp = cached("upnearest_w:" + pre, upsample_nearest_weight_floats(C, dim_out),
                              [&](float* dst) { KD_THROW_IF(launch_upsample_nearest_pack(wsrc, dst, dim_out, C, 0)); });
-    const size_t xo = x.at(), yo = y.off;
+    const Ref xr = at(x), yr = base(y);   // (the launch takes y's first channel as yoff)
     const int ldx = x.LD(), ldy = y.LD(), yoff = y.coff, Bx = x.B, H = x.H, W = x.W;
-    kd_unet* uu = u;
     const int64_t M = (int64_t)Bx * H * W;
     const int64_t m = 4 * M * dim_out * C * 9;
     emit([=](hipStream_t s) {
-      return launch_upsample_nearest_conv3x3(uu->P(xo), ldx, wp, b, uu->P(yo), ldy, yoff, Bx, H, W, C, dim_out, s);
+      return launch_upsample_nearest_conv3x3(xr.f(), ldx, wp, b, yr.f(), ldy, yoff, Bx, H, W, C, dim_out, s);
     }, "upsample nearest conv3 M" + std::to_string(M) + " Cin" + std::to_string(C) + " Cout" + std::to_string(dim_out), m);
     count_macs(m, 4 * M * dim_out * 4 * C);
     return y;
@@ -1703,43 +1689,39 @@ struct Builder {
   }
   T concat_skip(const T& x, const T& skip, float scale) {
     T y = alloc(x.B, x.H, x.W, x.C + skip.C);
-    size_t ao = x.at(), bo = skip.at(), yo = y.off;
     int Ca = x.C, Cb = skip.C, lda = x.LD(), ldb = skip.LD();
     int64_t rows = x.rows();
-    kd_unet* uu = u;
+    const Ref ar = at(x), br = at(skip), ya = at(y), yb = ya.floats(Ca);
     emit([=](hipStream_t s) {
-      if (launch_copy_scale_rows(uu->P(ao), lda, uu->P(yo), Ca + Cb, Ca, 1.0f, rows, s)) return 1;
-      return launch_copy_scale_rows(uu->P(bo), ldb, uu->P(yo) + Ca, Ca + Cb, Cb, scale, rows, s);
+      if (launch_copy_scale_rows(ar.f(), lda, ya.f(), Ca + Cb, Ca, 1.0f, rows, s)) return 1;
+      return launch_copy_scale_rows(br.f(), ldb, yb.f(), Ca + Cb, Cb, scale, rows, s);
     }, "concat rows" + std::to_string(rows) + " C" + std::to_string(Ca + Cb));
     return y;
   }
   // the same when x's producer already wrote its Ca channels into y (resnet / upsample with ct = &y)
   void concat_skip_tail(const T& y, int Ca, const T& skip, float scale) {
-    size_t bo = skip.at(), yo = y.off;
+    const Ref br = at(skip), yb = at(y).floats(Ca);
     int Cb = skip.C, ldb = skip.LD(), ldy = y.LD();
     int64_t rows = y.rows();
-    kd_unet* uu = u;
     emit([=](hipStream_t s) {
-      return launch_copy_scale_rows(uu->P(bo), ldb, uu->P(yo) + Ca, ldy, Cb, scale, rows, s);
+      return launch_copy_scale_rows(br.f(), ldb, yb.f(), ldy, Cb, scale, rows, s);
     }, "concat tail rows" + std::to_string(rows) + " C" + std::to_string(Ca + Cb));
   }
   // x into the first x.C channels of the concat buffer ct (whose skip half is already there)
   void concat_head(const T& ct, const T& x) {
-    size_t ao = x.at(), yo = ct.off;
+    const Ref ar = at(x), yr = at(ct);
     int Ca = x.C, lda = x.LD(), ldy = ct.LD();
     int64_t rows = x.rows();
-    kd_unet* uu = u;
-    emit([=](hipStream_t s) { return launch_copy_scale_rows(uu->P(ao), lda, uu->P(yo), ldy, Ca, 1.0f, rows, s); },
+    emit([=](hipStream_t s) { return launch_copy_scale_rows(ar.f(), lda, yr.f(), ldy, Ca, 1.0f, rows, s); },
          "concat head rows" + std::to_string(rows) + " C" + std::to_string(Ca));
   }
   // in place: channels [c0, c0 + n) of t times scale (a skip half whose consumer cannot fold the scale)
   void scale_slice(const T& t, int c0, int n, float scale) {
-    size_t o = t.off;
+    const Ref tr = at(t).floats(c0);
     int ld = t.LD();
     int64_t rows = t.rows();
-    kd_unet* uu = u;
     emit([=](hipStream_t s) {
-      return launch_copy_scale_rows(uu->P(o) + c0, ld, uu->P(o) + c0, ld, n, scale, rows, s);
+      return launch_copy_scale_rows(tr.f(), ld, tr.f(), ld, n, scale, rows, s);
     }, "scale slice rows" + std::to_string(rows) + " C" + std::to_string(n));
   }
 
@@ -1785,23 +1767,23 @@ struct Builder {
     int tcd = u->time_cond_dim, half = cfg.sinu_dim / 2, sw = cfg.sinu_dim + 1;
     int cd = cfg.cond_dim, ntt = cfg.num_time_tokens, ntok = c_tok.H * c_tok.W;
     const float* sw_w = P(hid + ".0.weights", half);
-    kd_unet* uu = u;
-    size_t eo = emb.off;
+    const kd_unet* io = u;   // the per-call inputs are read when the op runs
+    const Ref er = at(emb);
     int Bx = B;
     emit([=](hipStream_t s) {
-      const float* t = lowres ? uu->in_lowres_log_snr : uu->in_log_snr;
+      const float* t = lowres ? io->in_lowres_log_snr : io->in_log_snr;
       if (!t) {
         set_error(lowres ? "lowres_log_snr is required by this UNet" : "log_snr is required");
         return 1;
       }
-      return launch_sinu_emb(t, sw_w, uu->P(eo), Bx, half, s);
+      return launch_sinu_emb(t, sw_w, er.f(), Bx, half, s);
     });
-    skinny(emb.off, sw, P(hid + ".1.weight", (int64_t)tcd * sw), P(hid + ".1.bias", tcd), hidden.off, tcd, B, sw,
+    skinny(er, sw, P(hid + ".1.weight", (int64_t)tcd * sw), P(hid + ".1.bias", tcd), at(hidden), tcd, B, sw,
            tcd, ACT_NONE, ACT_SILU);
     // tokens: [B, ntt*cd] written at row tok_row of c (row stride ntok*cd per batch)
-    skinny(hidden.off, tcd, P(tok + ".0.weight", (int64_t)cd * ntt * tcd), P(tok + ".0.bias", cd * ntt),
-           c_tok.off + (size_t)tok_row * cd * sizeof(float), ntok * cd, B, tcd, cd * ntt, ACT_NONE, ACT_NONE);
-    skinny(hidden.off, tcd, P(cond + ".0.weight", (int64_t)tcd * tcd), P(cond + ".0.bias", tcd), t_out.off, tcd, B,
+    skinny(at(hidden), tcd, P(tok + ".0.weight", (int64_t)cd * ntt * tcd), P(tok + ".0.bias", cd * ntt),
+           at(c_tok).floats((int64_t)tok_row * cd), ntok * cd, B, tcd, cd * ntt, ACT_NONE, ACT_NONE);
+    skinny(at(hidden), tcd, P(cond + ".0.weight", (int64_t)tcd * tcd), P(cond + ".0.bias", tcd), at(t_out), tcd, B,
            tcd, tcd, ACT_NONE, ACT_NONE);
   }
 

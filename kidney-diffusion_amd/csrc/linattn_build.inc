@@ -57,10 +57,10 @@ T Builder::linear_attn_block(const T& x, const std::string& pre, const T* ctx, c
   const int m = has_ctx ? ctx->HW() : 0;
   T qc = alloc(Bx, Hh, Ww, C3);
   T part = alloc_bytes((size_t)Bx * nchunk * inner * 2 * sizeof(float));
-  kd_unet* uu = u;
+  const Ref qr = at(qc), pr = at(part);
   {
-    const size_t xo = qkv.off, yo = qc.off, po = part.off;
-    emit([=](hipStream_t s) { return launch_linattn_dwconv(uu->P(xo), wdw, uu->P(yo), uu->P(po), Bx, Hh, Ww, inner, s); },
+    const Ref xr = at(qkv);
+    emit([=](hipStream_t s) { return launch_linattn_dwconv(xr.f(), wdw, qr.f(), pr.f(), Bx, Hh, Ww, inner, s); },
          "linattn dwconv HW" + std::to_string(HW) + " C" + std::to_string(C3), (int64_t)Bx * HW * C3 * 9);
     u->macs += (int64_t)Bx * HW * C3 * 9;
   }
@@ -68,12 +68,10 @@ T Builder::linear_attn_block(const T& x, const std::string& pre, const T* ctx, c
   T ctxm = alloc(Bx, H, D, D);
   {
     T ws = alloc_bytes(linattn_ws_floats(Bx, H, HW) * sizeof(float));
-    const size_t qo = qc.off, po = part.off, wo = ws.off, co = ctxm.off, cko = has_ctx ? ckv.off : 0;
+    const Ref kr = qr.floats(inner), vr = qr.floats(2 * inner), wr = at(ws), cr = at(ctxm), ck = has_ctx ? at(ckv) : Ref();
     emit([=](hipStream_t s) {
-      const float* ckp = has_ctx ? uu->P(cko) : nullptr;
-      return launch_linattn_context(uu->P(qo) + inner, uu->P(qo) + 2 * inner, C3, uu->P(po), HW, ckp,
-                                    has_ctx ? ckp + inner : nullptr, 2 * inner, m, nullptr, nullptr, uu->P(wo), uu->P(co), Bx,
-                                    H, s);
+      return launch_linattn_context(kr.f(), vr.f(), C3, pr.f(), HW, ck.f(), ck.floats(inner).f(), 2 * inner, m, nullptr, nullptr,
+                                    wr.f(), cr.f(), Bx, H, s);
     }, "linattn context HW" + std::to_string(HW) + " m" + std::to_string(m), (int64_t)Bx * H * (HW + m) * D * D);
     u->macs += (int64_t)Bx * H * (HW + m) * D * D;
     free(ws);
@@ -82,10 +80,10 @@ T Builder::linear_attn_block(const T& x, const std::string& pre, const T* ctx, c
   if (has_ctx) free(ckv);
   T o = alloc(Bx, Hh, Ww, inner);
   {
-    const size_t qo = qc.off, co = ctxm.off, oo = o.off;
+    const Ref cr = at(ctxm), outr = at(o);
     const float scale = 1.0f / sqrtf((float)D);
     emit([=](hipStream_t s) {
-      return launch_linattn_apply(uu->P(qo), C3, uu->P(co), uu->P(oo), inner, Bx, HW, H, scale, 1, s);
+      return launch_linattn_apply(qr.f(), C3, cr.f(), outr.f(), inner, Bx, HW, H, scale, 1, s);
     }, "linattn apply N" + std::to_string(HW), (int64_t)Bx * HW * inner * D);
     u->macs += (int64_t)Bx * HW * inner * D;
   }
@@ -109,27 +107,26 @@ T Builder::linear_cross_attn(const T& x, const std::string& pre, const T& c) {
   free(xn);
   const float* nkv = P(pre + ".null_kv", 2 * D);
   const int Bx = x.B, m = c.HW();
-  kd_unet* uu = u;
   T ctxm;
   {   // a function of c alone (cond region)
     auto ph = cond_scope();
     T kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
     ctxm = alloc(Bx, H, D, D);
-    const size_t kvo = kv.off, co = ctxm.off;
+    const Ref kr = at(kv), vr = kr.floats(inner), cr = at(ctxm);
     emit([=](hipStream_t s) {
-      return launch_linattn_context(nullptr, nullptr, 0, nullptr, 0, uu->P(kvo), uu->P(kvo) + inner, 2 * inner, m, nkv,
-                                    nkv + D, nullptr, uu->P(co), Bx, H, s);
+      return launch_linattn_context(nullptr, nullptr, 0, nullptr, 0, kr.f(), vr.f(), 2 * inner, m, nkv, nkv + D, nullptr, cr.f(),
+                                    Bx, H, s);
     }, "linattn xcontext m" + std::to_string(m + 1), (int64_t)Bx * H * (m + 1) * D * D);
     if (phase != Phase::Text) u->macs += (int64_t)Bx * H * (m + 1) * D * D;
     free(kv);
   }
   T o = alloc(Bx, x.H, x.W, inner);
   {
-    const size_t qo = q.off, co = ctxm.off, oo = o.off;
+    const Ref qr = at(q), cr = at(ctxm), outr = at(o);
     const int N = x.HW();
     const float scale = 1.0f / sqrtf((float)D);
     emit([=](hipStream_t s) {
-      return launch_linattn_apply(uu->P(qo), inner, uu->P(co), uu->P(oo), inner, Bx, N, H, scale, 0, s);
+      return launch_linattn_apply(qr.f(), inner, cr.f(), outr.f(), inner, Bx, N, H, scale, 0, s);
     }, "linattn xapply N" + std::to_string(N), (int64_t)Bx * N * inner * D);
     u->macs += (int64_t)Bx * N * inner * D;
   }

@@ -19,7 +19,8 @@ void Builder::build_text() {
   const int ntok = cfg.text_tokens;
   u->text_embed_dim = ted;
   u->max_text_len = P;
-  kd_unet* uu = u;
+  const kd_unet* io = u;   // the per-call text inputs and output buffers are read through it when an op runs
+  const int Bx = B;
 
   // 1. project + select against the null embedding
   T tok = alloc(B, 1, P, cd);  // rows >= L stay unused
@@ -27,17 +28,15 @@ void Builder::build_text() {
   {
     const float* w = P_("text_to_cond.weight"), *bias = P_("text_to_cond.bias");
     const float* null_embed = P_("null_text_embed");
-    size_t to = tok.off, xo = x.off;
-    int Bx = B;
+    const Ref tr = at(tok), xr = at(x);
     emit([=](hipStream_t s) {
-      const int L = uu->in_text_len;
-      if (L < 1 || L > P || !uu->in_text_embeds) {   // (in_text_mask == nullptr: the library's text_mask = None)
+      const int L = io->in_text_len;
+      if (L < 1 || L > P || !io->in_text_embeds) {   // (in_text_mask == nullptr: the library's text_mask = None)
         set_error("text conditioning: text_embeds [B,L<=max_text_len,text_embed_dim] are required");
         return 1;
       }
-      if (launch_linear_skinny(uu->in_text_embeds, ted, w, bias, uu->P(to), cd, Bx * L, ted, cd, ACT_NONE, ACT_NONE, s))
-        return 1;
-      return launch_text_select(uu->P(to), uu->in_text_mask, null_embed, uu->P(xo), Bx, L, P, cd, uu->in_text_drop, s);
+      if (launch_linear_skinny(io->in_text_embeds, ted, w, bias, tr.f(), cd, Bx * L, ted, cd, ACT_NONE, ACT_NONE, s)) return 1;
+      return launch_text_select(tr.f(), io->in_text_mask, null_embed, xr.f(), Bx, L, P, cd, io->in_text_drop, s);
     });
   }
   free(tok);
@@ -46,27 +45,25 @@ void Builder::build_text() {
   T xp = alloc(B, 1, P, cd);
   {
     const float* pos = P_("attn_pool.pos_emb.weight");
-    size_t xo = x.off, yo = xp.off;
-    int Bx = B;
-    emit([=](hipStream_t s) { return launch_add_rows_bcast(uu->P(xo), pos, uu->P(yo), Bx, P, cd, s); });
+    const Ref xr = at(x), yr = at(xp);
+    emit([=](hipStream_t s) { return launch_add_rows_bcast(xr.f(), pos, yr.f(), Bx, P, cd, s); });
   }
   T lat = alloc(B, 1, ntok, cd);
   {
     T mp = alloc(B, 1, 1, cd);
-    size_t xo = x.off, mo = mp.off;
-    int Bx = B;
-    emit([=](hipStream_t s) { return launch_mean_rows(uu->P(xo), uu->P(mo), Bx, P, cd, s); });
+    const Ref xr = at(x), mr = at(mp);
+    emit([=](hipStream_t s) { return launch_mean_rows(xr.f(), mr.f(), Bx, P, cd, s); });
     T mpn = layernorm(mp, P_("attn_pool.to_latents_from_mean_pooled_seq.0.g"), nullptr);
     free(mp);
     // Linear(cd -> n_mp*cd) written as the first n_mp rows of every batch's latent block
-    skinny(mpn.off, cd, P_("attn_pool.to_latents_from_mean_pooled_seq.1.weight"),
-           P_("attn_pool.to_latents_from_mean_pooled_seq.1.bias"), lat.off, ntok * cd, B, cd, n_mp * cd, ACT_NONE,
+    skinny(at(mpn), cd, P_("attn_pool.to_latents_from_mean_pooled_seq.1.weight"),
+           P_("attn_pool.to_latents_from_mean_pooled_seq.1.bias"), at(lat), ntok * cd, B, cd, n_mp * cd, ACT_NONE,
            ACT_NONE);
     free(mpn);
     const float* latp = P_("attn_pool.latents");
-    size_t lo = lat.off;
+    const Ref lr = at(lat).floats((int64_t)n_mp * cd);
     emit([=](hipStream_t s) {  // learned latents broadcast to every batch element, rows n_mp..ntok
-      return launch_copy_rows(latp, 0, cd, uu->P(lo) + (size_t)n_mp * cd, (int64_t)ntok * cd, cd, n_lat, cd, Bx, s);
+      return launch_copy_rows(latp, 0, cd, lr.f(), (int64_t)ntok * cd, cd, n_lat, cd, Bx, s);
     });
   }
   free(x);
@@ -87,13 +84,12 @@ void Builder::build_text() {
     }
     T o = alloc(B, 1, ntok, inner);
     {
-      size_t qo = q.off, xo = kvx.off, lo = kvl.off, oo = o.off;
-      int Bx = B;
-      float scale = attn_scale();
+      const Ref qr = at(q), xr = at(kvx), lr = at(kvl), outr = at(o);
+        float scale = attn_scale();
       emit([=](hipStream_t s) {
-        KVSeg s0{uu->P(xo), uu->P(xo) + inner, 2 * inner, P};
-        KVSeg s1{uu->P(lo), uu->P(lo) + inner, 2 * inner, ntok};
-        return launch_attention(uu->P(qo), inner, nullptr, nullptr, s0, s1, uu->P(oo), inner, Bx, ntok, H, H, scale, s);
+        KVSeg s0{xr.f(), xr.floats(inner).f(), 2 * inner, P};
+        KVSeg s1{lr.f(), lr.floats(inner).f(), 2 * inner, ntok};
+        return launch_attention(qr.f(), inner, nullptr, nullptr, s0, s1, outr.f(), inner, Bx, ntok, H, H, scale, s);
       });
     }
     free(q);
@@ -118,35 +114,33 @@ void Builder::build_text() {
 
   // 3. outputs: pooled tokens and the non-attention text hiddens
   {
-    size_t lo = lat.off;
-    int Bx = B;
+    const Ref lr = at(lat);
     emit([=](hipStream_t s) {
-      if (!uu->out_text_tokens || !uu->out_text_hiddens) {
+      if (!io->out_text_tokens || !io->out_text_hiddens) {
         set_error("text conditioning: output buffers are required");
         return 1;
       }
-      return launch_copy_rows(uu->P(lo), (int64_t)ntok * cd, cd, uu->out_text_tokens, (int64_t)ntok * cd, cd, ntok, cd,
-                              Bx, s);
+      return launch_copy_rows(lr.f(), (int64_t)ntok * cd, cd, io->out_text_tokens, (int64_t)ntok * cd, cd, ntok, cd, Bx, s);
     });
     T mean = alloc(B, 1, 1, cd);
-    size_t mo = mean.off;
-    emit([=](hipStream_t s) { return launch_mean_rows(uu->P(lo), uu->P(mo), Bx, ntok, cd, s); });
+    const Ref mr = at(mean);
+    emit([=](hipStream_t s) { return launch_mean_rows(lr.f(), mr.f(), Bx, ntok, cd, s); });
     T mn = layernorm(mean, P_("to_text_non_attn_cond.0.weight"), P_("to_text_non_attn_cond.0.bias"));
     free(mean);
     T h = alloc(B, 1, 1, tcd);
-    skinny(mn.off, cd, P_("to_text_non_attn_cond.1.weight"), P_("to_text_non_attn_cond.1.bias"), h.off, tcd, B, cd, tcd,
+    skinny(at(mn), cd, P_("to_text_non_attn_cond.1.weight"), P_("to_text_non_attn_cond.1.bias"), at(h), tcd, B, cd, tcd,
            ACT_NONE, ACT_SILU);
     free(mn);
     T hh = alloc(B, 1, 1, tcd);
-    skinny(h.off, tcd, P_("to_text_non_attn_cond.3.weight"), P_("to_text_non_attn_cond.3.bias"), hh.off, tcd, B, tcd,
+    skinny(at(h), tcd, P_("to_text_non_attn_cond.3.weight"), P_("to_text_non_attn_cond.3.bias"), at(hh), tcd, B, tcd,
            tcd, ACT_NONE, ACT_NONE);
     free(h);
     const float* null_hidden = P_("null_text_hidden");
-    size_t ho = hh.off;
+    const Ref hr = at(hh);
     emit([=](hipStream_t s) {
-      if (uu->in_text_drop)  // cond_drop_prob = 1: every sample takes the learned null hidden
-        return launch_copy_rows(null_hidden, 0, tcd, uu->out_text_hiddens, tcd, tcd, 1, tcd, Bx, s);
-      return launch_copy_rows(uu->P(ho), tcd, tcd, uu->out_text_hiddens, tcd, tcd, 1, tcd, Bx, s);
+      if (io->in_text_drop)  // cond_drop_prob = 1: every sample takes the learned null hidden
+        return launch_copy_rows(null_hidden, 0, tcd, io->out_text_hiddens, tcd, tcd, 1, tcd, Bx, s);
+      return launch_copy_rows(hr.f(), tcd, tcd, io->out_text_hiddens, tcd, tcd, 1, tcd, Bx, s);
     });
     free(hh);
   }

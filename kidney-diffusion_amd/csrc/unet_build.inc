@@ -17,6 +17,8 @@ void Builder::build() {
   if (S % (1 << n_down)) throw std::runtime_error("image_size must be divisible by the total downsampling factor");
   if (dim % 32) throw std::runtime_error("dim must be a multiple of 32 (GroupNorm(8) over dim/8 channels, 16-B loads)");
 
+  const kd_unet* io = u;   // the per-call inputs and the output buffer are read through it when an op runs
+  const int Bx = B;
   collect_time_mlps();
   // use_linear_cross_attn: the level's first ResnetBlock on each path gets (linear) cross-attention
   for (int l = 0; l < L; ++l)
@@ -58,15 +60,13 @@ void Builder::build() {
   if (fin_has_static) {
     auto ph = scope(Phase::Static);
     fin_static = alloc(B, Ci, S, S);
-    size_t so = fin_static.off;
-    int Bx = B;
-    kd_unet* uu = u;
+    const Ref fr = at(fin_static);
     emit([=](hipStream_t s) {
-      if (!uu->in_lowres) {
+      if (!io->in_lowres) {
         set_error("lowres_cond_img must be given iff the UNet has lowres_cond");
         return 1;
       }
-      return launch_final_static(uu->in_lowres, wfin, bfin, uu->P(so), fin_c, dim, Ci, Bx, S, S, s);
+      return launch_final_static(io->in_lowres, wfin, bfin, fr.f(), fin_c, dim, Ci, Bx, S, S, s);
     });
   }
 
@@ -83,10 +83,9 @@ void Builder::build() {
       T t2 = alloc(B, 1, 1, tcd);
       time_trio("to_lowres_time_hiddens", "to_lowres_time_cond", "to_lowres_time_tokens", true, t2, c_raw,
                 cfg.num_time_tokens, emb, hidden);
-      size_t ao = t_emb.off, bo = t2.off;
+      const Ref ar = at(t_emb), br = at(t2);
       int64_t n = (int64_t)B * tcd;
-      kd_unet* uu = u;
-      emit([=](hipStream_t s) { return launch_add(uu->P(ao), uu->P(bo), uu->P(ao), n, s); });
+      emit([=](hipStream_t s) { return launch_add(ar.f(), br.f(), ar.f(), n, s); });
       free(t2);
     }
     free(emb);
@@ -94,26 +93,22 @@ void Builder::build() {
   }
   if (cfg.text_tokens > 0) {
     int nt = cfg.text_tokens;
-    size_t co = c_raw.off, to = t_emb.off;
-    int Bx = B;
+    const Ref cr = at(c_raw).floats((int64_t)n_time_tok * cd), tr = at(t_emb);
     int64_t n = (int64_t)B * tcd;
-    kd_unet* uu = u;
     emit([=](hipStream_t s) {
-      if (!uu->in_text_tokens || !uu->in_text_hiddens) {
+      if (!io->in_text_tokens || !io->in_text_hiddens) {
         set_error("this UNet was planned with text conditioning: text_tokens/text_hiddens are required");
         return 1;
       }
-      if (launch_copy_rows(uu->in_text_tokens, (int64_t)nt * cd, cd, uu->P(co) + (size_t)n_time_tok * cd,
-                           (int64_t)ntok * cd, cd, nt, cd, Bx, s))
-        return 1;
-      return launch_add(uu->P(to), uu->in_text_hiddens, uu->P(to), n, s);
+      if (launch_copy_rows(io->in_text_tokens, (int64_t)nt * cd, cd, cr.f(), (int64_t)ntok * cd, cd, nt, cd, Bx, s)) return 1;
+      return launch_add(tr.f(), io->in_text_hiddens, tr.f(), n, s);
     });
   }
   T c = layernorm(c_raw, P("norm_cond.weight", cd), P("norm_cond.bias", cd));
   free(c_raw);
   if (tmlp_total > 0) {
     t_ss = alloc(B, 1, 1, tmlp_total);
-    skinny(t_emb.off, tcd, tmlp_w, tmlp_b, t_ss.off, tmlp_total, B, tcd, tmlp_total, ACT_SILU, ACT_NONE);
+    skinny(at(t_emb), tcd, tmlp_w, tmlp_b, at(t_ss), tmlp_total, B, tcd, tmlp_total, ACT_SILU, ACT_NONE);
   }
   free(t_emb);
   cond_ph.exit();
@@ -133,13 +128,12 @@ void Builder::build() {
   const int ds[3] = {dim / 2, dim / 4, dim - dim / 2 - dim / 4};
   T init_static;
   {
-    kd_unet* uu = u;
     auto check_inputs = [=]() {
-      if ((Cc > 0) != (uu->in_cond != nullptr)) {
+      if ((Cc > 0) != (io->in_cond != nullptr)) {
         set_error("cond_images must be given iff the UNet has cond_images_channels > 0");
         return 1;
       }
-      if ((Cl > 0) != (uu->in_lowres != nullptr)) {
+      if ((Cl > 0) != (io->in_lowres != nullptr)) {
         set_error("lowres_cond_img must be given iff the UNet has lowres_cond");
         return 1;
       }
@@ -149,11 +143,11 @@ void Builder::build() {
       const int spad = (Cs + 3) & ~3;
       auto ph = scope(Phase::Static);
       T simg = alloc(B, S, S, spad);
-      size_t so = simg.off;
-      int Bx = B, HW = S * S;
+      const Ref sr = at(simg);
+      const int HW = S * S;
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_pack_init(uu->in_cond, Cc, nullptr, 0, uu->in_lowres, Cl, uu->P(so), spad, Bx, HW, s);
+        return launch_pack_init(io->in_cond, Cc, nullptr, 0, io->in_lowres, Cl, sr.f(), spad, Bx, HW, s);
       });
       init_static = alloc(B, S, S, dim);
       int off = 0;
@@ -190,7 +184,7 @@ void Builder::build() {
       const float* w15 = raw("init_conv.convs.2.weight", (int64_t)ds[2] * init_ch * 225);
       const int n3 = ds[0], n7 = ds[1], n15 = ds[2], Itot = init_ch, c0 = Cc;
       const int np = NPs;
-      float* wp = cached(uu->self_cond ? "init_conv_fused6" : "init_conv_fused", init_conv_weight_floats(n3, n7, n15, np), [&](float* dst) {
+      float* wp = cached(u->self_cond ? "init_conv_fused6" : "init_conv_fused", init_conv_weight_floats(n3, n7, n15, np), [&](float* dst) {
         KD_THROW_IF(launch_init_conv_pack(w3, w7, w15, dst, n3, n7, n15, Itot, c0, np, 0));
       });
       float* biasp = nullptr;
@@ -205,27 +199,26 @@ void Builder::build() {
         });
       }
       const bool sg = dim % 16 == 0 && ds[0] % 16 == 0 && ds[1] % 16 == 0 && ds[2] % 16 == 0;
-      const size_t sgo = sg ? add_seg(xt, 0, dim / 16, S * S / 32) : 0;
-      const size_t xo = xt.at(), ro = hoist ? init_static.off : 0;
-      const int ldy = xt.LD(), Bx = B;
+      const Ref seg = sg ? seg_at(add_seg(xt, 0, dim / 16, S * S / 32)) : Ref();
+      const Ref yr = at(xt), rr = hoist ? at(init_static) : Ref();
+      const int ldy = xt.LD();
       const int64_t m = (int64_t)B * S * S * np * (9 * n3 + 49 * n7 + 225 * n15);
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        return launch_init_conv(uu->in_x, uu->in_self_cond, Ci, np, wp, biasp, hoist ? uu->P(ro) : nullptr, uu->P(xo), ldy,
-                                sg ? (double*)uu->P(sgo) : nullptr, Bx, S, n3, n7, n15, s);
-      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (uu->self_cond ? " self-cond" : ""), m);
+        return launch_init_conv(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, n3, n7, n15, s);
+      }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (u->self_cond ? " self-cond" : ""), m);
       // K runs (3 / 7 / 15 kernel rows of np k values, padded to even) x 32-row tiles
       const int r3 = 3 * (((3 * np + 1) / 2) * 2), r7 = 7 * (((7 * np + 1) / 2) * 2), r15 = 15 * (((15 * np + 1) / 2) * 2);
       count_macs(m, (int64_t)B * S * S * (r3 * ((n3 + 31) / 32 * 32) + r7 * 32 + r15 * 32));
     } else {
       const int np = NPs, ipad = (np + 3) & ~3;
       T img = alloc(B, S, S, ipad);  // x's planes (| self_cond's: zeros when it is not given) + zero channels
-      size_t yo = img.off;
-      int Bx = B, HW = S * S;
+      const Ref ir = at(img);
+      const int HW = S * S;
       emit([=](hipStream_t s) {
         if (check_inputs()) return 1;
-        const float* sc = uu->self_cond ? uu->in_self_cond : nullptr;
-        return launch_pack_init(nullptr, 0, uu->in_x, Ci, sc, sc ? Ci : 0, uu->P(yo), ipad, Bx, HW, s);
+        const float* sc = io->self_cond ? io->in_self_cond : nullptr;
+        return launch_pack_init(nullptr, 0, io->in_x, Ci, sc, sc ? Ci : 0, ir.f(), ipad, Bx, HW, s);
       });
       int off = 0;
       for (int i = 0; i < 3; ++i) {
@@ -313,11 +306,10 @@ void Builder::build() {
       // serve ONE concat (its buffer's first half is written by that concat's producer), so the second entry
       // is a copy in a slot of its own; it is popped - and dies - before the original, whose partials it shares.
       T slot = make_slot();
-      size_t so = x.at(), d_o = slot.at();
+      const Ref sr = at(x), dr = at(slot);
       int lds_ = x.LD(), ldd = slot.LD(), Cc = x.C;
       int64_t rows = x.rows();
-      kd_unet* uu = u;
-      emit([=](hipStream_t s) { return launch_copy_scale_rows(uu->P(so), lds_, uu->P(d_o), ldd, Cc, 1.0f, rows, s); },
+      emit([=](hipStream_t s) { return launch_copy_scale_rows(sr.f(), lds_, dr.f(), ldd, Cc, 1.0f, rows, s); },
            "skip copy rows" + std::to_string(rows) + " C" + std::to_string(Cc));
       share_seg(x, slot);
       hiddens.push_back(slot);   // the stack owns the slot's reference
@@ -492,11 +484,9 @@ void Builder::build() {
     ConvOpt o;
     o.macs_override = (int64_t)B * S * S * Ci * fin_c * 9;
     T pm = conv(x, wfin_p, nullptr, fin_n, 1, 1, 0, o);
-    size_t po = pm.off, so = fin_has_static ? fin_static.off : 0;
-    int Bx = B;
-    kd_unet* uu = u;
+    const Ref pr = at(pm), fr = fin_has_static ? at(fin_static) : Ref();
     emit([=](hipStream_t s) {
-      return launch_final_gather(uu->P(po), fin_has_static ? uu->P(so) : nullptr, bfin, uu->out, Ci, Bx, S, S, s);
+      return launch_final_gather(pr.f(), fr.f(), bfin, io->out, Ci, Bx, S, S, s);
     }, "final gather");
     free(pm);
   }
