@@ -45,7 +45,9 @@ const char* kd_last_error(void);
  *      kd_linattn_apply; kd_attention_ex and kd_l2norm_heads (the attention core and the qk-norm with the plan's argument
  *      forms, for unit tests); kd_text_select, kd_add_rows_bcast, kd_mean_rows and kd_copy_rows (the text plan's small kernels,
  *      for unit tests); kd_unet_text_cond accepts d_text_mask = NULL (text_mask = None); kd_unet_ext_t gained `cross_embed_downsample`
- *      and `upsample_nearest` at its end (zero = the plans of before); kd_upsample_nearest_conv3x3_nhwc added */
+ *      and `upsample_nearest` at its end (zero = the plans of before); kd_upsample_nearest_conv3x3_nhwc added; kd_unet_create_ext2
+ *      with its struct kd_unet_ext2_t for `combine_upsample_fmaps` - kd_unet_create_ext is that call with ext2 = NULL - and
+ *      kd_upsample_nearest_gn_conv3x3_nhwc added */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -178,6 +180,18 @@ typedef struct kd_unet_ext {
  * every linear flag zero gives the same plan - the same launches and the same bits - as kd_unet_create_self_cond. */
 int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                        const kd_unet_ext_t* ext, kd_unet_t** out);
+/* Further structural options, for kd_unet_create_ext2; kd_unet_ext_t keeps its size.  combine_upsample_fmaps = 1
+ * (`Unet(combine_upsample_fmaps=True)`): the map of every up level i (after ups.i.2, before its upsample) goes through
+ * `upsample_combiner.fmap_convs.i` = GroupNorm(8) -> SiLU -> Conv2d(dim_out_i, dim, 3, padding 1) at full resolution (nearest
+ * upsampling by the integer factor between the two maps), and final_res_block reads cat(x, those L maps[, init conv
+ * residual]): dim (1 + L) [+ dim] channels.  Needs dim % 32 == 0 and every level's width % 8 == 0 (refused at build otherwise). */
+typedef struct kd_unet_ext2 {
+  int combine_upsample_fmaps;
+} kd_unet_ext2_t;
+/* kd_unet_create_ext with the options of `ext2` (NULL = all zero: the plan of kd_unet_create_ext, the same launches and the
+ * same bits). */
+int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, kd_unet_t** out);
 void kd_unet_destroy(kd_unet_t* u);
 /* bytes of HBM held (weights + workspace) and algorithmic MACs of one forward (whole batch) */
 int64_t kd_unet_hbm_bytes(const kd_unet_t* u);
@@ -400,6 +414,19 @@ int kd_conv2d_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias,
  * and nothing else touched.  Needs Cin % 8 == 0, Cout % 32 == 0, ldy % 4 == 0, yoff % 4 == 0. */
 int kd_upsample_nearest_conv3x3_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias, float* d_y, int ldy, int yoff,
                                      int B, int H, int W, int Cin, int Cout, void* stream);
+/* nn.Upsample(scale_factor s, nearest), s an integer >= 2, followed by [SiLU(A x + B)] and Conv2d(Cin, Cout, 3, padding 1) in
+ * one kernel (kernels_upcombine.hip).  An output pixel is, by its row and its column inside the s x s block of its low-res
+ * pixel, of one of 3 x 3 classes (first / interior / last); a class is a small conv over the low-res map with the 3x3 taps
+ * that fall on one input pixel summed, so there are nine distinct values per (low-res pixel, output channel) from 25 summed
+ * tap matrices, each stored to every pixel of its class.  s = 2 has the four corner classes only.  x: NHWC [B,H,W] rows of
+ * stride ldx (0 = Cin); d_ab (may be NULL: x as it is): [B][Cin][2] per-(image, channel) affine in kd_gn_fold_seg's form
+ * (times kd_wf_ab_scale()), applied with the SiLU as the patch is loaded - taps off the map are zero AFTER it; w: torch OIHW
+ * [Cout,Cin,3,3] (packed on each call of this test entry); y: NHWC [B,sH,sW] rows of stride ldy (0 = Cout), the result in
+ * channels [yoff, yoff + Cout) and nothing else touched.  Needs Cin % 8 == 0, Cout % 32 == 0, ldx, ldy, yoff % 4 == 0 and
+ * fewer than 2^31 output pixels. */
+int kd_upsample_nearest_gn_conv3x3_nhwc(const float* d_x, int ldx, const float* d_ab, const float* d_w_oihw, const float* d_bias,
+                                        float* d_y, int ldy, int yoff, int B, int H, int W, int Cin, int Cout, int scale,
+                                        void* stream);
 /* The same 3x3 / stride-1 / pad-1 convolution through the plan's Winograd F(2x2,3x3) path (used for
  * the deep ResnetBlock convs): fp32, differs from kd_conv2d_nhwc by re-association
  * only.  Needs even H, W; B*H*W/4 % 256 == 0; Cin % 32 == 0; Cout > 32. */

@@ -24,6 +24,11 @@ int kd_unet_create_self_cond(const kd_unet_config_t* cfg, const kd_param_t* para
 
 int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                        const kd_unet_ext_t* ext, kd_unet_t** out) {
+  return kd_unet_create_ext2(cfg, params, n_params, share_with, ext, nullptr, out);
+}
+
+int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, kd_unet_t** out) {
   const int self_cond = ext ? ext->self_cond : 0;
   if (!cfg || !params || !out) {
     set_error("kd_unet_create: null argument");
@@ -50,6 +55,7 @@ int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, in
     u->cross_embed_downsample = ext->cross_embed_downsample != 0;
     u->upsample_nearest = ext->upsample_nearest != 0;
   }
+  u->combine_upsample_fmaps = ext2 && ext2->combine_upsample_fmaps != 0;
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   u->cus = gemm_bf16x3_device_cus();   // read once: every plan-time question and every launch shape of this plan uses it
@@ -377,6 +383,27 @@ int kd_upsample_nearest_conv3x3_nhwc(const float* d_x, const float* d_w_oihw, co
   if (bufs.get(&wp, upsample_nearest_weight_floats(Cin, Cout) * sizeof(float))) return 1;
   int rc = launch_upsample_nearest_pack(d_w_oihw, wp, Cout, Cin, s);
   if (!rc) rc = launch_upsample_nearest_conv3x3(d_x, Cin, wp, d_bias, d_y, ldy, yoff, B, H, W, Cin, Cout, s);
+  return entry_finish(rc, s);
+}
+
+// nn.Upsample(s, nearest) -> [SiLU(A x + B)] -> Conv2d(Cin, Cout, 3, padding 1) through the plan's launches
+// (kernels_upcombine.hip): the pack of the 25 summed tap matrices, then the class GEMMs with the replicating stores
+int kd_upsample_nearest_gn_conv3x3_nhwc(const float* d_x, int ldx, const float* d_ab, const float* d_w_oihw, const float* d_bias,
+                                        float* d_y, int ldy, int yoff, int B, int H, int W, int Cin, int Cout, int scale,
+                                        void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (ldx == 0) ldx = Cin;
+  if (ldy == 0) ldy = Cout;
+  KD_REQUIRE(d_x && d_w_oihw && d_y, "kd_upsample_nearest_gn_conv3x3_nhwc: null argument");
+  if (const char* why = upsample_scale_refusal(ldx, ldy, yoff, B, H, W, Cin, Cout, scale)) {
+    set_error(why);
+    return 1;
+  }
+  EntryBufs bufs;
+  float* wp = nullptr;
+  if (bufs.get(&wp, upsample_scale_weight_floats(Cin, Cout) * sizeof(float))) return 1;
+  int rc = launch_upsample_scale_pack(d_w_oihw, wp, Cout, Cin, s);
+  if (!rc) rc = launch_upsample_scale_conv3x3(d_x, ldx, d_ab, wp, d_bias, d_y, ldy, yoff, B, H, W, Cin, Cout, scale, s);
   return entry_finish(rc, s);
 }
 

@@ -340,6 +340,16 @@ int launch_upsample_nearest_pack(const float* w_oihw, float* wp, int O, int I, h
 // y[b][2 y + p][2 x + q][yoff + n] (row stride ldy) = conv3x3(nearest_x2(x))[..] + bias; x [B][H][W] rows of stride ldx
 int launch_upsample_nearest_conv3x3(const float* x, int ldx, const float* wp, const float* bias, float* y, int ldy, int yoff, int B,
                                     int H, int W, int Cin, int Cout, hipStream_t s);
+// ---- nearest x s (integer s >= 2) + [affine + SiLU on load] + 3x3 conv as nine class GEMMs over the low-res map
+// (kernels_upcombine.hip): the UpsampleCombiner's Block over an up level's map at full resolution
+// nullptr where the kernel takes the shape, else the condition it misses (as above, and s >= 2, fewer than 2^31 output pixels)
+const char* upsample_scale_refusal(int ldx, int ldy, int yoff, int B, int H, int W, int Cin, int Cout, int s);
+size_t upsample_scale_weight_floats(int Cin, int Cout);   // the 25 summed tap matrices [25][Cout][Cin]
+int launch_upsample_scale_pack(const float* w_oihw, float* wp, int O, int I, hipStream_t s);
+// y[b][s y + dy][s x + dx][yoff + n] (row stride ldy) = conv3x3(nearest_xs(a))[..] + bias, a = SiLU(A x + B) with ab [B][Cin][2]
+// in launch_gn_fold_seg's form, or a = x where ab is nullptr; x [B][H][W] rows of stride ldx
+int launch_upsample_scale_conv3x3(const float* x, int ldx, const float* ab, const float* wp, const float* bias, float* y, int ldy,
+                                  int yoff, int B, int H, int W, int Cin, int Cout, int scale, hipStream_t s);
 
 // ---- final conv to the image's `ch` = 1 .. 4 channels (kernels_final.hip)
 int final_gemm_cols(int ch);   // width of P: the 9 ch (output, tap) columns padded for the 1x1 GEMM (32; 48 at ch = 4)

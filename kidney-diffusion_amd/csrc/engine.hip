@@ -275,6 +275,9 @@ struct kd_unet {
   // the library's other resampling forms (kd_unet_ext_t): Downsample slots hold a CrossEmbedLayer (kernel sizes 2 and 4);
   // Upsample slots hold nearest x2 + conv3x3 instead of conv1x1 -> SiLU -> PixelShuffle
   int cross_embed_downsample = 0, upsample_nearest = 0;
+  // Unet(combine_upsample_fmaps=True) (kd_unet_ext2_t): every up level's map goes through a Block of its own at full resolution
+  // into the concat in front of final_res_block
+  int combine_upsample_fmaps = 0;
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
@@ -561,9 +564,11 @@ struct Builder {
     return sp.off;
   }
   // the sources covering ALL C channels of x in order (at most two), or false
-  bool seg_sources(const T& x, SegPart (&out)[2], int& n) const {
+  // (G: the GroupNorm's groups, 0 = cfg.resnet_groups)
+  bool seg_sources(const T& x, SegPart (&out)[2], int& n, int G = 0) const {
     n = 0;
-    if (x.C % cfg.resnet_groups || (x.C / cfg.resnet_groups) % 16) return false;
+    if (G <= 0) G = cfg.resnet_groups;
+    if (x.C % G || (x.C / G) % 16) return false;
     auto it = seg_of.find(x.at());
     if (it == seg_of.end()) return false;
     std::vector<SegPart> v = it->second.parts;
@@ -1687,6 +1692,81 @@ struct Builder {
     if (ct) o.dst = ct;   // straight into the first dim_out channels of the following skip concat
     return conv(x, w, b, 4 * dim_out, 1, 1, 0, o);
   }
+  // ---- `Unet(combine_upsample_fmaps=True)`: `upsample_combiner.fmap_convs.i`, the library's Block with its own default of
+  // 8 groups and no FiLM, over up level i's map f brought to the full resolution by nearest upsampling with the integer
+  // factor s, into channels [yoff, yoff + dim) of the concat `cat` in front of final_res_block.  s >= 2: one launch of the
+  // class kernel over the LOW-RES map (kernels_upcombine.hip) - the statistics of the upsampled map are those of f, every
+  // pixel being replicated s^2 times; where f's producer left partials that tile 16-channel groups they are folded to the
+  // per-(image, channel) affine the kernel applies on load, else GroupNorm + SiLU run over f into a low-res temporary.
+  // s = 1 (the last level of a UNet that is not memory_efficient): GroupNorm + SiLU, then the conv on the generic path.
+  // A shape the kernel does not take is refused here, at build.
+  static constexpr int COMBINE_GROUPS = 8;
+  T gn_silu_plain(const T& x, const float* gamma, const float* beta, int G) {
+    const int Bx = x.B, HW = x.HW(), C = x.C, ldx = x.LD();
+    if (C % G || (C / G) % 4) throw std::runtime_error("upsample_combiner: GroupNorm(" + std::to_string(G) + ") needs groups of 4 n channels, C = " + std::to_string(C));
+    T st = alloc_bytes((size_t)Bx * G * 2 * sizeof(float)), part = alloc_bytes(gn_partial_bytes(Bx, HW, C, G));
+    T y = alloc(x.B, x.H, x.W, C);
+    const Ref xr = at(x), yr = at(y), sr = at(st), pr = at(part);
+    emit([=](hipStream_t s) { return launch_gn_stats(xr.f(), ldx, sr.f(), pr.d(), Bx, HW, C, G, 1e-5f, s); },
+         "gn stats HW" + std::to_string(HW) + " C" + std::to_string(C));
+    emit([=](hipStream_t s) { return launch_gn_apply_silu(xr.f(), ldx, sr.f(), gamma, beta, nullptr, 0, yr.f(), Bx, HW, C, G, s); },
+         "gn apply HW" + std::to_string(HW) + " C" + std::to_string(C));
+    free(st);
+    free(part);
+    return y;
+  }
+  void combine_fmap(const T& f, int i, int scale, const T& cat, int yoff) {
+    const int G = COMBINE_GROUPS, dim = cfg.dim, Cin = f.C, Bx = f.B, H = f.H, W = f.W;
+    const std::string pre = "upsample_combiner.fmap_convs." + std::to_string(i);
+    const float* gamma = P(pre + ".groupnorm.weight", Cin);
+    const float* beta = P(pre + ".groupnorm.bias", Cin);
+    const float* bias = P(pre + ".project.bias", dim);
+    if (cat.B != Bx || cat.H != scale * H || cat.W != scale * W || scale < 1)
+      throw std::runtime_error("plan: " + pre + ": the map is no integer fraction of the full resolution");
+    if (scale == 1) {
+      T a = gn_silu_plain(f, gamma, beta, G);
+      ConvOpt o;
+      o.dst = &cat;
+      o.yoff = yoff;
+      conv(a, pack_conv(pre + ".project.weight", dim, Cin, Cin, 3), bias, dim, 3, 1, 1, o);
+      free(a);
+      return;
+    }
+    if (const char* why = upsample_scale_refusal(f.LD(), cat.LD(), cat.coff + yoff, Bx, H, W, Cin, dim, scale))
+      throw std::runtime_error(std::string(why) + " (" + pre + ": Cin " + std::to_string(Cin) + ", Cout " + std::to_string(dim) + ")");
+    if ((f.coff & 3)) throw std::runtime_error("upsample_nearest_gn_conv3x3: input channel offset must be a multiple of 4 (" + pre + ")");
+    const float* wsrc = raw(pre + ".project.weight", (int64_t)dim * Cin * 9);
+    const float* wp = cached("upcombine_w:" + pre, upsample_scale_weight_floats(Cin, dim),
+                             [&](float* dst) { KD_THROW_IF(launch_upsample_scale_pack(wsrc, dst, dim, Cin, 0)); });
+    SegPart sp[2];
+    int nsp = 0;
+    bool fold = Cin % G == 0 && (Cin / G) % 16 == 0 && seg_sources(f, sp, nsp, G);
+    for (int k = 0; k < nsp; ++k) fold = fold && sp[k].scale == 1.0f && sp[k].ab_mul == 1.0f;   // (the map as it is in memory)
+    T src = f, ab;
+    if (fold) {
+      ab = alloc_bytes((size_t)Bx * Cin * 2 * sizeof(float));
+      const SegPart a = sp[0], b2 = nsp > 1 ? sp[1] : SegPart();
+      const Ref pa = seg_at(a.off), pb = nsp > 1 ? seg_at(b2.off) : Ref(), abr = at(ab);
+      const int HW = f.HW();
+      emit([=](hipStream_t s) {
+        SegSrc s0{pa.d(), a.nseg, a.nchunk, a.c0, a.scale, a.ab_mul};
+        SegSrc s1{pb.d(), b2.nseg, b2.nchunk, b2.c0, b2.scale, b2.ab_mul};
+        return launch_gn_fold_seg(s0, s1, gamma, beta, nullptr, 0, abr.f(), nullptr, Bx, Cin, G, (double)HW * (Cin / G), 1e-5f, s);
+      }, "gn fold seg HW" + std::to_string(HW) + " C" + std::to_string(Cin));
+    } else {
+      src = gn_silu_plain(f, gamma, beta, G);
+    }
+    const Ref xr = at(src), abr = fold ? at(ab) : Ref(), yr = base(cat);
+    const int ldx = src.LD(), ldy = cat.LD(), yo = cat.coff + yoff;
+    const int64_t M = (int64_t)Bx * H * W;
+    const int64_t m = M * scale * scale * dim * Cin * 9;
+    emit([=](hipStream_t s) {
+      return launch_upsample_scale_conv3x3(xr.f(), ldx, abr.f(), wp, bias, yr.f(), ldy, yo, Bx, H, W, Cin, dim, scale, s);
+    }, "upsample combine s=" + std::to_string(scale) + " M" + std::to_string(M) + " Cin" + std::to_string(Cin) + " Cout" +
+           std::to_string(dim) + (fold ? " affine" : ""), m);
+    count_macs(m, M * dim * Cin * (scale == 2 ? 16 : 25));
+    free(fold ? ab : src);
+  }
   T concat_skip(const T& x, const T& skip, float scale) {
     T y = alloc(x.B, x.H, x.W, x.C + skip.C);
     int Ca = x.C, Cb = skip.C, lda = x.LD(), ldb = skip.LD();
@@ -1708,12 +1788,12 @@ struct Builder {
     }, "concat tail rows" + std::to_string(rows) + " C" + std::to_string(Ca + Cb));
   }
   // x into the first x.C channels of the concat buffer ct (whose skip half is already there)
-  void concat_head(const T& ct, const T& x) {
+  void concat_head(const T& ct, const T& x, const char* what = "concat head") {
     const Ref ar = at(x), yr = at(ct);
     int Ca = x.C, lda = x.LD(), ldy = ct.LD();
     int64_t rows = x.rows();
     emit([=](hipStream_t s) { return launch_copy_scale_rows(ar.f(), lda, yr.f(), ldy, Ca, 1.0f, rows, s); },
-         "concat head rows" + std::to_string(rows) + " C" + std::to_string(Ca));
+         std::string(what) + " rows" + std::to_string(rows) + " C" + std::to_string(Ca));
   }
   // in place: channels [c0, c0 + n) of t times scale (a skip half whose consumer cannot fold the scale)
   void scale_slice(const T& t, int c0, int n, float scale) {

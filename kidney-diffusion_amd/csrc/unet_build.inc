@@ -32,6 +32,10 @@ void Builder::build() {
 
   std::vector<int> dims{dim};
   for (int l = 0; l < L; ++l) dims.push_back(dim * cfg.dim_mults[l]);
+  // combine_upsample_fmaps: width of the concat in front of final_res_block, [x: dim | up level 0 (deepest) .. L - 1: dim
+  // each | init conv residual: dim]
+  const bool combine = u->combine_upsample_fmaps != 0;
+  const int cat_w = dim * (1 + L) + (cfg.init_conv_to_final_conv_residual ? dim : 0);
 
   // scratch shared by every GroupNorm, sized for the largest (rows x channels) it will see
   {
@@ -166,12 +170,14 @@ void Builder::build() {
     }
     // init_conv_to_final_conv_residual: the init conv's output is the second half of the concat in front of
     // final_res_block, so it is written there from the start (a channel slice of that buffer): no copy later
+    // (combine_upsample_fmaps: that concat is x | the L combiner maps | this residual, and the slice is always used)
     T xt;
-    if (slot_on && cfg.init_conv_to_final_conv_residual) {
-      xt = alloc(B, S, S, 2 * dim);
+    if ((slot_on || combine) && cfg.init_conv_to_final_conv_residual) {
+      const int before = combine ? cat_w - dim : dim;
+      xt = alloc(B, S, S, before + dim);
       xt.C = dim;
-      xt.ld = 2 * dim;
-      xt.coff = dim;
+      xt.ld = before + dim;
+      xt.coff = before;
     } else {
       xt = alloc(B, S, S, dim);
     }
@@ -422,6 +428,8 @@ void Builder::build() {
     step(y);
     return -1;
   };
+  std::vector<T> up_maps;   // combine_upsample_fmaps: each level's map after its attention slot
+  T cat_buf;                // ... and the concat in front of final_res_block, at its full width (from the last level on)
   for (int i = 0; i < L; ++i) {
     const int l = L - 1 - i;
     const std::string pre = "ups." + std::to_string(i);
@@ -431,22 +439,46 @@ void Builder::build() {
     const bool attn = cfg.layer_attns[l] != 0;
     const bool lin = !attn && u->lin_attn[l] != 0;
     const bool ups = !is_last || cfg.memory_efficient;
+    // combine_upsample_fmaps: whichever launch produces the final x writes channels [0, dim) of the combiner's concat in
+    // place - the last upsample (memory_efficient), else the level's attention block or the skip conv of its last ResnetBlock
+    T head_slot;
+    if (combine && is_last) {
+      cat_buf = keep_init ? whole(init_residual) : alloc(x.B, S, S, cat_w);
+      head_slot = cat_buf;
+      head_slot.C = dim;
+      head_slot.ld = cat_w;
+      head_slot.coff = 0;
+    }
+    const bool head_here = combine && is_last && !ups && dim_out == dim && x.H == S && x.W == S;
+    const bool head_resnet = head_here && !attn && !lin;
+    auto took_head = [&]() {   // the ResnetBlock wrote into the concat: x is its first dim channels
+      if (head_resnet && x.off == cat_buf.off) x = head_slot;
+    };
     int sc0 = add_skip(dim_out);
     step(resnet(x, pre + ".0", dim_out, cfg.layer_cross_attns[l] || u->lin_cross[l] ? &c : nullptr, false,
-                nb > 0 ? offer_ct(x.B, x.H, x.W, dim_out) : nullptr, nullptr, sc0, skip_scale));
+                nb > 0 ? offer_ct(x.B, x.H, x.W, dim_out) : head_resnet ? &cat_buf : nullptr, nullptr, sc0, skip_scale));
+    if (nb == 0) took_head();
     for (int n = 0; n < nb; ++n) {
       sc0 = add_skip(dim_out);
       const bool next_is_skip = n + 1 < nb || (!attn && !lin && !ups && !is_last);
       step(resnet(x, pre + ".1." + std::to_string(n), dim_out, nullptr, cfg.use_gca != 0,
-                  next_is_skip ? offer_ct(x.B, x.H, x.W, dim_out) : nullptr, nullptr, sc0, skip_scale));
+                  next_is_skip ? offer_ct(x.B, x.H, x.W, dim_out) : head_resnet && n == nb - 1 ? &cat_buf : nullptr, nullptr, sc0,
+                  skip_scale));
+      if (n == nb - 1) took_head();
     }
-    if (attn) step(transformer(x, pre + ".2", &c));
-    if (lin) step(linear_attn_block(x, pre + ".2", &c));
+    if (attn) step(transformer(x, pre + ".2", &c, head_here ? &head_slot : nullptr));
+    if (lin) step(linear_attn_block(x, pre + ".2", &c, head_here ? &head_slot : nullptr));
+    if (combine) {   // the level's map lives on to the tail, as a skip tensor does
+      retain(x);
+      up_maps.push_back(x);
+    }
     if (ups) {
       const T* target = nullptr;
       T fin;
       if (!is_last) {
         target = offer_ct(x.B, 2 * x.H, 2 * x.W, dim_in);
+      } else if (combine) {
+        target = &cat_buf;
       } else if (keep_init && init_residual.ld != 0 && init_residual.coff == dim_in) {
         fin = whole(init_residual);   // the last upsample writes the first half of the concat in front of final_res_block
         target = &fin;
@@ -458,7 +490,22 @@ void Builder::build() {
   if (!hiddens.empty()) throw std::runtime_error("plan: skip stack not empty after the up path");
 
   // ---- tail
-  if (keep_init) {
+  if (combine) {
+    // cat(x, fmap_convs.i(nearest(up level i's map)) ..[, init conv residual]): x's channels are there already where its
+    // producer wrote them in place (else copied, row "combine head"); every combiner launch writes its slice
+    const T full = cat_buf;
+    if (full.C != cat_w || full.H != S || full.W != S || x.H != S || x.W != S || x.C != (x.off == full.off && x.ld == 0 ? cat_w : dim))
+      throw std::runtime_error("plan: combiner concat of the wrong shape");
+    if (x.off != full.off) concat_head(full, x, "combine head");
+    for (int i = 0; i < L; ++i) {
+      const T& f = up_maps[i];
+      if (f.H < 1 || S % f.H || f.W != f.H) throw std::runtime_error("plan: up level map is no integer fraction of the image");
+      combine_fmap(f, i, S / f.H, full, dim * (1 + i));
+      free(f);
+    }
+    if (x.off != full.off) free(x);
+    x = full;   // (keep_init: init_residual's reference is x's now; more than two sources: final_res_block takes its statistics itself)
+  } else if (keep_init) {
     if (init_residual.ld != 0) {   // the init conv wrote its half of this concat at the start of the forward
       T full = whole(init_residual);
       if (x.off != full.off) {

@@ -113,6 +113,10 @@ class kd_unet_ext_t(C.Structure):
                 ("cross_embed_downsample", C.c_int), ("upsample_nearest", C.c_int)]
 
 
+class kd_unet_ext2_t(C.Structure):
+    _fields_ = [("combine_upsample_fmaps", C.c_int)]
+
+
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
 SIGNATURES = {
     "kd_last_error": (C.c_char_p, []),
@@ -128,6 +132,8 @@ SIGNATURES = {
                                            C.c_int, C.POINTER(C.c_void_p)]),
     "kd_unet_create_ext": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
                                      C.POINTER(kd_unet_ext_t), C.POINTER(C.c_void_p)]),
+    "kd_unet_create_ext2": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
+                                      C.POINTER(kd_unet_ext_t), C.POINTER(kd_unet_ext2_t), C.POINTER(C.c_void_p)]),
     "kd_unet_weight_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_macs": (C.c_int64, [C.c_void_p]),
     "kd_unet_mfma_macs": (C.c_int64, [C.c_void_p]),
@@ -156,6 +162,7 @@ SIGNATURES = {
                                       C.c_int, C.c_int, C.c_void_p]),
     "kd_conv2d_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
     "kd_upsample_nearest_conv3x3_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
+    "kd_upsample_nearest_gn_conv3x3_nhwc": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
     "kd_conv3x3_winograd_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "kd_conv3x3_winograd4_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "kd_gemm_bf16x3": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),

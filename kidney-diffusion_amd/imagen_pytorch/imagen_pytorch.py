@@ -266,6 +266,12 @@ class Block(_Decl):
         self.project = nn.Conv2d(dim, dim_out, 3, padding=1)
 
 
+class UpsampleCombiner(_Decl):   # enabled form only: a disabled combiner has no parameters and is not declared
+    def __init__(self, dim_ins, dim_out):
+        super().__init__()
+        self.fmap_convs = nn.ModuleList([Block(d, dim_out, 8) for d in dim_ins])
+
+
 class ResnetBlock(_Decl):
     def __init__(self, dim, dim_out, *, cond_dim=None, time_cond_dim=None, groups=8, use_gca=False, heads=8,
                  dim_head=64, linear_attn=False):
@@ -304,6 +310,7 @@ class Unet(nn.Module):
         init_conv_to_final_conv_residual=False, use_global_context_attn=True, scale_skip_connection=True,
         final_resnet_block=True, final_conv_kernel_size=3, self_cond=False, pixel_shuffle_upsample=True,
         cosine_sim_attn=False, attn_qk_norm=None, downsample_form="unshuffle", mid_attn_form="transformer",
+        combine_upsample_fmaps=False,
     ):
         """`downsample_form` / `mid_attn_form` (engine extensions) name the two structural forks between library
         versions - "unshuffle" | "conv4x4" and "transformer" | "residual_attention"; load_state_dict() selects them
@@ -338,6 +345,9 @@ class Unet(nn.Module):
         # nearest x2 + conv3x3 instead of the PixelShuffleUpsample
         self.cross_embed_downsample = bool(cross_embed_downsample)
         self.pixel_shuffle_upsample = bool(pixel_shuffle_upsample)
+        # the library's UpsampleCombiner: every up level's map goes through a Block of its own at full resolution into the
+        # concat in front of final_res_block
+        self.combine_upsample_fmaps = bool(combine_upsample_fmaps)
         self.max_text_len = max_text_len
         self.dim = dim
         # self_cond: every forward also reads the previous step's thresholded x0 estimate (zeros when not given); the
@@ -392,7 +402,8 @@ class Unet(nn.Module):
                           ff_mult=ff_mult, num_time_tokens=num_time_tokens, sinu_dim=learned_sinu_pos_emb_dim,
                           groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn,
                           cross_embed_downsample=self.cross_embed_downsample,
-                          upsample_nearest=not self.pixel_shuffle_upsample)
+                          upsample_nearest=not self.pixel_shuffle_upsample,
+                          combine_upsample_fmaps=self.combine_upsample_fmaps)
 
         self.init_resnet_block = ResnetBlock(dim, dim, time_cond_dim=tcd, groups=groups[0],
                                              use_gca=use_global_context_attn, **ak) if memory_efficient else None
@@ -462,6 +473,9 @@ class Unet(nn.Module):
                 up(d_out, d_in) if (not is_last or memory_efficient) else _Stateless(),
             ]))
         fin = dim + (dim if init_conv_to_final_conv_residual else 0)
+        if self.combine_upsample_fmaps:   # Block's own default of 8 groups, not resnet_groups; up level i works at dims[L - i]
+            self.upsample_combiner = UpsampleCombiner(tuple(dims[L - i] for i in range(L)), dim)
+            fin += dim * L
         self.final_res_block = ResnetBlock(fin, dim, time_cond_dim=tcd, groups=groups[0], use_gca=True)
         self.final_conv = nn.Conv2d(dim + (channels if lowres_cond else 0), self.channels_out, 3, padding=1)
         nn.init.zeros_(self.final_conv.weight)
@@ -703,7 +717,9 @@ class Unet(nn.Module):
                 ext.use_linear_cross_attn[i] = int(bool(p["use_linear_cross_attn"][i]))
             ext.cross_embed_downsample = int(p["cross_embed_downsample"])
             ext.upsample_nearest = int(p["upsample_nearest"])
-            E.check(lib.kd_unet_create_ext(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(handle)))
+            ext2 = E.kd_unet_ext2_t()
+            ext2.combine_upsample_fmaps = int(p["combine_upsample_fmaps"])
+            E.check(lib.kd_unet_create_ext2(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(ext2), C.byref(handle)))
             del sd
         self._engines[key] = handle
         self._engines_fingerprint = self._weights_fingerprint()
