@@ -47,7 +47,10 @@ const char* kd_last_error(void);
  *      for unit tests); kd_unet_text_cond accepts d_text_mask = NULL (text_mask = None); kd_unet_ext_t gained `cross_embed_downsample`
  *      and `upsample_nearest` at its end (zero = the plans of before); kd_upsample_nearest_conv3x3_nhwc added; kd_unet_create_ext2
  *      with its struct kd_unet_ext2_t for `combine_upsample_fmaps` - kd_unet_create_ext is that call with ext2 = NULL - and
- *      kd_upsample_nearest_gn_conv3x3_nhwc added */
+ *      kd_upsample_nearest_gn_conv3x3_nhwc added; kd_unet_config_t::attn_dim_head accepts 32 and 128 beside 64 (kd_attention too);
+ *      kd_unet_create_ext3 with its struct kd_unet_ext3_t for `layer_attns_depth` - kd_unet_create_ext2 is that call with
+ *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
+ *      are those with D = 64) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -75,7 +78,7 @@ typedef struct kd_unet_config {
   int cond_on_text;
   int text_tokens;            /* number of pooled text tokens handed to forward (0 if none) */
   int attn_heads;             /* 8 */
-  int attn_dim_head;          /* 64 */
+  int attn_dim_head;          /* 32, 64 or 128 (64 with linear attention) */
   int ff_mult_x2;             /* 2*ff_mult, integer (4 for ff_mult=2) */
   int num_time_tokens;        /* 2 */
   int sinu_dim;               /* learned_sinu_pos_emb_dim, 16 */
@@ -192,6 +195,17 @@ typedef struct kd_unet_ext2 {
  * same bits). */
 int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                         const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, kd_unet_t** out);
+/* Further structural options, for kd_unet_create_ext3; the older structs keep their size.  layer_attns_depth[l]
+ * (`Unet(layer_attns_depth=...)`): the TransformerBlocks of level l (downs.l.3 and the matching ups.j.2) run that many
+ * (attention, feed-forward) pairs, parameters `<pre>.layers.{i}.{0,1}.*`; 0 means 1.  mid_attn keeps depth 1, as in the library.
+ * A linear-attention level (kd_unet_ext_t::use_linear_attn) takes depth 1 only.  Entries from num_levels on are ignored. */
+typedef struct kd_unet_ext3 {
+  int layer_attns_depth[KD_MAX_LEVELS];
+} kd_unet_ext3_t;
+/* kd_unet_create_ext2 with the options of `ext3` (NULL, all zero or all one: the plan of kd_unet_create_ext2, the same
+ * launches and the same bits). */
+int kd_unet_create_ext3(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3, kd_unet_t** out);
 void kd_unet_destroy(kd_unet_t* u);
 /* bytes of HBM held (weights + workspace) and algorithmic MACs of one forward (whole batch) */
 int64_t kd_unet_hbm_bytes(const kd_unet_t* u);
@@ -595,7 +609,7 @@ int kd_layernorm_linear_bf16x3(const float* d_x, const float* d_g, const float* 
                                const float* d_w, const float* d_bias, const float* d_res, int ldres, float* d_y, int ldy,
                                int N, void* d_planes, void* stream);
 /* Attention with fp32 softmax.  q [B,Nq,H,D] (already scaled), k/v [B,Nk,Hkv,D] with
- * Hkv in {1,H}; out [B,Nq,H,D].  D must be 64. */
+ * Hkv in {1,H}; out [B,Nq,H,D].  D must be 32, 64 or 128. */
 int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_out,
                  int B, int Nq, int Nk, int H, int Hkv, int D, void* stream);
 /* The same core with every argument the plan's launches pass (engine.hip transformer() / cross_attn(), text_build.inc), a
@@ -607,10 +621,20 @@ int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_
 int kd_attention_ex(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
                     const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
                     float scale, void* stream);
+/* kd_attention_ex for heads of D = 32, 64 or 128 floats (any other D is refused): every 64 above reads D, d_null_kv is [2][D].
+ * kd_attention_ex is this call with D = 64. */
+int kd_attention_ex_d(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
+                      const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
+                      int D, float scale, void* stream);
+/* Keys per LDS tile of the attention kernels' D-wide instantiations (64, 64 and 32 for D = 32, 64 and 128); 0 for any other D.
+ * For tests that place keys around a tile's edges. */
+int kd_attention_key_tile(int D);
 /* The qk-norm of kd_unet_config_t::attn_qk_norm, in place: each of the `heads` 64-wide segments at the start of every row
  * (stride ld >= heads 64) becomes x / max(||x||, 1e-12) (* d_scale_vec [64], may be NULL); columns past the segments are
  * not touched.  Synchronises before returning. */
 int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_scale_vec, void* stream);
+/* The same for segments of D = 32, 64 or 128 floats (d_scale_vec [D], ld >= heads D); kd_l2norm_heads is this call with D = 64. */
+int kd_l2norm_heads_d(float* d_x, int ld, int64_t rows, int heads, int D, const float* d_scale_vec, void* stream);
 /* The small kernels of the text-conditioning plan (text_build.inc) with the plan's argument forms, straight pass-throughs for
  * unit tests; each synchronises before returning.
  *   kd_text_select:    out [B][P][C]: row p = tok[b][p] where p < L, mask[b][p] != 0 and !drop, else null_embed[p].  tok [B][L][C]

@@ -29,6 +29,11 @@ int kd_unet_create_ext(const kd_unet_config_t* cfg, const kd_param_t* params, in
 
 int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                         const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, kd_unet_t** out) {
+  return kd_unet_create_ext3(cfg, params, n_params, share_with, ext, ext2, nullptr, out);
+}
+
+int kd_unet_create_ext3(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3, kd_unet_t** out) {
   const int self_cond = ext ? ext->self_cond : 0;
   if (!cfg || !params || !out) {
     set_error("kd_unet_create: null argument");
@@ -56,6 +61,15 @@ int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, i
     u->upsample_nearest = ext->upsample_nearest != 0;
   }
   u->combine_upsample_fmaps = ext2 && ext2->combine_upsample_fmaps != 0;
+  if (ext3)
+    for (int l = 0; l < KD_MAX_LEVELS && l < cfg->num_levels; ++l) {
+      if (ext3->layer_attns_depth[l] < 0) {
+        set_error("kd_unet_create: layer_attns_depth must not be negative (0 means 1)");
+        delete u;
+        return 1;
+      }
+      u->attn_depth[l] = ext3->layer_attns_depth[l] ? ext3->layer_attns_depth[l] : 1;
+    }
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   u->cus = gemm_bf16x3_device_cus();   // read once: every plan-time question and every launch shape of this plan uses it
@@ -902,10 +916,10 @@ int kd_layernorm_linear_bf16x3(const float* d_x, const float* d_g, const float* 
 
 int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_out, int B, int Nq, int Nk, int H,
                  int Hkv, int D, void* stream) {
-  KD_REQUIRE(D == 64, "kd_attention is built for D = 64");
+  KD_REQUIRE(D == 32 || D == 64 || D == 128, "kd_attention is built for D = 32, 64 and 128");
   KVSeg s0{d_k, d_v, Hkv * D, Nk};
   KVSeg s1{nullptr, nullptr, 0, 0};
-  return launch_attention(d_q, H * D, nullptr, nullptr, s0, s1, d_out, H * D, B, Nq, H, Hkv, 1.0f,
+  return launch_attention(d_q, H * D, nullptr, nullptr, s0, s1, d_out, H * D, B, Nq, H, Hkv, D, 1.0f,
                           (hipStream_t)stream);
 }
 
@@ -914,21 +928,38 @@ int kd_attention(const float* d_q, const float* d_k, const float* d_v, float* d_
 int kd_attention_ex(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
                     const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
                     float scale, void* stream) {
+  return kd_attention_ex_d(d_q, ldq, d_null_kv, d_k0, d_v0, ld0, n0, d_k1, d_v1, ld1, n1, d_out, ldo, B, Nq, H, Hkv, 64, scale,
+                           stream);
+}
+
+int kd_attention_ex_d(const float* d_q, int ldq, const float* d_null_kv, const float* d_k0, const float* d_v0, int ld0, int n0,
+                      const float* d_k1, const float* d_v1, int ld1, int n1, float* d_out, int ldo, int B, int Nq, int H, int Hkv,
+                      int D, float scale, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   KD_REQUIRE(d_q && d_out && B > 0 && H > 0 && n0 >= 0 && n1 >= 0, "kd_attention_ex: null argument or bad sizes");
   KD_REQUIRE((n0 == 0 || (d_k0 && d_v0)) && (n1 == 0 || (d_k1 && d_v1)), "kd_attention_ex: a segment with keys needs k and v");
   KD_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_null_kv | (uintptr_t)d_k0 | (uintptr_t)d_v0 | (uintptr_t)d_k1 | (uintptr_t)d_v1 |
                (uintptr_t)d_out) & 15) == 0, "kd_attention_ex: 16-byte aligned pointers");
+  KD_REQUIRE(D == 32 || D == 64 || D == 128, "kd_attention_ex_d: D must be 32, 64 or 128");
+  KD_REQUIRE(ldq >= H * D && ldo >= H * D && (n0 == 0 || ld0 >= Hkv * D) && (n1 == 0 || ld1 >= Hkv * D),
+             "kd_attention_ex: a row stride is shorter than its heads");
   KVSeg s0{d_k0, d_v0, ld0, n0};
   KVSeg s1{d_k1, d_v1, ld1, n1};
-  return entry_finish(launch_attention(d_q, ldq, d_null_kv, d_null_kv ? d_null_kv + 64 : nullptr, s0, s1, d_out, ldo, B,
-                                       Nq, H, Hkv, scale, s), s);
+  return entry_finish(launch_attention(d_q, ldq, d_null_kv, d_null_kv ? d_null_kv + D : nullptr, s0, s1, d_out, ldo, B,
+                                       Nq, H, Hkv, D, scale, s), s);
 }
 
+int kd_attention_key_tile(int D) { return attention_key_tile(D); }
+
 int kd_l2norm_heads(float* d_x, int ld, int64_t rows, int heads, const float* d_scale_vec, void* stream) {
+  return kd_l2norm_heads_d(d_x, ld, rows, heads, 64, d_scale_vec, stream);
+}
+
+int kd_l2norm_heads_d(float* d_x, int ld, int64_t rows, int heads, int D, const float* d_scale_vec, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  KD_REQUIRE(d_x && rows >= 0 && heads > 0 && ld >= heads * 64, "kd_l2norm_heads: null argument or ld < heads * 64");
-  return entry_finish(launch_l2norm_heads(d_x, ld, rows, heads, d_scale_vec, s), s);
+  KD_REQUIRE(D == 32 || D == 64 || D == 128, "kd_l2norm_heads_d: D must be 32, 64 or 128");
+  KD_REQUIRE(d_x && rows >= 0 && heads > 0 && ld >= heads * D, "kd_l2norm_heads: null argument or ld < heads * D");
+  return entry_finish(launch_l2norm_heads(d_x, ld, rows, heads, D, d_scale_vec, s), s);
 }
 
 // ---- the small kernels of the text-conditioning plan (text_build.inc), one pass-through each with the plan's argument forms

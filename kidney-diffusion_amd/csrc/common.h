@@ -280,7 +280,8 @@ struct KVSeg {
   int n;
 };
 int launch_attention(const float* q, int ldq, const float* null_k, const float* null_v, KVSeg s0, KVSeg s1,
-                     float* out, int ldo, int B, int Nq, int H, int Hkv, float scale, hipStream_t s);
+                     float* out, int ldo, int B, int Nq, int H, int Hkv, int D, float scale, hipStream_t s);
+int attention_key_tile(int D);   // keys per LDS tile of the D-wide instantiations (0: no such instantiation)
 // y[m][n] = act( sum_k f(x[m][k]) * w[n][k] + bias[n] ) for small M (<= 64); in_act applied to x
 int launch_linear_gemv(const float* x, const float* w, const float* bias, float* y, int K, int N, int in_act, int act,
                        hipStream_t s);
@@ -364,8 +365,8 @@ int launch_text_select(const float* tok, const float* mask, const float* null_em
                        int C, int drop, hipStream_t s);
 int launch_add_rows_bcast(const float* x, const float* add, float* y, int B, int R, int C, hipStream_t s);
 int launch_mean_rows(const float* x, float* y, int B, int R, int C, hipStream_t s);
-// in place: each 64-float head segment of x[row][h*64 ..] -> x / max(||x||, 1e-12) (* scale_vec[64] if given)
-int launch_l2norm_heads(float* x, int ld, int64_t rows, int heads, const float* scale_vec, hipStream_t s);
+// in place: each D-float head segment of x[row][h*D ..] -> x / max(||x||, 1e-12) (* scale_vec[D] if given); D = 32, 64, 128
+int launch_l2norm_heads(float* x, int ld, int64_t rows, int heads, int D, const float* scale_vec, hipStream_t s);
 int launch_cfg_combine(const float* cond, const float* nul, float* out, float scale, int64_t n, hipStream_t s);
 
 // ---- sampler (kernels_sampler.hip)

@@ -278,6 +278,8 @@ struct kd_unet {
   // Unet(combine_upsample_fmaps=True) (kd_unet_ext2_t): every up level's map goes through a Block of its own at full resolution
   // into the concat in front of final_res_block
   int combine_upsample_fmaps = 0;
+  // Unet(layer_attns_depth=...) (kd_unet_ext3_t): (attention, feed-forward) pairs of level l's TransformerBlocks, >= 1
+  int attn_depth[KD_MAX_LEVELS] = {1, 1, 1, 1, 1, 1, 1, 1};
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
@@ -976,34 +978,43 @@ struct Builder {
   }
 
   // ---- attention similarity variants (cfg.attn_qk_norm, include/kd_engine.h)
-  float attn_scale() const {
-    return cfg.attn_qk_norm == 1 ? 16.0f : cfg.attn_qk_norm == 2 ? 8.0f : 1.0f / sqrtf((float)cfg.attn_dim_head);
+  // (D = 0 in these helpers: cfg.attn_dim_head; cross_attn() passes the head width its module's weights have)
+  float attn_scale(int D = 0) const {
+    return cfg.attn_qk_norm == 1 ? 16.0f : cfg.attn_qk_norm == 2 ? 8.0f : 1.0f / sqrtf((float)(D ? D : cfg.attn_dim_head));
   }
-  // in place on a workspace tensor: normalise (and scale) the `heads` 64-wide segments at the start of each row
-  void qk_norm(const T& t, int ld, int heads, const float* scale_vec) {
+  // in place on a workspace tensor: normalise (and scale) the `heads` dim_head-wide segments at the start of each row
+  void qk_norm(const T& t, int ld, int heads, const float* scale_vec, int D = 0) {
     const Ref tr = at(t);   // (a column slice of a wider buffer: the fused q / kv projection)
     int64_t rows = t.rows();
-    emit([=](hipStream_t s) { return launch_l2norm_heads(tr.f(), ld, rows, heads, scale_vec, s); },
+    if (!D) D = cfg.attn_dim_head;
+    emit([=](hipStream_t s) { return launch_l2norm_heads(tr.f(), ld, rows, heads, D, scale_vec, s); },
          "qk l2norm rows" + std::to_string(rows) + " heads" + std::to_string(heads));
   }
-  const float* q_scale_of(const std::string& pre) { return cfg.attn_qk_norm == 2 ? P(pre + ".q_scale", cfg.attn_dim_head) : nullptr; }
-  const float* k_scale_of(const std::string& pre) { return cfg.attn_qk_norm == 2 ? P(pre + ".k_scale", cfg.attn_dim_head) : nullptr; }
+  const float* q_scale_of(const std::string& pre, int D = 0) { return cfg.attn_qk_norm == 2 ? P(pre + ".q_scale", D ? D : cfg.attn_dim_head) : nullptr; }
+  const float* k_scale_of(const std::string& pre, int D = 0) { return cfg.attn_qk_norm == 2 ? P(pre + ".k_scale", D ? D : cfg.attn_dim_head) : nullptr; }
   // learned null key / value [2][D]; with qk-norm the key row is normalised (and scaled) once, at plan build
-  const float* null_kv_of(const std::string& pre) {
-    const int D = cfg.attn_dim_head;
+  const float* null_kv_of(const std::string& pre, int D = 0) {
+    if (!D) D = cfg.attn_dim_head;
     const float* raw_nkv = P(pre + ".null_kv", 2 * D);
     if (!cfg.attn_qk_norm) return raw_nkv;
-    const float* ks = k_scale_of(pre);
+    const float* ks = k_scale_of(pre, D);
     return cached("null_kv_qknorm" + std::to_string(cfg.attn_qk_norm) + ":" + pre, (size_t)2 * D, [&](float* dst) {
       KD_HIP_THROW(hipMemcpyAsync(dst, raw_nkv, (size_t)2 * D * sizeof(float), hipMemcpyDeviceToDevice, 0));
-      KD_THROW_IF(launch_l2norm_heads(dst, 2 * D, 1, 1, ks, 0));
+      KD_THROW_IF(launch_l2norm_heads(dst, 2 * D, 1, 1, D, ks, 0));
     });
   }
 
   // ---- modules
   // cross attention of feature tokens to the conditioning tokens c [B,Nc,cond_dim]; returns attn(x)+x
+  // Its heads are what the module's weights say (null_kv [2][D], to_q [H D][dim]): the library builds mid_block1 / mid_block2
+  // without the UNet's attention kwargs - 8 heads of 64 whatever attn_heads / attn_dim_head - and every other ResnetBlock with
+  // them.
   T cross_attn(const T& x, const std::string& pre, const T& c) {
-    int H = cfg.attn_heads, D = cfg.attn_dim_head, inner = H * D, dim = x.C;
+    const int dim = x.C, D = (int)(numel(pre + ".null_kv") / 2), inner = (int)(numel(pre + ".to_q.weight") / dim);
+    if (D != 32 && D != 64 && D != 128)
+      throw std::runtime_error("'" + pre + "': the attention kernels are built for dim_head 32, 64 and 128");
+    const int H = inner / D;
+    if (H < 1 || H * D != inner) throw std::runtime_error("'" + pre + ".to_q.weight' is no whole number of heads");
     T xn = layernorm(x, P(pre + ".norm.g", dim), nullptr);
     T q = linear(xn, P(pre + ".to_q.weight", (int64_t)inner * dim), nullptr, inner);
     free(xn);
@@ -1011,19 +1022,19 @@ struct Builder {
     {   // K / V of the conditioning tokens: a function of c alone (cond region, see Phase::Cond)
       auto ph = cond_scope();
       kv = linear(c, P(pre + ".to_kv.weight", (int64_t)2 * inner * c.C), nullptr, 2 * inner);
-      if (cfg.attn_qk_norm) qk_norm(kv, 2 * inner, H, k_scale_of(pre));
+      if (cfg.attn_qk_norm) qk_norm(kv, 2 * inner, H, k_scale_of(pre, D), D);
     }
-    const float* nkv = null_kv_of(pre);
-    if (cfg.attn_qk_norm) qk_norm(q, inner, H, q_scale_of(pre));
+    const float* nkv = null_kv_of(pre, D);
+    if (cfg.attn_qk_norm) qk_norm(q, inner, H, q_scale_of(pre, D), D);
     T o = alloc(x.B, x.H, x.W, inner);
     {
       const Ref qr = at(q), kr = at(kv), vr = kr.floats(inner), outr = at(o);
       int Bx = x.B, Nq = x.HW(), Nc = c.HW();
-      float scale = attn_scale();
+      float scale = attn_scale(D);
       emit([=](hipStream_t s) {
         KVSeg s0{kr.f(), vr.f(), 2 * inner, Nc};
         KVSeg s1{nullptr, nullptr, 0, 0};
-        return launch_attention(qr.f(), inner, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, Nq, H, H, scale, s);
+        return launch_attention(qr.f(), inner, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, Nq, H, H, D, scale, s);
       }, "xattn Nq" + std::to_string(Nq) + " Nk" + std::to_string(Nc + 1));
       u->macs += (int64_t)Bx * H * Nq * (Nc + 1) * D * 2;
     }
@@ -1036,12 +1047,25 @@ struct Builder {
     return y;
   }
 
-  // TransformerBlock (depth 1): x = attn(x, ctx) + x ; x = ff(x) + x.
+  // TransformerBlock: `depth` times x = attn(x, ctx) + x ; x = ff(x) + x, parameters `<pre>.layers.{i}.{0,1}.*`.  Every
+  // layer has its own context K / V (a cond-region launch each); only the last layer's final GEMM writes into `dst`.
   // plain: the residual attention of earlier library versions (cfg.mid_attn_plain): parameters `<pre>.fn.fn.*`,
   // x = attn(x) + x and no feed-forward
-  T transformer(const T& x, const std::string& pre, const T* ctx, const T* dst = nullptr, bool plain = false) {
+  T transformer(const T& x, const std::string& pre, const T* ctx, const T* dst = nullptr, bool plain = false, int depth = 1) {
+    if (plain) return transformer_layer(x, pre + ".fn.fn", std::string(), ctx, dst, true);
+    if (depth < 1) throw std::runtime_error("plan: TransformerBlock depth must be at least 1");
+    T cur = x;
+    for (int i = 0; i < depth; ++i) {
+      const std::string l = pre + ".layers." + std::to_string(i);
+      T y = transformer_layer(cur, l + ".0", l + ".1", ctx, i == depth - 1 ? dst : nullptr, false);
+      if (i > 0) free(cur);   // (x itself is the caller's)
+      cur = y;
+    }
+    return cur;
+  }
+  // one (attention `a`, feed-forward `f`) pair of it
+  T transformer_layer(const T& x, const std::string& a, const std::string& f, const T* ctx, const T* dst, bool plain) {
     int H = cfg.attn_heads, D = cfg.attn_dim_head, inner = H * D, dim = x.C;
-    std::string a = plain ? pre + ".fn.fn" : pre + ".layers.0.0", f = pre + ".layers.0.1";
     const bool qkv1 = cfg.conv_algo == 0 && kd_switch("KD_QKV_FUSED", 1) != 0;
     // (one reader - the fused q / k / v GEMM: where that runs on the bf16x3 kernel the LayerNorm leaves its planes)
     T xn = layernorm(x, P(a + ".norm.g", dim), nullptr, nullptr, ACT_NONE, nullptr, nullptr, false,
@@ -1091,7 +1115,7 @@ struct Builder {
         KVSeg s0{nullptr, nullptr, 0, 0};
         if (ck) s0 = KVSeg{ck.f(), ck.floats(D).f(), 2 * D, Nc};
         KVSeg s1{kr.f(), kr.floats(D).f(), ldkv, N};
-        return launch_attention(qr.f(), ldq, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, N, H, 1, scale, s);
+        return launch_attention(qr.f(), ldq, nkv, nkv + D, s0, s1, outr.f(), inner, Bx, N, H, 1, D, scale, s);
       }, "attn N" + std::to_string(N));
       u->macs += (int64_t)Bx * H * N * (N + Nc + 1) * D * 2;
     }

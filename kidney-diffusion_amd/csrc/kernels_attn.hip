@@ -2,9 +2,9 @@
 //
 // The attention core is < 2 % of the UNet's FLOPs (QK^T/AV 0.1-1.8 %),
 // its projections are GEMMs and run on the MFMA kernel in kernels_conv.hip.  Two forms of the core,
-// both a flash-style single pass with fp32 online softmax over 64-key K/V tiles staged in LDS:
+// both a flash-style single pass with fp32 online softmax over K/V tiles staged in LDS, templates on the head width (32, 64, 128):
 // attention_mfma_kernel (launches that fill the chip) puts QK^T and PV on the fp32 matrix cores;
-// attention_kernel<KS> (small launches) keeps a query row in the VGPRs of KS adjacent lanes and reads
+// attention_kernel<KS, D, DS> (small launches) keeps a query row in the VGPRs of KS adjacent lanes and reads
 // K/V as wave-wide broadcasts.  Multi-query layout (one shared K/V head) is handled by
 // Hkv = 1.
 #include "common.h"
@@ -30,52 +30,62 @@ __device__ __forceinline__ float act_f(float v, int act) {
   return v;
 }
 
-// ------------------------------------------------------------------------- attention (D = 64)
-constexpr int AT_D = 64;
-constexpr int AT_KT = 64;      // keys per LDS tile
-constexpr int AT_LD = AT_D + 4;  // padded K/V rows: the KS lanes of a query read KS different rows without bank conflicts
+// ------------------------------------------------------------------------- attention (D = 32, 64, 128)
+// Keys per LDS tile, KT(D).  64 for D = 32 and 64.  D = 128 takes 32-key tiles because of the registers, not the LDS (a
+// 64-key K|V tile with padded rows, 2 * 64 * 132 * 4 = 67.6 KB, would still let two blocks share the CU's 160 KiB): with two
+// 32 x 32 score blocks beside the 64 + 64 registers of Q and O^T the matrix-core kernel compiles to 256 VGPRs and 8 bytes of
+// scratch per lane under __launch_bounds__(256, 2); with one score block (16 registers) it takes 210 and none.  The 32-key
+// tile is 33.8 KB, the footprint of the D = 64 kernels.
+constexpr int at_kt(int D) { return D == 128 ? 32 : 64; }
+int attention_key_tile(int D) { return D == 32 || D == 64 || D == 128 ? at_kt(D) : 0; }
 
 // KS = 1: one lane per query.  KS = 4 (small grids, e.g. one batch-1 patch of the ultra-res grid: 8 heads x
 // 1024 queries would fill 32 workgroups): 4 adjacent lanes share a query and take every 4th key each, with
 // their own online-softmax state; the states are merged with shuffles at the end.
-template <int KS>
+// DS (D = 128: 2, else 1) lanes share a (query, key split) and hold D / DS dims of q and o each - the 16-byte chunks
+// 4 (DS i + ds) .. + 3 - so that a lane keeps 64 + 64 registers at D = 128 as at D = 64: a partial dot product and one
+// shuffle per key, the softmax state is computed alike in the DS lanes.
+// Padded K/V rows: the KS x DS lanes of a query read KS x DS different 16-byte chunks without bank conflicts.
+template <int KS, int D, int DS>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ q, int ldq,
                                                         const float* __restrict__ null_k,
                                                         const float* __restrict__ null_v, KVSeg s0, KVSeg s1,
                                                         float* __restrict__ out, int ldo, int Nq, int Hkv,
                                                         float scale) {
-  __shared__ __attribute__((aligned(16))) float Ks[AT_KT * AT_LD];
-  __shared__ __attribute__((aligned(16))) float Vs[AT_KT * AT_LD];
+  constexpr int KT = at_kt(D), LD = D + 4 * DS, DL = D / DS;   // DL: dims per lane
+  __shared__ __attribute__((aligned(16))) float Ks[KT * LD];
+  __shared__ __attribute__((aligned(16))) float Vs[KT * LD];
   const int h = blockIdx.y, b = blockIdx.z;
   const int hk = Hkv == 1 ? 0 : h;
-  const int ks = threadIdx.x % KS;  // key split of this lane
-  const int qi = blockIdx.x * (256 / KS) + threadIdx.x / KS;
+  const int ds = threadIdx.x % DS;         // dim split of this lane
+  const int ks = threadIdx.x / DS % KS;    // key split of this lane
+  const int qi = blockIdx.x * (256 / (KS * DS)) + threadIdx.x / (KS * DS);
   const bool active = qi < Nq;
 
-  float qr[AT_D], o[AT_D];
+  float qr[DL], o[DL];
   if (active) {
-    const float* qp = q + ((int64_t)b * Nq + qi) * ldq + h * AT_D;
+    const float* qp = q + ((int64_t)b * Nq + qi) * ldq + h * D;
 #pragma unroll
-    for (int d4 = 0; d4 < AT_D / 4; ++d4) {
-      f32x4 t = *(const f32x4*)(qp + d4 * 4);
+    for (int d4 = 0; d4 < DL / 4; ++d4) {
+      f32x4 t = *(const f32x4*)(qp + (d4 * DS + ds) * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) qr[d4 * 4 + e] = t[e] * scale;
     }
   } else {
 #pragma unroll
-    for (int d = 0; d < AT_D; ++d) qr[d] = 0.f;
+    for (int d = 0; d < DL; ++d) qr[d] = 0.f;
   }
 #pragma unroll
-  for (int d = 0; d < AT_D; ++d) o[d] = 0.f;
+  for (int d = 0; d < DL; ++d) o[d] = 0.f;
   float mrun = -INFINITY, lrun = 0.f;
 
   const int n_null = null_k ? 1 : 0;
   const int Nk = n_null + s0.n + s1.n;
-  for (int j0 = 0; j0 < Nk; j0 += AT_KT) {
-    const int nj = min(AT_KT, Nk - j0);
+  for (int j0 = 0; j0 < Nk; j0 += KT) {
+    const int nj = min(KT, Nk - j0);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < nj * (AT_D / 4); idx += 256) {
-      int j = idx / (AT_D / 4), d4 = idx - j * (AT_D / 4);
+    for (int idx = threadIdx.x; idx < nj * (D / 4); idx += 256) {
+      int j = idx / (D / 4), d4 = idx - j * (D / 4);
       int key = j0 + j;
       const float *kp, *vp;
       if (key < n_null) {
@@ -83,125 +93,136 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         vp = null_v;
       } else if (key < n_null + s0.n) {
         int64_t r = (int64_t)b * s0.n + (key - n_null);
-        kp = s0.k + r * s0.ld + hk * AT_D;
-        vp = s0.v + r * s0.ld + hk * AT_D;
+        kp = s0.k + r * s0.ld + hk * D;
+        vp = s0.v + r * s0.ld + hk * D;
       } else {
         int64_t r = (int64_t)b * s1.n + (key - n_null - s0.n);
-        kp = s1.k + r * s1.ld + hk * AT_D;
-        vp = s1.v + r * s1.ld + hk * AT_D;
+        kp = s1.k + r * s1.ld + hk * D;
+        vp = s1.v + r * s1.ld + hk * D;
       }
-      *(f32x4*)(Ks + j * AT_LD + d4 * 4) = *(const f32x4*)(kp + d4 * 4);
-      *(f32x4*)(Vs + j * AT_LD + d4 * 4) = *(const f32x4*)(vp + d4 * 4);
+      *(f32x4*)(Ks + j * LD + d4 * 4) = *(const f32x4*)(kp + d4 * 4);
+      *(f32x4*)(Vs + j * LD + d4 * 4) = *(const f32x4*)(vp + d4 * 4);
     }
     __syncthreads();
     for (int j = ks; j < nj; j += KS) {
       float s0a = 0.f, s1a = 0.f, s2a = 0.f, s3a = 0.f;
 #pragma unroll
-      for (int d4 = 0; d4 < AT_D / 4; ++d4) {
-        f32x4 kk = *(const f32x4*)(Ks + j * AT_LD + d4 * 4);  // one address per key split: broadcast
+      for (int d4 = 0; d4 < DL / 4; ++d4) {
+        f32x4 kk = *(const f32x4*)(Ks + j * LD + (d4 * DS + ds) * 4);  // one address per key / dim split: broadcast
         s0a = fmaf(qr[d4 * 4 + 0], kk[0], s0a);
         s1a = fmaf(qr[d4 * 4 + 1], kk[1], s1a);
         s2a = fmaf(qr[d4 * 4 + 2], kk[2], s2a);
         s3a = fmaf(qr[d4 * 4 + 3], kk[3], s3a);
       }
       float sc = (s0a + s1a) + (s2a + s3a);
+      if (DS > 1) {   // (every j of this loop is run by all DS lanes of the split: they share ks)
+#pragma unroll
+        for (int off = 1; off < DS; off <<= 1) sc += __shfl_xor(sc, off, 64);
+      }
       float mnew = fmaxf(mrun, sc);
       float corr = expf(mrun - mnew);  // exp(-inf) = 0 on the first key
       float pj = expf(sc - mnew);
       lrun = lrun * corr + pj;
       if (corr != 1.0f) {
 #pragma unroll
-        for (int d = 0; d < AT_D; ++d) o[d] *= corr;
+        for (int d = 0; d < DL; ++d) o[d] *= corr;
       }
 #pragma unroll
-      for (int d4 = 0; d4 < AT_D / 4; ++d4) {
-        f32x4 vv = *(const f32x4*)(Vs + j * AT_LD + d4 * 4);
+      for (int d4 = 0; d4 < DL / 4; ++d4) {
+        f32x4 vv = *(const f32x4*)(Vs + j * LD + (d4 * DS + ds) * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[d4 * 4 + e] = fmaf(pj, vv[e], o[d4 * 4 + e]);
       }
       mrun = mnew;
     }
   }
-  if (KS > 1) {  // merge the KS softmax states of a query (adjacent lanes)
+  if (KS > 1) {  // merge the KS softmax states of a query (lanes DS apart)
     float m = mrun;
 #pragma unroll
-    for (int off = 1; off < KS; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    for (int off = DS; off < KS * DS; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     const float w = mrun == -INFINITY ? 0.f : expf(mrun - m);  // a split that saw no key contributes nothing
     lrun *= w;
 #pragma unroll
-    for (int off = 1; off < KS; off <<= 1) lrun += __shfl_xor(lrun, off, 64);
+    for (int off = DS; off < KS * DS; off <<= 1) lrun += __shfl_xor(lrun, off, 64);
 #pragma unroll
-    for (int d = 0; d < AT_D; ++d) {
+    for (int d = 0; d < DL; ++d) {
       float v = o[d] * w;
 #pragma unroll
-      for (int off = 1; off < KS; off <<= 1) v += __shfl_xor(v, off, 64);
+      for (int off = DS; off < KS * DS; off <<= 1) v += __shfl_xor(v, off, 64);
       o[d] = v;
     }
   }
   if (active && ks == 0) {
     float inv = 1.0f / lrun;
-    float* op = out + ((int64_t)b * Nq + qi) * ldo + h * AT_D;
+    float* op = out + ((int64_t)b * Nq + qi) * ldo + h * D;
 #pragma unroll
-    for (int d4 = 0; d4 < AT_D / 4; ++d4) {
+    for (int d4 = 0; d4 < DL / 4; ++d4) {
       f32x4 t = {o[d4 * 4] * inv, o[d4 * 4 + 1] * inv, o[d4 * 4 + 2] * inv, o[d4 * 4 + 3] * inv};
-      *(f32x4*)(op + d4 * 4) = t;
+      *(f32x4*)(op + (d4 * DS + ds) * 4) = t;
     }
   }
 }
 
-// ------------------------------------------------------------------------- attention on the matrix cores (D = 64)
+// ------------------------------------------------------------------------- attention on the matrix cores (D = 32, 64, 128)
 // Flash-style single pass with both contractions on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32
-// accumulation).  A wave owns 32 queries of one (batch, head); the block's 4 waves share 64-key K/V tiles in
+// accumulation).  A wave owns 32 queries of one (batch, head); the block's 4 waves share KT(D)-key K/V tiles in
 // LDS.  The scores are computed TRANSPOSED, S^T = K Q^T (A operand = K rows from LDS, B operand = the wave's
-// Q rows, held in registers for the whole pass): a lane of the 32x32 accumulator then holds 16 keys of ONE
+// Q rows, held in registers for the whole pass: D / 2 per lane): a lane of the 32x32 accumulator then holds 16 keys of ONE
 // query, so the online softmax is in-lane but for one shuffle with the lane that holds the query's other 16
 // keys, and the probabilities are already in the register layout the B operand of O^T += V^T P^T wants
 // (k-step r pairs the keys (r&3) + 8(r>>2) and that + 4, one per lane half) - P never leaves the registers.
-// O^T is transposed through LDS at the end for row-contiguous stores.
-constexpr int AM_LD = AT_D + 4;   // padded K/V rows (ds_read_b128 of 32 different keys: 4 banks apart)
-
+// O^T (D / 32 accumulators of 32 dims) is transposed through LDS at the end for row-contiguous stores, 64 dims at a time.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+template <int D>
 __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __restrict__ q, int ldq,
                                                                 const float* __restrict__ null_k,
                                                                 const float* __restrict__ null_v, KVSeg s0, KVSeg s1,
                                                                 float* __restrict__ out, int ldo, int Nq, int Hkv,
                                                                 float scale) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  __shared__ __attribute__((aligned(16))) float KV[2 * AT_KT * AM_LD];   // K tile | V tile; the output tile at the end
+  constexpr int KT = at_kt(D), NKT = KT / 32;   // 32-key score blocks per tile
+  constexpr int LD = D + 4;                     // padded K/V rows (ds_read_b128 of 32 different keys: 4 banks apart)
+  constexpr int DH = D / 2;                     // dims per lane half
+  constexpr int NO = D / 32;                    // O^T accumulators
+  constexpr int OW = D < 64 ? D : 64, OLD = OW + 4, NOP = OW / 32;   // output transpose: OW dims (NOP accumulators) per pass
+  constexpr int KV_FLOATS = 2 * KT * LD > 128 * OLD ? 2 * KT * LD : 128 * OLD;
+  __shared__ __attribute__((aligned(16))) float KV[KV_FLOATS];   // K tile | V tile; the output tile at the end
   float* Ks = KV;
-  float* Vs = KV + AT_KT * AM_LD;
+  float* Vs = KV + KT * LD;
   const int h = blockIdx.y, b = blockIdx.z;
   const int hk = Hkv == 1 ? 0 : h;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = lane & 31, khalf = lane >> 5;
   const int qi = blockIdx.x * 128 + wave * 32 + n;
 
-  float qv[32];   // Q[qi][32 * khalf + j] * scale: the B operand of k-step j (dims j and j + 32)
+  float qv[DH];   // Q[qi][DH * khalf + j] * scale: the B operand of k-step j (dims j and j + DH)
   if (qi < Nq) {
-    const float* qp = q + ((int64_t)b * Nq + qi) * ldq + h * AT_D + 32 * khalf;
+    const float* qp = q + ((int64_t)b * Nq + qi) * ldq + h * D + DH * khalf;
 #pragma unroll
-    for (int d4 = 0; d4 < 8; ++d4) {
+    for (int d4 = 0; d4 < DH / 4; ++d4) {
       f32x4 t = *(const f32x4*)(qp + d4 * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) qv[d4 * 4 + e] = t[e] * scale;
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < 32; ++j) qv[j] = 0.f;
+    for (int j = 0; j < DH; ++j) qv[j] = 0.f;
   }
-  f32x16 o0, o1;
+  f32x16 o[NO];   // o[c][r]: O^T[32 c + (r&3) + 8(r>>2) + 4 khalf][query n]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) o0[r] = o1[r] = 0.f;
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int c = 0; c < NO; ++c) o[c][r] = 0.f;
   float mrun = -INFINITY, lsum = 0.f;
 
   const int n_null = null_k ? 1 : 0;
   const int Nk = n_null + s0.n + s1.n;
-  for (int j0 = 0; j0 < Nk; j0 += AT_KT) {
-    const int nj = min(AT_KT, Nk - j0);
+  for (int j0 = 0; j0 < Nk; j0 += KT) {
+    const int nj = min(KT, Nk - j0);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < AT_KT * (AT_D / 4); idx += 256) {
-      int j = idx / (AT_D / 4), d4 = idx - j * (AT_D / 4);
+    for (int idx = threadIdx.x; idx < KT * (D / 4); idx += 256) {
+      int j = idx / (D / 4), d4 = idx - j * (D / 4);
       f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};   // rows past the last key: zeros (their p is 0)
       if (j < nj) {
         int key = j0 + j;
@@ -211,30 +232,30 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
           vp = null_v;
         } else if (key < n_null + s0.n) {
           int64_t r = (int64_t)b * s0.n + (key - n_null);
-          kp = s0.k + r * s0.ld + hk * AT_D;
-          vp = s0.v + r * s0.ld + hk * AT_D;
+          kp = s0.k + r * s0.ld + hk * D;
+          vp = s0.v + r * s0.ld + hk * D;
         } else {
           int64_t r = (int64_t)b * s1.n + (key - n_null - s0.n);
-          kp = s1.k + r * s1.ld + hk * AT_D;
-          vp = s1.v + r * s1.ld + hk * AT_D;
+          kp = s1.k + r * s1.ld + hk * D;
+          vp = s1.v + r * s1.ld + hk * D;
         }
         kk = *(const f32x4*)(kp + d4 * 4);
         vv = *(const f32x4*)(vp + d4 * 4);
       }
-      *(f32x4*)(Ks + j * AM_LD + d4 * 4) = kk;
-      *(f32x4*)(Vs + j * AM_LD + d4 * 4) = vv;
+      *(f32x4*)(Ks + j * LD + d4 * 4) = kk;
+      *(f32x4*)(Vs + j * LD + d4 * 4) = vv;
     }
     __syncthreads();
 
-    // S^T = K Q^T for the two 32-key halves of the tile
-    f32x16 st[2];
+    // S^T = K Q^T for the 32-key blocks of the tile
+    f32x16 st[NKT];
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
+    for (int kt = 0; kt < NKT; ++kt) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[kt][r] = 0.f;
-      const float* kr = Ks + (kt * 32 + n) * AM_LD + 32 * khalf;
+      const float* kr = Ks + (kt * 32 + n) * LD + DH * khalf;
 #pragma unroll
-      for (int j4 = 0; j4 < 8; ++j4) {
+      for (int j4 = 0; j4 < DH / 4; ++j4) {
         const f32x4 kk = *(const f32x4*)(kr + j4 * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -242,16 +263,16 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
       }
     }
     // online softmax: this lane holds keys kt*32 + (r&3) + 8(r>>2) + 4*khalf of query n
-    if (nj < AT_KT) {
+    if (nj < KT) {
 #pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
+      for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf >= nj) st[kt][r] = -INFINITY;
     }
     float mloc = -INFINITY;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) mloc = fmaxf(mloc, st[kt][r]);
     mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
@@ -259,7 +280,7 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
     const float corr = expf(mrun - mnew);      // exp(-inf) = 0 on the first tile
     float psum = 0.f;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         st[kt][r] = expf(st[kt][r] - mnew);
@@ -268,56 +289,69 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
     lsum = lsum * corr + psum;
     mrun = mnew;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      o0[r] *= corr;
-      o1[r] *= corr;
-    }
-    // O^T += V^T P^T: k-step r of half kt pairs the keys this lane half holds in register r
+    for (int r = 0; r < 16; ++r)
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+      for (int c = 0; c < NO; ++c) o[c][r] *= corr;
+    // O^T += V^T P^T: k-step r of block kt pairs the keys this lane half holds in register r
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float* vr = Vs + (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf) * AM_LD + n;
-        o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[0], st[kt][r], o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32], st[kt][r], o1, 0, 0, 0);
+        const float* vr = Vs + (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf) * LD + n;
+#pragma unroll
+        for (int c = 0; c < NO; ++c) o[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[32 * c], st[kt][r], o[c], 0, 0, 0);
       }
   }
   const float inv = 1.0f / (lsum + __shfl_xor(lsum, 32, 64));
-  __syncthreads();   // every wave is done with the last K/V tile
-  float* os = KV + (wave * 32 + n) * AM_LD;   // out tile [query][dim]
+  float* os = KV + (wave * 32 + n) * OLD;   // out tile [query][dim of this pass]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int d = (r & 3) + 8 * (r >> 2) + 4 * khalf;
-    os[d] = o0[r] * inv;
-    os[32 + d] = o1[r] * inv;
-  }
-  __syncthreads();
+  for (int p = 0; p < D / OW; ++p) {
+    __syncthreads();   // every wave is done with the last K/V tile (with the rows of the pass before)
 #pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const int ql = it * 4 + (lane >> 4), d4 = lane & 15;
-    const int qo = blockIdx.x * 128 + wave * 32 + ql;
-    if (qo < Nq)
-      *(f32x4*)(out + ((int64_t)b * Nq + qo) * ldo + h * AT_D + d4 * 4) =
-          *(const f32x4*)(KV + (wave * 32 + ql) * AM_LD + d4 * 4);
+    for (int r = 0; r < 16; ++r) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * khalf;
+#pragma unroll
+      for (int c = 0; c < NOP; ++c) os[32 * c + d] = o[p * NOP + c][r] * inv;
+    }
+    __syncthreads();
+    constexpr int RL = OW / 4;   // lanes (16-byte stores) per row
+#pragma unroll
+    for (int it = 0; it < 32 / (64 / RL); ++it) {
+      const int ql = it * (64 / RL) + lane / RL, d4 = lane % RL;
+      const int qo = blockIdx.x * 128 + wave * 32 + ql;
+      if (qo < Nq)
+        *(f32x4*)(out + ((int64_t)b * Nq + qo) * ldo + h * D + p * OW + d4 * 4) =
+            *(const f32x4*)(KV + (wave * 32 + ql) * OLD + d4 * 4);
+    }
   }
 #endif
 }
 
+template <int D>
+static void attention_launch(const float* q, int ldq, const float* null_k, const float* null_v, KVSeg s0, KVSeg s1, float* out,
+                             int ldo, int B, int Nq, int H, int Hkv, float scale, hipStream_t s) {
+  // both contractions on the matrix cores once there are 128-query blocks worth launching (a batch-1 patch with 1024
+  // tokens has 64 of them: 55 us there against 174 us on the vector kernel)
+  if (Nq >= 128 && (int64_t)((Nq + 127) / 128) * H * B >= 16) {
+    hipLaunchKernelGGL(attention_mfma_kernel<D>, dim3((Nq + 127) / 128, H, B), dim3(256), 0, s, q, ldq, null_k, null_v, s0,
+                       s1, out, ldo, Nq, Hkv, scale);
+  } else {  // small launches (batch-1 patches, the test shapes): 4 lanes per query on the vector ALU (8 at D = 128)
+    constexpr int DS = D == 128 ? 2 : 1, QB = 256 / (4 * DS);
+    hipLaunchKernelGGL((attention_kernel<4, D, DS>), dim3((Nq + QB - 1) / QB, H, B), dim3(256), 0, s, q, ldq, null_k, null_v,
+                       s0, s1, out, ldo, Nq, Hkv, scale);
+  }
+}
+
 int launch_attention(const float* q, int ldq, const float* null_k, const float* null_v, KVSeg s0, KVSeg s1,
-                     float* out, int ldo, int B, int Nq, int H, int Hkv, float scale, hipStream_t s) {
+                     float* out, int ldo, int B, int Nq, int H, int Hkv, int D, float scale, hipStream_t s) {
+  KD_REQUIRE(D == 32 || D == 64 || D == 128, "attention: the kernels are built for dim_head 32, 64 and 128");
   KD_REQUIRE(Hkv == 1 || Hkv == H, "attention: Hkv must be 1 (multi-query) or H");
   KD_REQUIRE(ldq % 4 == 0 && ldo % 4 == 0 && (s0.n == 0 || s0.ld % 4 == 0) && (s1.n == 0 || s1.ld % 4 == 0),
              "attention: strides % 4");
   KD_REQUIRE((null_k ? 1 : 0) + s0.n + s1.n > 0 && Nq > 0, "attention: empty");
-  // both contractions on the matrix cores once there are 128-query blocks worth launching (a batch-1 patch with 1024
-  // tokens has 64 of them: 55 us there against 174 us on the vector kernel)
-  if (Nq >= 128 && (int64_t)((Nq + 127) / 128) * H * B >= 16) {
-    hipLaunchKernelGGL(attention_mfma_kernel, dim3((Nq + 127) / 128, H, B), dim3(256), 0, s, q, ldq, null_k, null_v, s0,
-                       s1, out, ldo, Nq, Hkv, scale);
-  } else {  // small launches (batch-1 patches, the test shapes): 4 lanes per query on the vector ALU
-    hipLaunchKernelGGL(attention_kernel<4>, dim3((Nq + 63) / 64, H, B), dim3(256), 0, s, q, ldq, null_k, null_v, s0, s1,
-                       out, ldo, Nq, Hkv, scale);
-  }
+  if (D == 32) attention_launch<32>(q, ldq, null_k, null_v, s0, s1, out, ldo, B, Nq, H, Hkv, scale, s);
+  else if (D == 64) attention_launch<64>(q, ldq, null_k, null_v, s0, s1, out, ldo, B, Nq, H, Hkv, scale, s);
+  else attention_launch<128>(q, ldq, null_k, null_v, s0, s1, out, ldo, B, Nq, H, Hkv, scale, s);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

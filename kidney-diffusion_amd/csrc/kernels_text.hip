@@ -78,25 +78,41 @@ int launch_cfg_combine(const float* cond, const float* nul, float* out, float sc
 }
 
 // qk-norm attention variants (Unet(cosine_sim_attn=True) of imagen-pytorch 1.18.x; learned q_scale / k_scale of
-// later versions): every 64-wide head segment of a row is replaced by x / max(||x||, 1e-12) (* scale_vec) -
-// torch's F.normalize(dim=-1) followed by the learned per-channel scale.  One wave per (row, head), in place.
+// later versions): every D-wide head segment of a row is replaced by x / max(||x||, 1e-12) (* scale_vec [D]) -
+// torch's F.normalize(dim=-1) followed by the learned per-channel scale.  In place; min(D, 64) lanes per (row, head):
+// half a wave at D = 32, one wave at 64, one wave with two elements per lane (d and d + 64) at 128.
+template <int D>
 __global__ __launch_bounds__(256) void l2norm_heads_kernel(float* __restrict__ x, int ld, int64_t rows, int heads,
                                                           const float* __restrict__ scale_vec) {
-  const int lane = threadIdx.x & 63;
-  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (seg >= rows * heads) return;
-  float* p = x + (seg / heads) * ld + (seg % heads) * 64 + lane;
-  const float v = *p;
-  float ss = v * v;
+  constexpr int L = D < 64 ? D : 64, E = D / L;   // lanes per segment, elements per lane
+  const int lane = threadIdx.x % L;
+  const int64_t seg = (int64_t)blockIdx.x * (256 / L) + threadIdx.x / L;
+  if (seg >= rows * heads) return;   // (whole shuffle groups leave together)
+  float* p = x + (seg / heads) * ld + (seg % heads) * D + lane;
+  float v[E];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-  const float r = v / fmaxf(sqrtf(ss), 1e-12f);
-  *p = scale_vec ? r * scale_vec[lane] : r;
+  for (int e = 0; e < E; ++e) v[e] = p[e * 64];
+  float ss = v[0] * v[0];
+#pragma unroll
+  for (int e = 1; e < E; ++e) ss = fmaf(v[e], v[e], ss);
+#pragma unroll
+  for (int off = L / 2; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+  const float den = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const float r = v[e] / den;
+    p[e * 64] = scale_vec ? r * scale_vec[lane + e * 64] : r;
+  }
 }
-int launch_l2norm_heads(float* x, int ld, int64_t rows, int heads, const float* scale_vec, hipStream_t s) {
+int launch_l2norm_heads(float* x, int ld, int64_t rows, int heads, int D, const float* scale_vec, hipStream_t s) {
+  KD_REQUIRE(D == 32 || D == 64 || D == 128, "l2norm heads: the kernel is built for dim_head 32, 64 and 128");
   const int64_t segs = rows * heads;
   if (segs <= 0) return 0;
-  hipLaunchKernelGGL(l2norm_heads_kernel, dim3((unsigned)((segs + 3) / 4)), dim3(256), 0, s, x, ld, rows, heads, scale_vec);
+  const int per_block = D == 32 ? 8 : 4;
+  const dim3 grid((unsigned)((segs + per_block - 1) / per_block));
+  if (D == 32) hipLaunchKernelGGL(l2norm_heads_kernel<32>, grid, dim3(256), 0, s, x, ld, rows, heads, scale_vec);
+  else if (D == 64) hipLaunchKernelGGL(l2norm_heads_kernel<64>, grid, dim3(256), 0, s, x, ld, rows, heads, scale_vec);
+  else hipLaunchKernelGGL(l2norm_heads_kernel<128>, grid, dim3(256), 0, s, x, ld, rows, heads, scale_vec);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -89,7 +89,7 @@ void Builder::build_text() {
       emit([=](hipStream_t s) {
         KVSeg s0{xr.f(), xr.floats(inner).f(), 2 * inner, P};
         KVSeg s1{lr.f(), lr.floats(inner).f(), 2 * inner, ntok};
-        return launch_attention(qr.f(), inner, nullptr, nullptr, s0, s1, outr.f(), inner, Bx, ntok, H, H, scale, s);
+        return launch_attention(qr.f(), inner, nullptr, nullptr, s0, s1, outr.f(), inner, Bx, ntok, H, H, D, scale, s);
       });
     }
     free(q);

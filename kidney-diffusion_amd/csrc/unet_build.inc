@@ -11,7 +11,14 @@ void Builder::build() {
   if (L < 1 || L > KD_MAX_LEVELS) throw std::runtime_error("num_levels out of range");
   if (cfg.channels < 1 || cfg.channels > 4) throw std::runtime_error("images of 1 to 4 channels are supported");
   const int Ci = cfg.channels;   // image channels: x, the self-conditioning image, the low-res image and the output
-  if (cfg.attn_dim_head != 64) throw std::runtime_error("attention kernel is built for dim_head = 64");
+  if (cfg.attn_dim_head != 32 && cfg.attn_dim_head != 64 && cfg.attn_dim_head != 128)
+    throw std::runtime_error("the attention kernels are built for attn_dim_head 32, 64 and 128");
+  for (int l = 0; l < L; ++l)
+    if (u->lin_attn[l] || u->lin_cross[l]) {
+      if (cfg.attn_dim_head != 64) throw std::runtime_error("the linear-attention kernels are built for attn_dim_head = 64");
+      if (u->lin_attn[l] && !cfg.layer_attns[l] && u->attn_depth[l] != 1)
+        throw std::runtime_error("layer_attns_depth > 1 on a linear-attention level is not supported");
+    }
   if (B < 1 || S < 1) throw std::runtime_error("batch and image_size must be positive");
   const int n_down = cfg.memory_efficient ? L : L - 1;
   if (S % (1 << n_down)) throw std::runtime_error("image_size must be divisible by the total downsampling factor");
@@ -298,7 +305,7 @@ void Builder::build() {
     if (cfg.layer_attns[l]) {
       T slot;
       if (slot_on) slot = make_slot();
-      take(transformer(x, pre + ".3", &c, slot_on ? &slot : nullptr), slot, slot_on);
+      take(transformer(x, pre + ".3", &c, slot_on ? &slot : nullptr, false, u->attn_depth[l]), slot, slot_on);
       retain(x);
       hiddens.push_back(x);
     } else if (u->lin_attn[l]) {   // LinearAttentionTransformerBlock: where full attention is off
@@ -466,7 +473,7 @@ void Builder::build() {
                   skip_scale));
       if (n == nb - 1) took_head();
     }
-    if (attn) step(transformer(x, pre + ".2", &c, head_here ? &head_slot : nullptr));
+    if (attn) step(transformer(x, pre + ".2", &c, head_here ? &head_slot : nullptr, false, u->attn_depth[l]));
     if (lin) step(linear_attn_block(x, pre + ".2", &c, head_here ? &head_slot : nullptr));
     if (combine) {   // the level's map lives on to the tail, as a skip tensor does
       retain(x);

@@ -117,6 +117,10 @@ class kd_unet_ext2_t(C.Structure):
     _fields_ = [("combine_upsample_fmaps", C.c_int)]
 
 
+class kd_unet_ext3_t(C.Structure):
+    _fields_ = [("layer_attns_depth", C.c_int * KD_MAX_LEVELS)]
+
+
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
 SIGNATURES = {
     "kd_last_error": (C.c_char_p, []),
@@ -134,6 +138,9 @@ SIGNATURES = {
                                      C.POINTER(kd_unet_ext_t), C.POINTER(C.c_void_p)]),
     "kd_unet_create_ext2": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
                                       C.POINTER(kd_unet_ext_t), C.POINTER(kd_unet_ext2_t), C.POINTER(C.c_void_p)]),
+    "kd_unet_create_ext3": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
+                                      C.POINTER(kd_unet_ext_t), C.POINTER(kd_unet_ext2_t), C.POINTER(kd_unet_ext3_t),
+                                      C.POINTER(C.c_void_p)]),
     "kd_unet_weight_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_macs": (C.c_int64, [C.c_void_p]),
     "kd_unet_mfma_macs": (C.c_int64, [C.c_void_p]),
@@ -200,6 +207,11 @@ SIGNATURES = {
     "kd_layernorm_ex": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kd_layernorm_linear_bf16x3": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 3 +
                                    [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "kd_attention_ex_d": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_float, C.c_void_p]),
+    "kd_attention_key_tile": (C.c_int, [C.c_int]),
+    "kd_l2norm_heads_d": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "kd_attention": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "kd_attention_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -327,9 +327,11 @@ class Unet(nn.Module):
         if tuple(cross_embed_downsample_kernel_sizes) != (2, 4):
             raise NotImplementedError("cross_embed_downsample_kernel_sizes: the engine plans the library's default (2, 4) only")
         if bad or final_conv_kernel_size != 3 or tuple(init_cross_embed_kernel_sizes) != (3, 7, 15) \
-                or layer_attns_depth != 1 or attn_dim_head != 64 or channels not in (1, 2, 3, 4):
+                or channels not in (1, 2, 3, 4):
             raise NotImplementedError(
                 f"Unet option outside what the reference's configs use and the HIP engine plans: {bad or 'see kwargs'}")
+        if attn_dim_head not in (32, 64, 128):
+            raise NotImplementedError(f"attn_dim_head={attn_dim_head}: the attention kernels are built for 32, 64 and 128")
         if channels != 3 and channels_out is not None and channels_out != channels:
             raise NotImplementedError("channels_out must equal channels: the engine's final conv writes the image's channels")
 
@@ -395,10 +397,19 @@ class Unet(nn.Module):
         # the level's first ResnetBlocks get cross-attention, in its linear form
         lin = cast_tuple(use_linear_attn, L)
         lcross = cast_tuple(use_linear_cross_attn, L)
+        # layer_attns_depth: (attention, feed-forward) pairs of each level's TransformerBlocks
+        depths = tuple(int(d) for d in cast_tuple(layer_attns_depth, L))
+        assert len(depths) == L and all(d >= 1 for d in depths), "layer_attns_depth: one depth >= 1 per level"
+        if (any(lin) or any(lcross)) and attn_dim_head != 64:
+            raise NotImplementedError("use_linear_attn / use_linear_cross_attn with attn_dim_head != 64: "
+                                      "the linear-attention kernels are built for dim_head 64")
+        if any(ll and not la and d != 1 for ll, la, d in zip(lin, attns, depths)):
+            raise NotImplementedError("layer_attns_depth > 1 on a linear-attention level (use_linear_attn) is not planned: "
+                                      "the engine's LinearAttentionTransformerBlock has depth 1")
         assert len(set(groups)) == 1, "per-level resnet_groups are not planned by the engine"
         self._plan = dict(dim=dim, dim_mults=tuple(dim_mults), num_resnet_blocks=nrb, layer_attns=attns,
                           layer_cross_attns=cross, use_linear_attn=lin, use_linear_cross_attn=lcross,
-                          attn_heads=attn_heads, attn_dim_head=attn_dim_head,
+                          attn_heads=attn_heads, attn_dim_head=attn_dim_head, layer_attns_depth=depths,
                           ff_mult=ff_mult, num_time_tokens=num_time_tokens, sinu_dim=learned_sinu_pos_emb_dim,
                           groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn,
                           cross_embed_downsample=self.cross_embed_downsample,
@@ -411,9 +422,9 @@ class Unet(nn.Module):
         self.ups = nn.ModuleList([])
         skip_dims = []
 
-        def attn_block(d, la, ll):   # full attention wins over linear attention
+        def attn_block(d, la, ll, depth):   # full attention wins over linear attention
             if la:
-                return TransformerBlock(d, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak)
+                return TransformerBlock(d, depth=depth, ff_mult=ff_mult, context_dim=cond_dim, **ak)
             if ll:
                 return LinearAttentionTransformerBlock(d, depth=1, ff_mult=ff_mult, context_dim=cond_dim, **ak)
             return _Stateless()
@@ -428,7 +439,8 @@ class Unet(nn.Module):
                 return PixelShuffleUpsample(d, d_out)
             return nn.Sequential(_Stateless(), nn.Conv2d(d, d_out, 3, padding=1))   # nn.Upsample(2, nearest), conv
 
-        for ind, ((d_in, d_out), n, g, la, lc, ll, lx) in enumerate(zip(in_out, nrb, groups, attns, cross, lin, lcross)):
+        for ind, ((d_in, d_out), n, g, la, lc, ll, lx, dep) in enumerate(zip(in_out, nrb, groups, attns, cross, lin, lcross,
+                                                                            depths)):
             is_last = ind >= L - 1
             cur = d_in
             pre = None
@@ -446,11 +458,13 @@ class Unet(nn.Module):
                             linear_attn=bool(lx), **ak),
                 nn.ModuleList([ResnetBlock(cur, cur, time_cond_dim=tcd, groups=g, use_gca=use_global_context_attn)
                                for _ in range(n)]),
-                attn_block(cur, la, ll),
+                attn_block(cur, la, ll, dep),
                 post,
             ]))
         mid = dims[-1]
-        self.mid_block1 = ResnetBlock(mid, mid, cond_dim=cond_dim, time_cond_dim=tcd, groups=groups[-1], **ak)
+        # (the library builds the two middle ResnetBlocks without the attention kwargs: their cross-attention has its own
+        # defaults, 8 heads of 64, whatever attn_heads / attn_dim_head say)
+        self.mid_block1 = ResnetBlock(mid, mid, cond_dim=cond_dim, time_cond_dim=tcd, groups=groups[-1])
         assert downsample_form in ("unshuffle", "conv4x4") and mid_attn_form in ("transformer", "residual_attention")
         self.downsample_form, self.mid_attn_form = downsample_form, mid_attn_form
         self._dims = dims
@@ -458,10 +472,10 @@ class Unet(nn.Module):
         if attend_at_middle:
             self.mid_attn = TransformerBlock(mid, depth=1, ff_mult=2, **ak) if mid_attn_form == "transformer" \
                 else ResidualAttentionBlock(mid, **ak)
-        self.mid_block2 = ResnetBlock(mid, mid, cond_dim=cond_dim, time_cond_dim=tcd, groups=groups[-1], **ak)
-        for ind, ((d_in, d_out), n, g, la, lc, ll, lx) in enumerate(
+        self.mid_block2 = ResnetBlock(mid, mid, cond_dim=cond_dim, time_cond_dim=tcd, groups=groups[-1])
+        for ind, ((d_in, d_out), n, g, la, lc, ll, lx, dep) in enumerate(
                 zip(reversed(in_out), reversed(nrb), reversed(groups), reversed(attns), reversed(cross), reversed(lin),
-                    reversed(lcross))):
+                    reversed(lcross), reversed(depths))):
             is_last = ind == L - 1
             sd = skip_dims.pop()
             self.ups.append(nn.ModuleList([
@@ -469,7 +483,7 @@ class Unet(nn.Module):
                             linear_attn=bool(lx), **ak),
                 nn.ModuleList([ResnetBlock(d_out + sd, d_out, time_cond_dim=tcd, groups=g,
                                            use_gca=use_global_context_attn) for _ in range(n)]),
-                attn_block(d_out, la, ll),
+                attn_block(d_out, la, ll, dep),
                 up(d_out, d_in) if (not is_last or memory_efficient) else _Stateless(),
             ]))
         fin = dim + (dim if init_conv_to_final_conv_residual else 0)
@@ -719,7 +733,14 @@ class Unet(nn.Module):
             ext.upsample_nearest = int(p["upsample_nearest"])
             ext2 = E.kd_unet_ext2_t()
             ext2.combine_upsample_fmaps = int(p["combine_upsample_fmaps"])
-            E.check(lib.kd_unet_create_ext2(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(ext2), C.byref(handle)))
+            if any(d != 1 for d in p["layer_attns_depth"]):
+                ext3 = E.kd_unet_ext3_t()
+                for i in range(L):
+                    ext3.layer_attns_depth[i] = int(p["layer_attns_depth"][i])
+                E.check(lib.kd_unet_create_ext3(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(ext2), C.byref(ext3),
+                                                C.byref(handle)))
+            else:   # depth 1 everywhere: the entry of before (kd_unet_create_ext3 with ext3 = NULL)
+                E.check(lib.kd_unet_create_ext2(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(ext2), C.byref(handle)))
             del sd
         self._engines[key] = handle
         self._engines_fingerprint = self._weights_fingerprint()
