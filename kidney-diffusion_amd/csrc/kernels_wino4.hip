@@ -21,6 +21,11 @@
 // Cin = 512 .. 2048 (F(2x2,3x3): 5e-7, direct fp32 chain: 2.5e-7; scratch/wino43_accuracy.py), inside the 2e-5 the
 // UNet forward is held to (tests/test_fullsize_gpu.py).  The plan uses it where the 4x-smaller GEMM outweighs the
 // transform passes: Cin >= 512 (Builder::wino4_whole_ok).
+//
+// Cache policy and block order (profiles/README.md, 2026-10-19): V and D of the large maps are written once and read once, more
+// than a gigabyte later.  The fp32 V stores and the D loads are non-temporal, and the output transform walks its blocks XCD by
+// XCD.  Each was measured per kernel; what did not pay is not here: non-temporal stores of the plane form, any XCD-aware or 2 x 2
+// tile order of the input transform, sixteen tiles per workgroup.
 #include "common.h"
 
 namespace kd {
@@ -218,7 +223,7 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const float* __restrict__
     f32x2 trow[6];
     w4_bt(u[r], trow);
 #pragma unroll
-    for (int s = 0; s < 6; ++s) *(f32x2*)(out + (int64_t)(r * 6 + s) * pstride) = trow[s];
+    for (int s = 0; s < 6; ++s) __builtin_nontemporal_store(trow[s], (f32x2*)(out + (int64_t)(r * 6 + s) * pstride));
   }
 }
 
@@ -264,13 +269,19 @@ int launch_wino4_in3(const float* x, int ldx, const float* stats, const float* g
 // One thread: one tile x TWO channels -> 4x4 outputs (8-byte accesses); a wave = one tile x 128 consecutive channels
 // (C % 128 == 0) or a narrower run.  seg != nullptr: fp64 (sum, sum of squares) of the 16 outputs x 16 channels of every
 // 16-channel segment, entry [b][c / 16][tile of the image][2] (one chunk per tile: nchunk = (H/4)(W/4))
+// Workgroups are dealt round-robin over the eight XCDs; block id i takes block (i & 7) (n / 8) + (i >> 3) of the (tile, channel)
+// order, so that each XCD walks one contiguous eighth of it, as the bf16x3 GEMM maps its tiles: the rows of y and of each D plane
+// that neighbouring blocks share stay with one L2.  The blocks past the last multiple of eight keep their place.  Per step over
+// the 56 launches: 3.30 ms as launched, 3.14 with this order, 3.23 with non-temporal D loads, 2.89 with both.
 template <bool RES>   // (its own kernel: the residual's registers cost the plain form a wave per SIMD)
 __global__ __launch_bounds__(256) void wino4_out_kernel(const float* __restrict__ D, const float* __restrict__ bias,
                                                         const float* __restrict__ res, int ldres, float* __restrict__ y,
                                                         int ldy, double* __restrict__ seg, int B, int H, int W, int C,
                                                         int64_t nt) {
   const int Ht = H >> 2, Wt = W >> 2, C2 = C >> 1;
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned n8 = gridDim.x & ~7u;
+  const unsigned blk = blockIdx.x < n8 ? (blockIdx.x & 7) * (n8 >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+  const int64_t idx = (int64_t)blk * blockDim.x + threadIdx.x;
   if (idx >= nt * C2) return;   // (whole waves: nt C / 2 % 64 == 0 is required when seg != nullptr)
   const int c = (int)(idx % C2) * 2;
   const int64_t t = idx / C2;
@@ -284,7 +295,7 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const float* __restrict_
   for (int s = 0; s < 6; ++s) {
     f32x2 m[6];
 #pragma unroll
-    for (int r = 0; r < 6; ++r) m[r] = *(const f32x2*)(in + (int64_t)(r * 6 + s) * pstride);
+    for (int r = 0; r < 6; ++r) m[r] = __builtin_nontemporal_load((const f32x2*)(in + (int64_t)(r * 6 + s) * pstride));
     f32x2 ycol[4];
     w4_at(m, ycol);
 #pragma unroll
