@@ -1135,7 +1135,11 @@ struct Builder {
     }
     // x1 = LN(proj) g + x and the feed-forward's first LayerNorm h0 = LN(x1) g' in one pass over the rows
     T h0;
-    int hidden = dim * cfg.ff_mult_x2 / 2;
+    // the hidden width is what the block's own weights say: the library builds mid_attn with TransformerBlock's default
+    // ff_mult = 2 whatever the UNet's ff_mult (cfg.ff_mult_x2) is, and the levels' blocks with the UNet's
+    const int64_t ff_ne = numel(f + ".1.weight");
+    if (ff_ne % dim || (ff_ne / dim) % 4) throw std::runtime_error("'" + f + ".1.weight' is no [4 n][" + std::to_string(dim) + "] matrix");
+    const int hidden = (int)(ff_ne / dim);
     const bool gelu_late = linear_is_x3(proj, hidden);   // (h0 has proj's shape)
     T x1 = layernorm(proj, P(a + ".to_out.1.g", dim), nullptr, &x, ACT_NONE, P(f + ".0.g", dim), &h0, false, gelu_late ? 2 : 0);
     free(proj);

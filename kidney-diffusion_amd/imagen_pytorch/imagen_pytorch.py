@@ -334,6 +334,22 @@ class Unet(nn.Module):
             raise NotImplementedError(f"attn_dim_head={attn_dim_head}: the attention kernels are built for 32, 64 and 128")
         if channels != 3 and channels_out is not None and channels_out != channels:
             raise NotImplementedError("channels_out must equal channels: the engine's final conv writes the image's channels")
+        # scalar options the engine cannot plan: refused here, not by a launcher's precondition at the first forward
+        if cond_on_text and not attn_pool_text:
+            raise NotImplementedError("attn_pool_text=False with cond_on_text=True: the engine plans the text tokens through the "
+                                      "PerceiverResampler only (pass cond_on_text=False for a UNet without text conditioning)")
+        if cond_on_text and attn_pool_text and max_text_len > 512:
+            raise NotImplementedError(f"max_text_len={max_text_len}: the PerceiverResampler's position table holds 512 rows")
+        if learned_sinu_pos_emb_dim < 2 or learned_sinu_pos_emb_dim % 2:
+            raise NotImplementedError(f"learned_sinu_pos_emb_dim={learned_sinu_pos_emb_dim} must be even "
+                                      "(sines and cosines of learned_sinu_pos_emb_dim / 2 frequencies)")
+        if not float(ff_mult * 2).is_integer() or ff_mult <= 0:
+            raise NotImplementedError(f"ff_mult={ff_mult}: the engine plans feed-forward widths of dim * ff_mult for "
+                                      "multiples of 0.5")
+        if num_time_tokens < 1 or attn_heads < 1 or attn_pool_num_latents < 1:
+            raise NotImplementedError("num_time_tokens, attn_heads and attn_pool_num_latents must be at least 1")
+        if dim % 32:
+            raise NotImplementedError(f"dim={dim}: the engine plans UNets whose dim is a multiple of 32")
 
         self.channels = channels
         self.channels_out = default(channels_out, channels)
@@ -407,6 +423,22 @@ class Unet(nn.Module):
             raise NotImplementedError("layer_attns_depth > 1 on a linear-attention level (use_linear_attn) is not planned: "
                                       "the engine's LinearAttentionTransformerBlock has depth 1")
         assert len(set(groups)) == 1, "per-level resnet_groups are not planned by the engine"
+        # every GroupNorm of the plan is a ResnetBlock's block1 (over the block's input) or block2 (over its output), and the
+        # statistics pass reads whole groups in 16-byte steps: each such width must be a multiple of 4 * resnet_groups.
+        # (The UpsampleCombiner's Blocks have 8 groups of their own: dims[l] / 8 is a multiple of 4 since dim % 32 == 0.)
+        gn_widths = {dims[-1]}                                    # mid_block1 / mid_block2
+        if memory_efficient:
+            gn_widths.add(dim)                                    # init_resnet_block
+        for d_in, d_out in in_out:
+            cur = d_out if memory_efficient else d_in
+            gn_widths |= {cur, d_out, d_out + cur}                # the level's down blocks; its up blocks behind the skip concat
+        gn_widths |= {dim, dim * (1 + int(bool(init_conv_to_final_conv_residual)) + (L if combine_upsample_fmaps else 0))}
+        self._gn_widths = sorted(gn_widths)
+        bad_w = sorted(w for w in gn_widths if groups[0] < 1 or w % (4 * groups[0]))
+        if bad_w:
+            raise NotImplementedError(f"resnet_groups={groups[0]}: the GroupNorm over {bad_w[0]} channels would have groups of "
+                                      f"{bad_w[0] / max(groups[0], 1):g} channels, the engine plans multiples of 4 "
+                                      f"(ResnetBlock widths of this UNet: {sorted(gn_widths)})")
         self._plan = dict(dim=dim, dim_mults=tuple(dim_mults), num_resnet_blocks=nrb, layer_attns=attns,
                           layer_cross_attns=cross, use_linear_attn=lin, use_linear_cross_attn=lcross,
                           attn_heads=attn_heads, attn_dim_head=attn_dim_head, layer_attns_depth=depths,
