@@ -23,11 +23,12 @@ Tolerance: test_attention's rtol 1e-4, atol 2e-5 for every case, no family needs
 worst of the 224 launches of this file uses 0.09 of it, the fp32 torch evaluation of the same inputs 0.11; every test
 prints its figure).
 """
-import math
-
 import pytest
 import torch
 import torch.nn.functional as F
+
+import attention_cases as AC
+import helpers as H
 
 pytestmark = pytest.mark.gpu
 
@@ -35,21 +36,12 @@ D = 64
 RTOL, ATOL = 1e-4, 2e-5   # test_kernels_gpu.py::test_attention
 
 
+engine = H.engine   # (H is the head count inside the functions below)
+
+
 @pytest.fixture(scope="module")
 def lib():
-    from imagen_pytorch import _engine as E
-
-    return E.load()
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
+    return engine().load()
 
 
 # (B, Nq, H): which kernel launch_attention picks (kernels_attn.hip: matrix cores from Nq >= 128 and at least 16 blocks
@@ -62,76 +54,9 @@ QSHAPES = {
 }
 
 
-def _is_mfma(B, Nq, H):
-    return Nq >= 128 and ((Nq + 127) // 128) * H * B >= 16
-
-
 def test_query_shapes_reach_both_kernels():
-    assert [_is_mfma(*QSHAPES[n]) for n in ("vec70", "vec130", "mfma200", "mfma256")] == [False, False, True, True]
-    assert _is_mfma(1, 4096, 8) and not _is_mfma(1, 64, 8)
-
-
-# ------------------------------------------------------------------------------------------------ inputs
-def _inputs(family, B, Nq, H, Hkv, null, n0, n1, seed, marker=None):
-    """fp32 CPU tensors q [B,Nq,H,64], null_kv [2,64] | None, k0 / v0 [B,n0,Hkv,64], k1 / v1 [B,n1,Hkv,64] and the scale.
-    marker: index into the key list cat(null, seg0, seg1) of the key that gets the large logit."""
-    gen = g(seed)
-    rn = lambda *s: torch.randn(*s, generator=gen)
-    q = rn(B, Nq, H, D) * 0.5
-    nkv = rn(2, D) if null else None
-    k0, v0, k1, v1 = rn(B, n0, Hkv, D), rn(B, n0, Hkv, D), rn(B, n1, Hkv, D), rn(B, n1, Hkv, D)
-    Nk = int(null) + n0 + n1
-    scale = 0.125
-    if family == "plain":
-        pass
-    elif family == "cos16":   # attn_qk_norm = 1: unit q and k, logits in [-16, 16]
-        q, k0, k1 = F.normalize(q, dim=-1), F.normalize(k0, dim=-1), F.normalize(k1, dim=-1)
-        if null:
-            nkv[0] = F.normalize(nkv[0], dim=-1)
-        scale = 16.0
-    elif family == "ascending":   # key norms rise along the key list: the running maximum moves in every tile
-        f = lambda j: 0.5 + 3.5 * j / max(Nk - 1, 1)
-        if null:
-            nkv[0] *= f(0)
-        k0 *= f(int(null) + torch.arange(n0, dtype=torch.float32))[None, :, None, None]
-        k1 *= f(int(null) + n0 + torch.arange(n1, dtype=torch.float32))[None, :, None, None]
-    elif family == "marker":
-        # every query has 2 u in it, the marked key is c u: its logit is c / 8 * (2 +- 0.3) = ln(Nk) + 1 (+- 15 %), so
-        # the key holds about e / (1 + e) of the softmax whatever Nk: dropped, doubled or swapped it moves the output by
-        # O(1), and its value row is unlike any other (3 + d / 16)
-        u = F.normalize(rn(D), dim=-1)
-        q = rn(B, Nq, H, D) * 0.3 + 2 * u
-        c = 4 * (math.log(Nk) + 1)
-        vm = 3 + torch.arange(D, dtype=torch.float32) / 16
-        j = marker
-        if null and j == 0:
-            nkv[0], nkv[1] = c * u, vm
-        elif j < int(null) + n0:
-            k0[:, j - int(null)], v0[:, j - int(null)] = c * u, vm
-        else:
-            k1[:, j - int(null) - n0], v1[:, j - int(null) - n0] = c * u, vm
-    else:
-        raise ValueError(family)
-    return q, nkv, k0, v0, k1, v1, scale
-
-
-def _reference(q, nkv, k0, v0, k1, v1, scale):
-    """fp64 softmax(scale q k^T) v over cat(null, seg0, seg1), K / V expanded over the heads; one head at a time."""
-    B, Nq, H, _ = q.shape
-    ks, vs = [], []
-    if nkv is not None:
-        ks.append(nkv[0].expand(B, 1, H, D))
-        vs.append(nkv[1].expand(B, 1, H, D))
-    for k, v in ((k0, v0), (k1, v1)):
-        if k.shape[1]:
-            ks.append(k.expand(B, k.shape[1], H, D))
-            vs.append(v.expand(B, v.shape[1], H, D))
-    K, V = torch.cat(ks, dim=1).double(), torch.cat(vs, dim=1).double()
-    out = torch.empty(B, Nq, H, D, dtype=torch.float64)
-    for h in range(H):
-        sim = torch.einsum("bid,bjd->bij", q[:, :, h].double(), K[:, :, h]) * scale
-        out[:, :, h] = torch.einsum("bij,bjd->bid", sim.softmax(dim=-1), V[:, :, h])
-    return out
+    assert [AC.is_mfma(*QSHAPES[n]) for n in ("vec70", "vec130", "mfma200", "mfma256")] == [False, False, True, True]
+    assert AC.is_mfma(1, 4096, 8) and not AC.is_mfma(1, 64, 8)
 
 
 # ------------------------------------------------------------------------------------------------ device buffers
@@ -180,7 +105,7 @@ class _Bufs:
     def launch(self, lib, scale):
         import ctypes as C
 
-        E = _E()
+        E = engine()
         p = lambda a, n: C.c_void_p(a) if n else None   # an empty segment goes in as NULL pointers
         return lib.kd_attention_ex(C.c_void_p(self.q_ptr), self.ldq, E.ptr(self.nkv), p(self.k0_ptr, self.n0),
                                    p(self.v0_ptr, self.n0), self.ld0, self.n0, p(self.k1_ptr, self.n1), p(self.v1_ptr, self.n1),
@@ -200,14 +125,14 @@ class _Bufs:
 def _check(lib, device, layout, family, qshape, Hkv_is_H, null, n0, n1, pad, seed, marker=None, tag=""):
     B, Nq, H = qshape
     Hkv = H if Hkv_is_H else 1
-    q, nkv, k0, v0, k1, v1, scale = _inputs(family, B, Nq, H, Hkv, null, n0, n1, seed, marker)
+    q, nkv, k0, v0, k1, v1, scale = AC.inputs(D, family, B, Nq, H, Hkv, null, n0, n1, seed, marker)
     bufs = _Bufs(device, layout, q, nkv, k0, v0, k1, v1, pad)
-    _E().check(bufs.launch(lib, scale))
+    engine().check(bufs.launch(lib, scale))
     got = bufs.result()
-    ref = _reference(q, nkv, k0, v0, k1, v1, scale)
+    ref = AC.reference(q, nkv, k0, v0, k1, v1, scale)
     used = float(((got - ref).abs() / (ATOL + RTOL * ref.abs())).max())
     print(f"attention {layout} {family}{tag} B{B} Nq{Nq} H{H} Hkv{Hkv} keys {int(null)}+{n0}+{n1} "
-          f"{'mfma' if _is_mfma(B, Nq, H) else 'vec4'}: max|err| {float((got - ref).abs().max()):.2e}, {used:.3f} of the bound")
+          f"{'mfma' if AC.is_mfma(B, Nq, H) else 'vec4'}: max|err| {float((got - ref).abs().max()):.2e}, {used:.3f} of the bound")
     assert torch.allclose(got, ref, rtol=RTOL, atol=ATOL), used
 
 
@@ -293,9 +218,9 @@ def test_marker_key_at_plan_size(lib, device, where, marker, qshape):
 
 # ------------------------------------------------------------------------------------------------ refusals
 def test_attention_ex_refuses_what_the_kernels_cannot_do(lib, device):
-    E = _E()
+    E = engine()
     B, Nq, H = 1, 8, 8
-    q, nkv, k0, v0, k1, v1, scale = _inputs("plain", B, Nq, H, H, True, 4, 4, 7)
+    q, nkv, k0, v0, k1, v1, scale = AC.inputs(D, "plain", B, Nq, H, H, True, 4, 4, 7)
     bufs = _Bufs(device, "cross", q, nkv, k0, v0, k1, v1, 0)
     assert bufs.launch(lib, scale) == 0
     bufs.Hkv = 3
@@ -320,10 +245,6 @@ L2_REL = 1e-6   # fp32 torch is 5e-8 from fp64 on such inputs: an order of magni
 SENTINEL = 777.0
 
 
-def _rel(a, b):
-    return float((a.double() - b).norm() / b.norm().clamp(min=1e-300))
-
-
 @pytest.mark.parametrize("heads,extra,rows", [
     (1, 0, 7),      # rows * heads = 7: the last block has one idle wave
     (1, 12, 9),     # strided rows
@@ -337,8 +258,8 @@ def test_l2norm_heads(lib, device, heads, extra, rows, with_scale):
     """kd_l2norm_heads against fp64 F.normalize(x, dim=-1, eps=1e-12) * scale_vec per 64-wide head segment: strided rows
     whose other columns keep their sentinel, a segment count that does not fill the last block, an all-zero segment (0, not
     NaN) and a segment of norm 1e-13, below the floor (x / 1e-12, not a unit vector)."""
-    E = _E()
-    gen = g(17 + heads + rows)
+    E = engine()
+    gen = H.gen(17 + heads + rows)
     ld = heads * D + extra
     x = torch.randn(rows, heads, D, generator=gen) * torch.logspace(-3, 3, rows * heads).reshape(rows, heads, 1)
     zero_at, tiny_at = (1, 0), (rows - 1, heads - 1)
@@ -358,8 +279,8 @@ def test_l2norm_heads(lib, device, heads, extra, rows, with_scale):
     tiny_norm = float(x[tiny_at].double().norm())   # below the floor: x / 1e-12, a vector of norm 0.1, not a unit vector
     assert 0.5e-13 < tiny_norm < 2e-13
     assert abs(float((got[tiny_at].double() / (sv.double() if with_scale else 1.0)).norm()) - tiny_norm / 1e-12) < 1e-6
-    err, err_tiny = _rel(got, ref), _rel(got[tiny_at], ref[tiny_at])
-    worst = max(_rel(got[r, h], ref[r, h]) for r in range(rows) for h in range(heads) if (r, h) != zero_at)
+    err, err_tiny = AC.rel(got, ref), AC.rel(got[tiny_at], ref[tiny_at])
+    worst = max(AC.rel(got[r, h], ref[r, h]) for r in range(rows) for h in range(heads) if (r, h) != zero_at)
     print(f"l2norm heads {heads} ld {ld} rows {rows} scale {with_scale}: rel-L2 {err:.2e}, worst segment {worst:.2e}, "
           f"below the floor {err_tiny:.2e}")
     assert err < L2_REL and worst < L2_REL
@@ -367,14 +288,14 @@ def test_l2norm_heads(lib, device, heads, extra, rows, with_scale):
 
 def test_l2norm_heads_of_the_null_key(lib, device):
     """null_kv_of (engine.hip): the [2][64] null key / value as one row of stride 128 with one head - the value stays."""
-    E = _E()
-    nkv = torch.randn(2, D, generator=g(23)) * 3
-    sv = 1 + 0.3 * torch.randn(D, generator=g(24))
+    E = engine()
+    nkv = torch.randn(2, D, generator=H.gen(23)) * 3
+    sv = 1 + 0.3 * torch.randn(D, generator=H.gen(24))
     buf, svd = nkv.to(device), sv.to(device)
     E.check(lib.kd_l2norm_heads(E.ptr(buf), 2 * D, 1, 1, E.ptr(svd), E.current_stream()))
     out = buf.cpu()
     assert torch.equal(out[1], nkv[1])
-    assert _rel(out[0], F.normalize(nkv[0].double(), dim=-1, eps=1e-12) * sv.double()) < L2_REL
+    assert AC.rel(out[0], F.normalize(nkv[0].double(), dim=-1, eps=1e-12) * sv.double()) < L2_REL
 
 
 # ------------------------------------------------------------------------------------------------ composition
@@ -385,10 +306,10 @@ def test_qk_norm_then_attention_is_cosine_sim_attention(lib, device, qshape):
     of the raw inputs."""
     import ctypes as C
 
-    E = _E()
+    E = engine()
     B, Nq, H = qshape
     n0, n1 = 2, Nq
-    q, nkv, k0, v0, k1, v1, _ = _inputs("ascending", B, Nq, H, 1, True, n0, n1, 606)
+    q, nkv, k0, v0, k1, v1, _ = AC.inputs(D, "ascending", B, Nq, H, 1, True, n0, n1, 606)
     bufs = _Bufs(device, "self", q, nkv, k0, v0, k1, v1, 0)
     s = E.current_stream()
     E.check(lib.kd_l2norm_heads(C.c_void_p(bufs.q_ptr), bufs.ldq, B * Nq, H, None, s))
@@ -398,7 +319,7 @@ def test_qk_norm_then_attention_is_cosine_sim_attention(lib, device, qshape):
     E.check(bufs.launch(lib, 16.0))
     got = bufs.result()
     nrm = lambda t: F.normalize(t.double(), dim=-1, eps=1e-12)
-    ref = _reference(nrm(q), torch.stack([nrm(nkv[0]), nkv[1].double()]), nrm(k0), v0, nrm(k1), v1, 16.0)
+    ref = AC.reference(nrm(q), torch.stack([nrm(nkv[0]), nkv[1].double()]), nrm(k0), v0, nrm(k1), v1, 16.0)
     used = float(((got - ref).abs() / (ATOL + RTOL * ref.abs())).max())
     print(f"qk-norm + attention B{B} Nq{Nq} H{H}: {used:.3f} of the bound")
     assert torch.allclose(got, ref, rtol=RTOL, atol=ATOL), used

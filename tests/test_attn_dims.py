@@ -20,25 +20,15 @@ KW = dict(dim=32, dim_mults=(1, 2, 4), num_resnet_blocks=1, layer_attns=(False, 
 TEXT = dict(KW, cond_dim=64, cond_on_text=True, text_embed_dim=3)
 
 
-def _product(seed=0, **kw):
-    import imagen_pytorch as ip
-
-    return H.randomize_(ip.Unet(**kw), seed)
-
-
-def _layout(sd):
-    return {k: tuple(v.shape) for k, v in sd.items()}
-
-
 # ------------------------------------------------------------------------------- construction and state dict
 @pytest.mark.parametrize("d", [32, 128])
 @pytest.mark.parametrize("dep", [2, (1, 2, 3)])
 @pytest.mark.parametrize("base", ["plain", "text"])
 def test_state_dict_layout_equals_the_oracle_and_round_trips(d, dep, base):
     kw = dict(TEXT if base == "text" else KW, attn_dim_head=d, layer_attns_depth=dep)
-    p, r = _product(1, **kw), H.randomize_(R.Unet(**kw), 2)
+    p, r = H.random_product_unet(1, **kw), H.randomize_(R.Unet(**kw), 2)
     sp, sr = p.state_dict(), r.state_dict()
-    assert _layout(sp) == _layout(sr)
+    assert H.state_layout(sp) == H.state_layout(sr)
     depths = (dep,) * 3 if isinstance(dep, int) else dep
     assert p._plan["layer_attns_depth"] == depths and p._plan["attn_dim_head"] == d
     for l in (1, 2):   # the attention levels: downs.l.3 and ups.(2 - l).2
@@ -65,36 +55,37 @@ def test_state_dict_layout_equals_the_oracle_and_round_trips(d, dep, base):
     p.load_state_dict(sr, strict=True)
     got = p.state_dict()
     assert all(torch.equal(got[k], sr[k]) for k in sr)
-    r.load_state_dict(_product(3, **kw).state_dict(), strict=True)
+    r.load_state_dict(H.random_product_unet(3, **kw).state_dict(), strict=True)
 
 
 @pytest.mark.parametrize("d", [32, 128])
 def test_learned_scale_fork_sizes_q_scale_and_k_scale_by_dim_head(d):
     kw = dict(TEXT, attn_dim_head=d, layer_attns_depth=2)
-    p, r = _product(4, **kw, attn_qk_norm=2), H.randomize_(R.Unet(**kw, attn_qk_norm=2), 5)
+    p, r = H.random_product_unet(4, **kw, attn_qk_norm=2), H.randomize_(R.Unet(**kw, attn_qk_norm=2), 5)
     sp, sr = p.state_dict(), r.state_dict()
-    assert _layout(sp) == _layout(sr)
+    assert H.state_layout(sp) == H.state_layout(sr)
     scales = [k for k in sp if k.endswith(".q_scale") or k.endswith(".k_scale")]
     assert any(k.startswith("downs.1.3.layers.1.0.") for k in scales) and any(k.startswith("attn_pool.layers.") for k in scales)
     assert any(k.startswith("downs.1.1.cross_attn.") for k in scales) and any(k.startswith("mid_block1.cross_attn.") for k in scales)
     assert all(tuple(sp[k].shape) == ((64,) if k.startswith("mid_block") else (d,)) for k in scales)   # (mid blocks: 8 x 64)
     p.load_state_dict(sr, strict=True)
     # a Unet built without the fork follows a checkpoint that carries it
-    q = _product(6, **kw)
+    q = H.random_product_unet(6, **kw)
     assert not any(k.endswith(".q_scale") for k in q.state_dict())
     q.load_state_dict(sr, strict=True)
-    assert q.attn_qk_norm == 2 and _layout(q.state_dict()) == _layout(sr)
+    assert q.attn_qk_norm == 2 and H.state_layout(q.state_dict()) == H.state_layout(sr)
 
 
 def test_default_unet_is_unchanged():
-    d = _product(**KW)
-    assert _layout(d.state_dict()) == _layout(R.Unet(**KW).state_dict())
-    assert _layout(d.state_dict()) == _layout(_product(**KW, attn_dim_head=64, layer_attns_depth=1).state_dict())
+    d = H.random_product_unet(**KW)
+    assert H.state_layout(d.state_dict()) == H.state_layout(R.Unet(**KW).state_dict())
+    same = H.random_product_unet(**KW, attn_dim_head=64, layer_attns_depth=1)
+    assert H.state_layout(d.state_dict()) == H.state_layout(same.state_dict())
     assert d._plan["layer_attns_depth"] == (1, 1, 1) and d._plan["attn_dim_head"] == 64
 
 
 def test_cast_model_parameters_clones_keep_both_options():
-    u = _product(**KW, attn_dim_head=32, layer_attns_depth=(1, 2, 3))
+    u = H.random_product_unet(**KW, attn_dim_head=32, layer_attns_depth=(1, 2, 3))
     clone = u.cast_model_parameters(lowres_cond=True, text_embed_dim=None, channels=3, channels_out=3, cond_on_text=False)
     assert clone._plan["layer_attns_depth"] == (1, 2, 3) and clone._plan["attn_dim_head"] == 32
     assert "ups.0.2.layers.2.0.to_q.weight" in clone.state_dict()

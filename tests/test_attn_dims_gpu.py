@@ -10,6 +10,7 @@ tile of the D-wide instantiations (64, 64, 32).
 Tolerance of the attention core: test_attention_gpu.py's rtol 1e-4, atol 2e-5 for both D (every test prints the share of
 it that it uses, and the share fp32 torch attention on the CPU uses on the same inputs)."""
 import ctypes as C
+import functools
 import math
 import re
 
@@ -17,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attention_cases as AC
 import elucidated_ref as ER
 import helpers as H
 from oracle import imagen_ref as R
@@ -31,96 +33,24 @@ DS = [32, 128]
 NAN = float("nan")
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
+engine = H.engine   # (H is the head count inside some functions below)
 
 
 @pytest.fixture(scope="module")
 def lib():
-    return _E().load()
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
+    return engine().load()
 
 
 QSHAPES = {"vec70": (2, 70, 4),      # Nq < 128: attention_kernel<4, D, DS>
            "mfma200": (2, 200, 4)}   # 16 blocks of 128 queries, the last wave a quarter full: attention_mfma_kernel<D>
 
 
-def _is_mfma(B, Nq, H):
-    return Nq >= 128 and ((Nq + 127) // 128) * H * B >= 16
-
-
 def test_query_shapes_reach_both_kernels_and_tiles_are_known(lib):
-    assert [_is_mfma(*QSHAPES[n]) for n in ("vec70", "mfma200")] == [False, True]
+    assert [AC.is_mfma(*QSHAPES[n]) for n in ("vec70", "mfma200")] == [False, True]
     assert [lib.kd_attention_key_tile(d) for d in (32, 64, 128)] == [64, 64, 32]
 
 
-# ------------------------------------------------------------------------------------------------ inputs and reference
-def _inputs(D, family, B, Nq, H, Hkv, null, n0, n1, seed, marker=None):
-    """fp32 CPU tensors q [B,Nq,H,D], null_kv [2,D] | None, k0 / v0 [B,n0,Hkv,D], k1 / v1 [B,n1,Hkv,D] and the scale.
-    marker: index into the key list cat(null, seg0, seg1) of the key that gets the large logit."""
-    gen = g(seed)
-    rn = lambda *s: torch.randn(*s, generator=gen)
-    q = rn(B, Nq, H, D) * 0.5
-    nkv = rn(2, D) if null else None
-    k0, v0, k1, v1 = rn(B, n0, Hkv, D), rn(B, n0, Hkv, D), rn(B, n1, Hkv, D), rn(B, n1, Hkv, D)
-    Nk = int(null) + n0 + n1
-    scale = D ** -0.5
-    if family == "plain":
-        pass
-    elif family == "cos16":   # attn_qk_norm = 1: unit q and k, logits in [-16, 16]
-        q, k0, k1 = F.normalize(q, dim=-1), F.normalize(k0, dim=-1), F.normalize(k1, dim=-1)
-        if null:
-            nkv[0] = F.normalize(nkv[0], dim=-1)
-        scale = 16.0
-    elif family == "ascending":   # key norms rise along the key list: the running maximum moves in every tile
-        f = lambda j: 0.5 + 3.5 * j / max(Nk - 1, 1)
-        if null:
-            nkv[0] *= f(0)
-        k0 *= f(int(null) + torch.arange(n0, dtype=torch.float32))[None, :, None, None]
-        k1 *= f(int(null) + n0 + torch.arange(n1, dtype=torch.float32))[None, :, None, None]
-    elif family == "marker":
-        # every query has 2 u in it, the marked key is c u: its logit is c scale (2 +- noise) = ln(Nk) + 1 (+- 15 %), so the key
-        # holds about e / (1 + e) of the softmax whatever Nk; its value row is unlike any other and differs in every column
-        u = F.normalize(rn(D), dim=-1)
-        q = rn(B, Nq, H, D) * (0.3 * 8 * scale) + 2 * u
-        c = (math.log(Nk) + 1) / (2 * scale)
-        vm = 3 + torch.arange(D, dtype=torch.float32) / 16
-        j = marker
-        if null and j == 0:
-            nkv[0], nkv[1] = c * u, vm
-        elif j < int(null) + n0:
-            k0[:, j - int(null)], v0[:, j - int(null)] = c * u, vm
-        else:
-            k1[:, j - int(null) - n0], v1[:, j - int(null) - n0] = c * u, vm
-    else:
-        raise ValueError(family)
-    return q, nkv, k0, v0, k1, v1, scale
-
-
-def _reference(q, nkv, k0, v0, k1, v1, scale, dtype=torch.float64):
-    """softmax(scale q k^T) v over cat(null, seg0, seg1) in `dtype`, K / V expanded over the heads; one head at a time."""
-    B, Nq, H, D = q.shape
-    ks, vs = [], []
-    if nkv is not None:
-        ks.append(nkv[0].expand(B, 1, H, D))
-        vs.append(nkv[1].expand(B, 1, H, D))
-    for k, v in ((k0, v0), (k1, v1)):
-        if k.shape[1]:
-            ks.append(k.expand(B, k.shape[1], H, D))
-            vs.append(v.expand(B, v.shape[1], H, D))
-    K, V = torch.cat(ks, dim=1).to(dtype), torch.cat(vs, dim=1).to(dtype)
-    out = torch.empty(B, Nq, H, D, dtype=dtype)
-    for h in range(H):
-        sim = torch.einsum("bid,bjd->bij", q[:, :, h].to(dtype), K[:, :, h]) * scale
-        out[:, :, h] = torch.einsum("bij,bjd->bid", sim.softmax(dim=-1), V[:, :, h])
-    return out
-
-
+# ------------------------------------------------------------------------------------------------ device buffers
 class _Bufs:
     """The NaN-filled device buffers of one launch.  "self" (Hkv = 1, transformer()): q | k | v are columns of one buffer of
     row stride ldq = ld1 = inner + 2 D + 4, the context k | v rows of stride ld0 = 2 D + 8.  "cross" (Hkv = H, cross_attn() and
@@ -163,7 +93,7 @@ class _Bufs:
         self.out = nan(B * Nq + 1, self.ldo)   # (+ one guard row)
 
     def launch(self, lib, scale, D=None, plain_entry=False):
-        E = _E()
+        E = engine()
         p = lambda a, n: C.c_void_p(a) if n else None   # an empty segment goes in as NULL pointers
         head = (C.c_void_p(self.q_ptr), self.ldq, E.ptr(self.nkv), p(self.k0_ptr, self.n0), p(self.v0_ptr, self.n0), self.ld0,
                 self.n0, p(self.k1_ptr, self.n1), p(self.v1_ptr, self.n1), self.ld1, self.n1, E.ptr(self.out), self.ldo, self.B,
@@ -190,14 +120,14 @@ def _used(got, ref):
 def _check(lib, device, D, family, qshape, Hkv_is_H, null, n0, n1, seed, marker=None, tag=""):
     B, Nq, H = qshape
     Hkv = H if Hkv_is_H else 1
-    args = _inputs(D, family, B, Nq, H, Hkv, null, n0, n1, seed, marker)
+    args = AC.inputs(D, family, B, Nq, H, Hkv, null, n0, n1, seed, marker)
     bufs = _Bufs(device, D, *args[:6])
-    _E().check(bufs.launch(lib, args[6]))
+    engine().check(bufs.launch(lib, args[6]))
     got = bufs.result()
-    ref = _reference(*args)
-    used, used32 = _used(got, ref), _used(_reference(*args, dtype=torch.float32), ref)
+    ref = AC.reference(*args)
+    used, used32 = _used(got, ref), _used(AC.reference(*args, dtype=torch.float32), ref)
     print(f"attention D{D} {family}{tag} B{B} Nq{Nq} H{H} Hkv{Hkv} keys {int(null)}+{n0}+{n1} "
-          f"{'mfma' if _is_mfma(B, Nq, H) else 'vec'}: max|err| {float((got - ref).abs().max()):.2e}, {used:.3f} of the bound "
+          f"{'mfma' if AC.is_mfma(B, Nq, H) else 'vec'}: max|err| {float((got - ref).abs().max()):.2e}, {used:.3f} of the bound "
           f"(fp32 torch: {used32:.3f})")
     assert torch.allclose(got, ref, rtol=RTOL, atol=ATOL), used
     return used
@@ -257,11 +187,11 @@ def test_marker_moves_every_output_column(lib, device):
     """The marker family does what it is for: the reference output of a marked key list is, in every column of every head,
     far outside the tolerance from the reference with the marker's value row zeroed in its upper half (a kernel that
     wrote only the first 64 of 128 columns, or took them from another key, would be caught)."""
-    args = list(_inputs(128, "marker", 2, 70, 4, 1, True, 20, 94, 404, marker=32))
-    ref = _reference(*args)
+    args = list(AC.inputs(128, "marker", 2, 70, 4, 1, True, 20, 94, 404, marker=32))
+    ref = AC.reference(*args)
     args[5] = args[5].clone()   # v1: key 32 of the list is row 32 - 1 - 20 of segment 1
     args[5][:, 32 - 21, :, 64:] = 0
-    other = _reference(*args)
+    other = AC.reference(*args)
     assert bool(((ref - other).abs()[..., 64:] > 1.0).all()) and bool(((ref - other).abs()[..., :64] < 1e-9).all())
 
 
@@ -270,51 +200,47 @@ def test_marker_moves_every_output_column(lib, device):
 def test_d64_through_the_new_entry_is_bit_equal_to_kd_attention_ex(lib, device, qname):
     B, Nq, H = QSHAPES[qname]
     for Hkv in (1, H):
-        args = _inputs(64, "ascending", B, Nq, H, Hkv, True, 30, 98, 303)
+        args = AC.inputs(64, "ascending", B, Nq, H, Hkv, True, 30, 98, 303)
         a, b = _Bufs(device, 64, *args[:6]), _Bufs(device, 64, *args[:6])
-        _E().check(a.launch(lib, args[6], plain_entry=True))
-        _E().check(b.launch(lib, args[6]))
+        engine().check(a.launch(lib, args[6], plain_entry=True))
+        engine().check(b.launch(lib, args[6]))
         assert torch.equal(a.result(), b.result())
-        assert torch.allclose(a.result(), _reference(*args), rtol=RTOL, atol=ATOL)
+        assert torch.allclose(a.result(), AC.reference(*args), rtol=RTOL, atol=ATOL)
 
 
 def test_other_head_widths_are_refused(lib, device):
-    args = _inputs(32, "plain", 1, 8, 4, 4, True, 4, 4, 7)
+    args = AC.inputs(32, "plain", 1, 8, 4, 4, True, 4, 4, 7)
     bufs = _Bufs(device, 32, *args[:6])
     assert bufs.launch(lib, args[6]) == 0
     for bad in (48, 256, 0):
         assert bufs.launch(lib, args[6], D=bad) != 0
         assert all(v in lib.kd_last_error() for v in (b"32", b"64", b"128")), lib.kd_last_error()
     x = torch.zeros(4, 256, device=device)
-    assert lib.kd_l2norm_heads_d(_E().ptr(x), 256, 4, 1, 48, None, _E().current_stream()) != 0
+    assert lib.kd_l2norm_heads_d(engine().ptr(x), 256, 4, 1, 48, None, engine().current_stream()) != 0
     assert all(v in lib.kd_last_error() for v in (b"32", b"64", b"128"))
-    assert lib.kd_l2norm_heads_d(_E().ptr(x), 256, 4, 3, 128, None, _E().current_stream()) != 0   # ld < heads * D
+    assert lib.kd_l2norm_heads_d(engine().ptr(x), 256, 4, 3, 128, None, engine().current_stream()) != 0   # ld < heads * D
     q = torch.zeros(1, 4, 2, 48, device=device)
-    assert lib.kd_attention(_E().ptr(q), _E().ptr(q), _E().ptr(q), _E().ptr(q.clone()), 1, 4, 4, 2, 2, 48,
-                            _E().current_stream()) != 0
+    assert lib.kd_attention(engine().ptr(q), engine().ptr(q), engine().ptr(q), engine().ptr(q.clone()), 1, 4, 4, 2, 2, 48,
+                            engine().current_stream()) != 0
     assert b"32, 64 and 128" in lib.kd_last_error()
 
 
 @pytest.mark.parametrize("D", DS)
 def test_kd_attention_takes_the_three_widths(lib, device, D):
-    E = _E()
-    gen = g(D)
+    E = engine()
+    gen = H.gen(D)
     q, k, v = (torch.randn(2, n, 4, D, generator=gen) for n in (70, 90, 90))
     out = torch.full((2, 70, 4, D), NAN, device=device)
     qd, kd, vd = q.to(device), k.to(device), v.to(device)
     E.check(lib.kd_attention(E.ptr(qd), E.ptr(kd), E.ptr(vd), E.ptr(out), 2, 70, 90, 4, 4, D, E.current_stream()))
     torch.cuda.synchronize()
-    ref = _reference(q, None, k, v, k[:, :0], v[:, :0], 1.0)
+    ref = AC.reference(q, None, k, v, k[:, :0], v[:, :0], 1.0)
     assert torch.allclose(out.cpu().double(), ref, rtol=RTOL, atol=ATOL), _used(out.cpu(), ref)
 
 
 # ------------------------------------------------------------------------------------------------ qk-norm
 L2_REL = 1e-6   # test_attention_gpu.py: fp32 torch is 5e-8 from fp64 on such inputs, an order of magnitude for the summation order
 SENTINEL = 777.0
-
-
-def _rel(a, b):
-    return float((a.double() - b).norm() / b.norm().clamp(min=1e-300))
 
 
 @pytest.mark.parametrize("heads,extra,rows", [
@@ -329,8 +255,8 @@ def test_l2norm_heads(lib, device, D, heads, extra, rows, with_scale):
     """kd_l2norm_heads_d against fp64 F.normalize(x, dim=-1, eps=1e-12) * scale_vec per D-wide head segment: strided rows
     whose other columns keep their sentinel, a segment count that does not fill the last block, an all-zero segment (0, not
     NaN) and a segment of norm 1e-13, below the floor (x / 1e-12, not a unit vector)."""
-    E = _E()
-    gen = g(17 + heads + rows + D)
+    E = engine()
+    gen = H.gen(17 + heads + rows + D)
     ld = heads * D + extra
     x = torch.randn(rows, heads, D, generator=gen) * torch.logspace(-3, 3, rows * heads).reshape(rows, heads, 1)
     zero_at, tiny_at = (1, 0), (rows - 1, heads - 1)
@@ -350,8 +276,8 @@ def test_l2norm_heads(lib, device, D, heads, extra, rows, with_scale):
     tiny_norm = float(x[tiny_at].double().norm())   # below the floor: x / 1e-12, a vector of norm 0.1, not a unit vector
     assert 0.5e-13 < tiny_norm < 2e-13
     assert abs(float((got[tiny_at].double() / (sv.double() if with_scale else 1.0)).norm()) - tiny_norm / 1e-12) < 1e-6
-    err = _rel(got, ref)
-    worst = max(_rel(got[r, h], ref[r, h]) for r in range(rows) for h in range(heads) if (r, h) != zero_at)
+    err = AC.rel(got, ref)
+    worst = max(AC.rel(got[r, h], ref[r, h]) for r in range(rows) for h in range(heads) if (r, h) != zero_at)
     print(f"l2norm D{D} heads {heads} ld {ld} rows {rows} scale {with_scale}: rel-L2 {err:.2e}, worst segment {worst:.2e}")
     assert err < L2_REL and worst < L2_REL
 
@@ -359,19 +285,19 @@ def test_l2norm_heads(lib, device, D, heads, extra, rows, with_scale):
 @pytest.mark.parametrize("D", DS)
 def test_l2norm_heads_of_the_null_key(lib, device, D):
     """null_kv_of (engine.hip): the [2][D] null key / value as one row of stride 2 D with one head - the value stays."""
-    E = _E()
-    nkv = torch.randn(2, D, generator=g(23)) * 3
-    sv = 1 + 0.3 * torch.randn(D, generator=g(24))
+    E = engine()
+    nkv = torch.randn(2, D, generator=H.gen(23)) * 3
+    sv = 1 + 0.3 * torch.randn(D, generator=H.gen(24))
     buf, svd = nkv.to(device), sv.to(device)
     E.check(lib.kd_l2norm_heads_d(E.ptr(buf), 2 * D, 1, 1, D, E.ptr(svd), E.current_stream()))
     out = buf.cpu()
     assert torch.equal(out[1], nkv[1])
-    assert _rel(out[0], F.normalize(nkv[0].double(), dim=-1, eps=1e-12) * sv.double()) < L2_REL
+    assert AC.rel(out[0], F.normalize(nkv[0].double(), dim=-1, eps=1e-12) * sv.double()) < L2_REL
 
 
 def test_l2norm_d64_through_the_new_entry_is_bit_equal(lib, device):
-    E = _E()
-    x = torch.randn(37, 3 * 64 + 8, generator=g(5))
+    E = engine()
+    x = torch.randn(37, 3 * 64 + 8, generator=H.gen(5))
     a, b = x.to(device), x.to(device)
     E.check(lib.kd_l2norm_heads(E.ptr(a), 200, 37, 3, None, E.current_stream()))
     E.check(lib.kd_l2norm_heads_d(E.ptr(b), 200, 37, 3, 64, None, E.current_stream()))
@@ -385,49 +311,8 @@ BASE = dict(dim=32, dim_mults=(1, 2, 4), num_resnet_blocks=1, layer_attns=(False
             layer_cross_attns=(False, True, True), attn_heads=4)
 TEXT = dict(dim=32, dim_mults=(1, 2, 4), cond_dim=64, text_embed_dim=3, num_resnet_blocks=1, layer_attns=(False, True, True),
             layer_cross_attns=(False, True, True))   # tests/test_combine_fmaps_gpu.py
+_ref_unet = functools.partial(H.ref_unet, R.Unet)
 
-
-def _ref_unet(kw, seed, text=False, **extra):
-    tk = dict(cond_on_text=True) if text else dict(cond_on_text=False, text_embed_dim=None)
-    return H.randomize_(R.Unet(**{**kw, **tk, **extra}), seed).eval()
-
-
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
-def _unet_inputs(ou, B, S, seed):
-    gen = g(seed)
-    x = torch.randn(B, 3, S, S, generator=gen)
-    t = torch.randn(B, generator=gen) * 3
-    kw = {}
-    if ou.lowres_cond:
-        kw.update(lowres_cond_img=torch.randn(B, 3, S, S, generator=gen), lowres_noise_times=torch.full((B,), 1.5))
-    if ou.cond_on_text:
-        kw["text_embeds"] = torch.randn(B, 2, 3, generator=gen)
-    return x, t, kw
-
-
-def _forward_err(ou, device, B=2, S=32, seed=3):
-    pu = _product_like(ou, device)
-    x, t, kw = _unet_inputs(ou, B, S, seed)
-    with torch.no_grad():
-        ref = ou(x, t, **kw)
-    dv = {k: v.to(device) for k, v in kw.items()}
-    got = pu(x.to(device), t.to(device), **dv).cpu()
-    assert torch.equal(got, pu(x.to(device), t.to(device), **dv).cpu())   # no atomics: run-to-run bit-identical
-    return H.rel_l2(got, ref), pu
-
-
-def _labels(pu, B, S, device, with_text=False):
-    E = _E()
-    buf = C.create_string_buffer(1 << 20)
-    E.check(E.load().kd_unet_profile(pu.engine(B, S, device, with_text=with_text), 1, buf, len(buf), E.current_stream()))
-    return buf.value.decode()
 
 
 @pytest.mark.parametrize("name,kw,extra", [
@@ -441,10 +326,10 @@ def _labels(pu, B, S, device, with_text=False):
 ], ids=lambda v: v if isinstance(v, str) else "")
 def test_unet_forward_matches_the_oracle(device, name, kw, extra):
     ou = _ref_unet(kw, seed=11, **extra)
-    e, pu = _forward_err(ou, device)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"forward {name}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, 2, 32, device)
+    labels = H.plan_csv(pu, 2, 32, device)
     depths = pu._plan["layer_attns_depth"]
     # self-attention launches: the down and the up block of the two levels, mid_attn
     assert len(re.findall(r"(?<![a-z])attn N\d+", labels)) == 2 * (depths[1] + depths[2]) + 1
@@ -453,7 +338,7 @@ def test_unet_forward_matches_the_oracle(device, name, kw, extra):
 @pytest.mark.parametrize("D", DS)
 def test_unet_forward_with_text_runs_the_perceiver_and_the_cross_attention_at_d(device, D):
     ou = _ref_unet(TEXT, seed=15, text=True, attn_dim_head=D, layer_attns_depth=(1, 1, 2))
-    e, _ = _forward_err(ou, device)
+    e, _ = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"forward text D{D}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
 
@@ -466,7 +351,7 @@ def test_unet_forward_with_qk_norm(device, D, mode):
     ou = _ref_unet(TEXT, seed=19 + mode, text=True, attn_dim_head=D, attn_qk_norm=mode, layer_attns_depth=(1, 2, 1))
     if mode == 2:
         assert tuple(ou.state_dict()["downs.1.3.layers.1.0.q_scale"].shape) == (D,)
-    e, pu = _forward_err(ou, device)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     assert pu.attn_qk_norm == mode
     print(f"forward text D{D} qk-norm {mode}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
@@ -484,10 +369,10 @@ def test_depth_adds_the_further_layers_macs_and_launches(device):
     """Depth 2 and (1, 2, 3) against depth 1 on the same config: kd_unet_macs grows by exactly the further layers' MACs, and
     the launch count grows with them (a plan that ran layer 0 twice would also pass this - the forward tests, whose layers.1
     weights differ from layers.0's, would not)."""
-    lib = _E().load()
+    lib = engine().load()
     stats = {}
     for dep in (1, 2, (1, 2, 3)):
-        pu = _product_like(_ref_unet(BASE, seed=5, layer_attns_depth=dep), device)
+        pu = H.product_like(_ref_unet(BASE, seed=5, layer_attns_depth=dep), device)
         h = pu.engine(2, 32, device, with_text=False)
         stats[dep] = (lib.kd_unet_macs(h), lib.kd_unet_num_launches(h))
     B, H_, D, Nc, cd = 2, 4, 64, 2, 32
@@ -505,14 +390,14 @@ def test_depth_adds_the_further_layers_macs_and_launches(device):
 def test_default_unet_through_create_ext3_keeps_its_plan(device):
     """A D = 64, depth-1 UNet through kd_unet_create_ext3 with ext3 = NULL, with all-zero and with all-one depths: the
     launches and the bits of the plan kd_unet_create_ext2 builds (the entry Unet.engine() takes for such a UNet)."""
-    lib = _E().load()
-    ou = H.randomize_(R.Unet(**H.UNET_KW["small2"], lowres_cond=True, cond_on_text=False, text_embed_dim=None), 4).eval()
-    gen = g(5)
+    lib = engine().load()
+    ou = _ref_unet(H.UNET_KW["small2"], seed=4, lowres_cond=True)
+    gen = H.gen(5)
     x, t = torch.randn(2, 3, 32, 32, generator=gen), torch.randn(2, generator=gen)
     kw = dict(lowres_cond_img=torch.randn(2, 3, 32, 32, generator=gen), lowres_noise_times=torch.full((2,), 1.5),
               cond_images=torch.rand(2, 3, 32, 32, generator=gen))
     dv = {k: v.to(device) for k, v in kw.items()}
-    E = _E()
+    E = engine()
     ones = E.kd_unet_ext3_t()
     for i in range(E.KD_MAX_LEVELS):
         ones.layer_attns_depth[i] = 1
@@ -527,7 +412,7 @@ def test_default_unet_through_create_ext3_keeps_its_plan(device):
     }
     res = {}
     for name, fn in forms.items():
-        pu = _product_like(ou, device)
+        pu = H.product_like(ou, device)
         lib.kd_unet_create_ext2 = lambda *a, fn=fn, name=name: (seen.append(name), fn(*a))[1]
         try:
             h = pu.engine(2, 32, device, with_text=False)
@@ -542,32 +427,23 @@ def test_default_unet_through_create_ext3_keeps_its_plan(device):
 
 def test_engine_refuses_what_python_refuses(device):
     """The plan builder's own refusals, reached past the Python checks: dim_head 48, and a depth on a linear-attention level."""
-    pu = _product_like(_ref_unet(BASE, seed=1), device)
+    pu = H.product_like(_ref_unet(BASE, seed=1), device)
     pu._plan["attn_dim_head"] = 48
-    with pytest.raises(_E().EngineError, match="32, 64 and 128"):
+    with pytest.raises(engine().EngineError, match="32, 64 and 128"):
         pu.engine(2, 32, device, with_text=False)
     import imagen_pytorch as ip
 
-    lu = ip.Unet(**{**BASE, "layer_attns": (False, False, True)}, use_linear_attn=True, cond_on_text=False, text_embed_dim=None).to(device)
+    lu = ip.Unet(**{**BASE, "layer_attns": (False, False, True)}, use_linear_attn=True, **H.NOTEXT).to(device)
     lu._plan["layer_attns_depth"] = (1, 2, 1)
-    with pytest.raises(_E().EngineError, match="linear-attention level"):
+    with pytest.raises(engine().EngineError, match="linear-attention level"):
         lu.engine(2, 32, device, with_text=False)
 
 
 # ------------------------------------------------------------------------------------------------ sampling
-def _pair(device, cls_o, cls_p, unets, sizes, **kw):
-    import imagen_pytorch as ip
-
-    oim = cls_o(unets, image_sizes=sizes, **kw)
-    pim = getattr(ip, cls_p)([ip.Unet(**u._locals) for u in oim.unets], image_sizes=sizes, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
-
-
 def test_ddpm_text_guided_sampling_matches_the_oracle_and_graph_equals_eager(device):
     """Three DDPM steps with cond_scale = 3 on the text config at D = 128, depths (1, 2, 1)."""
     ou = _ref_unet(TEXT, seed=17, text=True, attn_dim_head=128, layer_attns_depth=(1, 2, 1))
-    oim, pim = _pair(device, RS.Imagen, "Imagen", [ou], (32,), timesteps=(3,), text_embed_dim=3)
+    oim, pim = H.imagen_pair(device, RS.Imagen, "Imagen", [ou], image_sizes=(32,), timesteps=(3,), text_embed_dim=3)
     text = torch.tensor([[0.0, 0.5, 0.2], [0.3, -0.4, 0.9]]).reshape(2, 1, 3)
     nf = RS.generator_noise_fn(5)
     ref = oim.sample(noise_fn=nf, text_embeds=text, cond_scale=3.0)
@@ -581,8 +457,8 @@ def test_ddpm_text_guided_sampling_matches_the_oracle_and_graph_equals_eager(dev
 def test_ddpm_inpainting_matches_the_oracle_and_graph_equals_eager(device):
     """Three DDPM steps with inpainting, 2 resamples, at D = 32, depth 2."""
     ou = _ref_unet(BASE, seed=21, attn_dim_head=32, layer_attns_depth=2)
-    oim, pim = _pair(device, RS.Imagen, "Imagen", [ou], (32,), timesteps=(3,), condition_on_text=False)
-    gen = g(3)
+    oim, pim = H.imagen_pair(device, RS.Imagen, "Imagen", [ou], image_sizes=(32,), timesteps=(3,), condition_on_text=False)
+    gen = H.gen(3)
     inp = torch.rand(2, 3, 32, 32, generator=gen)
     mask = torch.zeros(2, 32, 32, dtype=torch.bool)
     mask[:, 4:20, 6:30] = True
@@ -600,7 +476,8 @@ def test_ddpm_inpainting_matches_the_oracle_and_graph_equals_eager(device):
 def test_edm_sampling_matches_the_restatement_and_graph_equals_eager(device):
     """ElucidatedImagen, N = 3, at D = 128, depth (1, 1, 2)."""
     ou = _ref_unet(BASE, seed=23, attn_dim_head=128, layer_attns_depth=(1, 1, 2))
-    oim, pim = _pair(device, ER.ElucidatedImagen, "ElucidatedImagen", [ou], (32,), condition_on_text=False, num_sample_steps=3)
+    oim, pim = H.imagen_pair(device, ER.ElucidatedImagen, "ElucidatedImagen", [ou], image_sizes=(32,), condition_on_text=False,
+                             num_sample_steps=3)
     nf = RS.generator_noise_fn(13)
     ref = oim.sample(noise_fn=nf, batch_size=2)
     got = pim.sample(noise_fn=nf, batch_size=2, device=device)

@@ -18,17 +18,6 @@ pytestmark = pytest.mark.gpu
 CONV_REL = 2e-6      # as test_kernels_gpu.py / test_self_cond_gpu.py
 FWD_REL_L2 = 2e-5
 SAMPLE_ABS = 2e-3
-NOTEXT = dict(cond_on_text=False, text_embed_dim=None)
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 # ------------------------------------------------------------------------------- the init conv kernel
@@ -43,17 +32,17 @@ INIT_PLANES = [(1, False), (2, False), (4, False), (1, True), (2, True), (4, Tru
 
 def _init_conv_case(device, B, S, n3, n7, n15, Cx, with_sc, with_res):
     """(rc, got NCHW on the CPU, fp64 reference, its three parts, the added term, fp32 CPU error)"""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     NP = 2 * Cx if with_sc else Cx
     c0, C_out = 2, n3 + n7 + n15
     Itot = c0 + NP + Cx          # cond (2) | x | (self_cond) | lowres: the planes sit at channel offset 2
-    x = torch.randn(B, Cx, S, S, generator=_g(1))
-    sc = torch.rand(B, Cx, S, S, generator=_g(2)) * 2 - 1 if with_sc else None
-    ws = [torch.randn(n, Itot, k, k, generator=_g(10 + k)) * (NP * k * k) ** -0.5 for n, k in ((n3, 3), (n7, 7), (n15, 15))]
+    x = torch.randn(B, Cx, S, S, generator=H.gen(1))
+    sc = torch.rand(B, Cx, S, S, generator=H.gen(2)) * 2 - 1 if with_sc else None
+    ws = [torch.randn(n, Itot, k, k, generator=H.gen(10 + k)) * (NP * k * k) ** -0.5 for n, k in ((n3, 3), (n7, 7), (n15, 15))]
     inp = torch.cat((x, sc), 1) if with_sc else x
-    res = torch.randn(B, S, S, C_out, generator=_g(5)) if with_res else None
-    b = None if with_res else torch.randn(C_out, generator=_g(4))
+    res = torch.randn(B, S, S, C_out, generator=H.gen(5)) if with_res else None
+    b = None if with_res else torch.randn(C_out, generator=H.gen(4))
     add = (res.permute(0, 3, 1, 2) if with_res else b[None, :, None, None])
     parts64 = [F.conv2d(inp.double(), w[:, c0:c0 + NP].double(), padding=w.shape[-1] // 2) for w in ws]
     ref = torch.cat(parts64, 1) + add.double()
@@ -75,7 +64,7 @@ def test_init_conv_c_planes(device, B, S, n3, n7, n15, Cx, with_sc, with_res):
     """The per-step share of the init convs over C | 2 C planes at input channels 2 .. of wider weights, + bias or + a
     step-invariant residual, in one launch, against torch conv2d in fp64.  8 planes at dim 128 do not fit the kernel's
     LDS even as a ring (161.3 KiB): the entry refuses them before any launch, as the plan does (generic path)."""
-    E = _E()
+    E = H.engine()
     rc, got, ref, parts64, add, err_cpu = _init_conv_case(device, B, S, n3, n7, n15, Cx, with_sc, with_res)
     if Cx == 4 and with_sc and n3 == 64:
         assert rc != 0 and b"LDS" in E.load().kd_last_error()
@@ -93,12 +82,12 @@ def test_init_conv_c_planes(device, B, S, n3, n7, n15, Cx, with_sc, with_res):
 
 def test_init_conv_old_entry_is_the_three_channel_form(device):
     """kd_init_conv_planes_nchw (signature unchanged) == kd_init_conv_planes_c_nchw with channels = 3, bit for bit."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     B, S, n3, n7, n15, Itot, c0 = 1, 32, 16, 8, 8, 8, 2
-    x = torch.randn(B, 3, S, S, generator=_g(1)).to(device)
-    ws = [(torch.randn(n, Itot, k, k, generator=_g(k)) * (3 * k * k) ** -0.5).to(device) for n, k in ((n3, 3), (n7, 7), (n15, 15))]
-    b = torch.randn(n3 + n7 + n15, generator=_g(4)).to(device)
+    x = torch.randn(B, 3, S, S, generator=H.gen(1)).to(device)
+    ws = [(torch.randn(n, Itot, k, k, generator=H.gen(k)) * (3 * k * k) ** -0.5).to(device) for n, k in ((n3, 3), (n7, 7), (n15, 15))]
+    b = torch.randn(n3 + n7 + n15, generator=H.gen(4)).to(device)
     ys = [torch.full((B, S, S, n3 + n7 + n15), float("nan"), device=device) for _ in range(2)]
     E.check(lib.kd_init_conv_planes_nchw(E.ptr(x), None, E.ptr(ws[0]), E.ptr(ws[1]), E.ptr(ws[2]), Itot, c0, E.ptr(b), None,
                                          E.ptr(ys[0]), B, S, n3, n7, n15, 1, None, E.current_stream()))
@@ -111,7 +100,7 @@ def test_init_conv_old_entry_is_the_three_channel_form(device):
 def test_init_conv_generic_path_sees_c_planes(device, Cx):
     """48 px: a size the fused kernel refuses (S % 32 != 0) - its entry says so - and the plan's generic path (the C planes
     packed to 4-channel pixels, three implicit-GEMM convs with their biases) carries the forward of a base UNet."""
-    E = _E()
+    E = H.engine()
     rc, got, *_ = _init_conv_case(device, 1, 48, 16, 8, 8, Cx, False, False)
     assert rc != 0 and b"init conv kernel" in E.load().kd_last_error() and torch.isnan(got).all()
     e = _forward_err(device, "small1", Cx, False, 2, 48, seed=31)
@@ -126,7 +115,7 @@ def _final_inputs(B, H_, W, Cfeat):
     """One set of inputs per shape, shared by the channel cases (4 channels, the narrower cases take the first C)."""
     key = (B, H_, W, Cfeat)
     if key not in _FINAL_REF:
-        g = _g(7)
+        g = H.gen(7)
         _FINAL_REF[key] = dict(feat=torch.randn(B, H_, W, Cfeat, generator=g), lowres=torch.randn(B, 4, H_, W, generator=g),
                                w=torch.randn(4, Cfeat + 4, 3, 3, generator=g) * (9 * Cfeat) ** -0.5,
                                bias=torch.randn(4, generator=g))
@@ -142,7 +131,7 @@ def _final_inputs(B, H_, W, Cfeat):
 def test_final_conv(device, B, H_, W, Cfeat, Cx, with_lowres):
     """kd_final_conv_nchw: the plan's launches (pack, 1x1 GEMM to 9 C columns, the low-res planes' share, gather)
     against torch conv2d over cat(feat, lowres) in fp64."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     d = _final_inputs(B, H_, W, Cfeat)
     feat, bias = d["feat"], d["bias"][:Cx].contiguous()
@@ -173,37 +162,18 @@ ULTRA2 = dict(dim=128, dim_mults=(1, 2, 4, 8), num_resnet_blocks=2, memory_effic
               init_conv_to_final_conv_residual=True, cond_images_channels=3)   # train_ultra_res.py:39-48
 
 
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
 def _forward_err(device, name, Cx, lowres, B, S, seed, self_cond=False, fast=False):
     kw = ULTRA2 if name == "ultra2_full" else H.UNET_KW[name]
     cls = SR.Unet if self_cond else R.Unet
     extra = dict(self_cond=True) if self_cond else {}
-    ou = H.randomize_(cls(**kw, channels=Cx, lowres_cond=lowres, **extra, **NOTEXT), seed).eval()
+    ou = H.ref_unet(cls, kw, seed=seed, channels=Cx, lowres_cond=lowres, **extra)
     if fast:
         ou = H.fast_oracle(ou)
-    pu = _product_like(ou, device)
-    g = _g(3)
-    x = torch.randn(B, Cx, S, S, generator=g)
-    t = torch.randn(B, generator=g) * 3
-    kw_in = {}
-    if lowres:
-        kw_in.update(lowres_cond_img=torch.randn(B, Cx, S, S, generator=g), lowres_noise_times=torch.full((B,), 1.5))
-    if ou.has_cond_image:
-        kw_in["cond_images"] = torch.rand(B, 3, S, S, generator=g)
-    if self_cond:
-        kw_in["self_cond"] = torch.rand(B, Cx, S, S, generator=g) * 2 - 1
-    with torch.no_grad():
-        ref = ou(x, t, **kw_in)
+    x, t, kw_in = H.unet_inputs(ou, B, S, seed=3)
+    e, pu = H.forward_err(ou, device, x, t, kw_in)
+    # (the bits forward_err compared: its two runs were identical)
     got = pu(x.to(device), t.to(device), **{k: v.to(device) for k, v in kw_in.items()}).cpu()
     assert got.shape == (B, Cx, S, S) and torch.isfinite(got).all()
-    e = H.rel_l2(got, ref)
     print(f"forward {name} C={Cx} S={S} self_cond={self_cond}: rel-L2 {e:.2e}")
     return e
 
@@ -230,33 +200,27 @@ def test_full_width_unet_forward_of_four_channels_matches_the_oracle(device):
 def test_plans_of_every_channel_count_have_the_same_launches(device, S):
     """A channel count that fell to the generic init conv (three convs + a pack) at 32 px would show here; at 48 px every
     count runs the generic path."""
-    lib = _E().load()
+    lib = H.engine().load()
     counts = {}
     for Cx in (3, 1, 2, 4):
-        ou = R.Unet(**H.UNET_KW["small2"], channels=Cx, lowres_cond=True, **NOTEXT)
-        h = _product_like(ou, device).engine(2, S, device, with_text=False)
+        ou = R.Unet(**H.UNET_KW["small2"], channels=Cx, lowres_cond=True, **H.NOTEXT)
+        h = H.product_like(ou, device).engine(2, S, device, with_text=False)
         counts[Cx] = lib.kd_unet_num_launches(h)
     assert counts[1] == counts[2] == counts[4] == counts[3], counts
 
 
 # ------------------------------------------------------------------------------- sampling
 def _pair(device, names, sizes, channels, cls=(RS.Imagen, "Imagen"), seed=5, **kw):
-    import imagen_pytorch as ip
-
     ous = [R.NullUnet() if n is None else H.randomize_(
-        R.Unet(**H.UNET_KW[n], channels=channels, lowres_cond=i > 0, **NOTEXT), seed + i) for i, n in enumerate(names)]
-    oim = cls[0](ous, image_sizes=sizes, channels=channels, condition_on_text=False, **kw)
-    pus = [ip.NullUnet() if isinstance(u, R.NullUnet) else ip.Unet(**u._locals) for u in oim.unets]
-    pim = getattr(ip, cls[1])(pus, image_sizes=sizes, channels=channels, condition_on_text=False, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+        R.Unet(**H.UNET_KW[n], channels=channels, lowres_cond=i > 0, **H.NOTEXT), seed + i) for i, n in enumerate(names)]
+    return H.imagen_pair(device, *cls, ous, image_sizes=sizes, channels=channels, condition_on_text=False, **kw)
 
 
 def test_grayscale_cascade_with_dynamic_thresholding_matches_the_oracle(device):
     """C = 1, small1 -> small2 at (32, 64), T = 4, batch 2, dynamic thresholding in both stages: the quantile runs over
     C H W = H W values.  The thresholds of one step (kd_sample_last, which = 2) against the oracle's own: the sample is
     x0 / s, so the relative error of s is held to the bound of the samples."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     oim, pim = _pair(device, ["small1", "small2"], (32, 64), 1, timesteps=(4, 4), pred_objectives=("noise", "v"),
                      dynamic_thresholding=(True, True))
@@ -266,7 +230,7 @@ def test_grayscale_cascade_with_dynamic_thresholding_matches_the_oracle(device):
     got1 = pim.sample(noise_fn=nf, batch_size=B, stop_at_unet_number=1, device=device).cpu()
     assert got1.shape == (B, 1, 32, 32)
     e1 = float((got1 - ref1).abs().max())
-    cond = torch.rand(B, 3, 64, 64, generator=_g(2))
+    cond = torch.rand(B, 3, 64, 64, generator=H.gen(2))
     kw = dict(batch_size=B, start_at_unet_number=2)
     ref2 = oim.sample(noise_fn=nf, start_image_or_video=ref1, cond_images=cond, **kw)
     got2 = pim.sample(noise_fn=nf, start_image_or_video=ref1.to(device), cond_images=cond.to(device), device=device, **kw).cpu()
@@ -283,7 +247,7 @@ def test_grayscale_cascade_with_dynamic_thresholding_matches_the_oracle(device):
     sc.T = T
     for name, v in tables.items():
         setattr(sc, name, v.numpy().ctypes.data_as(C_.POINTER(C_.c_float)))
-    x = torch.randn(B, 1, S, S, generator=_g(6)) * 1.5
+    x = torch.randn(B, 1, S, S, generator=H.gen(6)) * 1.5
     sa = E.kd_sample_args_t()
     sa.objective, sa.dynamic_threshold, sa.percentile, sa.resample_times, sa.seed, sa.use_graph = 0, 1, 0.95, 1, 9, 1
     xd = x.to(device)
@@ -305,7 +269,7 @@ def test_four_channel_sr_stage_with_inpainting_matches_the_oracle(device):
     broadcast over the 4 channels, whose known pixels come back bit-exact."""
     oim, pim = _pair(device, [None, "small2"], (32, 64), 4, timesteps=(4, 4), pred_objectives=("noise", "v"))
     B = 2
-    g = _g(8)
+    g = H.gen(8)
     start = torch.rand(B, 4, 32, 32, generator=g)
     cond = torch.rand(B, 3, 64, 64, generator=g)
     inp = torch.rand(B, 4, 64, 64, generator=g)
@@ -338,9 +302,9 @@ def test_two_channel_elucidated_sampling_matches_the_restatement(device):
 
 def test_grayscale_graph_replay_equals_eager_launches(device):
     _, pim = _pair(device, [None, "small2"], (16, 32), 1, timesteps=(4, 4))
-    start = torch.rand(2, 1, 16, 16, generator=_g(1)).to(device)
+    start = torch.rand(2, 1, 16, 16, generator=H.gen(1)).to(device)
     kw = dict(noise_fn=RS.generator_noise_fn(7), batch_size=2, start_at_unet_number=2, start_image_or_video=start,
-              cond_images=torch.rand(2, 3, 32, 32, generator=_g(2)).to(device), device=device)
+              cond_images=torch.rand(2, 3, 32, 32, generator=H.gen(2)).to(device), device=device)
     a = pim.sample(use_graph=True, **kw)
     b = pim.sample(use_graph=False, **kw)
     assert a.shape == (2, 1, 32, 32) and torch.isfinite(a).all() and torch.equal(a, b)

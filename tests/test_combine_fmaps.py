@@ -2,6 +2,7 @@
 against the restatement in tests/combine_fmaps_ref.py, strict loading both ways, the new config struct and symbols, the
 class decomposition the kernel's weight pack rests on, and the new kernel file's resource usage."""
 import ctypes as C
+import functools
 import re
 import shutil
 import subprocess
@@ -19,18 +20,11 @@ KW = dict(dim=32, dim_mults=(1, 2, 4), num_resnet_blocks=1, layer_attns=(False, 
           layer_cross_attns=(False, False, True), cond_on_text=False, text_embed_dim=None)
 
 
-def _product(seed=0, **over):
-    import imagen_pytorch as ip
-
-    return H.randomize_(ip.Unet(**{**KW, **over}), seed)
+_product = functools.partial(H.random_product_unet, **KW)   # _product(seed=0, **over)
 
 
 def _ref(seed=0, **over):
     return H.randomize_(CR.Unet(**{**KW, **over}), seed)
-
-
-def _layout(sd):
-    return {k: tuple(v.shape) for k, v in sd.items()}
 
 
 # ------------------------------------------------------------------------------- state dict and constructor
@@ -40,7 +34,7 @@ def test_state_dict_layout_equals_the_restatement_and_round_trips(mem, init_res)
     over = dict(combine_upsample_fmaps=True, memory_efficient=mem, init_conv_to_final_conv_residual=init_res)
     p, r = _product(seed=1, **over), _ref(seed=2, **over)
     sp = p.state_dict()
-    assert _layout(sp) == _layout(r.state_dict())
+    assert H.state_layout(sp) == H.state_layout(r.state_dict())
     # up level i (deepest first) works at dims[L - i] = 128, 64, 32 channels; Block's own 8 groups
     for i, cin in enumerate((128, 64, 32)):
         pre = f"upsample_combiner.fmap_convs.{i}"
@@ -68,8 +62,8 @@ def test_default_unet_is_unchanged():
     for mem in (False, True):
         over = dict(memory_efficient=mem, init_conv_to_final_conv_residual=mem)
         d = _product(**over)
-        assert _layout(d.state_dict()) == _layout(R.Unet(**{**KW, **over}).state_dict())
-        assert _layout(d.state_dict()) == _layout(_product(combine_upsample_fmaps=False, **over).state_dict())
+        assert H.state_layout(d.state_dict()) == H.state_layout(R.Unet(**{**KW, **over}).state_dict())
+        assert H.state_layout(d.state_dict()) == H.state_layout(_product(combine_upsample_fmaps=False, **over).state_dict())
         assert not any(k.startswith("upsample_combiner") for k in d.state_dict())
         assert d._plan["combine_upsample_fmaps"] is False and not hasattr(d, "upsample_combiner")
     assert _product(combine_upsample_fmaps=True)._plan["combine_upsample_fmaps"] is True

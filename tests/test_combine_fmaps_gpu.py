@@ -2,7 +2,7 @@
 kernels_upcombine.hip against fp64 torch, the UNet forward and both samplers against the restatement in
 tests/combine_fmaps_ref.py, graph / eager bit identity, a default UNet's plan through kd_unet_create_ext2, and a strict
 ImagenTrainer.load."""
-import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -22,16 +22,6 @@ SAMPLE_ABS = 2e-3
 COMBINE = dict(combine_upsample_fmaps=True)
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 # ------------------------------------------------------------------------------- the kernel
 SHAPES = [(2, 3, 5, 32, 64, 4),     # partial tile both ways; every border class
           (1, 1, 1, 16, 32, 4),     # every neighbour tap is padding
@@ -47,9 +37,9 @@ def test_upsample_nearest_gn_conv3x3_matches_fp64(device, B, Hh, Ww, Cin, Cout, 
     raw map and [B][Cin][2] = (A, B) kd_wf_ab_scale() of GroupNorm(8) from the LOW-RES statistics (kd_gn_fold_seg's form);
     without it, the map already activated at low resolution.  beta is random, so SiLU(B) != 0 where a tap is padding.
     Dense, and into channels [0, Cout) and [32, 32 + Cout) of rows of Cout + 32 floats whose other channels must stay."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
-    g = _g(Hh * Ww + Cin + s)
+    g = H.gen(Hh * Ww + Cin + s)
     x = torch.randn(B, Hh, Ww, Cin, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) * (9 * Cin) ** -0.5
     bias = torch.randn(Cout, generator=g)
@@ -104,49 +94,7 @@ TEXT = dict(dim=32, dim_mults=(1, 2, 4), cond_dim=64, text_embed_dim=3, num_resn
             layer_cross_attns=(False, True, True))
 
 
-def _ref_unet(kw, lowres=False, seed=0, text=False, **extra):
-    tk = dict(cond_on_text=True) if text else dict(cond_on_text=False, text_embed_dim=None)
-    return H.randomize_(CR.Unet(**{**kw, **tk, **COMBINE, **extra}, lowres_cond=lowres), seed).eval()
-
-
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
-def _inputs(ou, B, S, seed):
-    g = _g(seed)
-    x = torch.randn(B, 3, S, S, generator=g)
-    t = torch.randn(B, generator=g) * 3
-    kw = {}
-    if ou.lowres_cond:
-        kw.update(lowres_cond_img=torch.randn(B, 3, S, S, generator=g), lowres_noise_times=torch.full((B,), 1.5))
-    if ou.self_cond:
-        kw["self_cond"] = torch.rand(B, 3, S, S, generator=g) * 2 - 1
-    if ou.cond_on_text:
-        kw["text_embeds"] = torch.randn(B, 2, 3, generator=g)
-    return x, t, kw
-
-
-def _forward_err(ou, device, B, S, seed=3):
-    pu = _product_like(ou, device)
-    x, t, kw = _inputs(ou, B, S, seed)
-    with torch.no_grad():
-        ref = ou(x, t, **kw)
-    dv = {k: v.to(device) for k, v in kw.items()}
-    got = pu(x.to(device), t.to(device), **dv).cpu()
-    assert torch.equal(got, pu(x.to(device), t.to(device), **dv).cpu())   # no atomics: run-to-run bit-identical
-    return H.rel_l2(got, ref), pu
-
-
-def _labels(pu, B, S, device, with_text=False):
-    E = _E()
-    buf = C.create_string_buffer(1 << 20)
-    E.check(E.load().kd_unet_profile(pu.engine(B, S, device, with_text=with_text), 1, buf, len(buf), E.current_stream()))
-    return buf.value.decode()
+_ref_unet = functools.partial(H.ref_unet, CR.Unet, **COMBINE)
 
 
 @pytest.mark.parametrize("B", [2, 3])
@@ -156,10 +104,10 @@ def test_unet_forward_matches_the_restatement(device, mem, B):
     memory_efficient (with the init conv residual behind the combiner's slices): 4, 8, 16 px - scales 8, 4, 2, and the last
     upsample writes x's channels of the concat in place."""
     ou = _ref_unet(SMALL, seed=11, memory_efficient=mem, init_conv_to_final_conv_residual=mem)
-    e, pu = _forward_err(ou, device, B, 32)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, B, 32, seed=3))
     print(f"combine forward mem={mem} B={B}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, B, 32, device)
+    labels = H.plan_csv(pu, B, 32, device)
     assert labels.count("upsample combine s=") == (3 if mem else 2)
     for s in ((8, 4, 2) if mem else (4, 2)):
         assert labels.count(f"upsample combine s={s} ") == 1
@@ -173,10 +121,10 @@ def test_unet_forward_with_an_attention_block_as_the_last_producer(device, outer
     kw = dict(SMALL, layer_attns=(outer == "attention", False, True))
     extra = dict(use_linear_attn=(True, False, False)) if outer == "linear_attention" else {}
     ou = _ref_unet(kw, seed=17, init_conv_to_final_conv_residual=True, **extra)
-    e, pu = _forward_err(ou, device, 2, 32)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"combine forward, {outer} at the outermost level: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, 2, 32, device)
+    labels = H.plan_csv(pu, 2, 32, device)
     assert labels.count("upsample combine s=") == 2 and "combine head" not in labels
 
 
@@ -186,10 +134,10 @@ def test_unet_forward_dim128_folds_the_partials_to_the_affine(device):
     launches take the gn_fold_seg affine (rows ending in "affine"); the attention level's map (512 channels, a token GEMM's
     output without partials) goes through GroupNorm + SiLU at low resolution."""
     ou = _ref_unet(WIDE, seed=12, memory_efficient=True)
-    e, pu = _forward_err(ou, device, 2, 64)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 64, seed=3))
     print(f"combine forward dim128 mem B=2: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, 2, 64, device)
+    labels = H.plan_csv(pu, 2, 64, device)
     rows = [r for r in labels.splitlines() if "upsample combine s=" in r]
     print("\n".join(rows))
     assert len(rows) == 3
@@ -198,8 +146,8 @@ def test_unet_forward_dim128_folds_the_partials_to_the_affine(device):
 
 
 def test_unet_forward_with_text_lowres_and_self_cond_matches_the_restatement(device):
-    ou = _ref_unet(TEXT, lowres=True, seed=15, text=True, self_cond=True)
-    e, _ = _forward_err(ou, device, 2, 32)
+    ou = _ref_unet(TEXT, lowres_cond=True, seed=15, text=True, self_cond=True)
+    e, _ = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"combine forward text + lowres + self_cond: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
 
@@ -207,22 +155,22 @@ def test_unet_forward_with_text_lowres_and_self_cond_matches_the_restatement(dev
 def test_unet_forward_with_both_resampling_switches_and_linear_attention(device):
     ou = _ref_unet(SMALL, seed=16, memory_efficient=True, init_conv_to_final_conv_residual=True, cross_embed_downsample=True,
                    pixel_shuffle_upsample=False, use_linear_attn=True)
-    e, pu = _forward_err(ou, device, 2, 32)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"combine forward cross-embed + nearest upsample + linear attention: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, 2, 32, device)
+    labels = H.plan_csv(pu, 2, 32, device)
     assert labels.count("upsample combine s=") == 3 and labels.count("upsample nearest conv3") == 3
 
 
 def test_default_unet_through_create_ext2_keeps_its_plan(device):
     """A default UNet built through kd_unet_create_ext2 with a zero ext2 has the launches and the bits of the plan
     kd_unet_create_ext builds."""
-    lib = _E().load()
+    lib = H.engine().load()
     from oracle import imagen_ref as R
 
-    ou = H.randomize_(R.Unet(**H.UNET_KW["small2"], lowres_cond=True, cond_on_text=False, text_embed_dim=None), 4).eval()
-    a, b = _product_like(ou, device), _product_like(ou, device)
-    g = _g(5)
+    ou = H.ref_unet(R.Unet, H.UNET_KW["small2"], seed=4, lowres_cond=True)
+    a, b = H.product_like(ou, device), H.product_like(ou, device)
+    g = H.gen(5)
     x, t = torch.randn(2, 3, 32, 32, generator=g), torch.randn(2, generator=g)
     kw = dict(lowres_cond_img=torch.randn(2, 3, 32, 32, generator=g), lowres_noise_times=torch.full((2,), 1.5),
               cond_images=torch.rand(2, 3, 32, 32, generator=g))
@@ -238,7 +186,7 @@ def test_default_unet_through_create_ext2_keeps_its_plan(device):
     assert called
     assert lib.kd_unet_num_launches(ha) == lib.kd_unet_num_launches(hb)
     assert torch.equal(a(x.to(device), t.to(device), **dv), b(x.to(device), t.to(device), **dv))
-    assert "upsample combine" not in _labels(a, 2, 32, device)
+    assert "upsample combine" not in H.plan_csv(a, 2, 32, device)
 
 
 # ------------------------------------------------------------------------------- sampling
@@ -248,20 +196,16 @@ SR2 = dict(dim=32, dim_mults=(1, 2), num_resnet_blocks=1, memory_efficient=True,
 
 
 def _cascade(device, cls_o, cls_p, seed, **kw):
-    import imagen_pytorch as ip
-
-    ous = [_ref_unet(BASE, seed=seed), _ref_unet(SR2, lowres=True, seed=seed + 1)]
-    oim = cls_o(ous, image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim = getattr(ip, cls_p)([ip.Unet(**u._locals) for u in oim.unets], image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
+    ous = [_ref_unet(BASE, seed=seed), _ref_unet(SR2, lowres_cond=True, seed=seed + 1)]
+    oim, pim = H.imagen_pair(device, cls_o, cls_p, ous, image_sizes=(32, 64), condition_on_text=False, **kw)
     assert all(u.combine_upsample_fmaps for u in pim.unets)
-    return oim, pim.to(device)
+    return oim, pim
 
 
 def test_ddpm_cascade_with_inpainting_matches_the_restatement(device):
     oim, pim = _cascade(device, SR.Imagen, "Imagen", 21, timesteps=(4, 4), pred_objectives=("noise", "v"))
     B = 2
-    g = _g(3)
+    g = H.gen(3)
     inp = torch.rand(B, 3, 64, 64, generator=g)
     mask = torch.zeros(B, 64, 64, dtype=torch.bool)
     mask[:, 8:40, 12:60] = True

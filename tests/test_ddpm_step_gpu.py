@@ -20,22 +20,16 @@ N = B * 3 * S * S
 OBJ = {"noise": 0, "v": 1, "x_start": 2}
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
 @pytest.fixture(scope="module")
 def plan(device):
-    pu = H.product_unet_like(H.oracle_unet("small1", seed=4)).to(device)
+    pu = H.product_like(H.oracle_unet("small1", seed=4), device)
     return pu, pu.engine(B, S, device, with_text=False)
 
 
 def _schedule(T):
     from imagen_pytorch.imagen_pytorch import GaussianDiffusionContinuousTimes
 
-    E = _E()
+    E = H.engine()
     tables = GaussianDiffusionContinuousTimes(noise_schedule="cosine", timesteps=T).step_tables()
     sc = E.kd_schedule_t()
     sc.T = T
@@ -45,27 +39,20 @@ def _schedule(T):
 
 
 def _args(objective, dynamic_threshold, use_graph=1, seed=9):
-    sa = _E().kd_sample_args_t()
+    sa = H.engine().kd_sample_args_t()
     sa.objective, sa.dynamic_threshold, sa.percentile, sa.resample_times = OBJ[objective], dynamic_threshold, 0.95, 1
     sa.seed, sa.use_graph = seed, use_graph
     return sa
 
 
 def _steps(h, sc, sa, x, k):
-    E = _E()
+    E = H.engine()
     E.check(E.load().kd_sample_steps(h, C.byref(sc), C.byref(sa), E.ptr(x), k, k + 1, E.current_stream()))
 
 
 def _last(h, device):
     """(pred, x0, thresholds) of the last iteration, fp64 on the CPU."""
-    E = _E()
-    out = []
-    for which, shape in ((0, SHP), (1, SHP), (2, (B,))):
-        t = torch.empty(shape, device=device)
-        E.check(E.load().kd_sample_last(h, which, E.ptr(t), E.current_stream()))
-        out.append(t)
-    torch.cuda.synchronize()
-    return [t.double().cpu() for t in out]
+    return [H.sample_last(h, which, shape, device) for which, shape in ((0, SHP), (1, SHP), (2, (B,)))]
 
 
 def _x0_of(objective, x, pred, alpha, sigma):
@@ -105,7 +92,7 @@ def test_ddpm_step_matches_fp64_expressions(device, plan, T, k, objective):
     f = lambda n: float(tab[n][k])
     for dyn in (1, 0):
         sa = _args(objective, dyn)
-        sa.d_noise_step = _E().ptr(noise)
+        sa.d_noise_step = H.engine().ptr(noise)
         x = x_in.to(device)
         _steps(h, sc, sa, x, k)
         pred, x0, thr = _last(h, device)
@@ -124,7 +111,7 @@ def test_ddpm_step_matches_fp64_expressions(device, plan, T, k, objective):
         if k == T - 1:   # no noise is added to the last step: another noise tensor, the same bits
             assert f("noise_scale") == 0.0
             other = torch.flip(noise, dims=(0,)) * 3 + 1
-            sa.d_noise_step = _E().ptr(other)
+            sa.d_noise_step = H.engine().ptr(other)
             x2 = x_in.to(device)
             _steps(h, sc, sa, x2, k)
             torch.cuda.synchronize()
@@ -164,7 +151,7 @@ def test_ddpm_inpaint_resample_slots_and_renoise(device, plan, k, objective):
     x rn_a + z_renoise[it] rn_b follows the first iteration only, and none at k = T - 1.  The first iteration is run alone
     (R = 1, its noise tensors offset so that its slot k is slot 2 k) and checked by itself; then the second is recomputed
     from it in fp64 and from the preds the R = 2 call left behind.  Slot it = k R + (R - 1 - r) for resample r = R - 1 .. 0."""
-    E = _E()
+    E = H.engine()
     pu, h = plan
     T, R = 6, 2
     sc, tab = _schedule(T)
@@ -215,7 +202,7 @@ PHILOX_ATOL = 2e-5   # test_philox_normal_matches_host_reference_and_is_normal: 
 def _philox(device, seed, purpose, it):
     from oracle.philox_ref import philox_normal
 
-    E = _E()
+    E = H.engine()
     sid = (purpose << 32) | it
     out = torch.empty(N, device=device)
     E.check(E.load().kd_philox_normal(E.ptr(out), N, seed, sid, E.current_stream()))
@@ -259,7 +246,7 @@ def test_ddpm_inpaint_and_renoise_draw_from_philox_streams_2_and_3(device, plan)
     Stream 3: with d_noise_renoise = NULL the first iteration's result y (run alone, R = 1) is re-noised to y rn_a + z rn_b,
     z from stream (3 << 32) | 4, and the unknown pixels reach the second forward unchanged: z = (alpha x0 + sigma pred -
     y rn_a) / rn_b there.  Two roundings in the re-noise, three in x0: bound 2e-5 + 5 2^-24 M / rn_b (rn_b = 0.37)."""
-    E = _E()
+    E = H.engine()
     pu, h = plan
     T, R, k, seed = 6, 2, 2, 0xD1B54A32D192ED03
     it0, it1 = k * R, k * R + 1
@@ -309,7 +296,7 @@ def test_ddpm_inpaint_and_renoise_draw_from_philox_streams_2_and_3(device, plan)
 def test_sample_finalize_is_clamp_paste_unnormalise(device, plan, inpaint):
     """kd_sample_finalize: (clamp(x, -1, 1), the known pixels pasted over it, + 1) * 0.5 - the same bits as fp32 torch,
     on values beyond +-1, exactly +-1 and inside."""
-    E = _E()
+    E = H.engine()
     pu, h = plan
     gen = torch.Generator().manual_seed(5)
     x = _randn(gen, *SHP)   # about a third beyond +-1

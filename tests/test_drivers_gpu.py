@@ -26,17 +26,10 @@ IMAGEN_KW = dict(image_sizes=(64, 256, 1024), pred_objectives=("noise", "noise",
 def _pair(device, cond_channels, timesteps, seed):
     """Oracle Imagen (CPU) and product Imagen (device) with the same weights: the three UNets of
     train_ultra_res.py:29-60 at dim 32."""
-    import imagen_pytorch as ip
-
-    ous = []
-    for s, name in ((1, "ultra1"), (2, "ultra2"), (3, "ultra3")):
-        kw = dict(H.UNET_KW[name], cond_images_channels=cond_channels)
-        ous.append(H.fast_oracle(H.randomize_(R.Unet(**kw, lowres_cond=s > 1, cond_on_text=False, text_embed_dim=None), seed + s).eval()))
+    ous = [H.fast_oracle(H.ref_unet(R.Unet, H.UNET_KW[name], seed=seed + s, cond_images_channels=cond_channels, lowres_cond=s > 1))
+           for s, name in ((1, "ultra1"), (2, "ultra2"), (3, "ultra3"))]
     oim = RS.Imagen(ous, timesteps=timesteps, **IMAGEN_KW)
-    pim = ip.Imagen([ip.Unet(**u._locals) for u in oim.unets], timesteps=timesteps, random_crop_sizes=(None, None, 256),
-                    **IMAGEN_KW)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+    return oim, H.product_imagen(oim, "Imagen", device, timesteps=timesteps, random_crop_sizes=(None, None, 256), **IMAGEN_KW)
 
 
 def _noise_fn(stage, task):

@@ -14,21 +14,12 @@ pytestmark = pytest.mark.gpu
 
 SAMPLE_ABS = 2e-3
 TRACE_REL_L2 = 2e-3
-
-
-def _pair(device, unets, sizes, **kw):
-    """(restatement, product) ElucidatedImagen over the same weights."""
-    import imagen_pytorch as ip
-
-    oim = ER.ElucidatedImagen(unets, image_sizes=sizes, **kw)
-    pu = [ip.NullUnet() if isinstance(u, R.NullUnet) else ip.Unet(**u._locals) for u in oim.unets]
-    pim = ip.ElucidatedImagen(pu, image_sizes=sizes, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+EDM = (ER.ElucidatedImagen, "ElucidatedImagen")   # (restatement, product class) of H.imagen_pair
 
 
 def _base(device, N=5):
-    return _pair(device, [H.oracle_unet("small1", seed=3)], (16,), condition_on_text=False, num_sample_steps=N)
+    return H.imagen_pair(device, *EDM, [H.oracle_unet("small1", seed=3)], image_sizes=(16,), condition_on_text=False,
+                         num_sample_steps=N)
 
 
 def test_base_unet_trace_and_sample_match_the_restatement(device):
@@ -47,8 +38,8 @@ def test_base_unet_trace_and_sample_match_the_restatement(device):
 
 def test_sr_stage_with_cond_images_and_inpainting_matches_the_restatement(device):
     ou = H.oracle_unet("small2", lowres_cond=True, seed=5)
-    oim, pim = _pair(device, [R.NullUnet(), ou], (16, 32), condition_on_text=False, num_sample_steps=3,
-                     sigma_max=(80, 320))
+    oim, pim = H.imagen_pair(device, *EDM, [R.NullUnet(), ou], image_sizes=(16, 32), condition_on_text=False, num_sample_steps=3,
+                                 sigma_max=(80, 320))
     g = torch.Generator().manual_seed(8)
     B = 2
     start = torch.rand(B, 3, 16, 16, generator=g)
@@ -80,7 +71,7 @@ def test_text_conditioned_sampling_with_guidance_matches_the_restatement(device,
     """tokens = 3: three embedding rows per sample, the middle one all zero (a false entry in sample()'s default mask): the
     conditioning table and the replayed graphs carry K / V of more than one text token."""
     ou = H.randomize_(R.Unet(**SEG_KW, cond_on_text=True), 17)
-    oim, pim = _pair(device, [ou], (16,), text_embed_dim=3, num_sample_steps=3)
+    oim, pim = H.imagen_pair(device, *EDM, [ou], image_sizes=(16,), text_embed_dim=3, num_sample_steps=3)
     B = 2
     g = torch.Generator().manual_seed(3)
     text = torch.tensor([0.0, 0.5, 0.2]).reshape(1, 1, 3).repeat_interleave(B, dim=0)
@@ -195,12 +186,6 @@ def _abi_setup(device, N=3, B=2, S=16):
     return E, pu, h, tab, sc, args, noise, g
 
 
-def _last(E, h, which, shape, device):
-    out = torch.empty(shape, device=device)
-    E.check(E.load().kd_sample_last(h, which, E.ptr(out), E.current_stream()))
-    return out.double().cpu()
-
-
 def _thr(den, s):
     s = s.clamp(min=1.0)[:, None, None, None]
     return torch.maximum(torch.minimum(den, s), -s) / s
@@ -217,8 +202,8 @@ def test_edm_kernels_match_fp64_expressions(device):
         x0 = (torch.randn(shp, generator=g) * 3).to(device)
         x = x0.clone()
         E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(x), k, k + 1, E.current_stream()))
-        net, den, s = _last(E, h, 0, shp, device), _last(E, h, 1, shp, device), _last(E, h, 2, (B,), device)
-        xh, d = _last(E, h, 3, shp, device), _last(E, h, 4, shp, device)
+        net, den, s = H.sample_last(h, 0, shp, device), H.sample_last(h, 1, shp, device), H.sample_last(h, 2, (B,), device)
+        xh, d = H.sample_last(h, 3, shp, device), H.sample_last(h, 4, shp, device)
         x0d, z = x0.double().cpu(), noise[k].double().cpu()
         # churn: x_hat = x + churn * (S_noise * z)
         assert H.rel_l2(xh, x0d + f("churn", k) * (float(sc.S_noise) * z)) < 1e-6, k
@@ -259,7 +244,7 @@ def test_edm_renoise_between_resamples(device):
     x_start = x.clone()
     # step k = 0: iteration r = 1 (churn[0], then re-noise ren[0]), then r = 0 (churn[1], no re-noise)
     E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(x), 0, 1, E.current_stream()))
-    xh = _last(E, h, 3, shp, device)
+    xh = H.sample_last(h, 3, shp, device)
     m = mask.bool().expand(shp).cpu()
     want_known = inp.double().cpu() + f("churn") * (float(sc.S_noise) * churn[1].double().cpu())
     assert H.rel_l2(xh[m], want_known[m]) < 1e-6
@@ -282,9 +267,9 @@ ULTRA2 = dict(dim=128, dim_mults=(1, 2, 4, 8), num_resnet_blocks=2, memory_effic
 
 
 def test_ultra_res_unet2_full_dims_matches_the_restatement(device):
-    ou = H.fast_oracle(H.randomize_(R.Unet(**ULTRA2, lowres_cond=True, cond_on_text=False, text_embed_dim=None), 82).eval())
-    oim, pim = _pair(device, [R.NullUnet(), ou], (64, 256), condition_on_text=False, num_sample_steps=3,
-                     sigma_max=(80, 320))
+    ou = H.fast_oracle(H.randomize_(R.Unet(**ULTRA2, lowres_cond=True, **H.NOTEXT), 82).eval())
+    oim, pim = H.imagen_pair(device, *EDM, [R.NullUnet(), ou], image_sizes=(64, 256), condition_on_text=False, num_sample_steps=3,
+                                 sigma_max=(80, 320))
     g = torch.Generator().manual_seed(9)
     B = 2
     start = torch.rand(B, 3, 64, 64, generator=g)

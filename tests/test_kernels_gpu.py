@@ -7,24 +7,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import helpers as H
+
 pytestmark = pytest.mark.gpu
+
+
+engine, g = H.engine, H.gen   # (H is the image height in the tests below)
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from imagen_pytorch import _engine as E
-
-    return E.load()
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
+    return engine().load()
 
 
 # fp32 tolerance for one contraction: |err| <= tol * sum|a||b| bound, expressed as rel-L2
@@ -58,7 +51,7 @@ CONV_REL = 2e-6
     (2, 8, 8, 96, 128, 2, 2, 0, 0),        # M = 32, K too short to split: generic small-M kernel
 ])
 def test_conv_igemm(lib, device, B, H, W, Cin, Cout, K, stride, pad, act):
-    E = _E()
+    E = engine()
     x = torch.randn(B, Cin, H, W, generator=g(1))
     w = torch.randn(Cout, Cin, K, K, generator=g(2)) * (Cin * K * K) ** -0.5
     b = torch.randn(Cout, generator=g(3))
@@ -90,7 +83,7 @@ def test_conv_igemm(lib, device, B, H, W, Cin, Cout, K, stride, pad, act):
 def test_init_cross_embed_conv_fused(lib, device, B, S, n3, n7, n15):
     """The three init convs (k = 3 / 7 / 15, zero padding k // 2) over a 3-plane NCHW image in one persistent
     kernel, against torch conv2d in fp64."""
-    E = _E()
+    E = engine()
     x = torch.randn(B, 3, S, S, generator=g(1))
     ws = [torch.randn(n, 3, k, k, generator=g(10 + k)) * (3 * k * k) ** -0.5 for n, k in ((n3, 3), (n7, 7), (n15, 15))]
     b = torch.randn(n3 + n7 + n15, generator=g(4))
@@ -121,7 +114,7 @@ def test_init_cross_embed_conv_fused(lib, device, B, S, n3, n7, n15):
 ])
 def test_conv1x1_pixel_shuffle_upsample(lib, device, B, H, W, Cin, Cout):
     """Upsample = conv1x1(C -> 4 Co) + PixelShuffle(2): the conv's epilogue writes the shuffled map directly."""
-    E = _E()
+    E = engine()
     x = torch.randn(B, Cin, H, W, generator=g(1))
     w = torch.randn(Cout, Cin, 1, 1, generator=g(2)) * Cin ** -0.5
     b = torch.randn(Cout, generator=g(3))
@@ -147,7 +140,7 @@ WINO_REL = 4e-6
     (4, 16, 16, 1024, 128),    # long K, Mt = 256 (one 256-row tile per slab)
 ])
 def test_conv3x3_winograd_matches_direct(lib, device, B, H, W, Cin, Cout):
-    E = _E()
+    E = engine()
     x = torch.randn(B, Cin, H, W, generator=g(1))
     w = torch.randn(Cout, Cin, 3, 3, generator=g(2)) * (Cin * 9) ** -0.5
     b = torch.randn(Cout, generator=g(3))
@@ -198,7 +191,7 @@ WINO4_REL = 8e-6
     (16, 16, 16, 1280, 768, False, True, 2),
 ])
 def test_conv3x3_winograd4_matches_direct(lib, device, B, H, W, Cin, Cout, res, stats, x3):
-    E = _E()
+    E = engine()
     h = torch.randn(B, Cin, H, W, generator=g(1)) * 1.2 + 0.2
     x = F.silu(h)                       # what these layers see: an activated, normalised map
     w = torch.randn(Cout, Cin, 3, 3, generator=g(2)) * (Cin * 9) ** -0.5
@@ -235,7 +228,7 @@ def test_conv3x3_winograd4_matches_direct(lib, device, B, H, W, Cin, Cout, res, 
 
 
 def test_conv3x3_winograd4_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(16, device=device)
     for shape in [(1, 18, 16, 32, 64), (1, 16, 16, 32, 64), (16, 16, 16, 48, 64), (16, 16, 16, 32, 96)]:
         rc = lib.kd_conv3x3_winograd4_nhwc(E.ptr(t), E.ptr(t), None, None, E.ptr(t), *shape, 8, 1e-5, None, 0, E.current_stream())
@@ -261,7 +254,7 @@ def test_conv3x3_winograd4_rejects_unsupported_shapes(lib, device):
 ])
 @pytest.mark.parametrize("a_planes", [1, 0])   # 1: A in plane form (the plan's); 0: A as fp32, split by the kernel's loader waves
 def test_gemm_bf16x3_matches_fp64(lib, device, G, M, N, K, scale_b, a_planes):
-    E = _E()
+    E = engine()
     a = (torch.randn(G, M, K, generator=g(5)) * torch.logspace(-3, 3, K)).to(device)   # 6 decades along k
     b = (torch.randn(G, N, K, generator=g(6)) * scale_b).to(device)
     a[0, 0, :4] = torch.tensor([0.0, -0.0, 1e-30, 1e30], device=device)   # zeros, a tiny and a huge value
@@ -299,7 +292,7 @@ def test_gemm_bf16x3_matches_fp64(lib, device, G, M, N, K, scale_b, a_planes):
     (73728, 128, 64, True, False, False, 0, 0),       # 288 tiles: a whole round and 32 left-over tiles that are not cut
 ])
 def test_linear_bf16x3_epilogues_match_fp64(lib, device, M, N, K, bias, res, gate, ldx, ldy):
-    E = _E()
+    E = engine()
     lda, ldo = ldx or K, ldy or N
     hw = 256
     xfull = (torch.randn(M, lda, generator=g(41)) * torch.logspace(-2, 2, lda)).to(device)
@@ -349,7 +342,7 @@ def test_linear_bf16x3_epilogues_match_fp64(lib, device, M, N, K, bias, res, gat
 
 
 def test_linear_bf16x3_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(16, device=device)
     for M, N, K, hw in [(128, 128, 64, 256), (256, 64, 64, 256), (256, 128, 48, 256)]:
         rc = lib.kd_linear_bf16x3(E.ptr(t), 0, E.ptr(t), None, None, 0, None, 0, None, hw, E.ptr(t), 0, M, N, K, 0, 0, None, E.current_stream())
@@ -374,7 +367,7 @@ def test_linear_bf16x3_rejects_unsupported_shapes(lib, device):
 def test_linear_bf16x3_upsample_form_matches_fp64(lib, device, B, H, W, K, Co, ldy, act):
     """conv1x1 -> SiLU -> PixelShuffle(2) of the library's Upsample through the bf16x3 kernel's epilogue: weight
     rows packed n' = (2 i + j) Co + c as the plan packs them, output [B, 2H, 2W, Co] written with row stride ldy."""
-    E = _E()
+    E = engine()
     M, N = B * H * W, 4 * Co
     x = torch.randn(M, K, generator=g(51)).to(device)
     wt = (torch.randn(N, K, generator=g(52)) * 0.1).to(device)        # torch layout: row c * 4 + i * 2 + j
@@ -414,7 +407,7 @@ def test_linear_bf16x3_upsample_form_matches_fp64(lib, device, B, H, W, K, Co, l
 def test_downsample_bf16x3_matches_fp64(lib, device, B, H, W, Cin, O, ldx):
     """Downsample of the library (pixel-unshuffle + conv1x1) through the bf16x3 kernel whose loader gathers the 2 x 2 input
     pixels: against the same op in fp64 from the torch weight layout [O][4 C] (k = c 4 + 2 s1 + s2)."""
-    E = _E()
+    E = engine()
     ld = ldx or Cin
     xf = torch.randn(B, H, W, ld, generator=g(61)).to(device)
     wt = (torch.randn(O, 4 * Cin, generator=g(62)) * 0.05).to(device)
@@ -448,7 +441,7 @@ def test_gemm_bf16x3_two_launches_sharing_the_chip_do_not_depend_on_each_other(l
     a grid run) may share the CUs in any interleaving: same bits as alone."""
     import threading
 
-    E = _E()
+    E = engine()
     shapes = [(36, 256, 1024, 1024), (36, 1024, 512, 256)]   # 288 tiles (32 cut in 8) and 576 tiles (64 cut in 2)
     data, alone = [], []
     for i, (G, M, N, K) in enumerate(shapes):
@@ -485,7 +478,7 @@ def test_gemm_bf16x3_two_launches_sharing_the_chip_do_not_depend_on_each_other(l
 
 
 def test_gemm_bf16x3_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(16, device=device)
     for shape in [(1, 128, 128, 32), (1, 256, 64, 32), (1, 256, 128, 16), (36, 4096 * 8, 128, 2048)]:
         rc = lib.kd_gemm_bf16x3(E.ptr(t), E.ptr(t), E.ptr(t), *shape, 0, E.current_stream())
@@ -493,7 +486,7 @@ def test_gemm_bf16x3_rejects_unsupported_shapes(lib, device):
 
 
 def test_conv3x3_winograd_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(16, device=device)
     rc = lib.kd_conv3x3_winograd_nhwc(E.ptr(t), E.ptr(t), None, E.ptr(t), 1, 15, 16, 32, 64, E.current_stream())
     assert rc != 0 and b"even" in lib.kd_last_error()
@@ -520,7 +513,7 @@ def test_conv3x3_winograd_rejects_unsupported_shapes(lib, device):
 def test_gn_conv3x3_winograd_fused_matches_torch(lib, device, B, H, W, Cin, Cout, G, film, res, ldx):
     """ResnetBlock `Block` = conv3x3(SiLU(FiLM(GroupNorm(x)))) with the activation applied to the raw patch in
     LDS inside the fused Winograd kernel (hardware exp2 / reciprocal: ~1 ulp each)."""
-    E = _E()
+    E = engine()
     x = torch.randn(B, Cin, H, W, generator=g(1)) * 1.5 + 0.3
     gamma = 1 + 0.2 * torch.randn(Cin, generator=g(5))
     beta = 0.2 * torch.randn(Cin, generator=g(6))
@@ -575,7 +568,7 @@ def test_gn_conv3x3_winograd_fused_at_benchmark_size_is_repeatable(lib, device):
     """The SR UNet's top level at the benchmark's batch (16 x 256 x 256 x 128 -> 128: 8192 items of 16 x 8 pixels on
     256 persistent workgroups, 32 items each): repeated launches are bit-identical (no race between the DMA stages, the
     V stores, the exchange and the barriers shows up under full occupancy) and image 0 matches an fp64 reference."""
-    E = _E()
+    E = engine()
     B, H, W, Cin, Cout, G = 16, 256, 256, 128, 128, 8
     gd = torch.Generator(device=device).manual_seed(5)
     x = torch.randn(B, H, W, Cin, device=device, generator=gd)
@@ -601,7 +594,7 @@ def test_gn_conv3x3_winograd_fused_at_benchmark_size_is_repeatable(lib, device):
 
 
 def test_gn_conv3x3_winograd_fused_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(4096, device=device)
     p = E.ptr(t)
     for shape, ldx, word in [((1, 20, 16, 32, 128), 0, b"% 8"), ((1, 16, 24, 32, 128), 0, b"% 16"), ((1, 16, 16, 30, 128), 0, b"% 4"),
@@ -614,7 +607,7 @@ def test_gn_conv3x3_winograd_fused_rejects_unsupported_shapes(lib, device):
 @pytest.mark.parametrize("B,HW,C,G,film", [(2, 64, 32, 8, False), (3, 100, 96, 8, True), (1, 4096, 128, 8, True),
                                            (2, 16, 1024, 8, True), (2, 300, 384, 8, False)])
 def test_groupnorm_film_silu(lib, device, B, HW, C, G, film):
-    E = _E()
+    E = engine()
     x = torch.randn(B, HW, C, generator=g(4)) * 2 + 0.5
     gamma, beta = torch.randn(C, generator=g(5)), torch.randn(C, generator=g(6))
     ss = torch.randn(B, 2 * C, generator=g(7)) * 0.3 if film else None
@@ -634,7 +627,7 @@ def test_groupnorm_film_silu(lib, device, B, HW, C, G, film):
 
 @pytest.mark.parametrize("rows,C,bias", [(7, 32, False), (300, 256, True), (64, 2048, False), (5, 4096, True)])
 def test_layernorm(lib, device, rows, C, bias):
-    E = _E()
+    E = engine()
     x = torch.randn(rows, C, generator=g(8)) * 3 + 1
     gg = torch.randn(C, generator=g(9))
     bb = torch.randn(C, generator=g(10)) if bias else None
@@ -652,7 +645,7 @@ def test_layernorm(lib, device, rows, C, bias):
     (5, 4096, 2, True, True), (7, 32, 1, False, True), (300, 256, 0, False, False), (33, 520, 2, True, False),
 ])
 def test_layernorm_forms_of_the_transformer_block(lib, device, rows, C, act, res, second):
-    E = _E()
+    E = engine()
     x = torch.randn(rows, C, generator=g(8)) * 3 + 1
     gg, g2 = torch.randn(C, generator=g(9)), torch.randn(C, generator=g(14))
     r = torch.randn(rows, C, generator=g(15)) if res else None
@@ -687,7 +680,7 @@ def test_layernorm_planes_feed_the_bf16x3_linear(lib, device, rows, C, N, act, r
     """The plan's LayerNorm -> Linear pairs (engine.hip transformer): the LayerNorm leaves the GEMM's A operand as three bf16
     planes.  The planes of a value add up to the fp32 LayerNorm output exactly, and the GEMM over them is bit-identical to
     the GEMM over the fp32 rows (same products, same order; only the loader differs)."""
-    E = _E()
+    E = engine()
     x = torch.randn(rows, C, generator=g(21)) * 2 + 0.5
     gg = torch.randn(C, generator=g(22))
     w = torch.randn(N, C, generator=g(23)) / C ** 0.5
@@ -727,7 +720,7 @@ def test_layernorm_planes_feed_the_bf16x3_linear(lib, device, rows, C, N, act, r
     (4, 512, 128, 8, 1),                   # exactly two full tiles, exactly 128 blocks
 ])
 def test_attention(lib, device, B, Nq, Nk, H, Hkv):
-    E = _E()
+    E = engine()
     D = 64
     q = torch.randn(B, Nq, H, D, generator=g(11)) * 0.5
     k = torch.randn(B, Nk, Hkv, D, generator=g(12))
@@ -745,7 +738,7 @@ def test_attention(lib, device, B, Nq, Nk, H, Hkv):
 @pytest.mark.parametrize("B,n,q", [(3, 12288, 0.95), (2, 196608, 0.95), (1, 1000, 0.5), (2, 37, 0.0), (2, 37, 1.0),
                                    (4, 4096, 0.95)])
 def test_quantile_abs_matches_torch(lib, device, B, n, q):
-    E = _E()
+    E = engine()
     x = torch.randn(B, n, generator=g(14)) * 1.7
     if n == 4096:  # heavy duplicates: forces the equal-bin branch of the radix select
         x = (x * 2).round() / 2
@@ -763,7 +756,7 @@ def test_quantile_abs_matches_torch(lib, device, B, n, q):
 def test_philox_normal_matches_host_reference_and_is_normal(lib, device):
     from oracle.philox_ref import philox_normal
 
-    E = _E()
+    E = engine()
     n = 1 << 20
     out = torch.empty(n, device=device)
     E.check(lib.kd_philox_normal(E.ptr(out), n, 0x1234567, (16 << 32) | 2, E.current_stream()))

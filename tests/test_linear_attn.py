@@ -1,6 +1,7 @@
 """Linear-attention UNets (library `Unet(use_linear_attn=..., use_linear_cross_attn=...)`) without a GPU: construction,
 the state-dict layout against the restatement in tests/linear_attn_ref.py, strict loading (also through ImagenTrainer),
 the per-level rules, and the resource usage of the new kernel file."""
+import functools
 import re
 import shutil
 import subprocess
@@ -18,18 +19,11 @@ KW = dict(dim=32, dim_mults=(1, 2, 4), num_resnet_blocks=1, layer_attns=(False, 
           cond_on_text=False, text_embed_dim=None)
 
 
-def _product(seed=0, **over):
-    import imagen_pytorch as ip
-
-    return H.randomize_(ip.Unet(**{**KW, **over}), seed)
+_product = functools.partial(H.random_product_unet, **KW)   # _product(seed=0, **over)
 
 
 def _ref(seed=0, **over):
     return H.randomize_(LR.Unet(**{**KW, **over}), seed)
-
-
-def _layout(sd):
-    return {k: tuple(v.shape) for k, v in sd.items()}
 
 
 def test_linear_attention_unet_constructs():
@@ -44,7 +38,7 @@ def test_linear_attention_unet_constructs():
 
 def test_state_dict_layout_equals_the_restatement():
     sp = _product().state_dict()
-    assert _layout(sp) == _layout(_ref().state_dict())
+    assert H.state_layout(sp) == H.state_layout(_ref().state_dict())
     assert tuple(sp["downs.0.3.layers.0.0.to_q.2.weight"].shape) == (512, 1, 3, 3)
     assert tuple(sp["downs.0.3.layers.0.0.to_k.1.weight"].shape) == (512, 32, 1, 1)
     assert tuple(sp["downs.0.3.layers.0.0.norm.g"].shape) == (1, 32, 1, 1)
@@ -110,7 +104,7 @@ def test_per_level_tuples_and_the_full_attention_precedence():
         assert type(u.downs[l][1].cross_attn).__name__ == "LinearCrossAttention"
         assert type(u.ups[2 - l][0].cross_attn).__name__ == "LinearCrossAttention"
     assert type(u.mid_block1.cross_attn).__name__ == "CrossAttention"   # the middle is unchanged
-    assert _layout(u.state_dict()) == _layout(_ref(**over).state_dict())
+    assert H.state_layout(u.state_dict()) == H.state_layout(_ref(**over).state_dict())
     assert u._plan["use_linear_attn"] == (True, False, True) and u._plan["use_linear_cross_attn"] == (True,) * 3
 
 
@@ -119,10 +113,10 @@ def test_memory_efficient_self_cond_and_qk_norm_layouts_equal_the_restatement():
 
     kw = dict(H.UNET_KW["ultra2"], use_linear_attn=True, use_linear_cross_attn=True, lowres_cond=True,
               cond_on_text=False, text_embed_dim=None)
-    assert _layout(ip.Unet(**kw).state_dict()) == _layout(LR.Unet(**kw).state_dict())
+    assert H.state_layout(ip.Unet(**kw).state_dict()) == H.state_layout(LR.Unet(**kw).state_dict())
     kw.update(self_cond=True, attn_qk_norm=2)
     sp = ip.Unet(**kw).state_dict()
-    assert _layout(sp) == _layout(LR.SelfCondUnet(**kw).state_dict())
+    assert H.state_layout(sp) == H.state_layout(LR.SelfCondUnet(**kw).state_dict())
     assert "downs.0.1.cross_attn.q_scale" in sp   # (loads with the module; the linear form does not use it)
 
 

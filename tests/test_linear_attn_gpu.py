@@ -3,6 +3,7 @@ kernels_linattn.hip against fp64 torch, the UNet forward and both samplers again
 tests/linear_attn_ref.py, graph / eager and run-to-run bit identity, and the plan of a UNet without linear attention
 through kd_unet_create_ext."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -20,16 +21,6 @@ FWD_REL_L2 = 2e-5
 SAMPLE_ABS = 2e-3
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 def _rel(a, b):
     return float((a.double() - b.double()).norm() / b.double().norm())
 
@@ -42,11 +33,11 @@ def _at(t, floats):   # device pointer of a column slice (the kernels take row s
 @pytest.mark.parametrize("B,Hh,Ww,heads", [(2, 13, 21, 2), (1, 9, 8, 1), (3, 24, 40, 8)])
 def test_dwconv_and_k_partials(device, B, Hh, Ww, heads):
     """Maps that are not powers of two, H W not a multiple of the chunk."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     inner = 64 * heads
-    x = torch.randn(B, Hh, Ww, 3 * inner, generator=_g(1))
-    ws = [torch.randn(inner, 1, 3, 3, generator=_g(2 + i)) / 3 for i in range(3)]
+    x = torch.randn(B, Hh, Ww, 3 * inner, generator=H.gen(1))
+    ws = [torch.randn(inner, 1, 3, 3, generator=H.gen(2 + i)) / 3 for i in range(3)]
     chunk = lib.kd_linattn_chunk_tokens()
     HW = Hh * Ww
     nch = (HW + chunk - 1) // chunk
@@ -78,11 +69,11 @@ def _partials(k, chunk):   # [B, HW, inner] -> the dwconv kernel's (max, sum exp
 @pytest.mark.parametrize("HW,m,null", [(273, 0, False), (273, 5, False), (4113, 37, False), (100, 3, True), (0, 7, True),
                                        (0, 37, False)])
 def test_context_reduction(device, HW, m, null):
-    E = _E()
+    E = H.engine()
     lib = E.load()
     B, heads = 2, 3
     inner = 64 * heads
-    g = _g(HW + m)
+    g = H.gen(HW + m)
     qkv = torch.randn(B, max(HW, 1), 3 * inner, generator=g) * 2
     ckv = torch.randn(B, max(m, 1), 2 * inner, generator=g) * 2
     nkv = torch.randn(2, 64, generator=g)
@@ -111,11 +102,11 @@ def test_context_reduction(device, HW, m, null):
 @pytest.mark.parametrize("silu", [0, 1])
 @pytest.mark.parametrize("N", [1, 100, 192])
 def test_apply(device, N, silu):
-    E = _E()
+    E = H.engine()
     lib = E.load()
     B, heads = 2, 3
     inner = 64 * heads
-    g = _g(N)
+    g = H.gen(N)
     q = torch.randn(B, N, 3 * inner, generator=g) * 3   # q = columns [0, inner) of a q | k | v map
     ctx = torch.randn(B, heads, 64, 64, generator=g) * 0.1
     qs = q[..., :inner].double().reshape(B, N, heads, 64).softmax(-1) * 0.125
@@ -141,29 +132,7 @@ SEG = dict(dim=32, dim_mults=(1, 2, 3, 4), cond_dim=64, text_embed_dim=3, num_re
            cond_images_channels=4, use_linear_attn=True, use_linear_cross_attn=(True, False, True, False))
 
 
-def _ref_unet(kw, lowres=False, seed=0, text=False, cls=LR.Unet, **extra):
-    tk = dict(cond_on_text=True) if text else dict(cond_on_text=False, text_embed_dim=None)
-    return H.randomize_(cls(**kw, lowres_cond=lowres, **tk, **extra), seed).eval()
-
-
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
-def _inputs(ou, B, S, seed):
-    g = _g(seed)
-    x = torch.randn(B, 3, S, S, generator=g)
-    t = torch.randn(B, generator=g) * 3
-    kw = {}
-    if ou.lowres_cond:
-        kw.update(lowres_cond_img=torch.randn(B, 3, S, S, generator=g), lowres_noise_times=torch.full((B,), 1.5))
-    if ou.has_cond_image:
-        kw["cond_images"] = torch.rand(B, ou.cond_images_channels, S, S, generator=g)
-    return x, t, kw
+_ref_unet = functools.partial(H.ref_unet, LR.Unet)
 
 
 @pytest.mark.parametrize("case", ["small_b2", "small_b5", "small_self_cond", "ultra2_256_b2", "ultra2_256_b16"])
@@ -174,35 +143,29 @@ def test_unet_forward_matches_the_restatement(device, case):
     if case.startswith("small"):
         B, S = (5, 32) if case == "small_b5" else (2, 32)
         if case == "small_self_cond":
-            ou = _ref_unet(SMALL, seed=11, cls=LR.SelfCondUnet, self_cond=True)
-            sc = torch.rand(B, 3, S, S, generator=_g(9)) * 2 - 1
+            ou = H.ref_unet(LR.SelfCondUnet, SMALL, seed=11, self_cond=True)
+            sc = torch.rand(B, 3, S, S, generator=H.gen(9)) * 2 - 1
         else:
             ou = _ref_unet(SMALL, seed=11)
     else:
         B, S = (16 if case.endswith("b16") else 2), 256
-        ou = H.fast_oracle(_ref_unet(ULTRA2, lowres=True, seed=12))
-    pu = _product_like(ou, device)
-    x, t, kw = _inputs(ou, B, S, seed=3)
-    skw = {} if sc is None else dict(self_cond=sc)
-    with torch.no_grad():
-        ref = ou(x, t, **kw, **skw)
-    dv = {k: v.to(device) for k, v in {**kw, **skw}.items()}
-    got = pu(x.to(device), t.to(device), **dv).cpu()
-    got2 = pu(x.to(device), t.to(device), **dv).cpu()
-    e = H.rel_l2(got, ref)
+        ou = H.fast_oracle(_ref_unet(ULTRA2, lowres_cond=True, seed=12))
+    x, t, kw = H.unet_inputs(ou, B, S, seed=3)
+    if sc is not None:
+        kw["self_cond"] = sc   # (drawn last and from a generator of its own: x, t and the other planes are as without it)
+    e, _ = H.forward_err(ou, device, x, t, kw)   # (asserts that a second run gives the same bits)
     print(f"linear-attention forward {case}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    assert torch.equal(got, got2)   # no atomics: run-to-run bit-identical
 
 
 def test_plain_unet_through_the_new_export_keeps_its_plan(device):
     """A UNet without linear attention built through kd_unet_create_ext has the launches and the bits of the plan
     kd_unet_create_shared (= kd_unet_create) builds."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
-    ou = H.randomize_(LR.Unet(**H.UNET_KW["small2"], lowres_cond=True, cond_on_text=False, text_embed_dim=None), 4).eval()
-    a, b = _product_like(ou, device), _product_like(ou, device)
-    x, t, kw = _inputs(ou, 2, 32, seed=5)
+    ou = _ref_unet(H.UNET_KW["small2"], seed=4, lowres_cond=True)
+    a, b = H.product_like(ou, device), H.product_like(ou, device)
+    x, t, kw = H.unet_inputs(ou, 2, 32, seed=5)
     dv = {k: v.to(device) for k, v in kw.items()}
     ha = a.engine(2, 32, device, with_text=False)
     orig = lib.kd_unet_create_ext
@@ -216,36 +179,23 @@ def test_plain_unet_through_the_new_export_keeps_its_plan(device):
     yb = b(x.to(device), t.to(device), **dv)
     assert torch.equal(ya, yb)
     ol = _ref_unet(SMALL, seed=6)
-    lin = _product_like(ol, device)
-    xl, tl, _ = _inputs(ol, 2, 32, seed=7)
+    lin = H.product_like(ol, device)
+    xl, tl, _ = H.unet_inputs(ol, 2, 32, seed=7)
     lin(xl.to(device), tl.to(device))   # (the profile replays the inputs of the last forward)
-    hl = lin.engine(2, 32, device, with_text=False)
-    buf = C.create_string_buffer(1 << 20)
-    E.check(lib.kd_unet_profile(hl, 1, buf, len(buf), E.current_stream()))
-    labels = buf.value.decode()
+    labels = H.plan_csv(lin, 2, 32, device)
     # 2 levels x 2 paths of linear blocks, one LinearCrossAttention on each path of level 1
     assert labels.count("linattn dwconv") == 4 and labels.count("linattn apply") == 4, labels.count("linattn dwconv")
     assert labels.count("linattn xapply") == 2
 
 
 # ------------------------------------------------------------------------------- sampling
-def _pair(device, cls_o, cls_p, unets, sizes, **kw):
-    import imagen_pytorch as ip
-
-    oim = cls_o(unets, image_sizes=sizes, **kw)
-    pu = [ip.Unet(**u._locals) for u in oim.unets]
-    pim = getattr(ip, cls_p)(pu, image_sizes=sizes, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
-
-
 def test_ddpm_text_guided_inpainting_matches_the_restatement(device):
     """T = 4, inpainting with 2 resamples, cond_scale = 3 on a text UNet with linear attention and linear
     cross-attention."""
     ou = _ref_unet(SEG, seed=17, text=True)
-    oim, pim = _pair(device, RS.Imagen, "Imagen", [ou], (32,), timesteps=(4,), text_embed_dim=3)
+    oim, pim = H.imagen_pair(device, RS.Imagen, "Imagen", [ou], image_sizes=(32,), timesteps=(4,), text_embed_dim=3)
     B = 2
-    g = _g(3)
+    g = H.gen(3)
     text = torch.tensor([0.0, 0.5, 0.2]).reshape(1, 1, 3).repeat_interleave(B, dim=0)
     labels = F.one_hot(torch.randint(0, 4, (B, 32, 32), generator=g), 4).permute(0, 3, 1, 2).float()
     inp = torch.rand(B, 3, 32, 32, generator=g)
@@ -264,8 +214,8 @@ def test_ddpm_text_guided_inpainting_matches_the_restatement(device):
 
 def test_edm_sampling_matches_the_restatement(device):
     ou = _ref_unet(SMALL, seed=23)
-    oim, pim = _pair(device, ER.ElucidatedImagen, "ElucidatedImagen", [ou], (32,), condition_on_text=False,
-                     num_sample_steps=4)
+    oim, pim = H.imagen_pair(device, ER.ElucidatedImagen, "ElucidatedImagen", [ou], image_sizes=(32,), condition_on_text=False,
+                             num_sample_steps=4)
     nf = RS.generator_noise_fn(13)
     ref = oim.sample(noise_fn=nf, batch_size=2)
     got = pim.sample(noise_fn=nf, batch_size=2, device=device).cpu()
@@ -276,7 +226,7 @@ def test_edm_sampling_matches_the_restatement(device):
 
 def test_graph_equals_eager_and_table_on_equals_off(device):
     ou = _ref_unet(SMALL, seed=25)
-    _, pim = _pair(device, RS.Imagen, "Imagen", [ou], (32,), timesteps=(4,), condition_on_text=False)
+    _, pim = H.imagen_pair(device, RS.Imagen, "Imagen", [ou], image_sizes=(32,), timesteps=(4,), condition_on_text=False)
     nf = RS.generator_noise_fn(7)
     runs = {}
     for use_graph in (True, False):

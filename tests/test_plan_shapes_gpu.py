@@ -30,12 +30,6 @@ RING = 4
 _ids = lambda c: c.id
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
 def _set_plan(pu, plan):
     for k in PC.PLAN_ATTRS:   # engine extensions, read when a forward looks its plan up (0 = the default rule)
         setattr(pu, k, plan.get(k, 0))
@@ -90,7 +84,7 @@ class Sweep:
     def labels(self, pu, case, inp):
         """The label column of kd_unet_profile, one per launch (it runs the plan again, on the pointers of the last forward:
         the inputs stay alive here)."""
-        E = _E()
+        E = H.engine()
         _set_plan(pu, case.plan)
         x, t, kw = self.dev(inp)
         pu(x, t, **kw)
@@ -186,7 +180,7 @@ def test_packed_weights_do_not_depend_on_the_order_the_plans_were_built_in(sweep
     store is filled by whichever plan asks for a key first ("wino4:" + prefix, "res_conv_skipscaled:" + prefix + ":" + c0,
     "x3lin:" + pointer + shape ...), so every batch must give the same bits on both - and the bits of a UNet that owns that
     one plan alone, and of the module's UNet, whose plans were built in the order the tests ran."""
-    lib = _E().load()
+    lib = H.engine().load()
     cases = [c for c in PC.SWEEP if (c.model, c.S) == ("B", 64)]
     assert [c.B for c in cases] == list(range(1, 9))
     up, down = sweep.product("B"), sweep.product("B")
@@ -315,7 +309,7 @@ def full_size(device):
             u = ip.Unet(dim=128, dim_mults=(1, 2, 4, 8), num_resnet_blocks=2, memory_efficient=True,
                         layer_attns=(False, False, False, True), layer_cross_attns=(False, False, True, True),
                         init_conv_to_final_conv_residual=True, cond_images_channels=3, lowres_cond=True,
-                        cond_on_text=False, text_embed_dim=None)
+                        **H.NOTEXT)
         return u.to_empty(device=device)
 
     u = build()

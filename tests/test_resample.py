@@ -2,6 +2,7 @@
 GPU: the state-dict layout against the restatement in tests/resample_ref.py, strict loading, the version-fork hook, the
 config structs, the phase identity the upsample kernel's weight pack rests on, and the new kernel file's resource usage."""
 import ctypes as C
+import functools
 import re
 import shutil
 import subprocess
@@ -21,18 +22,11 @@ SWITCHES = {"cross_embed": dict(cross_embed_downsample=True), "nearest": dict(pi
             "both": dict(cross_embed_downsample=True, pixel_shuffle_upsample=False)}
 
 
-def _product(seed=0, **over):
-    import imagen_pytorch as ip
-
-    return H.randomize_(ip.Unet(**{**KW, **over}), seed)
+_product = functools.partial(H.random_product_unet, **KW)   # _product(seed=0, **over)
 
 
 def _ref(seed=0, **over):
     return H.randomize_(RR.Unet(**{**KW, **over}), seed)
-
-
-def _layout(sd):
-    return {k: tuple(v.shape) for k, v in sd.items()}
 
 
 @pytest.mark.parametrize("mem", [False, True])
@@ -43,7 +37,7 @@ def test_state_dict_layout_equals_the_restatement_and_round_trips(sw, mem):
     over = dict(SWITCHES[sw], memory_efficient=mem)
     p, r = _product(seed=1, **over), _ref(seed=2, **over)
     sp = p.state_dict()
-    assert _layout(sp) == _layout(r.state_dict())
+    assert H.state_layout(sp) == H.state_layout(r.state_dict())
     if "cross_embed_downsample" in over:
         pre = "downs.0.0" if mem else "downs.0.4"
         assert tuple(sp[pre + ".convs.0.weight"].shape) == (16, 32, 2, 2) and tuple(sp[pre + ".convs.0.bias"].shape) == (16,)
@@ -73,9 +67,9 @@ def test_cross_embed_keys_do_not_trigger_the_version_fork_hook(capsys):
     assert not calls and p.downsample_form == "unshuffle" and p._locals["downsample_form"] == "unshuffle"
     assert capsys.readouterr().out == ""
     # asked directly, the fork leaves a cross-embed UNet's downsample slots alone
-    before = _layout(p.state_dict())
+    before = H.state_layout(p.state_dict())
     orig(downsample_form="conv4x4")
-    assert _layout(p.state_dict()) == before and p.downsample_form == "unshuffle"
+    assert H.state_layout(p.state_dict()) == before and p.downsample_form == "unshuffle"
     assert type(p.downs[0][4]).__name__ == "CrossEmbedLayer"
 
 

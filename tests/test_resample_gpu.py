@@ -2,7 +2,7 @@
 torch, the UNet forward and both samplers with `cross_embed_downsample=True` / `pixel_shuffle_upsample=False` against the
 restatement in tests/resample_ref.py, graph / eager bit identity, a default UNet's plan through the extended
 kd_unet_ext_t, and a strict ImagenTrainer.load."""
-import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -23,25 +23,15 @@ SWITCHES = {"cross_embed": dict(cross_embed_downsample=True), "nearest": dict(pi
             "both": dict(cross_embed_downsample=True, pixel_shuffle_upsample=False)}
 
 
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 # ------------------------------------------------------------------------------- the kernel
 @pytest.mark.parametrize("B,Hh,Ww,Cin,Cout", [(2, 8, 8, 32, 64), (1, 4, 12, 96, 32), (3, 16, 16, 64, 128)])
 def test_upsample_nearest_conv3x3_matches_fp64(device, B, Hh, Ww, Cin, Cout):
     """Dense, and into channels [0, Cout) and [32, 32 + Cout) of rows of Cout + 32 floats whose other channels must stay as
     they were.  (2, 8, 8): half a tile in x, the border taps of every phase; (1, 4, 12): half a tile in y, a partial one in
     x, three k-steps per input pixel row, one column tile; (3, 16, 16): two row tiles per image, two column tiles."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
-    g = _g(Hh * Ww + Cin)
+    g = H.gen(Hh * Ww + Cin)
     x = torch.randn(B, Hh, Ww, Cin, generator=g)
     w = torch.randn(Cout, Cin, 3, 3, generator=g) * (9 * Cin) ** -0.5
     bias = torch.randn(Cout, generator=g)
@@ -79,49 +69,7 @@ TEXT = dict(dim=32, dim_mults=(1, 2, 4), cond_dim=64, text_embed_dim=3, num_resn
             layer_cross_attns=(False, True, True))
 
 
-def _ref_unet(kw, lowres=False, seed=0, text=False, **extra):
-    tk = dict(cond_on_text=True) if text else dict(cond_on_text=False, text_embed_dim=None)
-    return H.randomize_(RR.Unet(**{**kw, **tk, **extra}, lowres_cond=lowres), seed).eval()
-
-
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
-def _inputs(ou, B, S, seed):
-    g = _g(seed)
-    x = torch.randn(B, 3, S, S, generator=g)
-    t = torch.randn(B, generator=g) * 3
-    kw = {}
-    if ou.lowres_cond:
-        kw.update(lowres_cond_img=torch.randn(B, 3, S, S, generator=g), lowres_noise_times=torch.full((B,), 1.5))
-    if ou.self_cond:
-        kw["self_cond"] = torch.rand(B, 3, S, S, generator=g) * 2 - 1
-    if ou.cond_on_text:
-        kw["text_embeds"] = torch.randn(B, 2, 3, generator=g)
-    return x, t, kw
-
-
-def _forward_err(ou, device, B, S, seed=3):
-    pu = _product_like(ou, device)
-    x, t, kw = _inputs(ou, B, S, seed)
-    with torch.no_grad():
-        ref = ou(x, t, **kw)
-    dv = {k: v.to(device) for k, v in kw.items()}
-    got = pu(x.to(device), t.to(device), **dv).cpu()
-    assert torch.equal(got, pu(x.to(device), t.to(device), **dv).cpu())   # no atomics: run-to-run bit-identical
-    return H.rel_l2(got, ref), pu
-
-
-def _labels(pu, B, S, device, with_text=False):
-    E = _E()
-    buf = C.create_string_buffer(1 << 20)
-    E.check(E.load().kd_unet_profile(pu.engine(B, S, device, with_text=with_text), 1, buf, len(buf), E.current_stream()))
-    return buf.value.decode()
+_ref_unet = functools.partial(H.ref_unet, RR.Unet)
 
 
 @pytest.mark.parametrize("B", [2, 3])
@@ -131,10 +79,10 @@ def test_unet_forward_matches_the_restatement(device, sw, mem, B):
     """memory_efficient adds the pre-downsample position (downs.L.0, three CrossEmbedLayers) and the last level's upsample
     (into the first half of the concat in front of final_res_block when init_conv_to_final_conv_residual is on)."""
     ou = _ref_unet(SMALL, seed=11, memory_efficient=mem, init_conv_to_final_conv_residual=mem, **SWITCHES[sw])
-    e, pu = _forward_err(ou, device, B, 32)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, B, 32, seed=3))
     print(f"resample forward {sw} mem={mem} B={B}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, B, 32, device)
+    labels = H.plan_csv(pu, B, 32, device)
     n_up = 3 if mem else 2
     assert labels.count("upsample nearest conv3") == (n_up if "pixel_shuffle_upsample" in SWITCHES[sw] else 0)
     if "cross_embed_downsample" in SWITCHES[sw]:
@@ -146,10 +94,10 @@ def test_unet_forward_dim128_runs_the_2x2_half_where_the_plan_says(device):
     below the 64 whole tiles of 256 x 128 the bf16x3 kernel's epilogue form asks for, so the plan must have taken the generic
     conv for both (rows "conv k2 s2"), and none of the bf16x3 downsample rows ("conv k2 x3")."""
     ou = _ref_unet(WIDE, seed=12, **SWITCHES["both"])
-    e, pu = _forward_err(ou, device, 4, 64)
+    e, pu = H.forward_err(ou, device, *H.unet_inputs(ou, 4, 64, seed=3))
     print(f"resample forward dim128 both B=4: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, 4, 64, device)
+    labels = H.plan_csv(pu, 4, 64, device)
     assert labels.count("conv k2 s2") == 2 and labels.count("conv k4 s2") == 2 and "conv k2 x3" not in labels
     assert labels.count("upsample nearest conv3") == 2
 
@@ -158,12 +106,12 @@ def test_unet_forward_dim128_runs_the_2x2_half_where_the_plan_says(device):
 def test_unet_forward_with_conditioning_matches_the_restatement(device, case):
     both = SWITCHES["both"]
     if case == "lowres":
-        ou = _ref_unet(SMALL, lowres=True, seed=13, memory_efficient=True, **both)
+        ou = _ref_unet(SMALL, lowres_cond=True, seed=13, memory_efficient=True, **both)
     elif case == "self_cond":
         ou = _ref_unet(SMALL, seed=14, self_cond=True, **both)
     else:
         ou = _ref_unet(TEXT, seed=15, text=True, **both)
-    e, _ = _forward_err(ou, device, 2, 32)
+    e, _ = H.forward_err(ou, device, *H.unet_inputs(ou, 2, 32, seed=3))
     print(f"resample forward both + {case}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
 
@@ -171,10 +119,10 @@ def test_unet_forward_with_conditioning_matches_the_restatement(device, case):
 def test_default_unet_through_the_extended_ext_keeps_its_plan(device):
     """A default UNet built through kd_unet_create_ext with the two new fields zero has the launches and the bits of the
     plan kd_unet_create_shared builds."""
-    lib = _E().load()
-    ou = H.randomize_(RR.Unet(**H.UNET_KW["small2"], lowres_cond=True, cond_on_text=False, text_embed_dim=None), 4).eval()
-    a, b = _product_like(ou, device), _product_like(ou, device)
-    g = _g(5)
+    lib = H.engine().load()
+    ou = _ref_unet(H.UNET_KW["small2"], seed=4, lowres_cond=True)
+    a, b = H.product_like(ou, device), H.product_like(ou, device)
+    g = H.gen(5)
     x, t = torch.randn(2, 3, 32, 32, generator=g), torch.randn(2, generator=g)
     kw = dict(lowres_cond_img=torch.randn(2, 3, 32, 32, generator=g), lowres_noise_times=torch.full((2,), 1.5),
               cond_images=torch.rand(2, 3, 32, 32, generator=g))
@@ -188,7 +136,7 @@ def test_default_unet_through_the_extended_ext_keeps_its_plan(device):
         lib.kd_unet_create_ext = orig
     assert lib.kd_unet_num_launches(ha) == lib.kd_unet_num_launches(hb)
     assert torch.equal(a(x.to(device), t.to(device), **dv), b(x.to(device), t.to(device), **dv))
-    assert "upsample nearest" not in _labels(a, 2, 32, device) and "conv k4 s2" not in _labels(a, 2, 32, device)
+    assert "upsample nearest" not in H.plan_csv(a, 2, 32, device) and "conv k4 s2" not in H.plan_csv(a, 2, 32, device)
 
 
 # ------------------------------------------------------------------------------- sampling
@@ -198,17 +146,12 @@ SR2 = dict(dim=32, dim_mults=(1, 2), num_resnet_blocks=1, memory_efficient=True,
 
 
 def _cascade(device, cls_o, cls_p, seed, **kw):
-    import imagen_pytorch as ip
-
-    ous = [_ref_unet(BASE, seed=seed, **SWITCHES["both"]), _ref_unet(SR2, lowres=True, seed=seed + 1, **SWITCHES["both"])]
-    oim = cls_o(ous, image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim = getattr(ip, cls_p)([ip.Unet(**u._locals) for u in oim.unets], image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+    ous = [_ref_unet(BASE, seed=seed, **SWITCHES["both"]), _ref_unet(SR2, lowres_cond=True, seed=seed + 1, **SWITCHES["both"])]
+    return H.imagen_pair(device, cls_o, cls_p, ous, image_sizes=(32, 64), condition_on_text=False, **kw)
 
 
 def _inpaint(B, seed):
-    g = _g(seed)
+    g = H.gen(seed)
     inp = torch.rand(B, 3, 64, 64, generator=g)
     mask = torch.zeros(B, 64, 64, dtype=torch.bool)
     mask[:, 8:40, 12:60] = True

@@ -9,36 +9,19 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import helpers as H
+
 pytestmark = pytest.mark.gpu
 
 U24 = 2.0 ** -24   # one fp32 rounding, relative
 
 
+engine, g, dp, nan_dev = H.engine, H.gen, H.dev_ptr, H.nan_dev   # (H is the image height in the tests below)
+
+
 @pytest.fixture(scope="module")
 def lib():
-    from imagen_pytorch import _engine as E
-
-    return E.load()
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def dp(t):
-    """Device address of a (possibly strided, possibly fp64) tensor view: the entries take the strides as arguments."""
-    assert t is None or t.is_cuda
-    return None if t is None else t.data_ptr()
-
-
-def nan_dev(*shape, dtype=torch.float32):
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda:0")
+    return engine().load()
 
 
 def act64(v, act):
@@ -90,7 +73,7 @@ def _c3_stacked_time_mlp_width():
 
 @pytest.mark.parametrize("M,K,N,ldx,ldy,xoff,in_act,act", SKINNY)
 def test_linear_skinny_matches_fp64(lib, device, M, K, N, ldx, ldy, xoff, in_act, act):
-    E = _E()
+    E = engine()
     if N == "c3":
         N = _c3_stacked_time_mlp_width()
         assert N == 27648, N   # (the plan's label "skinny M16 K1024 N27648")
@@ -124,7 +107,7 @@ def test_linear_skinny_matches_fp64(lib, device, M, K, N, ldx, ldy, xoff, in_act
 
 
 def test_linear_skinny_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(64, device=device)
     for M, K, N, ldx, ldy, ia, a in [(0, 16, 16, 16, 16, 0, 0), (4, 16, 16, 8, 16, 0, 0), (4, 16, 16, 16, 8, 0, 0),
                                      (4, 16, 16, 16, 16, 4, 0), (4, 16, 16, 16, 16, 0, -1)]:
@@ -161,7 +144,7 @@ def _gca_ref(x, wk, bk, w0, b0, w2, b2):
 @pytest.mark.parametrize("B,HW,C", GCA_SHAPES)
 @pytest.mark.parametrize("logits", ["plain", "peaked", "uniform"])
 def test_global_context_gate_matches_fp64(lib, device, B, HW, C, logits):
-    E = _E()
+    E = engine()
     hid = max(3, C // 2)
     x = _gca_input(B, HW, C)
     gen = g(12)
@@ -216,7 +199,7 @@ def test_global_context_gate_matches_fp64(lib, device, B, HW, C, logits):
 
 
 def test_global_context_gate_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(4096, device=device)
     for B, HW, C, hid, path in [(2, 16, 1024, 512, 2), (2, 16, 640, 320, 2), (2, 16, 64, 32, 3), (2, 16, 66, 33, 1),
                                 (2, 16, 4096, 2048, 1), (0, 16, 64, 32, 1)]:
@@ -241,7 +224,7 @@ def _gate_add_rows_per_chunk(B, HW):
     (3, 77, 1280, True, 1280 + 64, 1280 + 128),   # 320 float4: a partial second pass
 ])
 def test_gate_add_and_its_partials_match_fp64(lib, device, B, HW, C, gate, ldr, ldy):
-    E = _E()
+    E = engine()
     ldr, ldy = ldr or C, ldy or C
     gen = g(21)
     a = torch.randn(B, HW, C, generator=gen)
@@ -284,7 +267,7 @@ def test_gate_add_and_its_partials_match_fp64(lib, device, B, HW, C, gate, ldr, 
 
 
 def test_gate_add_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(4096, device=device)
     s = torch.zeros(64, dtype=torch.float64, device=device)
     for C, ldr, ldy, seg, off in [(62, 0, 0, False, 0), (40, 0, 0, True, 0), (64, 32, 0, False, 0), (64, 0, 66, False, 0),
@@ -322,7 +305,7 @@ def _gn_ref(xcat, G, eps):
     pytest.param(2, 512, 256, 256, 32, 8, 8, 2 ** -0.5, 2 ** -0.5, True, 36.0, id="mean-30x-std"),
 ])
 def test_gn_fold_seg_matches_fp64(lib, device, B, HW, C0, C1, nch0, nch1, G, scale1, abm, film, offset):
-    E = _E()
+    E = engine()
     C = C0 + C1
     gen = g(31)
     x0 = torch.randn(B, HW, C0, generator=gen) * 1.3 + 0.2 + offset
@@ -378,7 +361,7 @@ def test_gn_fold_seg_matches_fp64(lib, device, B, HW, C0, C1, nch0, nch1, G, sca
 
 
 def test_gn_fold_seg_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(4096, device=device)
     s = torch.zeros(4096, dtype=torch.float64, device=device)
     for nseg0, nseg1, C, G, seg1, ld_ss in [(4, 0, 64, 8, False, 0), (4, 0, 48, 1, False, 0), (2, 2, 64, 2, False, 0),
@@ -463,7 +446,7 @@ def _check_out_seg(tag, seg, y):
 
 @pytest.mark.parametrize("B,H,Cx,Cs,sscale,Cout,mode,ips", CHAIN)
 def test_resnet_block_winograd4_chain_matches_fp64(lib, device, B, H, Cx, Cs, sscale, Cout, mode, ips):
-    E = _E()
+    E = engine()
     W, Cin, G, eps = H, Cx + Cs, 8, 1e-5
     key = (B, H, Cx, Cs, sscale, Cout)
     gen = g(41)
@@ -539,7 +522,7 @@ def test_resnet_block_winograd4_chain_matches_fp64(lib, device, B, H, Cx, Cs, ss
 
 
 def test_gn_conv3x3_winograd4_rejects_unsupported_shapes(lib, device):
-    E = _E()
+    E = engine()
     t = torch.zeros(4096, device=device)
     for B, H, Cin, Cout, mode, ips, ldx, skip_c0 in [
             (1, 18, 128, 128, -1, 0, 0, -1),     # H % 4

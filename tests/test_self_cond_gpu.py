@@ -2,6 +2,7 @@
 UNet forward and both samplers against the restatement in tests/self_cond_ref.py, and the engine's carried estimate
 (graph / eager, conditioning table, split step ranges, kd_sample_set_self_cond, launch counts)."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -17,16 +18,7 @@ pytestmark = pytest.mark.gpu
 CONV_REL = 2e-6      # as test_kernels_gpu.py
 FWD_REL_L2 = 2e-5
 SAMPLE_ABS = 2e-3
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
+DDPM, EDM = (SR.Imagen, "Imagen"), (SR.ElucidatedImagen, "ElucidatedImagen")   # (restatement, product class) of H.imagen_pair
 
 
 # ------------------------------------------------------------------------------- the kernel
@@ -39,15 +31,15 @@ def _g(seed):
 def test_init_conv_six_planes(device, B, S, n3, n7, n15, with_res):
     """The per-step share of a self-conditioned UNet's init convs: planes x | self_cond (input channels c0 .. c0 + 5 of
     weights over 8 channels) in one launch, + bias or + a step-invariant residual, against torch conv2d in fp64."""
-    E = _E()
+    E = H.engine()
     lib = E.load()
     Itot, c0, C_ = 8, 2, n3 + n7 + n15
-    x = torch.randn(B, 3, S, S, generator=_g(1))
-    sc = torch.rand(B, 3, S, S, generator=_g(2)) * 2 - 1
-    ws = [torch.randn(n, Itot, k, k, generator=_g(10 + k)) * (6 * k * k) ** -0.5 for n, k in ((n3, 3), (n7, 7), (n15, 15))]
+    x = torch.randn(B, 3, S, S, generator=H.gen(1))
+    sc = torch.rand(B, 3, S, S, generator=H.gen(2)) * 2 - 1
+    ws = [torch.randn(n, Itot, k, k, generator=H.gen(10 + k)) * (6 * k * k) ** -0.5 for n, k in ((n3, 3), (n7, 7), (n15, 15))]
     inp = torch.cat((x, sc), 1)
-    res = torch.randn(B, S, S, C_, generator=_g(5)) if with_res else None
-    b = None if with_res else torch.randn(C_, generator=_g(4))
+    res = torch.randn(B, S, S, C_, generator=H.gen(5)) if with_res else None
+    b = None if with_res else torch.randn(C_, generator=H.gen(4))
     add = (res.permute(0, 3, 1, 2) if with_res else b[None, :, None, None])
     parts64 = [F.conv2d(inp.double(), w[:, c0:c0 + 6].double(), padding=w.shape[-1] // 2) for w in ws]
     ref = torch.cat(parts64, 1) + add.double()
@@ -70,19 +62,7 @@ def test_init_conv_six_planes(device, B, S, n3, n7, n15, with_res):
 
 
 # ------------------------------------------------------------------------------- the UNet forward
-def _ref_unet(kw, lowres=False, seed=0, self_cond=True, text=False):
-    extra = dict(cond_on_text=False, text_embed_dim=None) if not text else dict(cond_on_text=True)
-    return H.randomize_(SR.Unet(**kw, lowres_cond=lowres, self_cond=self_cond, **extra), seed).eval()
-
-
-def _product_like(ou, device):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    return u.to(device)
-
-
+_ref_unet = functools.partial(H.ref_unet, SR.Unet, self_cond=True)
 ULTRA2 = dict(dim=128, dim_mults=(1, 2, 4, 8), num_resnet_blocks=2, memory_efficient=True,
               layer_attns=(False, False, False, True), layer_cross_attns=(False, False, True, True),
               init_conv_to_final_conv_residual=True, cond_images_channels=3)   # train_ultra_res.py:39-48
@@ -98,11 +78,11 @@ def test_unet_forward_with_self_cond_matches_the_restatement(device, case):
         kw, lowres, B, S = ULTRA2, True, 16, 64
     else:
         kw, lowres, B, S = H.UNET_KW["small2"], True, 2, 48 if case == "sr_generic" else 32
-    ou = _ref_unet(kw, lowres=lowres, seed=11)
+    ou = _ref_unet(kw, lowres_cond=lowres, seed=11)
     if case == "ultra2_b16":
         ou = H.fast_oracle(ou)
-    pu = _product_like(ou, device)
-    g = _g(3)
+    pu = H.product_like(ou, device)
+    g = H.gen(3)
     x = torch.randn(B, 3, S, S, generator=g)
     sc = torch.rand(B, 3, S, S, generator=g) * 2 - 1
     t = torch.randn(B, generator=g) * 3
@@ -124,31 +104,21 @@ def test_unet_forward_with_self_cond_matches_the_restatement(device, case):
 
 
 def test_fused_plan_has_the_plain_plans_launch_count(device):
-    E = _E()
+    E = H.engine()
     lib = E.load()
     counts = []
     for self_cond in (False, True):
-        pu = _product_like(_ref_unet(H.UNET_KW["small2"], lowres=True, seed=2, self_cond=self_cond), device)
+        pu = H.product_like(_ref_unet(H.UNET_KW["small2"], lowres_cond=True, seed=2, self_cond=self_cond), device)
         h = pu.engine(2, 32, device, with_text=False)
         counts.append(lib.kd_unet_num_launches(h))
     assert counts[0] == counts[1]
 
 
 # ------------------------------------------------------------------------------- DDPM sampling
-def _ddpm_pair(device, unets, sizes, **kw):
-    import imagen_pytorch as ip
-
-    oim = SR.Imagen(unets, image_sizes=sizes, **kw)
-    pu = [ip.NullUnet() if isinstance(u, R.NullUnet) else ip.Unet(**u._locals) for u in oim.unets]
-    pim = ip.Imagen(pu, image_sizes=sizes, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
-
-
 @pytest.mark.parametrize("objective,dyn", [("noise", True), ("v", False), ("v", True)])
 def test_ddpm_base_sampling_matches_the_restatement(device, objective, dyn):
-    oim, pim = _ddpm_pair(device, [_ref_unet(H.UNET_KW["small1"], seed=21)], (32,), timesteps=(4,),
-                          pred_objectives=(objective,), dynamic_thresholding=(dyn,), condition_on_text=False)
+    oim, pim = H.imagen_pair(device, *DDPM, [_ref_unet(H.UNET_KW["small1"], seed=21)], image_sizes=(32,),
+                             timesteps=(4,), pred_objectives=(objective,), dynamic_thresholding=(dyn,), condition_on_text=False)
     nf = RS.generator_noise_fn(31)
     ref = oim.sample(noise_fn=nf, batch_size=2)
     got = pim.sample(noise_fn=nf, batch_size=2, device=device).cpu()
@@ -160,10 +130,11 @@ def test_ddpm_base_sampling_matches_the_restatement(device, objective, dyn):
 def test_ddpm_sr_stage_with_inpainting_matches_the_restatement(device):
     """Mixed cascade (only unet2 self-conditioned), SR + cond images + inpainting with R = 2: x_start carries across
     resamples."""
-    u2 = _ref_unet(H.UNET_KW["small2"], lowres=True, seed=22)
-    oim, pim = _ddpm_pair(device, [R.NullUnet(), u2], (16, 32), timesteps=(3, 3), condition_on_text=False)
+    u2 = _ref_unet(H.UNET_KW["small2"], lowres_cond=True, seed=22)
+    oim, pim = H.imagen_pair(device, *DDPM, [R.NullUnet(), u2], image_sizes=(16, 32), timesteps=(3, 3),
+                             condition_on_text=False)
     assert pim.unets[1].self_cond
-    g = _g(8)
+    g = H.gen(8)
     B = 2
     start = torch.rand(B, 3, 16, 16, generator=g)
     cond = torch.rand(B, 3, 32, 32, generator=g)
@@ -188,9 +159,9 @@ SEG_KW = dict(dim=32, dim_mults=(1, 2, 3, 4), cond_dim=64, text_embed_dim=3, num
 
 def test_ddpm_text_guided_sampling_matches_the_restatement(device):
     ou = _ref_unet(SEG_KW, seed=17, text=True)
-    oim, pim = _ddpm_pair(device, [ou], (32,), timesteps=(3,), text_embed_dim=3)
+    oim, pim = H.imagen_pair(device, *DDPM, [ou], image_sizes=(32,), timesteps=(3,), text_embed_dim=3)
     B = 2
-    g = _g(3)
+    g = H.gen(3)
     text = torch.tensor([0.0, 0.5, 0.2]).reshape(1, 1, 3).repeat_interleave(B, dim=0)
     labels = F.one_hot(torch.randint(0, 4, (B, 32, 32), generator=g), 4).permute(0, 3, 1, 2).float()
     nf = RS.generator_noise_fn(5)
@@ -203,19 +174,9 @@ def test_ddpm_text_guided_sampling_matches_the_restatement(device):
 
 
 # ------------------------------------------------------------------------------- EDM sampling
-def _edm_pair(device, unets, sizes, **kw):
-    import imagen_pytorch as ip
-
-    oim = SR.ElucidatedImagen(unets, image_sizes=sizes, **kw)
-    pu = [ip.NullUnet() if isinstance(u, R.NullUnet) else ip.Unet(**u._locals) for u in oim.unets]
-    pim = ip.ElucidatedImagen(pu, image_sizes=sizes, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
-
-
 def test_edm_base_sampling_matches_the_restatement(device):
-    oim, pim = _edm_pair(device, [_ref_unet(H.UNET_KW["small1"], seed=23)], (32,), condition_on_text=False,
-                         num_sample_steps=4)
+    oim, pim = H.imagen_pair(device, *EDM, [_ref_unet(H.UNET_KW["small1"], seed=23)],
+                             image_sizes=(32,), condition_on_text=False, num_sample_steps=4)
     nf = RS.generator_noise_fn(13)
     ref = oim.sample(noise_fn=nf, batch_size=2)
     got = pim.sample(noise_fn=nf, batch_size=2, device=device).cpu()
@@ -225,10 +186,10 @@ def test_edm_base_sampling_matches_the_restatement(device):
 
 
 def test_edm_sr_stage_with_inpainting_matches_the_restatement(device):
-    u2 = _ref_unet(H.UNET_KW["small2"], lowres=True, seed=24)
-    oim, pim = _edm_pair(device, [R.NullUnet(), u2], (16, 32), condition_on_text=False, num_sample_steps=3,
-                         sigma_max=(80, 320))
-    g = _g(9)
+    u2 = _ref_unet(H.UNET_KW["small2"], lowres_cond=True, seed=24)
+    oim, pim = H.imagen_pair(device, *EDM, [R.NullUnet(), u2], image_sizes=(16, 32),
+                             condition_on_text=False, num_sample_steps=3, sigma_max=(80, 320))
+    g = H.gen(9)
     B = 2
     start = torch.rand(B, 3, 16, 16, generator=g)
     cond = torch.rand(B, 3, 32, 32, generator=g)
@@ -251,14 +212,15 @@ def test_graph_equals_eager_table_on_equals_off_and_split_ranges_equal_one_call(
     """Bit for bit: captured graph against eager launches, the conditioning table on against off, and per-step calls
     (trace: kd_sample_steps(k, k + 1), continuing from the estimate the plan holds) against one kd_sample_loop; for the
     DDPM and the EDM sampler."""
-    u = _ref_unet(H.UNET_KW["small2"], lowres=True, seed=25)
-    for make in (lambda: _ddpm_pair(device, [R.NullUnet(), u], (16, 32), timesteps=(4, 4), condition_on_text=False),
-                 lambda: _edm_pair(device, [R.NullUnet(), u], (16, 32), condition_on_text=False, num_sample_steps=4)):
+    u = _ref_unet(H.UNET_KW["small2"], lowres_cond=True, seed=25)
+    ikw = dict(image_sizes=(16, 32), condition_on_text=False)
+    for make in (lambda: H.imagen_pair(device, *DDPM, [R.NullUnet(), u], timesteps=(4, 4), **ikw),
+                 lambda: H.imagen_pair(device, *EDM, [R.NullUnet(), u], num_sample_steps=4, **ikw)):
         _, pim = make()
-        start = torch.rand(2, 3, 16, 16, generator=_g(1)).to(device)
+        start = torch.rand(2, 3, 16, 16, generator=H.gen(1)).to(device)
         nf = RS.generator_noise_fn(7)
         kw = dict(noise_fn=nf, batch_size=2, start_at_unet_number=2, start_image_or_video=start,
-                  cond_images=torch.rand(2, 3, 32, 32, generator=_g(2)).to(device), device=device)
+                  cond_images=torch.rand(2, 3, 32, 32, generator=H.gen(2)).to(device), device=device)
         runs = {}
         for use_graph in (True, False):
             for table in (0, -1):
@@ -272,10 +234,10 @@ def test_graph_equals_eager_table_on_equals_off_and_split_ranges_equal_one_call(
 
 
 def test_set_self_cond_then_one_step_matches_one_restated_step(device):
-    E = _E()
+    E = H.engine()
     lib = E.load()
     ou = _ref_unet(H.UNET_KW["small1"], seed=26)
-    oim, pim = _ddpm_pair(device, [ou], (32,), timesteps=(5,), condition_on_text=False)
+    oim, pim = H.imagen_pair(device, *DDPM, [ou], image_sizes=(32,), timesteps=(5,), condition_on_text=False)
     pu = pim.unets[0]
     B, S, T, k = 2, 32, 5, 2
     h = pu.engine(B, S, device, with_text=False)
@@ -284,7 +246,7 @@ def test_set_self_cond_then_one_step_matches_one_restated_step(device):
     sc.T = T
     for name, v in tables.items():
         setattr(sc, name, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
-    g = _g(6)
+    g = H.gen(6)
     noise = torch.randn(T, B, 3, S, S, generator=g)
     x = torch.randn(B, 3, S, S, generator=g)
     xs = torch.rand(B, 3, S, S, generator=g) * 2 - 1
@@ -319,16 +281,16 @@ def test_zeroed_self_cond_weights_sample_like_the_plain_unet(device):
     with torch.no_grad():
         for i in range(3):
             ou.init_conv.convs[i].weight[:, SR.self_cond_channels(ou)] = 0.0
-    plain = R.Unet(**H.UNET_KW["small1"], cond_on_text=False, text_embed_dim=None).eval()
+    plain = R.Unet(**H.UNET_KW["small1"], **H.NOTEXT).eval()
     plain.load_state_dict(SR.plain_state_dict(ou.state_dict(), ou), strict=True)
     nf = RS.generator_noise_fn(15)
-    for pair, tol in ((_ddpm_pair, 1e-5), (_edm_pair, 5e-4)):
-        kw = dict(timesteps=(4,)) if pair is _ddpm_pair else dict(num_sample_steps=4)
-        _, a = pair(device, [ou], (32,), condition_on_text=False, **kw)
-        _, b = pair(device, [plain], (32,), condition_on_text=False, **kw)
+    for cls, tol in ((DDPM, 1e-5), (EDM, 5e-4)):
+        kw = dict(timesteps=(4,)) if cls is DDPM else dict(num_sample_steps=4)
+        _, a = H.imagen_pair(device, *cls, [ou], image_sizes=(32,), condition_on_text=False, **kw)
+        _, b = H.imagen_pair(device, *cls, [plain], image_sizes=(32,), condition_on_text=False, **kw)
         assert a.unets[0].self_cond and not b.unets[0].self_cond
         sa = a.sample(noise_fn=nf, batch_size=2, device=device).cpu()
         sb = b.sample(noise_fn=nf, batch_size=2, device=device).cpu()
         err = float((sa - sb).abs().max())
-        print(f"{pair.__name__}: zeroed self-cond weights vs plain: max|diff| {err:.2e}")
+        print(f"{cls[1]}: zeroed self-cond weights vs plain: max|diff| {err:.2e}")
         assert err < tol

@@ -38,10 +38,6 @@ def E():
     return _engine
 
 
-def g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 def guarded(n, device, fill=None):
     """(buffer, region): n floats between two NaN guards; the region is NaN too unless `fill` [n] is given."""
     buf = torch.full((GUARD + n + GUARD,), NAN, device=device)
@@ -114,8 +110,8 @@ def test_text_select_is_bit_equal_to_where(E, device, B, L, P, Cd, kind):
     the L tokens are kept and the rows from L on are the zero padding.  tok has no rows past L, null_embed is random per
     position."""
     lib = E.load()
-    tok = torch.randn(B, L, Cd, generator=g(1))
-    null = torch.randn(P, Cd, generator=g(2))
+    tok = torch.randn(B, L, Cd, generator=H.gen(1))
+    null = torch.randn(P, Cd, generator=H.gen(2))
     mask = _select_mask(kind, B, L)
     # tok and mask lie at the very end of their allocations' used part, NaN behind them: a read of row L poisons the output
     tbuf, tdev = guarded(B * L * Cd, device, tok)
@@ -152,8 +148,8 @@ def test_text_select_rejects_more_tokens_than_positions(E, device):
 def test_add_rows_bcast_is_bit_equal_to_torch(E, device, B, R, Cd):
     lib = E.load()
     assert (B, R, Cd) != (5, 256, 1024) or B * R * Cd > 4096 * 256
-    x = torch.randn(B, R, Cd, generator=g(3))
-    add = torch.randn(R, Cd, generator=g(4))   # random per row: an index taken % C instead of % (R C) shows
+    x = torch.randn(B, R, Cd, generator=H.gen(3))
+    add = torch.randn(R, Cd, generator=H.gen(4))   # random per row: an index taken % C instead of % (R C) shows
     n = B * R * Cd
     obuf, out = guarded(n, device)
     xd, ad = x.to(device), add.to(device)
@@ -169,7 +165,7 @@ def test_mean_rows_matches_fp64(E, device, B, R, Cd):
     """Sequential fp32 summation of R terms: |error of the sum| <= (R - 1) 2^-24 sum|x| to first order, so the mean is within
     R 2^-24 mean|x|, plus one rounding of the result (the division)."""
     lib = E.load()
-    x = torch.randn(B, R, Cd, generator=g(5)) + 0.5
+    x = torch.randn(B, R, Cd, generator=H.gen(5)) + 0.5
     obuf, out = guarded(B * Cd, device)
     xd = x.to(device)
     E.check(lib.kd_mean_rows(E.ptr(xd), E.ptr(out), B, R, Cd, E.current_stream()))
@@ -190,7 +186,7 @@ def test_copy_rows_broadcasts_the_latents_behind_the_mean_pooled_rows(E, device)
     lib = E.load()
     B, n_mp, n_lat, Cd = 3, 4, 32, 64
     ntok = n_mp + n_lat
-    lat = torch.randn(n_lat, Cd, generator=g(6))
+    lat = torch.randn(n_lat, Cd, generator=H.gen(6))
     obuf, out = guarded(B * ntok * Cd, device)
     ld = lat.to(device)
     E.check(lib.kd_copy_rows(E.ptr(ld), 0, Cd, fptr(out, n_mp * Cd), ntok * Cd, Cd, n_lat, Cd, B, E.current_stream()))
@@ -205,7 +201,7 @@ def test_copy_rows_with_unequal_row_and_batch_strides(E, device):
     lib = E.load()
     B, rows, Cd, lds, ldd = 3, 5, 24, 32, 28
     sbs, dbs = rows * lds + 16, rows * ldd + 8
-    src = torch.randn(B * sbs, generator=g(7))
+    src = torch.randn(B * sbs, generator=H.gen(7))
     obuf, out = guarded(B * dbs, device)
     sd = src.to(device)
     E.check(lib.kd_copy_rows(E.ptr(sd), sbs, lds, E.ptr(out), dbs, ldd, rows, Cd, B, E.current_stream()))
@@ -226,7 +222,7 @@ def test_copy_rows_of_one_row(E, device, bcast):
     drop - from null_text_hidden with batch stride 0."""
     lib = E.load()
     B, Cd = 3, 128
-    src = torch.randn(1 if bcast else B, Cd, generator=g(8))
+    src = torch.randn(1 if bcast else B, Cd, generator=H.gen(8))
     obuf, out = guarded(B * Cd, device)
     sd = src.to(device)
     E.check(lib.kd_copy_rows(E.ptr(sd), 0 if bcast else Cd, Cd, E.ptr(out), Cd, Cd, 1, Cd, B, E.current_stream()))
@@ -237,7 +233,7 @@ def test_copy_rows_of_one_row(E, device, bcast):
 @pytest.mark.parametrize("rows,Cd,B", [(0, 16, 2), (4, 0, 2), (4, 16, 0)])
 def test_copy_rows_of_nothing_writes_nothing(E, device, rows, Cd, B):
     lib = E.load()
-    src = torch.randn(256, generator=g(9)).to(device)
+    src = torch.randn(256, generator=H.gen(9)).to(device)
     obuf, out = guarded(256, device)
     E.check(lib.kd_copy_rows(E.ptr(src), 64, 16, E.ptr(out), 64, 16, rows, Cd, B, E.current_stream()))
     assert torch.isnan(obuf.cpu()).all()
@@ -253,8 +249,8 @@ def test_cfg_combine_matches_fp64(E, device, n, alias):
     """out = null + (cond - null) * scale: three fp32 roundings (difference, product, sum; two under a contracted
     multiply-add), each at most 2^-24 of a term no larger than |null| + |scale| |cond - null|.  Scale 0 returns null."""
     lib = E.load()
-    cond = torch.randn(n, generator=g(10))
-    null = torch.randn(n, generator=g(11)) * 0.7 + 0.2
+    cond = torch.randn(n, generator=H.gen(10))
+    null = torch.randn(n, generator=H.gen(11)) * 0.7 + 0.2
     nd = null.to(device)
     c64, n64 = cond.double(), null.double()
     for scale in CFG_SCALES:
@@ -355,7 +351,7 @@ def _engine(pu, device, text, mask, drop):
 
 def _check_against_oracle(pairs, device, ted, P, L, kind, qk=0):
     ou, ou64, pu = pairs(ted, P, qk)
-    text = torch.randn(BATCH, L, ted, generator=g(100 + L))
+    text = torch.randn(BATCH, L, ted, generator=H.gen(100 + L))
     mask = _branch_mask(kind, L, P)
     for drop in (False, True):
         tok64, hid64 = _oracle(ou64, text, mask, drop)
@@ -414,7 +410,7 @@ def test_text_mask_none_keeps_the_zero_padding(pairs, device):
     null_text_embed into the rows from L on)."""
     ted, P, L = 3, 8, 3
     ou, ou64, pu = pairs(ted, P)
-    text = torch.randn(BATCH, L, ted, generator=g(100 + L))
+    text = torch.randn(BATCH, L, ted, generator=H.gen(100 + L))
     tok_none, hid_none = _engine(pu, device, text, None, False)
     tok_ones, hid_ones = _engine(pu, device, text, torch.ones(BATCH, L, dtype=torch.bool), False)
     r_none, _ = _oracle(ou64, text, None, False)
@@ -425,7 +421,7 @@ def test_text_mask_none_keeps_the_zero_padding(pairs, device):
     assert gap > 1e-2, "the two calls must be different functions for this test to mean anything"
     assert H.rel_l2(tok_none, r_none) < 1e-4 * gap and H.rel_l2(tok_ones, r_ones) < 1e-4 * gap
     # at L == max_text_len there is no padding and the two calls are one
-    text8 = torch.randn(BATCH, P, ted, generator=g(108))
+    text8 = torch.randn(BATCH, P, ted, generator=H.gen(108))
     a = _engine(pu, device, text8, None, False)
     b = _engine(pu, device, text8, torch.ones(BATCH, P, dtype=torch.bool), False)
     assert bit_equal(a[0], b[0]) and bit_equal(a[1], b[1])

@@ -18,14 +18,8 @@ SAMPLE_ABS = 2e-3
 
 
 def _pair(device, seed=5, T=4):
-    import imagen_pytorch as ip
-
-    ou = H.oracle_unet("small1", seed=seed)
-    oim = RS.Imagen([ou], image_sizes=(16,), timesteps=(T,), pred_objectives=("noise",), condition_on_text=False)
-    pim = ip.Imagen([ip.Unet(**oim.unets[0]._locals)], image_sizes=(16,), timesteps=(T,), pred_objectives=("noise",),
-                    condition_on_text=False)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+    return H.imagen_pair(device, RS.Imagen, "Imagen", [H.oracle_unet("small1", seed=seed)], image_sizes=(16,), timesteps=(T,),
+                         pred_objectives=("noise",), condition_on_text=False)
 
 
 def test_trainer_load_and_sample_use_the_ema_weights(device, tmp_path):

@@ -44,15 +44,14 @@ selfcond128 10 F(4x4,3x3) layers on bf16x3 (V as fp32) + 16 F(2x2,3x3) GEMM laye
 wino4_all 18 F(4x4,3x3) layers, wino4_sets2 36 launch sets (20 on bf16x3), wino_fused 30 fused layers, x3_linear128 two
 token GEMMs on bf16x3.
 """
-import ctypes as C
 import json
 from pathlib import Path
 
 import pytest
 import torch
 
+import helpers as H
 import trajectory_ref as TR
-from oracle import imagen_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -78,14 +77,8 @@ def oracle():
 
 def _product(case, device, plan):
     """The product sampler over the oracle's weights, its sampled UNet set to the plan variant."""
-    import imagen_pytorch as ip
-
-    oim = case.imagen
-    pus = [ip.NullUnet() if isinstance(u, R.NullUnet) else ip.Unet(**u._locals) for u in oim.unets]
-    cls = ip.ElucidatedImagen if case.cfg["sampler"] == "edm" else ip.Imagen
-    pim = cls(pus, **case.imagen_kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    pim = pim.to(device)
+    cls = "ElucidatedImagen" if case.cfg["sampler"] == "edm" else "Imagen"
+    pim = H.product_imagen(case.imagen, cls, device, **case.imagen_kw)
     for k, v in TR.PLANS[plan].items():
         setattr(pim.unets[-1], k, v)
     return pim
@@ -96,10 +89,8 @@ def _sample(pim, case, device, **kw):
     return pim.sample(noise_fn=case.noise_fn(), device=device, **skw, **kw).cpu()
 
 
-def _labels(pim, case, device):
+def _case_labels(pim, case, device):
     """kd_unet_profile labels of the plan sample() will run: one forward at the configuration's batch and size first."""
-    from imagen_pytorch import _engine as E
-
     pu, B, S = pim.unets[-1], case.cfg["batch"], case.cfg["size"]
     g = torch.Generator().manual_seed(1)
     x, t = torch.randn(B, 3, S, S, generator=g).to(device), (torch.randn(B, generator=g) * 3).to(device)
@@ -109,13 +100,10 @@ def _labels(pim, case, device):
     if pu.has_cond_image:
         kw.update(cond_images=torch.rand(B, 3, S, S, generator=g).to(device))
     pu(x, t, **kw)
-    buf = C.create_string_buffer(1 << 20)
-    E.check(E.load().kd_unet_profile(pu.engine(B, S, device, with_text=False), 1, buf, len(buf), E.current_stream()))
-    return [row.split(",")[1] for row in buf.value.decode().strip().split("\n")[1:]]
+    return H.plan_labels(pu, B, S, device)
 
 
-def _count(labels, prefix):
-    return sum(l.startswith(prefix) for l in labels)
+_count = H.count_labels
 
 
 def _check_plan(plan, labels, default_labels):
@@ -152,7 +140,7 @@ _default_labels = {}
 
 def _labels_of_default(case, device):
     if case.name not in _default_labels:
-        _default_labels[case.name] = _labels(_product(case, device, "default"), case, device)
+        _default_labels[case.name] = _case_labels(_product(case, device, "default"), case, device)
     return _default_labels[case.name]
 
 
@@ -162,13 +150,13 @@ def test_trajectory_stays_inside_the_envelope(device, oracle, name, plan):
     env = ENV["configs"][name]
     T = case.T
     pim = _product(case, device, plan)
-    labels = _labels(pim, case, device)
+    labels = _case_labels(pim, case, device)
     print(f"\n{name}:")
     _check_plan(plan, labels, labels if plan == "default" else _labels_of_default(case, device))
     if case.cfg["unet"] is TR.MODEL_A:   # 256 queries x 8 heads x 4: launch_attention takes the matrix-core kernel from 128 queries
         assert _count(labels, "attn N256") >= 1
     if plan == "wino4_sets2":   # twice the launches of the whole-batch plan
-        assert _count(labels, "wino4 gemm") == 2 * _count(_labels(_product(case, device, "wino4_all"), case, device), "wino4 gemm")
+        assert _count(labels, "wino4 gemm") == 2 * _count(_case_labels(_product(case, device, "wino4_all"), case, device), "wino4 gemm")
     trace = []
     final = _sample(pim, case, device, trace=trace)
     assert len(trace) == T == len(env["rel"])

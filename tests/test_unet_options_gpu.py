@@ -6,7 +6,7 @@ structural options must build (kd_unet_profile labels, launch counts), both samp
 eager / conditioning-table bit identity, and a strict ImagenTrainer.load.  Bounds: the project's own (tests/test_unet_gpu.py).
 
 What the engine refuses is decided in Unet.__init__ and tested in tests/test_unet_options.py, never here."""
-import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -22,12 +22,6 @@ pytestmark = pytest.mark.gpu
 FWD_REL_L2 = 2e-5
 SAMPLE_ABS = 2e-3
 PLANS = {"default": {}, "fp32_mfma": dict(gemm_bf16x3=-1), "direct": dict(conv_algo=1)}
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
 
 
 @pytest.fixture(scope="module")
@@ -46,39 +40,20 @@ def oracle():
     return get
 
 
-def _product_like(ou, device, **plan):
-    import imagen_pytorch as ip
-
-    u = ip.Unet(**ou._locals)
-    u.load_state_dict(ou.state_dict(), strict=True)
-    for k, v in plan.items():   # engine extensions, read when the plan is built
-        setattr(u, k, v)
-    return u.to(device)
-
-
 def _forward_err(oracle, name, device, **plan):
     ou, (x, t, kw), ref = oracle(name)
-    pu = _product_like(ou, device, **plan)
-    dv = {k: v.to(device) for k, v in kw.items()}
-    got = pu(x.to(device), t.to(device), **dv).cpu()
-    assert torch.equal(got, pu(x.to(device), t.to(device), **dv).cpu())   # no atomics: run-to-run bit-identical
-    return H.rel_l2(got, ref), pu
+    return H.forward_err(ou, device, x, t, kw, ref=ref, **plan)
 
 
 def _handle(pu, case, device):
     return pu.engine(case["B"], case["S"], device, with_text=bool(case["text"]))
 
 
-def _labels(pu, case, device):
-    """The label column of kd_unet_profile (the strings of Builder's emit() calls, engine.hip), one per launch."""
-    E = _E()
-    buf = C.create_string_buffer(1 << 20)
-    E.check(E.load().kd_unet_profile(_handle(pu, case, device), 1, buf, len(buf), E.current_stream()))
-    return [row.split(",")[1] for row in buf.value.decode().strip().split("\n")[1:]]
+def _case_labels(pu, case, device):
+    return H.plan_labels(_handle(pu, case, device))
 
 
-def _count(labels, *prefixes):
-    return sum(l.startswith(prefixes) for l in labels)
+_count = H.count_labels
 
 
 def _check_gca_rows(pu, labels):
@@ -106,30 +81,30 @@ def test_without_global_context_only_final_res_block_is_gated(device, oracle, na
     or in the skip conv with block2's output as its residual - no GlobalContext launch and no gate_add but final_res_block's."""
     case = OC.ALL[name]
     ou, (x, t, kw), _ = oracle(name)
-    pu = _product_like(ou, device)
+    pu = H.product_like(ou, device)
     pu(x.to(device), t.to(device), **{k: v.to(device) for k, v in kw.items()})
-    labels = _labels(pu, case, device)
+    labels = _case_labels(pu, case, device)
     assert _check_gca_rows(pu, labels) == ["final_res_block"]
     assert _count(labels, "gate_add") == (0 if case["kw"].get("init_conv_to_final_conv_residual") else 1)
     # the same model with GlobalContext on has a gated launch per inner ResnetBlock more
-    on = _product_like(SR.Unet(**{**ou._locals, "use_global_context_attn": True}), device)
+    on = H.product_like(SR.Unet(**{**ou._locals, "use_global_context_attn": True}), device)
     on(x.to(device), t.to(device), **{k: v.to(device) for k, v in kw.items()})
-    assert len(_check_gca_rows(on, _labels(on, case, device))) > 1
+    assert len(_check_gca_rows(on, _case_labels(on, case, device))) > 1
 
 
 def test_attend_at_middle_off_drops_the_middle_transformer(device, oracle):
     case = OC.ALL["no_mid_attn"]
     ou, (x, t, kw), _ = oracle("no_mid_attn")
-    lib = _E().load()
-    off = _product_like(ou, device)
-    on = _product_like(SR.Unet(**{**ou._locals, "attend_at_middle": True}), device)
+    lib = H.engine().load()
+    off = H.product_like(ou, device)
+    on = H.product_like(SR.Unet(**{**ou._locals, "attend_at_middle": True}), device)
     n_off, n_on = (lib.kd_unet_num_launches(_handle(u, case, device)) for u in (off, on))
     print(f"options attend_at_middle: {n_on} launches with the middle TransformerBlock, {n_off} without")
     assert n_off < n_on
     rows = {}
     for key, u in (("off", off), ("on", on)):
         u(x.to(device), t.to(device))
-        rows[key] = _count(_labels(u, case, device), "attn N")
+        rows[key] = _count(_case_labels(u, case, device), "attn N")
     # self-attention launches: a TransformerBlock on the down and the up path of levels 1 and 2, and the middle one
     assert rows == {"off": 4, "on": 5}
 
@@ -149,9 +124,9 @@ def default_gn_rows(device):
     def get(case, inputs):
         if not done:
             x, t, _ = inputs
-            p8 = _product_like(SR.Unet(**case["base"], cond_on_text=False, text_embed_dim=None), device)
+            p8 = H.product_like(SR.Unet(**case["base"], **H.NOTEXT), device)
             p8(x.to(device), t.to(device))
-            done.append(_gn_rows(_labels(p8, case, device)))
+            done.append(_gn_rows(_case_labels(p8, case, device)))
         return done[0]
 
     return get
@@ -163,7 +138,7 @@ def test_fast_plan_forward_matches_the_oracle(device, oracle, default_gn_rows, n
     e, pu = _forward_err(oracle, name, device)
     print(f"options forward {name} B={case['B']}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, case, device)
+    labels = _case_labels(pu, case, device)
     n_stats, n_fold = _count(labels, "gn stats"), _count(labels, "gn fold seg")
     print(f"  {n_stats} 'gn stats' rows, {n_fold} 'gn fold seg' rows, {_count(labels, 'wino4_in')} F(4x4,3x3) layers, "
           f"{len(labels)} launches")
@@ -194,7 +169,7 @@ def test_fast_model_forward_on_the_other_plans(device, oracle, name, plan):
     e, pu = _forward_err(oracle, name, device, **PLANS[plan])
     print(f"options forward {name} plan {plan}: rel-L2 {e:.2e}")
     assert e < FWD_REL_L2
-    labels = _labels(pu, case, device)
+    labels = _case_labels(pu, case, device)
     if plan == "fp32_mfma":
         assert not any("x3" in l for l in labels), [l for l in labels if "x3" in l]
     else:
@@ -202,18 +177,12 @@ def test_fast_model_forward_on_the_other_plans(device, oracle, name, plan):
 
 
 # ------------------------------------------------------------------------------- c. sampling
-def _ref_unet(kw, seed, **extra):
-    return H.randomize_(SR.Unet(**{**kw, **extra}, cond_on_text=False, text_embed_dim=None), seed).eval()
+_ref_unet = functools.partial(H.ref_unet, SR.Unet)
 
 
 def _cascade(device, cls_o, cls_p, seed, **kw):
-    import imagen_pytorch as ip
-
-    ous = [_ref_unet(OC.BASE, seed), _ref_unet(OC.SR2, seed + 1, lowres_cond=True)]
-    oim = cls_o(ous, image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim = getattr(ip, cls_p)([ip.Unet(**u._locals) for u in oim.unets], image_sizes=(32, 64), condition_on_text=False, **kw)
-    pim.load_state_dict(oim.state_dict(), strict=True)
-    return oim, pim.to(device)
+    ous = [_ref_unet(OC.BASE, seed=seed), _ref_unet(OC.SR2, seed=seed + 1, lowres_cond=True)]
+    return H.imagen_pair(device, cls_o, cls_p, ous, image_sizes=(32, 64), condition_on_text=False, **kw)
 
 
 def test_ddpm_cascade_with_inpainting_matches_the_oracle(device):
@@ -260,7 +229,7 @@ def test_trainer_loads_a_checkpoint_of_the_base_unet_strictly_and_samples_from_i
     import imagen_pytorch as ip
 
     kw = dict(image_sizes=(32,), timesteps=(4,), condition_on_text=False)
-    online, ema_u = _ref_unet(OC.BASE, 61), _ref_unet(OC.BASE, 62)
+    online, ema_u = _ref_unet(OC.BASE, seed=61), _ref_unet(OC.BASE, seed=62)
     oim_online, oim_ema = RS.Imagen([online], **kw), RS.Imagen([ema_u], **kw)
     ema = {f"0.ema_model.{k}": v for k, v in ema_u.state_dict().items()}
     path = tmp_path / "ckpt.pt"

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import helpers as H
+
 pytestmark = pytest.mark.gpu
 
 U24 = 2.0 ** -24   # one fp32 rounding, relative
@@ -29,26 +31,12 @@ SHAPES = [  # (B, H, W, Cin, Cout): one set of images
 MODES = [pytest.param(2, id="v-fp32"), pytest.param(1, id="v-planes")]
 
 
+engine, dp, nan_dev = H.engine, H.dev_ptr, H.nan_dev   # (H is the image height in the functions below)
+
+
 @pytest.fixture(scope="module")
 def lib():
-    from imagen_pytorch import _engine as E
-
-    return E.load()
-
-
-def _E():
-    from imagen_pytorch import _engine as E
-
-    return E
-
-
-def dp(t):
-    assert t is None or t.is_cuda
-    return None if t is None else t.data_ptr()
-
-
-def nan_dev(*shape, dtype=torch.float32):
-    return torch.full(shape, float("nan"), dtype=dtype, device="cuda:0")
+    return engine().load()
 
 
 _cases = {}
@@ -123,7 +111,7 @@ def _check(tag, y, seg, ref):
 
 
 def _run_full(lib, device, c, B, H, W, Cin, Cout, mode, nsets=2):
-    E = _E()
+    E = engine()
     dv = lambda t: t.contiguous().to(device)
     Bn = nsets * B
     xd, resd, ssd, st = dv(c["xbuf"][:Bn]), dv(c["resbuf"][:Bn]), dv(c["ss"][:Bn]), dv(c["stats_full"][:Bn])
@@ -140,7 +128,7 @@ def _run_full(lib, device, c, B, H, W, Cin, Cout, mode, nsets=2):
 @pytest.mark.parametrize("B,H,W,Cin,Cout", SHAPES)
 def test_wino4_plain(lib, device, B, H, W, Cin, Cout, mode):
     """dense x, no FiLM, no residual (the output transform's form without one), one set"""
-    E = _E()
+    E = engine()
     c = _case(B, H, W, Cin, Cout)
     dv = lambda t: t.contiguous().to(device)
     xd, st = dv(c["x_plain"]), dv(c["stats_plain"])
