@@ -50,7 +50,7 @@ const char* kd_last_error(void);
  *      kd_upsample_nearest_gn_conv3x3_nhwc added; kd_unet_config_t::attn_dim_head accepts 32 and 128 beside 64 (kd_attention too);
  *      kd_unet_create_ext3 with its struct kd_unet_ext3_t for `layer_attns_depth` - kd_unet_create_ext2 is that call with
  *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
- *      are those with D = 64) */
+ *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -413,6 +413,25 @@ int kd_edm_sample_steps(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_s
  * Individual kernels, exported so that tests/ can check each one against the oracle through
  * the same ABI the plan uses internally.
  * ---------------------------------------------------------------------------------------- */
+
+/* Test infrastructure, not part of the sampling path: sets every 32-bit word of the plan's scratch to `word` with
+ * hipMemsetD32Async on `stream` and reports the bytes filled in *bytes_filled (may be NULL).  At the start of a forward or
+ * of a sampling call every byte of that scratch is undefined - nothing initialises it when it is allocated - so results
+ * must not change under this call, whatever the word (tests/test_poisoned_scratch_gpu.py: NaN, 1e30, 0).
+ *   Filled: the activation workspace (every tensor has its producer in the same forward; the step-invariant planes are
+ *   rewritten at the start of every kd_unet_forward and of every sampling call), the conditioning region (written by the
+ *   conditioning ops, or restored whole from the table, in every forward), the bf16x3 GEMMs' k-cut slabs if the plan has
+ *   such layers, and those of the sampler's buffers that exist: UNet output, guidance output, x0 estimate, thresholds,
+ *   times, EDM x_hat / d / UNet input (each written inside an iteration before it is read), the self-conditioning planes
+ *   (zeroed at step 0 of a call) and the quantile workspace (integers, every one set by the quantile's first kernel
+ *   before another indexes or counts with it).
+ *   Left alone, as state that outlives a call: weights and packed weights with the index tables cached beside them, the
+ *   device-resident iteration counter and seed, the schedule tables, the conditioning table and its row layout,
+ *   captured graphs, and the text conditioning's outputs (the caller's buffers).
+ * Call it only where nothing is live: before a whole forward or sampling call - read kd_sample_last first, seed
+ * kd_sample_set_self_cond afterwards - and do not run kd_unet_profile behind it (it replays the steps without the
+ * step-invariant part). */
+int kd_unet_poison_scratch(kd_unet_t* u, uint32_t word, int64_t* bytes_filled, void* stream);
 
 /* 2-D convolution as implicit GEMM on fp32 MFMA.  x: NHWC [B,Hi,Wi,Cin]; w: torch OIHW
  * [Cout,Cin,KH,KW] (re-packed internally on each call of this test entry); y: NHWC.

@@ -231,6 +231,52 @@ int kd_unet_profile(kd_unet_t* u, int iters, char* buf, size_t buflen, void* str
   return 0;
 }
 
+// Test infrastructure (tests/test_poisoned_scratch_gpu.py): every 32-bit word of what is scratch by contract at the start
+// of a forward or of a sampling call becomes `word`.  None of it was initialised when it was allocated, so a plan whose
+// results change under this call reads memory that no op of the same call has written.
+//   filled - every op that reads it has a writer earlier in the same call:
+//     ws        the arena: every tensor is written by the op that produces it; what static_ops leave there lives from
+//               them to the last step of the same call, never across calls (so: not between kd_unet_forward's static part and
+//               its steps - there is no entry that separates them - and not between the steps of one sampling call)
+//     cond_ws   written by the conditioning ops of every forward, or restored whole from the table by the step's gather
+//     x3_ws     the k-cut slabs of a bf16x3 GEMM: its parts store them, the summing launch behind it reads them
+//     sampler   pred, pred_null, x0, thresh, time, xhat, d, net_in: written by the kernels of an iteration before they
+//               are read (kd_sample_last reports the last call's: read it before poisoning); self_cond: zeroed at step 0
+//               of a call (a caller that continues with k_begin > 0 seeds it after this call, kd_sample_set_self_cond);
+//               qws: the quantile's QState and histograms are integers - q_init_kernel sets every one of them at the
+//               start of each launch_quantile_abs, before q_hist / q_scan / q_next / q_final index or count with them
+//   left alone - state that outlives a call:
+//     the packed weights and every table cached with them (the fused Winograd kernel's item lists are indices);
+//     iter and seed (set by launch_iter_set / launch_seed_set per call, read as a table index and a Philox key);
+//     ddpm_tab / edm_tab (keyed on their content: an unchanged schedule uploads nothing); the conditioning table
+//     smp.cond.tab (rows built once per schedule); d_cond_segs (row layout, read as offsets); captured graphs; the text
+//     conditioning's outputs, which live in the caller's buffers.
+// Apart from those integers of qws, no word of the filled buffers is ever used as an index, a count or an address.
+int kd_unet_poison_scratch(kd_unet_t* u, uint32_t word, int64_t* bytes_filled, void* stream) {
+  if (!u) {
+    set_error("kd_unet_poison_scratch: null argument");
+    return 1;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const Sampler& m = u->smp;
+  const size_t img = image_bytes(u), per_b = (size_t)u->cfg.batch * sizeof(float);
+  const std::pair<void*, size_t> bufs[] = {
+      {u->ws, u->ws_bytes},   {u->cond_ws, u->cond_bytes}, {u->x3_ws, gemm_bf16x3_workspace_bytes()},
+      {m.pred, img},          {m.pred_null, img},          {m.x0, img},
+      {m.thresh, per_b},      {m.time, per_b},             {m.xhat, img},
+      {m.d, img},             {m.net_in, img},             {m.self_cond, img},
+      {m.qws, quantile_ws_bytes(u->cfg.batch)}};
+  int64_t total = 0;
+  for (const auto& b : bufs) {
+    if (!b.first || !b.second) continue;   // (the sampler's come with the first sampling call, x3_ws with the first bf16x3 layer)
+    KD_REQUIRE(b.second % 4 == 0, "kd_unet_poison_scratch: a scratch buffer is not a whole number of words");
+    KD_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)b.first, (int)word, b.second / 4, s));
+    total += (int64_t)b.second;
+  }
+  if (bytes_filled) *bytes_filled = total;
+  return 0;
+}
+
 int kd_sample_steps(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
                     int k_begin, int k_end, void* stream) {
   return sample_steps(u, sched, args, d_img, k_begin, k_end, (hipStream_t)stream);
@@ -335,6 +381,13 @@ int entry_finish(int rc, hipStream_t s) {
   hipError_t e = hipStreamSynchronize(s);
   if (rc) return rc;
   KD_HIP_CHECK(e);
+  return 0;
+}
+// the slab workspace of a test entry's bf16x3 GEMMs, every byte 0xFF (NaN as float): the launch must not depend on what
+// the slabs held (kd_unet_poison_scratch holds the plans to the same)
+int entry_x3_ws(EntryBufs& bufs, void** ws, hipStream_t s) {
+  if (bufs.get(ws, gemm_bf16x3_workspace_bytes())) return 1;
+  KD_HIP_CHECK(hipMemsetAsync(*ws, 0xFF, gemm_bf16x3_workspace_bytes(), s));
   return 0;
 }
 // the launch shape of a bf16x3 GEMM of a test entry point: one per call, for the device that is current
@@ -471,9 +524,8 @@ int kd_conv3x3_winograd4_nhwc(const float* d_x, const float* d_w_oihw, const flo
   if (bufs.get(&V, (size_t)36 * Mt * Cin * (gemm_bf16x3 == 1 ? 6 : sizeof(float)))) return 1;
   if (bufs.get(&D, (size_t)36 * Mt * Cout * sizeof(float))) return 1;
   if (gemm_bf16x3 && bufs.get(&U3, (size_t)36 * Cout * Cin * 6)) return 1;
-  if (gemm_bf16x3 && bufs.get(&x3ws, gemm_bf16x3_workspace_bytes())) return 1;
+  if (gemm_bf16x3 && entry_x3_ws(bufs, &x3ws, s)) return 1;
   if (d_out_stats && bufs.get(&seg, (size_t)B * (Cout / 16) * nchunk * 2 * sizeof(double))) return 1;
-  if (gemm_bf16x3) KD_HIP_CHECK(hipMemsetAsync(x3ws, 0, gemm_bf16x3_workspace_bytes(), s));   // (nothing queued yet)
   int rc = launch_wino4_pack(d_w_oihw, U, Cout, Cin, s);
   if (!rc && gemm_bf16x3) {
     rc = launch_split3(U, U3, 36, Cout, Cin, s);
@@ -505,7 +557,7 @@ int kd_gemm_bf16x3(const float* d_a, const float* d_b, float* d_c, int G, int M,
   void *A3 = nullptr, *B3 = nullptr, *ws = nullptr;
   if (bufs.get(&B3, (size_t)G * N * K * 6)) return 1;
   if (a_planes && bufs.get(&A3, (size_t)G * M * K * 6)) return 1;   // (a_planes == 0: the loader waves split A)
-  if (bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;   // slabs of the left-over tiles' k-parts
+  if (entry_x3_ws(bufs, &ws, s)) return 1;   // slabs of the left-over tiles' k-parts
   int rc = a_planes ? launch_split3(d_a, A3, G, M, K, s) : 0;
   if (!rc) rc = launch_split3(d_b, B3, G, N, K, s);
   if (!rc) rc = launch_gemm_bf16x3(a_planes ? A3 : (const void*)d_a, B3, d_c, G, M, N, K, entry_x3_shape(G, M, N, K), ws, s, !a_planes);
@@ -535,7 +587,7 @@ int kd_downsample_bf16x3(const float* d_x, int ldx, const float* d_w, const floa
   float *wt = nullptr, *wk = nullptr;
   void *W3 = nullptr, *ws = nullptr;
   if (bufs.get(&wt, (size_t)O * K * 4) || bufs.get(&wk, (size_t)O * K * 4) || bufs.get(&W3, (size_t)O * K * 6) ||
-      bufs.get(&ws, gemm_bf16x3_workspace_bytes()))
+      entry_x3_ws(bufs, &ws, s))
     return 1;
   int rc = launch_pack_unshuffle(d_w, wt, O, C, s);
   for (int t = 0; t < 4 && !rc; ++t) rc = launch_copy_scale_rows(wt + (size_t)t * O * C, C, wk + (size_t)t * C, K, C, 1.0f, O, s);
@@ -569,7 +621,7 @@ int kd_linear_bf16x3(const float* d_x, int ldx, const float* d_w, const float* d
                                              "rows, hw % 256 == 0 under a gate");
   EntryBufs bufs;
   void *W3 = nullptr, *ws = nullptr;
-  if (bufs.get(&W3, (size_t)N * K * 6) || bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
+  if (bufs.get(&W3, (size_t)N * K * 6) || entry_x3_ws(bufs, &ws, s)) return 1;
   int rc = launch_split3(d_w, W3, 1, N, K, s);
   if (!rc) rc = launch_gemm_bf16x3(d_x, W3, d_y, 1, M, N, K, sh, ws, s, true, true, &e);
   return entry_finish(rc, s);
@@ -751,7 +803,7 @@ int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats
   if (bufs.get(&V, planes ? (size_t)36 * Mt * Cin * 6 : (size_t)36 * Mt * Cin * sizeof(float))) return 1;
   if (bufs.get((void**)&D, (size_t)36 * Mt * Cout * sizeof(float))) return 1;
   if (x3 && bufs.get(&U3, ((size_t)36 * Cout * Cin * 3 + 1) / 2 * sizeof(float))) return 1;
-  if (x3 && bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
+  if (x3 && entry_x3_ws(bufs, &ws, s)) return 1;
   int rc = launch_wino4_pack(d_w_oihw, U, Cout, Cin, s);
   if (!rc && x3) rc = launch_split3(U, U3, 36, Cout, Cin, s);
   const int64_t HW = (int64_t)H * W, nchunk = (H / 4) * (W / 4);
@@ -907,7 +959,7 @@ int kd_layernorm_linear_bf16x3(const float* d_x, const float* d_g, const float* 
   KD_REQUIRE(gemm_bf16x3_epi_ok(rows, N, C, e, sh), "kd_layernorm_linear_bf16x3 needs rows % 256 == 0, N % 128 == 0, C % 32 == 0");
   EntryBufs bufs;
   void *W3 = nullptr, *ws = nullptr;
-  if (bufs.get(&W3, (size_t)N * C * 6) || bufs.get(&ws, gemm_bf16x3_workspace_bytes())) return 1;
+  if (bufs.get(&W3, (size_t)N * C * 6) || entry_x3_ws(bufs, &ws, s)) return 1;
   int rc = launch_split3(d_w, W3, 1, N, C, s);
   if (!rc) rc = launch_layernorm(d_x, C, d_g, d_beta, nullptr, 0, (float*)d_planes, rows, C, eps, s, in_act, nullptr, nullptr, nullptr, 0, 1);
   if (!rc) rc = launch_gemm_bf16x3(d_planes, W3, d_y, 1, rows, N, C, sh, ws, s, false, true, &e);

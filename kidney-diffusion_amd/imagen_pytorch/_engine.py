@@ -152,6 +152,7 @@ SIGNATURES = {
     "kd_unet_text_cond": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     "kd_unet_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.c_void_p]),
+    "kd_unet_poison_scratch": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.c_void_p]),
     "kd_unet_forward": (C.c_int, [C.c_void_p] + [C.c_void_p] * 8 + [C.c_void_p]),
     "kd_unet_forward_self_cond": (C.c_int, [C.c_void_p] + [C.c_void_p] * 9 + [C.c_void_p]),
     "kd_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,

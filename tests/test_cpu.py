@@ -345,7 +345,7 @@ def test_library_loads_and_exports_every_symbol_the_header_declares():
     declared = set(re.findall(r"\b(kd_[a-z0-9_]+)\s*\(", header))
     declared -= {"kd_sampler_create"}  # mentioned in prose only
     assert {"kd_unet_create", "kd_unet_forward", "kd_sample_loop", "kd_sample_steps", "kd_conv2d_nhwc",
-            "kd_quantile_abs", "kd_philox_normal"} <= declared
+            "kd_quantile_abs", "kd_philox_normal", "kd_unet_poison_scratch"} <= declared
     lib = E.load()
     for sym in sorted(declared):
         assert hasattr(lib, sym), f"libkd_engine.so does not export {sym}"
