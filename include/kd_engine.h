@@ -50,7 +50,8 @@ const char* kd_last_error(void);
  *      kd_upsample_nearest_gn_conv3x3_nhwc added; kd_unet_config_t::attn_dim_head accepts 32 and 128 beside 64 (kd_attention too);
  *      kd_unet_create_ext3 with its struct kd_unet_ext3_t for `layer_attns_depth` - kd_unet_create_ext2 is that call with
  *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
- *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure) */
+ *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure); kd_sample_args_t gained `seeds` at its end
+ *      (NULL = the keying of before) and kd_philox_normal_rows added */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -333,7 +334,27 @@ typedef struct kd_sample_args {
   float lowres_log_snr_value;
   int cond_table;
   int cond_table_max_mb;
+  /* Per-image Philox keys: a HOST pointer to B values, copied stream-ordered inside the call (the array is free when
+   * the call returns), or NULL (a zero-initialised struct): `seed` keys the whole batch tensor as before, the counter
+   * being the element index over all B images.  With seeds, image b is keyed seeds[b] and its counter runs inside the
+   * image, so it draws bit for bit what a batch-1 call with seed = seeds[b] draws; `seed` is then not read.  Keys and
+   * mode live in device memory: the captured step graph serves an int seed, a seed list and any values of either. */
+  const uint64_t* seeds;
 } kd_sample_args_t;
+
+/* Philox stream ids (the `stream_id` of kd_philox_normal; what the sampler draws when a d_noise_* pointer is NULL):
+ * purpose in the high 32 bits, iteration k*R + (R-1-r) in the low 32 (k the schedule step, r the resample counting down
+ * from R-1; R = 1 without inpainting).  Purposes: 1 the DDPM step's noise (d_noise_step), 2 the noised known pixels of
+ * the DDPM inpaint mix (d_noise_inpaint), 3 the DDPM re-noise (d_noise_renoise), 4 the EDM churn (d_noise_step of
+ * kd_edm_sample_*), 5 the EDM re-noise (d_noise_renoise), 16 the caller's own draws (the Python package: low 32 bits 1 =
+ * low-res augmentation noise, 2 = x_T).  Element j of a stream is component j % 4 of the Philox4x32-10 block at counter
+ * (j / 4, stream id) under the key. */
+#define KD_PHILOX_PURPOSE_STEP 1
+#define KD_PHILOX_PURPOSE_INPAINT 2
+#define KD_PHILOX_PURPOSE_RENOISE 3
+#define KD_PHILOX_PURPOSE_EDM_CHURN 4
+#define KD_PHILOX_PURPOSE_EDM_RENOISE 5
+#define KD_PHILOX_PURPOSE_USER 16
 
 /* In: d_img = x_T [B,3,S,S].  Out: d_img = unnormalised sample in [0,1] (clamp, final inpaint
  * paste and (x+1)/2 included).  Runs all T*R denoising iterations on `stream`. */
@@ -676,6 +697,10 @@ size_t kd_quantile_workspace_bytes(int B);
 /* Standard-normal Philox4x32-10 fill (the generator kd_sample_loop uses when no noise tensors
  * are given): element i of stream `stream_id` under `seed`. */
 int kd_philox_normal(float* d_out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
+/* The per-image form: row b of d_out [B][n] is what kd_philox_normal writes for (n, seeds[b], stream_id), bit for bit.
+ * `seeds` is a HOST pointer to B keys, read before the call returns.  Needs n % 4 == 0, n >= 4 and a 16-byte aligned
+ * d_out (refused with an error, nothing launched, otherwise). */
+int kd_philox_normal_rows(float* d_out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream);
 
 #ifdef __cplusplus
 }

@@ -247,7 +247,7 @@ int kd_unet_profile(kd_unet_t* u, int iters, char* buf, size_t buflen, void* str
 //               start of each launch_quantile_abs, before q_hist / q_scan / q_next / q_final index or count with them
 //   left alone - state that outlives a call:
 //     the packed weights and every table cached with them (the fused Winograd kernel's item lists are indices);
-//     iter and seed (set by launch_iter_set / launch_seed_set per call, read as a table index and a Philox key);
+//     iter and the seed block (set by launch_iter_set / launch_seed_set per call, read as a table index and Philox keys);
 //     ddpm_tab / edm_tab (keyed on their content: an unchanged schedule uploads nothing); the conditioning table
 //     smp.cond.tab (rows built once per schedule); d_cond_segs (row layout, read as offsets); captured graphs; the text
 //     conditioning's outputs, which live in the caller's buffers.
@@ -1059,6 +1059,9 @@ int kd_cfg_combine(const float* d_cond, const float* d_null, float* d_out, float
 
 int kd_philox_normal(float* d_out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
   return launch_philox_normal(d_out, n, seed, stream_id, (hipStream_t)stream);
+}
+int kd_philox_normal_rows(float* d_out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream) {
+  return launch_philox_normal_rows(d_out, B, n, seeds, stream_id, (hipStream_t)stream);
 }
 
 }  // extern "C"

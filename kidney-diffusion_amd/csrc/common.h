@@ -384,8 +384,11 @@ int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const f
 int launch_inpaint_mix(float* x, const float* inp, const float* mask, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int B, int C, int64_t hw,
                        hipStream_t s);
-// the Philox key lives in device memory (d_seed) so that one captured step graph serves every seed
-int launch_seed_set(uint64_t* d_seed, uint64_t value, hipStream_t s);
+// The Philox keys live in device memory (d_seed, SEED_ROWS + B words) so that one captured step graph serves every seed
+// and either keying: [SEED_BATCH] keys the whole batch tensor; [SEED_MODE] != 0: image b draws from [SEED_ROWS + b] with the
+// counter running inside the image.  seeds: host pointer to B keys (per-image mode) or nullptr; SEED_CHUNK keys per launch.
+enum { SEED_BATCH = 0, SEED_MODE = 1, SEED_ROWS = 2, SEED_CHUNK = 32 };
+int launch_seed_set(uint64_t* d_seed, uint64_t value, const uint64_t* seeds, int B, hipStream_t s);
 int launch_renoise(float* x, const float* noise, int64_t noise_stride, const uint64_t* d_seed, const StepTables& tb,
                    const int* d_iter, int R, int T, int B, int64_t per, hipStream_t s);
 int launch_iter_set(int* d_iter, int value, hipStream_t s);
@@ -417,5 +420,7 @@ int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* d
 
 int launch_iter_inc(int* d_iter, hipStream_t s);
 int launch_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);
+// row b of out[B][n] = launch_philox_normal(n, seeds[b], stream_id); seeds on the host, n % 4 == 0
+int launch_philox_normal_rows(float* out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, hipStream_t s);
 
 }  // namespace kd

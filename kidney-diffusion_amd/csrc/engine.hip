@@ -232,7 +232,7 @@ struct Sampler {
   float *xhat = nullptr, *d = nullptr, *net_in = nullptr;
   float* self_cond = nullptr;   // self_cond plans: the thresholded x0 estimate carried to the next forward [B,3,S,S]
   int* iter = nullptr;
-  uint64_t* seed = nullptr;   // Philox key, device-resident so the step graph does not depend on it
+  uint64_t* seed = nullptr;   // Philox keys [SEED_ROWS + B] (common.h), device-resident so the step graph does not depend on them
   void* qws = nullptr;
   DevBufs mem;
   DeviceTable ddpm_tab;   // 9 x T (kd_schedule_t)

@@ -5,6 +5,9 @@
 // Every kernel reads the current iteration index from device memory (d_iter) and looks its
 // per-step scalars up in device tables, so that one captured hipGraph serves all T*R
 // iterations.  iteration it -> timestep k = it / R, resample slot ri = it % R (r = R-1-ri).
+//
+// The kernels that draw noise walk the batch with blockIdx.y = image and read their Philox key through noise_key():
+// one key and one counter over the whole batch tensor, or a key per image with the counter inside the image.
 #include "common.h"
 
 #pragma clang fp contract(off)  // keep mul/add separate so that the arithmetic follows torch's op order
@@ -73,10 +76,62 @@ int launch_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t sid, hip
   return 0;
 }
 
-__device__ __forceinline__ f32x4 noise4(const float* noise, int64_t noise_stride, uint64_t seed, uint32_t purpose,
-                                        int it, int64_t i4) {
+// Row b of out[B][n] from (seeds[b], sid) with the counter running inside the row: what philox_normal_kernel writes for
+// (n, seeds[b], sid).  The keys travel as a kernel argument, SEED_CHUNK rows per launch.
+struct SeedChunk {
+  uint64_t v[SEED_CHUNK];
+};
+__global__ __launch_bounds__(256) void philox_normal_rows_kernel(float* __restrict__ out, int64_t n4, SeedChunk seeds,
+                                                                 uint64_t sid) {
+  const uint64_t seed = seeds.v[blockIdx.y];
+  float* row = out + (int64_t)blockIdx.y * n4 * 4;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n4; j += (int64_t)gridDim.x * blockDim.x)
+    *(f32x4*)(row + j * 4) = philox_normal4(seed, sid, (uint64_t)j);
+}
+// grid of the kernels that walk [B][per4] with blockIdx.y = image: as many blocks as grid_for gives the flat walk
+static inline dim3 grid_rows(int64_t per4, int B) {
+  const int cap = 4096 / B < 1 ? 1 : 4096 / B;
+  const int gx = grid_for(per4);
+  return dim3((unsigned)(gx > cap ? cap : gx), (unsigned)B);
+}
+int launch_philox_normal_rows(float* out, int B, int64_t n, const uint64_t* seeds, uint64_t sid, hipStream_t s) {
+  KD_REQUIRE(out != nullptr && seeds != nullptr, "philox rows: null argument");
+  KD_REQUIRE(B >= 1 && n >= 4 && n % 4 == 0, "philox rows: the row length must be a positive multiple of 4");
+  KD_REQUIRE(((uintptr_t)out & 15) == 0, "philox rows: out must be 16-byte aligned");
+  for (int b0 = 0; b0 < B; b0 += SEED_CHUNK) {
+    const int nb = std::min(B - b0, (int)SEED_CHUNK);
+    SeedChunk c{};
+    for (int b = 0; b < nb; ++b) c.v[b] = seeds[b0 + b];
+    hipLaunchKernelGGL(philox_normal_rows_kernel, grid_rows(n / 4, nb), dim3(256), 0, s, out + (int64_t)b0 * n, n / 4, c, sid);
+  }
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// The key block in device memory (Sampler::seed): [SEED_BATCH] keys the whole batch tensor, the counter being the float4
+// index over all B images; [SEED_MODE] != 0 switches to one key per image, [SEED_ROWS + b], with the counter running
+// inside the image - image b then draws what a batch-1 call keyed seeds[b] draws.  Both words are read by the kernels,
+// so one captured step serves either mode and any keys.
+struct NoiseKey {
+  uint64_t seed;
+  uint64_t ctr0;   // counter of the image's first float4
+};
+__device__ __forceinline__ NoiseKey noise_key(const uint64_t* __restrict__ d_seed, int b, int64_t per4) {
+  NoiseKey k;
+  if (d_seed[SEED_MODE] != 0) {
+    k.seed = d_seed[SEED_ROWS + b];
+    k.ctr0 = 0;
+  } else {
+    k.seed = d_seed[SEED_BATCH];
+    k.ctr0 = (uint64_t)((int64_t)b * per4);
+  }
+  return k;
+}
+// four draws for float4 j of image b (flat float4 index i4 = b * per4 + j)
+__device__ __forceinline__ f32x4 noise4(const float* noise, int64_t noise_stride, NoiseKey key, uint32_t purpose, int it,
+                                        int64_t i4, int64_t j) {
   if (noise) return *(const f32x4*)(noise + (int64_t)it * noise_stride + i4 * 4);
-  return philox_normal4(seed, stream_id(purpose, (uint32_t)it), (uint64_t)i4);
+  return philox_normal4(key.seed, stream_id(purpose, (uint32_t)it), key.ctr0 + (uint64_t)j);
 }
 
 // ------------------------------------------------------------------------- per-step helpers
@@ -155,9 +210,22 @@ int launch_cond_scatter(const float* ws, float* tab, const CondSeg* d_segs, int 
 
 __global__ void iter_inc_kernel(int* d_iter) { *d_iter += 1; }
 __global__ void iter_set_kernel(int* d_iter, int v) { *d_iter = v; }
-__global__ void seed_set_kernel(uint64_t* d_seed, uint64_t v) { *d_seed = v; }
-int launch_seed_set(uint64_t* d_seed, uint64_t value, hipStream_t s) {
-  hipLaunchKernelGGL(seed_set_kernel, dim3(1), dim3(1), 0, s, d_seed, value);
+__global__ void seed_set_kernel(uint64_t* d_seed, uint64_t v, uint64_t per_image) {
+  d_seed[SEED_BATCH] = v;
+  d_seed[SEED_MODE] = per_image;
+}
+__global__ void seed_rows_kernel(uint64_t* d_rows, SeedChunk c, int n) {
+  if ((int)threadIdx.x < n) d_rows[threadIdx.x] = c.v[threadIdx.x];
+}
+// seeds: host pointer to B keys or nullptr; they travel as kernel arguments, so the caller's array is free on return
+int launch_seed_set(uint64_t* d_seed, uint64_t value, const uint64_t* seeds, int B, hipStream_t s) {
+  hipLaunchKernelGGL(seed_set_kernel, dim3(1), dim3(1), 0, s, d_seed, value, (uint64_t)(seeds != nullptr));
+  for (int b0 = 0; seeds && b0 < B; b0 += SEED_CHUNK) {
+    const int nb = std::min(B - b0, (int)SEED_CHUNK);
+    SeedChunk c{};
+    for (int b = 0; b < nb; ++b) c.v[b] = seeds[b0 + b];
+    hipLaunchKernelGGL(seed_rows_kernel, dim3(1), dim3(64), 0, s, d_seed + SEED_ROWS + b0, c, nb);
+  }
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -339,19 +407,19 @@ __global__ void ddpm_update_kernel(float* __restrict__ x, const float* __restric
                                    const float* __restrict__ s_thresh, const float* __restrict__ noise,
                                    int64_t noise_stride, const uint64_t* __restrict__ d_seed, StepTables tb,
                                    const int* __restrict__ d_iter, int R, int dynamic_threshold, int64_t per4,
-                                   int64_t total4, float* __restrict__ sc_out) {
-  const uint64_t seed = *d_seed;  // device-resident: the captured step graph is seed-independent
+                                   float* __restrict__ sc_out) {
+  const int b = blockIdx.y;   // one grid row per image: no division splits the flat index
+  const NoiseKey key = noise_key(d_seed, b, per4);  // device-resident: the captured step graph is seed-independent
   const int it = *d_iter;
   const int k = it / R;
   const float alpha = tb.alpha[k], alpha_next = tb.alpha_next[k], c = tb.c[k], ns = tb.noise_scale[k];
   const float one_minus_c = 1.0f - c;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int b = (int)(i / per4);
-    float s = 1.0f;
-    if (dynamic_threshold) s = fmaxf(s_thresh[b], 1.0f);
+  float s = 1.0f;
+  if (dynamic_threshold) s = fmaxf(s_thresh[b], 1.0f);
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)b * per4 + j;
     f32x4 xv = *(const f32x4*)(x + i * 4), x0v = *(const f32x4*)(x0 + i * 4);
-    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_STEP, it, i), o, xsv;
+    f32x4 z = noise4(noise, noise_stride, key, PURPOSE_STEP, it, i, j), o, xsv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float xs = fminf(fmaxf(x0v[e], -s), s) / s;
@@ -367,9 +435,9 @@ int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const f
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int dynamic_threshold, int B,
                        int64_t per, hipStream_t s, float* sc_out) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
-  int64_t total4 = (int64_t)B * per / 4;
-  hipLaunchKernelGGL(ddpm_update_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, x0, s_thresh, noise,
-                     noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per / 4, total4, sc_out);
+  KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
+  hipLaunchKernelGGL(ddpm_update_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, x0, s_thresh, noise,
+                     noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per / 4, sc_out);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -379,18 +447,17 @@ int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const f
 __global__ void inpaint_mix_kernel(float* __restrict__ x, const float* __restrict__ inp,
                                    const float* __restrict__ mask, const float* __restrict__ noise,
                                    int64_t noise_stride, const uint64_t* __restrict__ d_seed, StepTables tb,
-                                   const int* __restrict__ d_iter, int R, int C, int64_t hw4, int64_t total4) {
-  const uint64_t seed = *d_seed;
+                                   const int* __restrict__ d_iter, int R, int64_t hw4, int64_t per4) {
+  const int b = blockIdx.y;
+  const NoiseKey key = noise_key(d_seed, b, per4);
   const int it = *d_iter;
   const int k = it / R;
   const float alpha = tb.alpha[k], sigma = tb.sigma[k];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t plane = i / hw4, p4 = i - plane * hw4;
-    int64_t b = plane / C;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)b * per4 + j, p4 = j % hw4;   // (the mask has one plane per image)
     f32x4 m = *(const f32x4*)(mask + (b * hw4 + p4) * 4);
     f32x4 xv = *(const f32x4*)(x + i * 4), iv = *(const f32x4*)(inp + i * 4);
-    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_INPAINT, it, i), o;
+    f32x4 z = noise4(noise, noise_stride, key, PURPOSE_INPAINT, it, i, j), o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float noised = alpha * iv[e] + sigma * z[e];
@@ -403,9 +470,9 @@ int launch_inpaint_mix(float* x, const float* inp, const float* mask, const floa
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int B, int C, int64_t hw,
                        hipStream_t s) {
   KD_REQUIRE(hw % 4 == 0, "H*W must be a multiple of 4");
-  int64_t total4 = (int64_t)B * C * hw / 4;
-  hipLaunchKernelGGL(inpaint_mix_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, inp, mask, noise,
-                     noise_stride, d_seed, tb, d_iter, R, C, hw / 4, total4);
+  KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
+  hipLaunchKernelGGL(inpaint_mix_kernel, grid_rows(C * hw / 4, B), dim3(256), 0, s, x, inp, mask, noise,
+                     noise_stride, d_seed, tb, d_iter, R, hw / 4, C * hw / 4);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -413,16 +480,17 @@ int launch_inpaint_mix(float* x, const float* inp, const float* mask, const floa
 // re-noise t_next -> t after a non-final resample:  x = x*rn_a + noise*rn_b   (skipped when r == 0 or last k)
 __global__ void renoise_kernel(float* __restrict__ x, const float* __restrict__ noise, int64_t noise_stride,
                                const uint64_t* __restrict__ d_seed, StepTables tb,
-                               const int* __restrict__ d_iter, int R, int T, int64_t total4) {
-  const uint64_t seed = *d_seed;
+                               const int* __restrict__ d_iter, int R, int T, int64_t per4) {
+  const int b = blockIdx.y;
+  const NoiseKey key = noise_key(d_seed, b, per4);
   const int it = *d_iter;
   const int k = it / R, ri = it - k * R;
   if (ri == R - 1 || k == T - 1) return;
   const float a = tb.rn_a[k], bco = tb.rn_b[k];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)b * per4 + j;
     f32x4 xv = *(const f32x4*)(x + i * 4);
-    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_RENOISE, it, i), o;
+    f32x4 z = noise4(noise, noise_stride, key, PURPOSE_RENOISE, it, i, j), o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = xv[e] * a + z[e] * bco;
     *(f32x4*)(x + i * 4) = o;
@@ -430,9 +498,10 @@ __global__ void renoise_kernel(float* __restrict__ x, const float* __restrict__ 
 }
 int launch_renoise(float* x, const float* noise, int64_t noise_stride, const uint64_t* d_seed, const StepTables& tb,
                    const int* d_iter, int R, int T, int B, int64_t per, hipStream_t s) {
-  int64_t total4 = (int64_t)B * per / 4;
-  hipLaunchKernelGGL(renoise_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, noise, noise_stride, d_seed, tb,
-                     d_iter, R, T, total4);
+  KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
+  KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
+  hipLaunchKernelGGL(renoise_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, noise, noise_stride, d_seed, tb,
+                     d_iter, R, T, per / 4);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -448,18 +517,20 @@ int launch_renoise(float* x, const float* noise, int64_t noise_stride, const uin
 __global__ void edm_churn_kernel(const float* __restrict__ x, float* __restrict__ xh, float* __restrict__ net_in,
                                  const float* __restrict__ inp, const float* __restrict__ mask,
                                  const float* __restrict__ noise, int64_t noise_stride, const uint64_t* __restrict__ d_seed,
-                                 EdmTables tb, float s_noise, const int* __restrict__ d_iter, int R, int C, int64_t hw4,
-                                 int64_t total4) {
-  const uint64_t seed = *d_seed;
+                                 EdmTables tb, float s_noise, const int* __restrict__ d_iter, int R, int64_t hw4,
+                                 int64_t per4) {
+  const int b = blockIdx.y;
+  const NoiseKey key = noise_key(d_seed, b, per4);
   const int it = *d_iter;
   const int k = it / R;
   const float churn = tb.churn[k], c_in = tb.c_in_hat[k];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)b * per4 + j;
     f32x4 xv = *(const f32x4*)(x + i * 4);
-    f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_EDM_CHURN, it, i), o, ci;
+    f32x4 z = noise4(noise, noise_stride, key, PURPOSE_EDM_CHURN, it, i, j), o, ci;
     f32x4 m = {0.f, 0.f, 0.f, 0.f}, iv = {0.f, 0.f, 0.f, 0.f};
     if (inp) {
-      const int64_t plane = i / hw4, p4 = i - plane * hw4, b = plane / C;
+      const int64_t p4 = j % hw4;
       m = *(const f32x4*)(mask + (b * hw4 + p4) * 4);
       iv = *(const f32x4*)(inp + i * 4);
     }
@@ -477,9 +548,9 @@ int launch_edm_churn(const float* x, float* xh, float* net_in, const float* inp,
                      int64_t noise_stride, const uint64_t* d_seed, const EdmTables& tb, float s_noise, const int* d_iter,
                      int R, int B, int C, int64_t hw, hipStream_t s) {
   KD_REQUIRE(hw % 4 == 0, "H*W must be a multiple of 4");
-  const int64_t total4 = (int64_t)B * C * hw / 4;
-  hipLaunchKernelGGL(edm_churn_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, xh, net_in, inp, mask, noise,
-                     noise_stride, d_seed, tb, s_noise, d_iter, R, C, hw / 4, total4);
+  KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
+  hipLaunchKernelGGL(edm_churn_kernel, grid_rows(C * hw / 4, B), dim3(256), 0, s, x, xh, net_in, inp, mask, noise,
+                     noise_stride, d_seed, tb, s_noise, d_iter, R, hw / 4, C * hw / 4);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -548,14 +619,16 @@ __global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__
                                 const float* __restrict__ den, const float* __restrict__ s_thresh,
                                 const float* __restrict__ noise, int64_t noise_stride, const uint64_t* __restrict__ d_seed,
                                 EdmTables tb, const int* __restrict__ d_iter, int R, int N, int renoise,
-                                int dynamic_threshold, int64_t per4, int64_t total4, float* __restrict__ sc_out) {
-  const uint64_t seed = *d_seed;
+                                int dynamic_threshold, int64_t per4, float* __restrict__ sc_out) {
+  const int b = blockIdx.y;
+  const NoiseKey key = noise_key(d_seed, b, per4);
   const int it = *d_iter;
   const int k = it / R, ri = it - k * R;
   const bool rn = renoise && ri != R - 1 && k != N - 1;
   const float sn = tb.sigma_next[k], step = tb.heun_step[k], rs = tb.renoise[k];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float s = dynamic_threshold ? fmaxf(s_thresh[i / per4], 1.0f) : 1.0f;
+  const float s = dynamic_threshold ? fmaxf(s_thresh[b], 1.0f) : 1.0f;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)b * per4 + j;
     f32x4 xv = *(const f32x4*)(x + i * 4), hv = *(const f32x4*)(xh + i * 4), dv = *(const f32x4*)(d_in + i * 4),
           nv = *(const f32x4*)(den + i * 4), o, tv;
 #pragma unroll
@@ -566,7 +639,7 @@ __global__ void edm_heun_kernel(float* __restrict__ x, const float* __restrict__
     }
     if (sc_out) *(f32x4*)(sc_out + i * 4) = tv;   // self-conditioning: the next step's first forward reads it
     if (rn) {
-      f32x4 z = noise4(noise, noise_stride, seed, PURPOSE_EDM_RENOISE, it, i);
+      f32x4 z = noise4(noise, noise_stride, key, PURPOSE_EDM_RENOISE, it, i, j);
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = o[e] + rs * z[e];
     }
@@ -578,9 +651,9 @@ int launch_edm_heun(float* x, const float* xh, const float* d_in, const float* d
                     const int* d_iter, int R, int N, int renoise, int dynamic_threshold, int B, int64_t per,
                     hipStream_t s, float* sc_out) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
-  const int64_t total4 = (int64_t)B * per / 4;
-  hipLaunchKernelGGL(edm_heun_kernel, dim3(grid_for(total4)), dim3(256), 0, s, x, xh, d_in, den, s_thresh, noise,
-                     noise_stride, d_seed, tb, d_iter, R, N, renoise, dynamic_threshold, per / 4, total4, sc_out);
+  KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
+  hipLaunchKernelGGL(edm_heun_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, xh, d_in, den, s_thresh, noise,
+                     noise_stride, d_seed, tb, d_iter, R, N, renoise, dynamic_threshold, per / 4, sc_out);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

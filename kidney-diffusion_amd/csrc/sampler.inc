@@ -57,7 +57,8 @@ static int sampler_scratch(kd_unet* u, bool guidance = false, bool edm = false) 
   const size_t img = image_bytes(u);
   auto need = [&](auto*& p, size_t bytes) { return p ? 0 : m.mem.get(&p, bytes); };
   if (need(m.pred, img) || need(m.x0, img) || need(m.thresh, (size_t)B * sizeof(float)) ||
-      need(m.time, (size_t)B * sizeof(float)) || need(m.iter, sizeof(int)) || need(m.seed, sizeof(uint64_t)) ||
+      need(m.time, (size_t)B * sizeof(float)) || need(m.iter, sizeof(int)) ||
+      need(m.seed, (size_t)(SEED_ROWS + B) * sizeof(uint64_t)) ||
       need(m.qws, quantile_ws_bytes(B)))
     return 1;
   if (guidance && need(m.pred_null, img)) return 1;
@@ -95,7 +96,7 @@ static int begin_call(kd_unet* u, const void* sched, const kd_sample_args_t* a, 
     KD_REQUIRE(a->d_null_text_tokens && a->d_null_text_hiddens && a->d_text_tokens && a->d_text_hiddens,
                "cond_scale != 1 needs the conditional and the null text conditioning");
   set_inputs(u, edm ? m.net_in : d_img, a, m.time, m.self_cond, m.pred);
-  if (launch_seed_set(m.seed, a->seed, s)) return 1;
+  if (launch_seed_set(m.seed, a->seed, a->seeds, u->cfg.batch, s)) return 1;   // (every call: k_begin > 0 re-keys too)
   return run_static(u, s);   // conditioning planes are constant over the loop
 }
 

@@ -96,6 +96,7 @@ class kd_sample_args_t(C.Structure):
         ("lowres_log_snr_value", C.c_float),
         ("cond_table", C.c_int),
         ("cond_table_max_mb", C.c_int),
+        ("seeds", C.POINTER(C.c_uint64)),   # host array of B per-image keys, or NULL: `seed` keys the whole batch
     ]
 
 
@@ -228,7 +229,19 @@ SIGNATURES = {
     "kd_quantile_workspace_bytes": (C.c_size_t, [C.c_int]),
     "kd_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
     "kd_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "kd_philox_normal_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
 }
+
+
+def stream_id(purpose: int, iteration: int) -> int:
+    """Philox stream id of include/kd_engine.h: purpose (1 .. 5 the sampler's draws, 16 the caller's) in the high 32
+    bits, iteration k * R + (R - 1 - r) in the low 32."""
+    return (int(purpose) << 32) | (int(iteration) & 0xFFFFFFFF)
+
+
+def seed_array(seeds):
+    """Host array of per-image Philox keys for kd_sample_args_t.seeds / kd_philox_normal_rows (keep it alive over the call)."""
+    return (C.c_uint64 * len(seeds))(*[int(s) for s in seeds])
 
 _lib = None
 ABI_VERSION = 2   # KD_ENGINE_ABI_VERSION of include/kd_engine.h

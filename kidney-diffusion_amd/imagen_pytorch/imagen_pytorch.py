@@ -921,6 +921,37 @@ def resize_image_to(image, target_image_size, mode="nearest"):
     return F.interpolate(image, target_image_size, mode=mode)
 
 
+STAGE_SEED_STRIDE = 0x9E3779B97F4A7C15   # stage s of a cascade draws under (seed + STAGE_SEED_STRIDE * s) mod 2^64
+
+
+def normalize_seed(seed, batch_size):
+    """``sample(seed=...)``: None and an int pass through (one key for the whole batch tensor); a sequence of ints or a
+    1-D integer tensor of length ``batch_size`` becomes a list of python ints in [0, 2^64), one Philox key per image.
+    Anything else raises ValueError.  Needs no GPU."""
+    import numbers
+
+    if seed is None or (isinstance(seed, numbers.Integral) and not isinstance(seed, bool)):
+        return seed
+    if torch.is_tensor(seed):
+        if seed.dim() != 1 or seed.dtype.is_floating_point or seed.dtype.is_complex or seed.dtype == torch.bool:
+            raise ValueError(f"seed tensor must be 1-D and of an integer dtype, got shape {tuple(seed.shape)} {seed.dtype}")
+        seeds = seed.tolist()
+    elif isinstance(seed, (str, bytes)) or not hasattr(seed, "__len__") or not hasattr(seed, "__iter__"):
+        raise ValueError(f"seed must be an int, a sequence of ints or a 1-D integer tensor, got {type(seed).__name__}")
+    else:
+        seeds = list(seed)
+    if len(seeds) != batch_size:
+        raise ValueError(f"seed holds {len(seeds)} values for a batch of {batch_size}: one per image is needed")
+    out = []
+    for s in seeds:
+        if not isinstance(s, numbers.Integral) or isinstance(s, bool):
+            raise ValueError(f"per-image seeds must be ints, got {s!r}")
+        if not 0 <= int(s) < 2 ** 64:
+            raise ValueError(f"per-image seed {int(s)} is outside [0, 2^64)")
+        out.append(int(s))
+    return out
+
+
 # ============================================================================ Imagen
 class Imagen(nn.Module):
     def __init__(self, unets, *, image_sizes, text_encoder_name=None, text_embed_dim=None, channels=3,
@@ -989,12 +1020,21 @@ class Imagen(nn.Module):
         """Signature of the library's ``Imagen.sample``.  Extensions (keyword-only):
         ``noise_fn(tag, shape)`` injects every Gaussian draw (parity tests, see oracle/sampler_ref.py
         for the tags); ``seed`` keys the on-device Philox stream when no ``noise_fn`` is given
-        (default: drawn from torch's global generator, so ``torch.manual_seed`` reproduces a run)."""
+        (default: drawn from torch's global generator, so ``torch.manual_seed`` reproduces a run).  An int keys
+        one stream over the whole batch tensor; a sequence of ints or a 1-D integer tensor of length ``batch_size``
+        keys every image by itself: image b then draws the noise of ``sample(batch_size=1, seed=seed[b])``, whatever
+        batch it runs in."""
         for name, v in dict(texts=texts, video_frames=video_frames, cond_video_frames=cond_video_frames,
                             post_cond_video_frames=post_cond_video_frames, inpaint_videos=inpaint_videos,
                             init_images=init_images, skip_steps=skip_steps).items():
             if exists(v):
                 raise NotImplementedError(f"sample({name}=...) is not used by the reference and not planned")
+        n_images = batch_size   # as settled below: the batched tensor arguments win over batch_size
+        if not self.unconditional and exists(text_embeds):
+            n_images = text_embeds.shape[0]
+        if exists(inpaint_images) and self.unconditional and n_images == 1:
+            n_images = inpaint_images.shape[0]
+        seed = normalize_seed(seed, n_images)
         E.require_gpu()
         device = torch.device(default(device, self.device))
         if device.type != "cuda":
@@ -1066,13 +1106,22 @@ class Imagen(nn.Module):
         lib = E.load()
         shape = (batch, self.channels, size, size)
         f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        stage_seed = (seed + 0x9E3779B97F4A7C15 * stage) % (2 ** 64)
+        per_image = isinstance(seed, list)   # normalize_seed: one key per image, each derived per stage like the int
+        if per_image:
+            stage_seeds = E.seed_array([(s + STAGE_SEED_STRIDE * stage) % (2 ** 64) for s in seed])
+            stage_seed = 0
+        else:
+            stage_seed = (seed + STAGE_SEED_STRIDE * stage) % (2 ** 64)
 
         def gauss(tag, shp, sid):
             if exists(noise_fn):
                 return f32(noise_fn(tag, tuple(shp)))
             out = torch.empty(shp, device=device, dtype=torch.float32)
-            E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), stage_seed, sid, E.current_stream()))
+            if per_image:   # row b is the batch-1 draw under image b's key
+                E.check(lib.kd_philox_normal_rows(E.ptr(out), shp[0], out.numel() // shp[0], stage_seeds, sid,
+                                                  E.current_stream()))
+            else:
+                E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), stage_seed, sid, E.current_stream()))
             return out
 
         # The engine caches the captured step graph keyed on the device addresses it was captured with.
@@ -1118,6 +1167,8 @@ class Imagen(nn.Module):
             args.d_lowres, args.d_lowres_log_snr, args.d_cond_images = E.ptr(lowres), E.ptr(lowres_log_snr), E.ptr(cond)
             args.d_inpaint_images, args.d_inpaint_masks = E.ptr(inp), E.ptr(msk)
             args.seed = stage_seed
+            if per_image:
+                args.seeds = stage_seeds
             args.use_graph = int(bool(use_graph))
             if unet.lowres_cond:   # one augmentation level for the whole batch (the library's sample() has no other form):
                 args.lowres_log_snr_uniform = 1          # lets the engine table the time conditioning per schedule step

@@ -16,7 +16,7 @@ import torch
 from packaging import version
 from torch import nn
 
-from .imagen_pytorch import Imagen, NullUnet, exists
+from .imagen_pytorch import Imagen, NullUnet, exists, normalize_seed
 from .version import __version__
 
 
@@ -151,7 +151,9 @@ class ImagenTrainer(nn.Module):
         `max_batch_size` splits the call the way the library's `imagen_sample_in_chunks` does: `batch_size` (or the
         leading dimension of the batched tensor arguments) is cut into chunks of at most `max_batch_size`, every
         tensor argument whose leading dimension equals the batch is cut alongside, and the outputs are joined in
-        order (tensors concatenated, PIL lists chained, per-unet lists joined per unet)."""
+        order (tensors concatenated, PIL lists chained, per-unet lists joined per unet).  Per-image seeds (a sequence
+        or a 1-D tensor) are cut alongside, so a chunked call draws the noise of the unchunked one; an int seed gives
+        chunk k the key `seed + 1000003 * k`."""
         kwargs.setdefault("device", self.device)
         max_batch_size = kwargs.pop("max_batch_size", None)
         with self.use_ema_unets():
@@ -179,13 +181,15 @@ class ImagenTrainer(nn.Module):
         def cut(v, n0, n1):
             return v[n0:n1] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == batch_size else v
 
-        seed = kwargs.get("seed")
+        seed = normalize_seed(kwargs.get("seed"), batch_size)
         outs, n0 = [], 0
         for k, b in enumerate(sizes):
             kw = {name: cut(v, n0, n0 + b) for name, v in kwargs.items()}
             if "batch_size" in kw or self.imagen.unconditional:
                 kw["batch_size"] = b
-            if seed is not None:   # a seeded call stays reproducible and its chunks draw different noise
+            if isinstance(seed, list):   # per-image keys are cut alongside the batch: the noise of the unchunked call
+                kw["seed"] = seed[n0:n0 + b]
+            elif seed is not None:   # a seeded call stays reproducible and its chunks draw different noise
                 kw["seed"] = int(seed) + 1000003 * k
             outs.append(self.imagen.sample(*[cut(a, n0, n0 + b) for a in args], **kw))
             n0 += b

@@ -527,7 +527,7 @@ def outpaint_canvas(sample_fn: Callable, num_patches_width: int, overlap: float 
 
 
 def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch.device, use_graph: bool = True,
-                     seed: Optional[int] = None, max_batch=1):
+                     seed: Optional[int] = None, max_batch=1, per_patch_seeds: bool = False):
     """sample_fn over the drop-in `imagen_pytorch.Imagen` (HIP engine).  `load_imagen(stage)` returns
     the Imagen holding the real unet of that stage (the reference re-loads one stage at a time,
     sample_ultra_res.py:79; a cache keeps all three resident here).  With `max_batch` = 1 each patch
@@ -537,8 +537,15 @@ def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch
     `sample()` call: they are independent (a wave holds no two neighbours), every patch keeps its own
     conditioning / low-res / inpaint tensors, and a batch-1 pass of the 64-px and 256-px UNets is
     weight-bandwidth bound, so a batch of 8 costs about as much as two single patches.  The plans of
-    the different batch sizes share one packed-weight store (kd_unet_create_shared)."""
+    the different batch sizes share one packed-weight store (kd_unet_create_shared).
+
+    With `seed` given, a `sample()` call is keyed by the first task of its batch, so a patch's noise follows the way the
+    wave was cut into calls (`max_batch`, the number of ranks).  `per_patch_seeds=True` keys every patch by its own task
+    instead (the same formula, one seed per image): a patch then draws the same noise in any batch on any rank."""
     cache = {}
+
+    def task_seed(stage, task):
+        return seed + 7919 * stage + 104729 * hash(task) % (2 ** 31)
 
     def cap(stage):
         m = max_batch.get(stage, 1) if isinstance(max_batch, dict) else max_batch
@@ -562,7 +569,7 @@ def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch
                       start_image_or_video=stack(lows[sl]), start_at_unet_number=stage, stop_at_unet_number=stage,
                       use_tqdm=False, device=device, use_graph=use_graph)
             if seed is not None:
-                kw["seed"] = seed + 7919 * stage + 104729 * hash(tasks[n0]) % (2 ** 31)
+                kw["seed"] = [task_seed(stage, t) for t in tasks[sl]] if per_patch_seeds else task_seed(stage, tasks[n0])
             elif base_seed is not None:   # drawn by the scheduler on its own thread (overlapped stage groups)
                 kw["seed"] = (base_seed + n0) % (2 ** 31 - 1)
             # the reference passes the (possibly all-zero) inpaint tensors for every grid patch (:149-174) and none
