@@ -51,7 +51,7 @@ const char* kd_last_error(void);
  *      kd_unet_create_ext3 with its struct kd_unet_ext3_t for `layer_attns_depth` - kd_unet_create_ext2 is that call with
  *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
  *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure); kd_sample_args_t gained `seeds` at its end
- *      (NULL = the keying of before) and kd_philox_normal_rows added */
+ *      (NULL = the keying of before) and kd_philox_normal_rows added; kd_sample_start added (the start of a stage, x_T) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -362,7 +362,10 @@ int kd_sample_loop(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_arg
                    float* d_img, void* stream);
 /* Runs iterations [k_begin, k_end) only, without the final clamp/unnormalise (used by bench.py
  * to time exactly K steps, and by tests to compare intermediate states).  Self-conditioned plans: k_begin == 0 starts
- * from self_cond = zeros; k_begin > 0 continues from the estimate the plan holds (kd_sample_set_self_cond). */
+ * from self_cond = zeros; k_begin > 0 continues from the estimate the plan holds (kd_sample_set_self_cond).
+ * sample(skip_steps = s > 0) is kd_sample_set_self_cond(u, NULL, stream) on a self-conditioned plan, then
+ * kd_sample_steps(u, ..., s, T) on the x_T of kd_sample_start, then kd_sample_finalize: step k of such a run reads row k
+ * of the tables and draws from the stream ids of step k of a full run. */
 int kd_sample_steps(kd_unet_t* u, const kd_schedule_t* sched, const kd_sample_args_t* args,
                     float* d_img, int k_begin, int k_end, void* stream);
 /* Builds (force != 0: rebuilds) the conditioning-table rows of schedule steps [k_begin, k_end) without sampling, so
@@ -382,7 +385,8 @@ int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream);
 /* which = 5 (self_cond plans): the self-conditioning planes the plan holds [B,3,S,S] - after a step, the thresholded x0
  * estimate the next forward will read.
  * Self_cond plans: sets that estimate (d_x_start [B,3,S,S], NULL = zeros) before a kd_sample_steps /
- * kd_edm_sample_steps call with k_begin > 0. */
+ * kd_edm_sample_steps call with k_begin > 0.  NULL is what a run from step skip_steps > 0 starts with (the library's
+ * self_cond = None), whatever an earlier call left in the plan. */
 int kd_sample_set_self_cond(kd_unet_t* u, const float* d_x_start, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -426,7 +430,9 @@ int kd_edm_sample_loop(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sa
                        void* stream);
 /* Steps [k_begin, k_end) only, without the final clamp / unnormalise.  kd_sample_last then reports the last forward of
  * the last iteration: which = 0 its UNet output after guidance, 1 the denoised estimate c_skip x + c_out net before
- * the threshold, 2 the thresholds; 3 x_hat and 4 d = (x_hat - thr(den)) / sigma_hat of that iteration. */
+ * the threshold, 2 the thresholds; 3 x_hat and 4 d = (x_hat - thr(den)) / sigma_hat of that iteration.
+ * sample(skip_steps = s > 0) runs [s, N) on x = sigma_0 z + image (kd_sample_start with scale = sigma[0], whatever s
+ * is), behind kd_sample_set_self_cond(u, NULL, stream) on a self-conditioned plan, and then kd_sample_finalize. */
 int kd_edm_sample_steps(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
                         int k_begin, int k_end, void* stream);
 
@@ -701,6 +707,21 @@ int kd_philox_normal(float* d_out, int64_t n, uint64_t seed, uint64_t stream_id,
  * `seeds` is a HOST pointer to B keys, read before the call returns.  Needs n % 4 == 0, n >= 4 and a 16-byte aligned
  * d_out (refused with an error, nothing launched, otherwise). */
 int kd_philox_normal_rows(float* d_out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream);
+/* The start of a stage (x_T) in one launch: d_x[b,c,y,x] = scale * z[b,c,y,x] + (2 * d_init[b,c,sy,sx] - 1), d_x [B,C,S,S].
+ *   z      N(0,1) of Philox stream (16 << 32) | 2, the x_T draw: under `seed` with the counter over the whole batch tensor
+ *          (seeds == NULL: the bits of kd_philox_normal over B C S S elements), under the HOST array `seeds` of B keys with
+ *          the counter inside the image (the bits of kd_philox_normal_rows; read before the call returns), or, when
+ *          d_noise [B,C,S,S] is given, read from it (seed and seeds are then not used).
+ *   scale  1 for the DDPM sampler, sigma_0 for the EDM sampler; scale = 1 gives z's bits.
+ *   d_init [B,C,Hs,Ws] in [0,1], or NULL: the image term is left out.  The source pixel is torch's
+ *          F.interpolate(mode="nearest"): sy = min((int)floorf((float)y * ((float)Hs / (float)S)), Hs - 1), sx likewise
+ *          with Ws; Hs = Ws = S is the identity.  Hs, Ws need not be equal nor multiples of anything.
+ * The arithmetic keeps torch's op order without contraction: 2 v, - 1, scale z, the sum.  Needs C S S % 4 == 0 and 16-byte
+ * aligned d_x / d_noise (refused with an error, nothing launched, otherwise).  sample() of the Python package starts
+ * every stage through this call; init_images / skip_steps then continue with kd_sample_steps / kd_edm_sample_steps from
+ * k_begin = skip_steps. */
+int kd_sample_start(float* d_x, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* d_noise,
+                    const float* d_init, int Hs, int Ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1063,5 +1063,9 @@ int kd_philox_normal(float* d_out, int64_t n, uint64_t seed, uint64_t stream_id,
 int kd_philox_normal_rows(float* d_out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, void* stream) {
   return launch_philox_normal_rows(d_out, B, n, seeds, stream_id, (hipStream_t)stream);
 }
+int kd_sample_start(float* d_x, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* d_noise,
+                    const float* d_init, int Hs, int Ws, void* stream) {
+  return launch_sample_start(d_x, B, C, S, scale, seed, seeds, d_noise, d_init, Hs, Ws, (hipStream_t)stream);
+}
 
 }  // extern "C"

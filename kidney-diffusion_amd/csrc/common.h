@@ -422,5 +422,9 @@ int launch_iter_inc(int* d_iter, hipStream_t s);
 int launch_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, hipStream_t s);
 // row b of out[B][n] = launch_philox_normal(n, seeds[b], stream_id); seeds on the host, n % 4 == 0
 int launch_philox_normal_rows(float* out, int B, int64_t n, const uint64_t* seeds, uint64_t stream_id, hipStream_t s);
+// x_T of a stage: out[B,C,S,S] = scale * z + (2 * nearest(init [B,C,Hs,Ws]) - 1); z from stream (16 << 32) | 2 under `seed`
+// (whole-batch counter) or host `seeds` (per image), or read from `noise`; init == nullptr leaves the image term out
+int launch_sample_start(float* out, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* noise,
+                        const float* init, int Hs, int Ws, hipStream_t s);
 
 }  // namespace kd

@@ -108,6 +108,77 @@ int launch_philox_normal_rows(float* out, int B, int64_t n, const uint64_t* seed
   return 0;
 }
 
+// The start of a stage: x[b,c,y,x] = scale * z + (2 * init[b,c,sy,sx] - 1), one float4 of x per thread and Philox call.
+// z is the draw of kd_philox_normal (per_image == 0: key keys.v[0], counter over the whole batch tensor) or of
+// kd_philox_normal_rows (per_image != 0: key keys.v[image of the launch], counter inside the image), or it is read from
+// `noise`.  The source pixel follows torch's nearest rule, min((int)floorf(dst * ((float)in / (float)out)), in - 1), the
+// ratios ry / rx divided in fp32 by the host; the gather is scalar, so the source rows need no alignment.  The pointers
+// are those of the launch's first image; b0 is that image's index in the batch (the counter of the whole-batch stream).
+__global__ __launch_bounds__(256) void sample_start_kernel(float* __restrict__ out, const float* __restrict__ noise,
+                                                           const float* __restrict__ init, int C, int S, int Hs, int Ws,
+                                                           float ry, float rx, float scale, SeedChunk keys, int per_image,
+                                                           int64_t b0, uint64_t sid) {
+  const int b = blockIdx.y;
+  const int64_t plane = (int64_t)S * S, per4 = C * plane / 4;
+  const uint64_t seed = keys.v[per_image ? b : 0];
+  const uint64_t ctr0 = per_image ? 0 : (uint64_t)((b0 + b) * per4);
+  float* row = out + (int64_t)b * per4 * 4;
+  const float* zrow = noise ? noise + (int64_t)b * per4 * 4 : nullptr;
+  const float* src = init ? init + (int64_t)b * C * Hs * Ws : nullptr;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
+    f32x4 z = zrow ? *(const f32x4*)(zrow + j * 4) : philox_normal4(seed, sid, ctr0 + (uint64_t)j);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = z[e] * scale;
+    if (src) {
+      int c = (int)(j * 4 / plane);   // (c, y, x) of the float4's first element; a float4 may cross a row or a plane
+      const int rem = (int)(j * 4 - c * plane);
+      int y = rem / S, x = rem - y * S;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int sy = min((int)floorf((float)y * ry), Hs - 1);
+        const int sx = min((int)floorf((float)x * rx), Ws - 1);
+        float t = 2.0f * src[((int64_t)c * Hs + sy) * Ws + sx];
+        t = t - 1.0f;
+        o[e] = o[e] + t;
+        if (++x == S) {
+          x = 0;
+          if (++y == S) {
+            y = 0;
+            ++c;   // (c == C only behind the image's last element: not read)
+          }
+        }
+      }
+    }
+    *(f32x4*)(row + j * 4) = o;
+  }
+}
+int launch_sample_start(float* out, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* noise,
+                        const float* init, int Hs, int Ws, hipStream_t s) {
+  KD_REQUIRE(out != nullptr, "sample start: null output");
+  KD_REQUIRE(B >= 1 && B <= 65535 && C >= 1 && C <= 1024 && S >= 1 && S <= 16384,
+             "sample start: batch, channels or image size out of range");
+  const int64_t n = (int64_t)C * S * S;
+  KD_REQUIRE(n % 4 == 0, "sample start: the row length C * S * S must be a multiple of 4");
+  KD_REQUIRE(((uintptr_t)out & 15) == 0 && ((uintptr_t)noise & 15) == 0, "sample start: out and noise must be 16-byte aligned");
+  KD_REQUIRE(init == nullptr || (Hs >= 1 && Ws >= 1 && Hs <= 16384 && Ws <= 16384), "sample start: source size out of range");
+  const float ry = init ? (float)Hs / (float)S : 1.0f, rx = init ? (float)Ws / (float)S : 1.0f;
+  const bool per_image = seeds != nullptr && noise == nullptr;
+  const uint64_t sid = ((uint64_t)PURPOSE_USER << 32) | 2;   // the caller's x_T stream (include/kd_engine.h)
+  const int step = per_image ? (int)SEED_CHUNK : B;   // per-image keys travel as a kernel argument, SEED_CHUNK per launch
+  for (int b0 = 0; b0 < B; b0 += step) {
+    const int nb = std::min(B - b0, step);
+    SeedChunk keys{};
+    keys.v[0] = seed;
+    for (int b = 0; per_image && b < nb; ++b) keys.v[b] = seeds[b0 + b];
+    hipLaunchKernelGGL(sample_start_kernel, grid_rows(n / 4, nb), dim3(256), 0, s, out + (int64_t)b0 * n,
+                       noise ? noise + (int64_t)b0 * n : nullptr, init ? init + (int64_t)b0 * C * Hs * Ws : nullptr, C, S, Hs,
+                       Ws, ry, rx, scale, keys, per_image ? 1 : 0, (int64_t)b0, sid);
+  }
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // The key block in device memory (Sampler::seed): [SEED_BATCH] keys the whole batch tensor, the counter being the float4
 // index over all B images; [SEED_MODE] != 0 switches to one key per image, [SEED_ROWS + b], with the counter running
 // inside the image - image b then draws what a batch-1 call keyed seeds[b] draws.  Both words are read by the kernels,

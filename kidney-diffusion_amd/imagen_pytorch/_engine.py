@@ -230,6 +230,8 @@ SIGNATURES = {
     "kd_cfg_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
     "kd_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "kd_philox_normal_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
+    "kd_sample_start": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_uint64),
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
 

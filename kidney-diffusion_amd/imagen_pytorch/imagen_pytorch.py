@@ -952,6 +952,52 @@ def normalize_seed(seed, batch_size):
     return out
 
 
+def normalize_init_images(init_images, skip_steps, *, steps, batch_size, channels, start_at_unet_number=1,
+                          stop_at_unet_number=None):
+    """``sample(init_images=..., skip_steps=...)`` cast per UNet, as the library does: ``init_images`` is None, one tensor
+    [batch, channels, H, W] used by every UNet sampled, or a tuple / list with one entry (tensor or None) per UNet;
+    ``skip_steps`` is None (0), an int, or a tuple / list with one entry (int or None) per UNet.  ``steps[i]`` is the
+    number of schedule steps of UNet i + 1; its skip must lie in 0 .. steps[i] - 1.  Returns a list of
+    ``(float tensor in [0, 1] or None, skip)``, one pair per UNet; entries of UNets that ``start_at_unet_number`` /
+    ``stop_at_unet_number`` leave out are not looked at and come back as ``(None, 0)``.  uint8 images are divided by 255,
+    as cond_images are.  Anything else raises ValueError.  Needs no GPU."""
+    import numbers
+
+    n = len(steps)
+
+    def per_unet(v, name):
+        if isinstance(v, (tuple, list)):
+            if len(v) != n:
+                raise ValueError(f"{name} holds {len(v)} entries for {n} unets: one per unet is needed")
+            return list(v)
+        return [v] * n
+
+    inits, skips = per_unet(init_images, "init_images"), per_unet(skip_steps, "skip_steps")
+    out = []
+    for i, (init, skip, T) in enumerate(zip(inits, skips, steps)):
+        num = i + 1
+        if num < start_at_unet_number or (exists(stop_at_unet_number) and num > stop_at_unet_number):
+            out.append((None, 0))
+            continue
+        skip = default(skip, 0)
+        if not isinstance(skip, numbers.Integral) or isinstance(skip, bool):
+            raise ValueError(f"skip_steps of unet {num} must be an int, got {skip!r}")
+        if not 0 <= int(skip) < T:
+            raise ValueError(f"skip_steps={int(skip)} of unet {num} is outside 0 .. {T - 1}, the steps of its schedule")
+        if exists(init):
+            if not torch.is_tensor(init):
+                raise ValueError(f"init_images of unet {num} must be a tensor or None, got {type(init).__name__}")
+            if init.dim() != 4 or init.shape[0] != batch_size or init.shape[1] != channels or 0 in init.shape[2:]:
+                raise ValueError(f"init_images of unet {num} must be [batch {batch_size}, channels {channels}, H, W], "
+                                 f"got {tuple(init.shape)}")
+            if init.dtype == torch.uint8:
+                init = init.float() / 255.0
+            elif not init.dtype.is_floating_point:
+                raise ValueError(f"init_images of unet {num} must be of a floating dtype or uint8, got {init.dtype}")
+        out.append((init, int(skip)))
+    return out
+
+
 # ============================================================================ Imagen
 class Imagen(nn.Module):
     def __init__(self, unets, *, image_sizes, text_encoder_name=None, text_embed_dim=None, channels=3,
@@ -1023,10 +1069,13 @@ class Imagen(nn.Module):
         (default: drawn from torch's global generator, so ``torch.manual_seed`` reproduces a run).  An int keys
         one stream over the whole batch tensor; a sequence of ints or a 1-D integer tensor of length ``batch_size``
         keys every image by itself: image b then draws the noise of ``sample(batch_size=1, seed=seed[b])``, whatever
-        batch it runs in."""
+        batch it runs in.
+        ``init_images`` / ``skip_steps`` (the library's, cast per UNet by ``normalize_init_images``): the stage starts from
+        ``z + nearest(2 init - 1)`` (EDM: ``sigma_0 z + ...``, sigma_0 the first sigma of the full schedule) and walks the
+        schedule steps ``skip .. T - 1`` only; a step keeps its index, hence its table rows, noise streams and
+        ``noise_fn`` tags, and ``trace`` receives one state per step walked."""
         for name, v in dict(texts=texts, video_frames=video_frames, cond_video_frames=cond_video_frames,
-                            post_cond_video_frames=post_cond_video_frames, inpaint_videos=inpaint_videos,
-                            init_images=init_images, skip_steps=skip_steps).items():
+                            post_cond_video_frames=post_cond_video_frames, inpaint_videos=inpaint_videos).items():
             if exists(v):
                 raise NotImplementedError(f"sample({name}=...) is not used by the reference and not planned")
         n_images = batch_size   # as settled below: the batched tensor arguments win over batch_size
@@ -1035,6 +1084,9 @@ class Imagen(nn.Module):
         if exists(inpaint_images) and self.unconditional and n_images == 1:
             n_images = inpaint_images.shape[0]
         seed = normalize_seed(seed, n_images)
+        starts = normalize_init_images(init_images, skip_steps, steps=self._num_steps(), batch_size=n_images,
+                                       channels=self.channels, start_at_unet_number=start_at_unet_number,
+                                       stop_at_unet_number=stop_at_unet_number)
         E.require_gpu()
         device = torch.device(default(device, self.device))
         if device.type != "cuda":
@@ -1072,9 +1124,9 @@ class Imagen(nn.Module):
             img = resize_image_to(f32(start_image_or_video), self.image_sizes[start_at_unet_number - 2])
 
         outputs = []
-        for num, unet, size, sched, obj, dyn, cs in zip(
+        for num, unet, size, sched, obj, dyn, cs, (init_image, skip) in zip(
                 range(1, n + 1), self.unets, self.image_sizes, self.noise_schedulers, self.pred_objectives,
-                self.dynamic_thresholding, cond_scale):
+                self.dynamic_thresholding, cond_scale, starts):
             if num < start_at_unet_number:
                 continue
             assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
@@ -1083,7 +1135,7 @@ class Imagen(nn.Module):
             img = self._p_sample_loop(
                 unet, num, size, sched, obj, dyn, batch_size, device, img, cond_images, inpaint_images,
                 inpaint_masks, inpaint_resample_times, lowres_sample_noise_level, noise_fn, seed, use_graph, trace,
-                text_embeds=text_embeds, text_masks=text_masks, cond_scale=float(cs))
+                text_embeds=text_embeds, text_masks=text_masks, cond_scale=float(cs), init_image=init_image, skip=skip)
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == num:
                 break
@@ -1102,7 +1154,7 @@ class Imagen(nn.Module):
 
     def _p_sample_loop(self, unet, stage, size, sched, objective, dynamic_threshold, batch, device, prev_img,
                        cond_images, inpaint_images, inpaint_masks, resample_times, lowres_level, noise_fn, seed,
-                       use_graph, trace, text_embeds=None, text_masks=None, cond_scale=1.0):
+                       use_graph, trace, text_embeds=None, text_masks=None, cond_scale=1.0, init_image=None, skip=0):
         lib = E.load()
         shape = (batch, self.channels, size, size)
         f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
@@ -1175,7 +1227,18 @@ class Imagen(nn.Module):
                 args.lowres_log_snr_value = float(ls[0])
             args.cond_table = int(getattr(self, "cond_table", 0))   # engine extension: < 0 switches the table off
             keep = []
-            img = stable("img", gauss(("init", stage), shape, (16 << 32) | 2))
+            # x_T = scale * z + (2 * nearest(init_image) - 1), written into the stable buffer by one engine call: z drawn in
+            # the kernel (stream (16 << 32) | 2 under the stage's key or keys) or read from the injected tensor
+            img = io.get("img")
+            if img is None or img.shape != shape:
+                img = io["img"] = torch.empty(shape, device=device, dtype=torch.float32)
+            z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
+            init_image = f32(init_image)
+            hs, ws = init_image.shape[2:] if exists(init_image) else (0, 0)
+            E.check(lib.kd_sample_start(E.ptr(img), batch, self.channels, size, self._start_scale(stage), stage_seed,
+                                        stage_seeds if per_image else None, E.ptr(z), E.ptr(init_image), hs, ws,
+                                        E.current_stream()))
+            keep += [z, init_image]
             with_text = exists(text_embeds) and unet.cond_on_text
             h = unet.engine(batch, size, device, with_text=with_text)
             if with_text:  # step-invariant: pooled text tokens + text hiddens, once per stage
@@ -1191,13 +1254,16 @@ class Imagen(nn.Module):
                     args.d_null_text_tokens, args.d_null_text_hiddens = E.ptr(ntok), E.ptr(nhid)
 
             def stack(kind, T):   # injected noise of every iteration, [T*R, *shape], indexed k*R + (R-1-r)
-                ts = [noise_fn((kind, stage, k, r), shape) for k in range(T) for r in reversed(range(R))]
+                ts = [noise_fn((kind, stage, k, r), shape) for k in range(skip, T) for r in reversed(range(R))]
                 t = f32(torch.stack(ts))
+                if skip:   # the steps not walked are not asked for; a step keeps its slot
+                    t = torch.cat([t.new_zeros((skip * R, *t.shape[1:])), t])
                 keep.append(t)
                 return E.ptr(t)
 
             self._stage_loop(lib, h, args, img, stage=stage, sched=sched, objective=objective, has_inpaint=has_inpaint,
-                             R=R, stack=stack if exists(noise_fn) else None, trace=trace)
+                             R=R, stack=stack if exists(noise_fn) else None, trace=trace, skip=skip,
+                             self_cond=bool(unet.self_cond))
             # No host synchronisation here: the engine copies the schedule tables into its own staging buffer inside
             # the call, and the injected-noise tensors in `keep` are device memory of torch's current stream - the
             # caching allocator re-uses it for later allocations of that stream only, i.e. after these launches.
@@ -1205,9 +1271,19 @@ class Imagen(nn.Module):
             img = img.clone()  # the stable buffer is overwritten by the next call (stream-ordered copy)
         return img
 
-    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace):
+    def _num_steps(self):
+        """Schedule steps of every UNet's sampler: what skip_steps is checked against."""
+        return [s.num_timesteps for s in self.noise_schedulers]
+
+    def _start_scale(self, stage):
+        """x_T = scale * N(0,1) (+ the init image): 1 for the DDPM sampler."""
+        return 1.0
+
+    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
+                    self_cond=False):
         """The sampler proper of one stage, in place on `img` (x_T in, the unnormalised sample out): the DDPM loop of
-        p_sample_loop.  `stack(kind, T)` gives the injected noise of a kind (None: on-device Philox)."""
+        p_sample_loop over the steps skip .. T - 1.  `stack(kind, T)` gives the injected noise of a kind (None: on-device
+        Philox).  A self-conditioned plan starts step `skip` > 0 from zeros, as step 0 does by itself."""
         T = sched.num_timesteps
         tables = sched.step_tables()
         sc = E.kd_schedule_t()
@@ -1221,10 +1297,15 @@ class Imagen(nn.Module):
                 args.d_noise_inpaint = stack("inpaint", T)
                 if R > 1:
                     args.d_noise_renoise = stack("renoise", T)
+        if skip > 0 and self_cond:
+            E.check(lib.kd_sample_set_self_cond(h, None, E.current_stream()))
         if exists(trace):
-            for k in range(T):
+            for k in range(skip, T):
                 E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
                 trace.append(img.clone())
+            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
+        elif skip > 0:
+            E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), skip, T, E.current_stream()))
             E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
         else:
             E.check(lib.kd_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
@@ -1297,25 +1378,39 @@ class ElucidatedImagen(Imagen):
         """Host tables of UNet `unet_number`'s sampler (edm_step_tables)."""
         return edm_step_tables(**self.hparams[unet_number - 1])
 
-    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace):
-        """one_unet_sample of the library's ElucidatedImagen on the engine: x = sigma_0 * N(0,1), then per step churn,
-        a preconditioned forward and the Euler step, and (not on the last step) a second forward and the Heun
-        correction; RePaint re-noise between resamples.  Noise tags ("churn" | "renoise", stage, k, r)."""
+    def _num_steps(self):
+        return [hp["num_sample_steps"] for hp in self.hparams]
+
+    def _start_scale(self, stage):
+        """x = sigma_0 * N(0,1) (+ the init image): the first sigma of the full schedule, whatever skip_steps is; a python
+        float of the fp32 value, so the kernel's product is the library's fp32 tensor product."""
+        return float(self.step_tables(stage)["init_sigma"])
+
+    def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
+                    self_cond=False):
+        """one_unet_sample of the library's ElucidatedImagen on the engine, on x = sigma_0 * N(0,1) (+ the init image) as
+        kd_sample_start wrote it: per step skip .. N - 1 churn, a preconditioned forward and the Euler step, and (not on
+        the last step) a second forward and the Heun correction; RePaint re-noise between resamples.  Noise tags
+        ("churn" | "renoise", stage, k, r)."""
         tab = self.step_tables(stage)
         N = self.hparams[stage - 1]["num_sample_steps"]
         sc = E.kd_edm_schedule_t()
         sc.N, sc.S_noise = N, float(self.hparams[stage - 1]["S_noise"])
         for name, _ in E.kd_edm_schedule_t._fields_[2:]:
             setattr(sc, name, tab[name].numpy().ctypes.data_as(C.POINTER(C.c_float)))
-        img.mul_(float(tab["init_sigma"]))   # x = sigma_0 * N(0,1), fp32 as the library's tensor product
         if exists(stack):
             args.d_noise_step = stack("churn", N)
             if has_inpaint and R > 1:
                 args.d_noise_renoise = stack("renoise", N)
+        if skip > 0 and self_cond:
+            E.check(lib.kd_sample_set_self_cond(h, None, E.current_stream()))
         if exists(trace):
-            for k in range(N):
+            for k in range(skip, N):
                 E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
                 trace.append(img.clone())
+            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
+        elif skip > 0:
+            E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), skip, N, E.current_stream()))
             E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
         else:
             E.check(lib.kd_edm_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))

@@ -151,7 +151,8 @@ class ImagenTrainer(nn.Module):
         `max_batch_size` splits the call the way the library's `imagen_sample_in_chunks` does: `batch_size` (or the
         leading dimension of the batched tensor arguments) is cut into chunks of at most `max_batch_size`, every
         tensor argument whose leading dimension equals the batch is cut alongside, and the outputs are joined in
-        order (tensors concatenated, PIL lists chained, per-unet lists joined per unet).  Per-image seeds (a sequence
+        order (tensors concatenated, PIL lists chained, per-unet lists joined per unet).  `init_images` is cut like
+        the batch, as one tensor or as every tensor of a per-unet tuple; `skip_steps` passes through.  Per-image seeds (a sequence
         or a 1-D tensor) are cut alongside, so a chunked call draws the noise of the unchunked one; an int seed gives
         chunk k the key `seed + 1000003 * k`."""
         kwargs.setdefault("device", self.device)
@@ -179,6 +180,8 @@ class ImagenTrainer(nn.Module):
             return self.imagen.sample(*args, **kwargs)
 
         def cut(v, n0, n1):
+            if isinstance(v, (tuple, list)) and any(torch.is_tensor(e) for e in v):   # per-unet init_images: every tensor
+                return type(v)(cut(e, n0, n1) for e in v)
             return v[n0:n1] if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == batch_size else v
 
         seed = normalize_seed(kwargs.get("seed"), batch_size)
