@@ -51,7 +51,8 @@ const char* kd_last_error(void);
  *      kd_unet_create_ext3 with its struct kd_unet_ext3_t for `layer_attns_depth` - kd_unet_create_ext2 is that call with
  *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
  *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure); kd_sample_args_t gained `seeds` at its end
- *      (NULL = the keying of before) and kd_philox_normal_rows added; kd_sample_start added (the start of a stage, x_T) */
+ *      (NULL = the keying of before) and kd_philox_normal_rows added; kd_sample_start added (the start of a stage, x_T);
+ *      kd_solver_sample_loop / kd_solver_sample_steps with their struct kd_solver_schedule_t added (DDIM, DPM-Solver++(2M)) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -388,6 +389,43 @@ int kd_sample_last(kd_unet_t* u, int which, float* d_out, void* stream);
  * kd_edm_sample_steps call with k_begin > 0.  NULL is what a run from step skip_steps > 0 starts with (the library's
  * self_cond = None), whatever an earlier call left in the plan. */
 int kd_sample_set_self_cond(kd_unet_t* u, const float* d_x_start, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Few-step solvers for DDPM-trained UNets (an engine extension; the library has neither): DDIM(eta) and the second-order
+ * multistep DPM-Solver++(2M) in its data-prediction form.  An iteration is kd_sample_steps' - inpaint mix, time input,
+ * guided forward, x0 estimate, dynamic threshold, re-noise - with one other update:
+ *     x <- coef_x[k] x + coef_x0[k] x0c + coef_prev[k] hist + coef_noise[k] N(0,1)
+ * x0c = clamp(x0, -s, s) / s the thresholded estimate of this step, hist the x0c the previous step kept.  The host puts
+ * the solver into the coefficients (the Python package: solver_tables; DESIGN.md "Few-step solvers").  A term whose
+ * coefficient is 0 is left out and its operand is not read: no noise is drawn for a deterministic step, and a first-order
+ * step (coef_prev == 0, which the first step a call walks must be) does not depend on what the plan holds.  hist takes a
+ * step's x0c in its last resample slot, so all R resamples of step k read the estimate of step k - 1; it lives in the plan
+ * from the first call whose schedule has a coef_prev != 0 and persists between calls, as the self-conditioning estimate does.
+ * ---------------------------------------------------------------------------------------- */
+/* All arrays have T entries; log_snr, alpha, sigma, rn_a, rn_b as in kd_schedule_t - rn_a / rn_b may be NULL without
+ * resampling - and the four coefficients are required. */
+typedef struct kd_solver_schedule {
+  int T;
+  const float* log_snr;
+  const float* alpha;
+  const float* sigma;
+  const float* rn_a;
+  const float* rn_b;
+  const float* coef_x;
+  const float* coef_x0;
+  const float* coef_prev;
+  const float* coef_noise;
+} kd_solver_schedule_t;
+
+/* kd_sample_loop with the solver's update: kd_sample_args_t as there; d_noise_step [T*R,B,C,S,S] is read (NULL: Philox
+ * purpose 1, the stream ids of kd_sample_loop) only in steps with coef_noise != 0.  The path keeps its own tables and
+ * captured iterations, so a plan may alternate between kd_sample_*, kd_edm_sample_* and these without re-capturing. */
+int kd_solver_sample_loop(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                          void* stream);
+/* Steps [k_begin, k_end) only, without the final clamp / unnormalise; kd_sample_last reports pred / x0 / thresholds as
+ * after kd_sample_steps.  k_begin > 0 continues from the self-conditioning estimate and the history the plan holds. */
+int kd_solver_sample_steps(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                           int k_begin, int k_end, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * EDM sampler.  Replaces `ElucidatedImagen.sample` / `one_unet_sample` / `preconditioned_network_forward` of

@@ -243,6 +243,8 @@ int kd_unet_profile(kd_unet_t* u, int iters, char* buf, size_t buflen, void* str
 //     sampler   pred, pred_null, x0, thresh, time, xhat, d, net_in: written by the kernels of an iteration before they
 //               are read (kd_sample_last reports the last call's: read it before poisoning); self_cond: zeroed at step 0
 //               of a call (a caller that continues with k_begin > 0 seeds it after this call, kd_sample_set_self_cond);
+//               hist (few-step solvers): the first step a call walks is first order and does not read it, and its
+//               last resample slot writes it (a caller that continues with k_begin > 0 poisons before the first call);
 //               qws: the quantile's QState and histograms are integers - q_init_kernel sets every one of them at the
 //               start of each launch_quantile_abs, before q_hist / q_scan / q_next / q_final index or count with them
 //   left alone - state that outlives a call:
@@ -265,6 +267,7 @@ int kd_unet_poison_scratch(kd_unet_t* u, uint32_t word, int64_t* bytes_filled, v
       {m.pred, img},          {m.pred_null, img},          {m.x0, img},
       {m.thresh, per_b},      {m.time, per_b},             {m.xhat, img},
       {m.d, img},             {m.net_in, img},             {m.self_cond, img},
+      {m.hist, img},
       {m.qws, quantile_ws_bytes(u->cfg.batch)}};
   int64_t total = 0;
   for (const auto& b : bufs) {
@@ -312,6 +315,21 @@ int kd_edm_sample_loop(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sa
     return 1;
   }
   if (edm_sample_steps(u, sched, args, d_img, 0, sched->N, (hipStream_t)stream)) return 1;
+  return kd_sample_finalize(u, args, d_img, stream);
+}
+
+int kd_solver_sample_steps(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                           int k_begin, int k_end, void* stream) {
+  return solver_sample_steps(u, sched, args, d_img, k_begin, k_end, (hipStream_t)stream);
+}
+
+int kd_solver_sample_loop(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                          void* stream) {
+  if (!sched) {
+    set_error("kd_solver_sample_loop: null schedule");
+    return 1;
+  }
+  if (solver_sample_steps(u, sched, args, d_img, 0, sched->T, (hipStream_t)stream)) return 1;
   return kd_sample_finalize(u, args, d_img, stream);
 }
 

@@ -381,6 +381,15 @@ size_t quantile_ws_bytes(int B);
 int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int dynamic_threshold,
                        int B, int64_t per, hipStream_t s, float* sc_out = nullptr);   // sc_out: thresholded x0 (self_cond)
+// Few-step solvers (DDIM, DPM-Solver++(2M)): x = coef_x x + coef_x0 x0c + coef_prev hist + coef_noise N(0,1), device arrays
+// of T floats (kd_solver_schedule_t).  hist: the thresholded estimate the previous step kept, or nullptr when no step of
+// the schedule reads one; it takes this step's in the last resample slot.
+struct SolverTables {
+  const float *coef_x, *coef_x0, *coef_prev, *coef_noise;
+};
+int launch_solver_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
+                         const uint64_t* d_seed, const SolverTables& tb, const int* d_iter, int R, int dynamic_threshold,
+                         int B, int64_t per, hipStream_t s, float* hist, float* sc_out);
 int launch_inpaint_mix(float* x, const float* inp, const float* mask, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int B, int C, int64_t hw,
                        hipStream_t s);

@@ -108,6 +108,14 @@ class kd_edm_schedule_t(C.Structure):
                   "c_skip_hat", "c_out_hat", "c_noise_hat", "c_in_next", "c_skip_next", "c_out_next", "c_noise_next")
     ]
 
+
+class kd_solver_schedule_t(C.Structure):
+    _fields_ = [("T", C.c_int)] + [
+        (n, C.POINTER(C.c_float))
+        for n in ("log_snr", "alpha", "sigma", "rn_a", "rn_b", "coef_x", "coef_x0", "coef_prev", "coef_noise")
+    ]
+
+
 class kd_unet_ext_t(C.Structure):
     _fields_ = [("self_cond", C.c_int), ("use_linear_attn", C.c_int * KD_MAX_LEVELS),
                 ("use_linear_cross_attn", C.c_int * KD_MAX_LEVELS),
@@ -169,6 +177,10 @@ SIGNATURES = {
                                      C.c_void_p]),
     "kd_edm_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_edm_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
                                       C.c_int, C.c_int, C.c_void_p]),
+    "kd_solver_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_solver_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                        C.c_void_p]),
+    "kd_solver_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_solver_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                         C.c_int, C.c_int, C.c_void_p]),
     "kd_conv2d_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
     "kd_upsample_nearest_conv3x3_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "kd_upsample_nearest_gn_conv3x3_nhwc": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),

@@ -896,7 +896,14 @@ class GaussianDiffusionContinuousTimes(nn.Module):
             self.log_snr = alpha_cosine_log_snr
         else:
             raise ValueError(f"invalid noise schedule {noise_schedule}")
+        self.noise_schedule = noise_schedule
         self.num_timesteps = timesteps
+
+    def with_timesteps(self, timesteps):
+        """The schedule of the same kind on `timesteps` steps (time is continuous: sample(sample_steps=...))."""
+        if timesteps == self.num_timesteps:
+            return self
+        return GaussianDiffusionContinuousTimes(noise_schedule=self.noise_schedule, timesteps=timesteps)
 
     def step_tables(self):
         ts = torch.linspace(1.0, 0.0, self.num_timesteps + 1)
@@ -913,6 +920,93 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         names = ("log_snr", "alpha", "sigma", "alpha_next", "sigma_next", "c", "noise_scale", "rn_a", "rn_b")
         vals = (ls, alpha, sigma, alpha_next, sigma_next, c, noise_scale, rn_a, rn_b)
         return {n: v.to(torch.float32).contiguous() for n, v in zip(names, vals)}
+
+
+SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")
+
+
+def solver_tables(step_tables, sampler, eta=0.0, skip=0):
+    """Coefficients of the few-step solvers' update  x <- coef_x x + coef_x0 x0c + coef_prev hist + coef_noise z  for every
+    step of a schedule (the arrays of kd_solver_schedule_t; DESIGN.md "Few-step solvers").  ``step_tables`` are the fp32
+    entries of ``GaussianDiffusionContinuousTimes.step_tables()``; they are evaluated in float64 and rounded to fp32 once.
+    With a, s = alpha, sigma at t_k, a', s' those at t_{k+1} and c the table's c:
+
+    ``"ddim"``, 0 <= eta <= 1: d = eta sqrt(s'^2 c) (the ancestral step's posterior deviation, from the table's c),
+    A = sqrt(max(s'^2 - d^2, 0)) / s, B = a' - A a, P = 0, S = d; the last step adds no noise (S = 0, its A and B still
+    formed with d).  eta = 1 is the ancestral step, eta = 0 is deterministic.
+
+    ``"dpmpp_2m"`` (DPM-Solver++(2M), data prediction): lambda = log_snr / 2, h_k = lambda'_k - lambda_k,
+    b_k = -a' expm1(-h_k), A = s' / s, S = 0; first-order steps - the first step walked (k == ``skip``) and the last -
+    have B = b, P = 0; every other step w = h_k / (2 h_{k-1}), B = b (1 + w), P = -b w.
+
+    Pure host arithmetic; needs no GPU."""
+    if sampler not in ("ddim", "dpmpp_2m"):
+        raise ValueError(f"solver_tables: sampler must be 'ddim' or 'dpmpp_2m', got {sampler!r}")
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError(f"solver_tables: eta={eta} is outside [0, 1]")
+    if eta != 0 and sampler != "ddim":
+        raise ValueError(f"solver_tables: eta={eta} needs sampler 'ddim', got {sampler!r}")
+    t = {n: step_tables[n].to(torch.float64) for n in ("log_snr", "alpha", "sigma", "alpha_next", "sigma_next", "c")}
+    a, s, an, sn = t["alpha"], t["sigma"], t["alpha_next"], t["sigma_next"]
+    N = a.numel()
+    if not 0 <= int(skip) < N:
+        raise ValueError(f"solver_tables: skip={skip} is outside 0 .. {N - 1}")
+    P = torch.zeros(N, dtype=torch.float64)
+    S = torch.zeros(N, dtype=torch.float64)
+    if sampler == "ddim":
+        d = float(eta) * torch.sqrt(sn ** 2 * t["c"])
+        A = torch.sqrt((sn ** 2 - d ** 2).clamp(min=0.0)) / s
+        B = an - A * a
+        S = d.clone()
+        S[N - 1] = 0.0
+    else:
+        lam = t["log_snr"] / 2
+        # log-SNR at t_{k+1}: the next row's entry; behind the last row the tables hold alpha and sigma alone
+        lam_next = torch.cat([lam[1:], torch.log(an[-1:] / sn[-1:])])
+        h = lam_next - lam
+        b = -an * torch.expm1(-h)
+        A = sn / s
+        B = b.clone()
+        for k in range(int(skip) + 1, N - 1):
+            w = h[k] / (2 * h[k - 1])
+            B[k] = b[k] * (1 + w)
+            P[k] = -b[k] * w
+    names = ("coef_x", "coef_x0", "coef_prev", "coef_noise")
+    return {n: v.to(torch.float32).contiguous() for n, v in zip(names, (A, B, P, S))}
+
+
+def normalize_sampler(sampler, sampler_eta, sample_steps, num_unets):
+    """``sample(sampler=..., sampler_eta=..., sample_steps=...)`` cast per UNet: each is a scalar or a tuple / list with
+    one entry per UNet.  ``sampler``: None or ``"ddpm"`` (the ancestral sampler), ``"ddim"``, ``"dpmpp_2m"``;
+    ``sampler_eta`` in [0, 1], non-zero only with ``"ddim"``; ``sample_steps`` None (the constructor's timesteps) or an
+    int >= 1.  Returns a list of ``(name, eta, steps or None)``.  Anything else raises ValueError.  Needs no GPU."""
+    import numbers
+
+    def per_unet(v, name):
+        if isinstance(v, (tuple, list)):
+            if len(v) != num_unets:
+                raise ValueError(f"{name} holds {len(v)} entries for {num_unets} unets: one per unet is needed")
+            return list(v)
+        return [v] * num_unets
+
+    out = []
+    for i, (name, eta, steps) in enumerate(zip(per_unet(sampler, "sampler"), per_unet(sampler_eta, "sampler_eta"),
+                                               per_unet(sample_steps, "sample_steps"))):
+        num = i + 1
+        name = default(name, "ddpm")
+        if name not in SAMPLERS:
+            raise ValueError(f"sampler of unet {num} must be one of {SAMPLERS} or None, got {name!r}")
+        eta = default(eta, 0.0)
+        if not isinstance(eta, numbers.Real) or isinstance(eta, bool) or not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"sampler_eta of unet {num} must be a number in [0, 1], got {eta!r}")
+        if float(eta) != 0.0 and name != "ddim":
+            raise ValueError(f"sampler_eta={eta} of unet {num} needs sampler='ddim', got {name!r}")
+        if exists(steps):
+            if not isinstance(steps, numbers.Integral) or isinstance(steps, bool) or int(steps) < 1:
+                raise ValueError(f"sample_steps of unet {num} must be an int >= 1 or None, got {steps!r}")
+            steps = int(steps)
+        out.append((name, float(eta), steps))
+    return out
 
 
 def resize_image_to(image, target_image_size, mode="nearest"):
@@ -1062,7 +1156,8 @@ class Imagen(nn.Module):
                cond_scale=1.0, lowres_sample_noise_level=None, start_at_unet_number=1, start_image_or_video=None,
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, device=None,
                use_tqdm=True, use_one_unet_in_gpu=True, *, noise_fn: Optional[Callable] = None,
-               seed: Optional[int] = None, use_graph: bool = True, trace: Optional[list] = None):
+               seed: Optional[int] = None, use_graph: bool = True, trace: Optional[list] = None,
+               sampler=None, sampler_eta=0.0, sample_steps=None):
         """Signature of the library's ``Imagen.sample``.  Extensions (keyword-only):
         ``noise_fn(tag, shape)`` injects every Gaussian draw (parity tests, see oracle/sampler_ref.py
         for the tags); ``seed`` keys the on-device Philox stream when no ``noise_fn`` is given
@@ -1073,7 +1168,13 @@ class Imagen(nn.Module):
         ``init_images`` / ``skip_steps`` (the library's, cast per UNet by ``normalize_init_images``): the stage starts from
         ``z + nearest(2 init - 1)`` (EDM: ``sigma_0 z + ...``, sigma_0 the first sigma of the full schedule) and walks the
         schedule steps ``skip .. T - 1`` only; a step keeps its index, hence its table rows, noise streams and
-        ``noise_fn`` tags, and ``trace`` receives one state per step walked."""
+        ``noise_fn`` tags, and ``trace`` receives one state per step walked.
+        ``sampler`` / ``sampler_eta`` / ``sample_steps`` (a scalar or one entry per UNet, ``normalize_sampler``): few-step
+        sampling of the same DDPM-trained weights.  ``sampler`` None or ``"ddpm"`` is the ancestral sampler, ``"ddim"`` is
+        DDIM(``sampler_eta``) and ``"dpmpp_2m"`` DPM-Solver++(2M) with data prediction (``solver_tables``);
+        ``sample_steps=N`` walks the N-step schedule of the UNet's kind instead of the constructor's ``timesteps``, with any
+        sampler, and is what ``skip_steps`` then counts in.  DDIM(eta > 0) draws the ancestral step's noise (``noise_fn`` tag
+        ``("step", stage, k, r)``, Philox purpose 1); DDIM(0) and 2M draw none."""
         for name, v in dict(texts=texts, video_frames=video_frames, cond_video_frames=cond_video_frames,
                             post_cond_video_frames=post_cond_video_frames, inpaint_videos=inpaint_videos).items():
             if exists(v):
@@ -1084,7 +1185,10 @@ class Imagen(nn.Module):
         if exists(inpaint_images) and self.unconditional and n_images == 1:
             n_images = inpaint_images.shape[0]
         seed = normalize_seed(seed, n_images)
-        starts = normalize_init_images(init_images, skip_steps, steps=self._num_steps(), batch_size=n_images,
+        solvers = self._solver_args(sampler, sampler_eta, sample_steps)
+        starts = normalize_init_images(init_images, skip_steps,
+                                       steps=[default(st, T) for (_, _, st), T in zip(solvers, self._num_steps())],
+                                       batch_size=n_images,
                                        channels=self.channels, start_at_unet_number=start_at_unet_number,
                                        stop_at_unet_number=stop_at_unet_number)
         E.require_gpu()
@@ -1124,18 +1228,21 @@ class Imagen(nn.Module):
             img = resize_image_to(f32(start_image_or_video), self.image_sizes[start_at_unet_number - 2])
 
         outputs = []
-        for num, unet, size, sched, obj, dyn, cs, (init_image, skip) in zip(
+        for num, unet, size, sched, obj, dyn, cs, (init_image, skip), (solver, eta, steps) in zip(
                 range(1, n + 1), self.unets, self.image_sizes, self.noise_schedulers, self.pred_objectives,
-                self.dynamic_thresholding, cond_scale, starts):
+                self.dynamic_thresholding, cond_scale, starts, solvers):
             if num < start_at_unet_number:
                 continue
             assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
             assert not (cs != 1.0 and not self.condition_on_text), \
                 "imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)"
+            if exists(steps):
+                sched = sched.with_timesteps(steps)
             img = self._p_sample_loop(
                 unet, num, size, sched, obj, dyn, batch_size, device, img, cond_images, inpaint_images,
                 inpaint_masks, inpaint_resample_times, lowres_sample_noise_level, noise_fn, seed, use_graph, trace,
-                text_embeds=text_embeds, text_masks=text_masks, cond_scale=float(cs), init_image=init_image, skip=skip)
+                text_embeds=text_embeds, text_masks=text_masks, cond_scale=float(cs), init_image=init_image, skip=skip,
+                solver=(solver, eta))
             outputs.append(img)
             if exists(stop_at_unet_number) and stop_at_unet_number == num:
                 break
@@ -1154,7 +1261,8 @@ class Imagen(nn.Module):
 
     def _p_sample_loop(self, unet, stage, size, sched, objective, dynamic_threshold, batch, device, prev_img,
                        cond_images, inpaint_images, inpaint_masks, resample_times, lowres_level, noise_fn, seed,
-                       use_graph, trace, text_embeds=None, text_masks=None, cond_scale=1.0, init_image=None, skip=0):
+                       use_graph, trace, text_embeds=None, text_masks=None, cond_scale=1.0, init_image=None, skip=0,
+                       solver=("ddpm", 0.0)):
         lib = E.load()
         shape = (batch, self.channels, size, size)
         f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
@@ -1263,7 +1371,7 @@ class Imagen(nn.Module):
 
             self._stage_loop(lib, h, args, img, stage=stage, sched=sched, objective=objective, has_inpaint=has_inpaint,
                              R=R, stack=stack if exists(noise_fn) else None, trace=trace, skip=skip,
-                             self_cond=bool(unet.self_cond))
+                             self_cond=bool(unet.self_cond), solver=solver)
             # No host synchronisation here: the engine copies the schedule tables into its own staging buffer inside
             # the call, and the injected-noise tensors in `keep` are device memory of torch's current stream - the
             # caching allocator re-uses it for later allocations of that stream only, i.e. after these launches.
@@ -1275,24 +1383,39 @@ class Imagen(nn.Module):
         """Schedule steps of every UNet's sampler: what skip_steps is checked against."""
         return [s.num_timesteps for s in self.noise_schedulers]
 
+    def _solver_args(self, sampler, sampler_eta, sample_steps):
+        """sample()'s sampler / sampler_eta / sample_steps per UNet: [(name, eta, steps or None)]."""
+        return normalize_sampler(sampler, sampler_eta, sample_steps, len(self.unets))
+
     def _start_scale(self, stage):
         """x_T = scale * N(0,1) (+ the init image): 1 for the DDPM sampler."""
         return 1.0
 
     def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
-                    self_cond=False):
+                    self_cond=False, solver=("ddpm", 0.0)):
         """The sampler proper of one stage, in place on `img` (x_T in, the unnormalised sample out): the DDPM loop of
-        p_sample_loop over the steps skip .. T - 1.  `stack(kind, T)` gives the injected noise of a kind (None: on-device
-        Philox).  A self-conditioned plan starts step `skip` > 0 from zeros, as step 0 does by itself."""
+        p_sample_loop over the steps skip .. T - 1, its update the ancestral one or that of `solver` = (name, eta).
+        `stack(kind, T)` gives the injected noise of a kind (None: on-device Philox).  A self-conditioned plan starts step
+        `skip` > 0 from zeros, as step 0 does by itself."""
         T = sched.num_timesteps
         tables = sched.step_tables()
-        sc = E.kd_schedule_t()
+        name, eta = solver
+        if name == "ddpm":
+            sc = E.kd_schedule_t()
+            steps_fn, loop_fn = lib.kd_sample_steps, lib.kd_sample_loop
+        else:   # the solver's coefficients in place of the ancestral step's; its own entries, tables and step graph
+            coefs = solver_tables(tables, name, eta=eta, skip=skip)
+            tables = {n: tables[n] for n in ("log_snr", "alpha", "sigma", "rn_a", "rn_b")}
+            tables.update(coefs)
+            sc = E.kd_solver_schedule_t()
+            steps_fn, loop_fn = lib.kd_solver_sample_steps, lib.kd_solver_sample_loop
         sc.T = T
-        for name, v in tables.items():
-            setattr(sc, name, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
+        for n, v in tables.items():
+            setattr(sc, n, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
         args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
         if exists(stack):
-            args.d_noise_step = stack("step", T)
+            if name == "ddpm" or (name == "ddim" and eta > 0):   # DDIM(0) and 2M draw nothing in the step
+                args.d_noise_step = stack("step", T)
             if has_inpaint:
                 args.d_noise_inpaint = stack("inpaint", T)
                 if R > 1:
@@ -1301,14 +1424,14 @@ class Imagen(nn.Module):
             E.check(lib.kd_sample_set_self_cond(h, None, E.current_stream()))
         if exists(trace):
             for k in range(skip, T):
-                E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
+                E.check(steps_fn(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
                 trace.append(img.clone())
             E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
         elif skip > 0:
-            E.check(lib.kd_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), skip, T, E.current_stream()))
+            E.check(steps_fn(h, C.byref(sc), C.byref(args), E.ptr(img), skip, T, E.current_stream()))
             E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
         else:
-            E.check(lib.kd_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
+            E.check(loop_fn(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
 
 
 # ============================================================================ ElucidatedImagen (EDM)
@@ -1381,13 +1504,20 @@ class ElucidatedImagen(Imagen):
     def _num_steps(self):
         return [hp["num_sample_steps"] for hp in self.hparams]
 
+    def _solver_args(self, sampler, sampler_eta, sample_steps):
+        """ElucidatedImagen has its own sampler and step count (num_sample_steps): the DDPM solvers do not apply."""
+        if exists(sampler) or exists(sample_steps) or sampler_eta not in (0, 0.0, None):
+            raise ValueError("ElucidatedImagen.sample takes no sampler / sampler_eta / sample_steps: it samples with the EDM "
+                             "Heun sampler on num_sample_steps steps")
+        return [("ddpm", 0.0, None)] * len(self.unets)
+
     def _start_scale(self, stage):
         """x = sigma_0 * N(0,1) (+ the init image): the first sigma of the full schedule, whatever skip_steps is; a python
         float of the fp32 value, so the kernel's product is the library's fp32 tensor product."""
         return float(self.step_tables(stage)["init_sigma"])
 
     def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
-                    self_cond=False):
+                    self_cond=False, solver=None):
         """one_unet_sample of the library's ElucidatedImagen on the engine, on x = sigma_0 * N(0,1) (+ the init image) as
         kd_sample_start wrote it: per step skip .. N - 1 churn, a preconditioned forward and the Euler step, and (not on
         the last step) a second forward and the Heun correction; RePaint re-noise between resamples.  Noise tags

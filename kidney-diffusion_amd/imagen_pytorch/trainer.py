@@ -154,7 +154,8 @@ class ImagenTrainer(nn.Module):
         order (tensors concatenated, PIL lists chained, per-unet lists joined per unet).  `init_images` is cut like
         the batch, as one tensor or as every tensor of a per-unet tuple; `skip_steps` passes through.  Per-image seeds (a sequence
         or a 1-D tensor) are cut alongside, so a chunked call draws the noise of the unchunked one; an int seed gives
-        chunk k the key `seed + 1000003 * k`."""
+        chunk k the key `seed + 1000003 * k`.  `sampler`, `sampler_eta` and `sample_steps` (few-step sampling,
+        `Imagen.sample`) pass through to every chunk."""
         kwargs.setdefault("device", self.device)
         max_batch_size = kwargs.pop("max_batch_size", None)
         with self.use_ema_unets():

@@ -527,7 +527,8 @@ def outpaint_canvas(sample_fn: Callable, num_patches_width: int, overlap: float 
 
 
 def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch.device, use_graph: bool = True,
-                     seed: Optional[int] = None, max_batch=1, per_patch_seeds: bool = False):
+                     seed: Optional[int] = None, max_batch=1, per_patch_seeds: bool = False, sampler=None,
+                     sampler_eta=0.0, sample_steps=None):
     """sample_fn over the drop-in `imagen_pytorch.Imagen` (HIP engine).  `load_imagen(stage)` returns
     the Imagen holding the real unet of that stage (the reference re-loads one stage at a time,
     sample_ultra_res.py:79; a cache keeps all three resident here).  With `max_batch` = 1 each patch
@@ -541,8 +542,17 @@ def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch
 
     With `seed` given, a `sample()` call is keyed by the first task of its batch, so a patch's noise follows the way the
     wave was cut into calls (`max_batch`, the number of ranks).  `per_patch_seeds=True` keys every patch by its own task
-    instead (the same formula, one seed per image): a patch then draws the same noise in any batch on any rank."""
+    instead (the same formula, one seed per image): a patch then draws the same noise in any batch on any rank.
+
+    `sampler`, `sampler_eta`, `sample_steps` (each one value for every stage, or {stage: value}; a stage the dict leaves out
+    keeps the default) go to every `sample()` call of the stage, `warm()`'s included: few-step sampling of the patches
+    (`Imagen.sample`)."""
     cache = {}
+
+    def solver_kw(stage):
+        pick = lambda v, d: v.get(stage, d) if isinstance(v, dict) else v
+        kw = dict(sampler=pick(sampler, None), sampler_eta=pick(sampler_eta, 0.0), sample_steps=pick(sample_steps, None))
+        return {k: v for k, v in kw.items() if v is not None and not (k == "sampler_eta" and v == 0)}   # defaults: the call of before
 
     def task_seed(stage, task):
         return seed + 7919 * stage + 104729 * hash(task) % (2 ** 31)
@@ -567,7 +577,7 @@ def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch
             b = len(tasks[sl])
             kw = dict(batch_size=b, return_pil_images=False, cond_images=stack(conds[sl]),
                       start_image_or_video=stack(lows[sl]), start_at_unet_number=stage, stop_at_unet_number=stage,
-                      use_tqdm=False, device=device, use_graph=use_graph)
+                      use_tqdm=False, device=device, use_graph=use_graph, **solver_kw(stage))
             if seed is not None:
                 kw["seed"] = [task_seed(stage, t) for t in tasks[sl]] if per_patch_seeds else task_seed(stage, tasks[n0])
             elif base_seed is not None:   # drawn by the scheduler on its own thread (overlapped stage groups)
