@@ -52,7 +52,11 @@ const char* kd_last_error(void);
  *      ext3 = NULL - and kd_attention_ex_d, kd_l2norm_heads_d, kd_attention_key_tile added (kd_attention_ex / kd_l2norm_heads
  *      are those with D = 64); kd_unet_poison_scratch added (test infrastructure); kd_sample_args_t gained `seeds` at its end
  *      (NULL = the keying of before) and kd_philox_normal_rows added; kd_sample_start added (the start of a stage, x_T);
- *      kd_solver_sample_loop / kd_solver_sample_steps with their struct kd_solver_schedule_t added (DDIM, DPM-Solver++(2M)) */
+ *      kd_solver_sample_loop / kd_solver_sample_steps with their struct kd_solver_schedule_t added (DDIM, DPM-Solver++(2M));
+ *      kd_unet_create_ext4 with its struct kd_unet_ext4_t for the first and the last layer's structural switches
+ *      (`init_cross_embed`, `init_conv_kernel_size`, `init_cross_embed_kernel_sizes`, `final_conv_kernel_size`,
+ *      `final_resnet_block`, `scale_skip_connection`) - kd_unet_create_ext3 is that call with ext4 = NULL - and
+ *      kd_final_conv_k_nchw, kd_init_conv_plain_nchw added */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -208,6 +212,34 @@ typedef struct kd_unet_ext3 {
  * launches and the same bits). */
 int kd_unet_create_ext3(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                         const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3, kd_unet_t** out);
+/* Further structural options, for kd_unet_create_ext4; the older structs keep their size.  0 is the library's default in
+ * every field.
+ *   init_plain = 1 (`Unet(init_cross_embed=False)`): the first layer is one Conv2d(init_channels, dim, k, padding k / 2),
+ *     parameters `init_conv.{weight,bias}`, k = init_kernel_size (`init_conv_kernel_size`; 0 means 7; odd, 1 .. 15).
+ *   n_init_kernel_sizes = 1 .. 4 (`Unet(init_cross_embed_kernel_sizes=...)`; 0 means the three sizes 3, 7, 15):
+ *     init_kernel_sizes[i], ascending, odd, 1 .. 15, are the sizes of the CrossEmbedLayer's convs `init_conv.convs.i`, of
+ *     widths dim / 2, dim / 4, .., the rest (each a multiple of 4).  Ignored with init_plain.
+ *   final_kernel_size (`final_conv_kernel_size`; 0 means 3): 1, 3, 5 or 7, `final_conv.weight` [C][fin][k][k].
+ *   no_final_resnet_block = 1 (`Unet(final_resnet_block=False)`): there is no `final_res_block`; final_conv reads
+ *     cat(x[, the UpsampleCombiner's maps][, the init conv residual][, lowres_cond_img]).
+ *   no_skip_scale = 1 (`Unet(scale_skip_connection=False)`): skip tensors enter the up path unscaled; no scale pass runs.
+ *   init_generic = 1 (engine extension, for A/B measurements): the init conv's per-step share runs on the generic conv path
+ *     (pack of the planes + one implicit-GEMM conv per kernel size) even where a one-kernel form takes the shape. */
+typedef struct kd_unet_ext4 {
+  int init_plain;
+  int init_kernel_size;
+  int init_kernel_sizes[4];
+  int n_init_kernel_sizes;
+  int final_kernel_size;
+  int no_final_resnet_block;
+  int no_skip_scale;
+  int init_generic;
+} kd_unet_ext4_t;
+/* kd_unet_create_ext3 with the options of `ext4` (NULL or all zero: the plan of kd_unet_create_ext3, the same launches and
+ * the same bits). */
+int kd_unet_create_ext4(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3,
+                        const kd_unet_ext4_t* ext4, kd_unet_t** out);
 void kd_unet_destroy(kd_unet_t* u);
 /* bytes of HBM held (weights + workspace) and algorithmic MACs of one forward (whole batch) */
 int64_t kd_unet_hbm_bytes(const kd_unet_t* u);
@@ -672,6 +704,21 @@ int kd_init_conv_planes_c_nchw(const float* d_x, const float* d_self_cond, const
  * NULL.  Needs Cfeat % 4 == 0. */
 int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
                        int B, int H, int W, int Cfeat, int channels, void* stream);
+/* The same for `Unet(final_conv_kernel_size=ksize)`, ksize = 1, 3, 5 or 7: d_w_oihw [channels][Cfeat + Cl][ksize][ksize],
+ * zero padding ksize / 2.  ksize = 3 runs the launches of kd_final_conv_nchw (the same bits); the other sizes the 1x1 GEMM to
+ * the (output, tap) columns and the k x k gather of kernels_final.hip. */
+int kd_final_conv_k_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                         int B, int H, int W, int Cfeat, int channels, int ksize, void* stream);
+/* The per-step share of a plain init conv (`Unet(init_cross_embed=False)`) in the plan's one-kernel form (kernels_init.hip):
+ * y[b][py][px][0 .. n) (NHWC rows of stride ldy floats, first channel at d_y) = Conv2d(ksize, padding ksize / 2) of the
+ * per-step planes + (d_bias [n] | d_res: dense NHWC [B][S][S][n], may both be NULL).  d_x, d_self_cond: [B][channels][S][S]
+ * (d_self_cond NULL: x alone), d_w OIHW [n][Itot][ksize][ksize] of whose input channels c0 .. are the per-step planes.
+ * d_seg != NULL: the GroupNorm partials of y, [B][n / 16][S * S / 32][2] doubles (sum, sum of squares per 16 channels and
+ * run of 32 pixels; needs n % 16 == 0).  Fails - as the plan's predicate does, the plan then takes the generic conv - unless
+ * ksize is 3, 5 or 7, S % 32 == 0, n % 4 == 0, n <= 128 and the weights fit the kernel's 160 KB of LDS. */
+int kd_init_conv_plain_nchw(const float* d_x, const float* d_self_cond, const float* d_w, int Itot, int c0, const float* d_bias,
+                            const float* d_res, float* d_y, int ldy, double* d_seg, int B, int S, int n, int ksize, int channels,
+                            int iters, float* ms, void* stream);
 /* GroupNorm(G) + optional FiLM (scale+1, shift: [B,2C] = [scale | shift]) + SiLU, NHWC. */
 int kd_groupnorm_silu_nhwc(const float* d_x, const float* d_gamma, const float* d_beta,
                            const float* d_scale_shift, float* d_y, int B, int HW, int C, int G,

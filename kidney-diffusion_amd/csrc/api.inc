@@ -34,6 +34,12 @@ int kd_unet_create_ext2(const kd_unet_config_t* cfg, const kd_param_t* params, i
 
 int kd_unet_create_ext3(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
                         const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3, kd_unet_t** out) {
+  return kd_unet_create_ext4(cfg, params, n_params, share_with, ext, ext2, ext3, nullptr, out);
+}
+
+int kd_unet_create_ext4(const kd_unet_config_t* cfg, const kd_param_t* params, int n_params, const kd_unet_t* share_with,
+                        const kd_unet_ext_t* ext, const kd_unet_ext2_t* ext2, const kd_unet_ext3_t* ext3,
+                        const kd_unet_ext4_t* ext4, kd_unet_t** out) {
   const int self_cond = ext ? ext->self_cond : 0;
   if (!cfg || !params || !out) {
     set_error("kd_unet_create: null argument");
@@ -70,6 +76,39 @@ int kd_unet_create_ext3(const kd_unet_config_t* cfg, const kd_param_t* params, i
       }
       u->attn_depth[l] = ext3->layer_attns_depth[l] ? ext3->layer_attns_depth[l] : 1;
     }
+  if (ext4) {
+    const char* bad = nullptr;
+    auto odd15 = [](int k) { return k >= 1 && k <= 15 && (k & 1); };
+    if (ext4->init_plain) {
+      u->init_plain = 1;
+      u->n_init_ks = 1;
+      u->init_ks[0] = ext4->init_kernel_size ? ext4->init_kernel_size : 7;
+      if (!odd15(u->init_ks[0])) bad = "kd_unet_create: init_kernel_size must be odd, 1 .. 15 (0 means 7)";
+    } else if (ext4->n_init_kernel_sizes) {
+      const int n = ext4->n_init_kernel_sizes;
+      if (n < 1 || n > 4) {
+        bad = "kd_unet_create: n_init_kernel_sizes must be 1 .. 4 (0 means the sizes 3, 7, 15)";
+      } else {
+        u->n_init_ks = n;
+        for (int i = 0; i < n; ++i) {
+          u->init_ks[i] = ext4->init_kernel_sizes[i];
+          if (!odd15(u->init_ks[i]) || (i && u->init_ks[i] < u->init_ks[i - 1]))
+            bad = "kd_unet_create: init_kernel_sizes must be odd, 1 .. 15, in ascending order";
+        }
+      }
+    }
+    u->final_ks = ext4->final_kernel_size ? ext4->final_kernel_size : 3;
+    if (u->final_ks != 1 && u->final_ks != 3 && u->final_ks != 5 && u->final_ks != 7)
+      bad = "kd_unet_create: final_kernel_size must be 1, 3, 5 or 7 (0 means 3)";
+    u->no_final_res = ext4->no_final_resnet_block != 0;
+    if (ext4->no_skip_scale) u->skip_scale = 1.0f;
+    u->init_generic = ext4->init_generic != 0;
+    if (bad) {
+      set_error(bad);
+      delete u;
+      return 1;
+    }
+  }
   // plans of one UNet (other batch / image size) share its packed weights
   u->wstore = share_with ? share_with->wstore : std::make_shared<WeightStore>();
   u->cus = gemm_bf16x3_device_cus();   // read once: every plan-time question and every launch shape of this plan uses it
@@ -908,6 +947,47 @@ int kd_init_conv_planes_c_nchw(const float* d_x, const float* d_self_cond, const
   return 0;
 }
 
+// The per-step share of a plain init conv through the plan's one-kernel form (kernels_init.hip, init_plain_kernel)
+int kd_init_conv_plain_nchw(const float* d_x, const float* d_self_cond, const float* d_w, int Itot, int c0, const float* d_bias,
+                            const float* d_res, float* d_y, int ldy, double* d_seg, int B, int S, int n, int ksize, int channels,
+                            int iters, float* ms, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_init_conv_plain_nchw: 1 to 4 image channels");
+  const int np = d_self_cond ? 2 * channels : channels;
+  KD_REQUIRE(d_x && d_w && d_y && iters >= 1, "kd_init_conv_plain_nchw: null argument or iters < 1");
+  KD_REQUIRE(B >= 1 && S >= 1, "kd_init_conv_plain_nchw: empty shape");
+  KD_REQUIRE(c0 >= 0 && c0 + np <= Itot, "kd_init_conv_plain_nchw: input channels c0 .. c0 + planes - 1 out of range");
+  KD_REQUIRE(init_plain_ok(S, n, ksize, np),
+             "plain init conv kernel: kernel size 3, 5 or 7, S % 32 == 0, n % 4 == 0, n <= 128 and the weights must fit LDS");
+  KD_REQUIRE(ldy >= n, "kd_init_conv_plain_nchw: ldy below the output's channels");
+  EntryBufs bufs;
+  float* wp = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (bufs.get(&wp, init_plain_weight_floats(n, ksize, np) * sizeof(float))) return 1;
+  int rc = launch_init_plain_pack(d_w, wp, n, Itot, c0, np, ksize, s);
+  if (!rc && ms) {
+    rc = hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, s) != hipSuccess;
+    if (rc) set_error("kd_init_conv_plain_nchw: event setup failed");
+  }
+  for (int i = 0; i < iters && !rc; ++i)
+    rc = launch_init_plain(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, ldy, d_seg, B, S, n, ksize, s);
+  if (!rc && ms && hipEventRecord(e1, s) != hipSuccess) {
+    set_error("kd_init_conv_plain_nchw: event record failed");
+    rc = 1;
+  }
+  hipError_t e = hipStreamSynchronize(s);
+  if (!rc && ms && e == hipSuccess) {
+    float t = 0.f;
+    e = hipEventElapsedTime(&t, e0, e1);
+    *ms = t / iters;
+  }
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  KD_HIP_CHECK(e);
+  return 0;
+}
+
 // The final 3x3 conv to the image's channels as the plan runs it (unet_build.inc tail, kernels_final.hip): weight pack,
 // the 1x1 GEMM to the (output, tap) columns, the low-res planes' step-invariant share when d_lowres is given, the gather
 int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
@@ -934,6 +1014,36 @@ int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* 
     rc = launch_conv_igemm(p, s);
   }
   if (!rc) rc = launch_final_gather(pm, stat, d_bias, d_out, channels, B, H, W, s);
+  return entry_finish(rc, s);
+}
+
+// The same for final_conv_kernel_size = ksize (1 | 3 | 5 | 7): the k x k launches of the plan (ksize = 3: kd_final_conv_nchw)
+int kd_final_conv_k_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                         int B, int H, int W, int Cfeat, int channels, int ksize, void* stream) {
+  if (ksize == 3) return kd_final_conv_nchw(d_feat, d_w_oihw, d_bias, d_lowres, d_out, B, H, W, Cfeat, channels, stream);
+  hipStream_t s = (hipStream_t)stream;
+  KD_REQUIRE(d_feat && d_w_oihw && d_bias && d_out, "kd_final_conv_k_nchw: null argument");
+  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_final_conv_k_nchw: 1 to 4 image channels");
+  KD_REQUIRE(ksize == 1 || ksize == 5 || ksize == 7, "kd_final_conv_k_nchw: kernel size 1, 3, 5 or 7");
+  KD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cfeat >= 4 && Cfeat % 4 == 0 && (int64_t)B * H * W < 0x7fffffff / 208,
+             "kd_final_conv_k_nchw needs a non-empty map below 2^31 / 208 pixels and Cfeat % 4 == 0");
+  const int Ctot = Cfeat + (d_lowres ? channels : 0), nf = final_gemm_cols_k(channels, ksize);
+  EntryBufs bufs;
+  float *wp = nullptr, *pm = nullptr, *stat = nullptr;
+  if (bufs.get(&wp, (size_t)nf * Cfeat * sizeof(float)) || bufs.get(&pm, (size_t)B * H * W * nf * sizeof(float))) return 1;
+  if (d_lowres && bufs.get(&stat, (size_t)B * channels * H * W * sizeof(float))) return 1;
+  int rc = launch_pack_final_k(d_w_oihw, wp, Ctot, Cfeat, channels, ksize, s);
+  if (!rc && d_lowres) rc = launch_final_static(d_lowres, d_w_oihw, d_bias, stat, Ctot, Cfeat, channels, B, H, W, s, ksize);
+  if (!rc) {
+    ConvParams p{};
+    p.x = d_feat; p.w = wp; p.y = pm;
+    p.B = B; p.Hi = H; p.Wi = W; p.Cin = Cfeat; p.ldx = Cfeat;
+    p.Ho = H; p.Wo = W; p.Cout = nf;
+    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
+    p.out_mode = OUT_NHWC; p.ldy = nf;
+    rc = launch_conv_igemm(p, s);
+  }
+  if (!rc) rc = launch_final_gather_k(pm, stat, d_bias, d_out, channels, ksize, B, H, W, s);
   return entry_finish(rc, s);
 }
 

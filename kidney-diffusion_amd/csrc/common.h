@@ -311,6 +311,13 @@ int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, fl
 // each; sc (np = 2 cx only, nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
 int launch_init_conv(const float* x_nchw, const float* sc_nchw, int cx, int np, const float* wp, const float* bias, const float* res,
                      float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
+// ---- Unet(init_cross_embed=False): the per-step share of one k x k conv (k = 3 | 5 | 7) of the np planes to n <= 128 channels in
+// one kernel of the same form; false where k is another size or the kernel's LDS does not hold the weights
+bool init_plain_ok(int S, int n, int k, int np);
+size_t init_plain_weight_floats(int n, int k, int np);
+int launch_init_plain_pack(const float* w_oihw, float* out, int n, int Itot, int c0, int np, int k, hipStream_t s);
+int launch_init_plain(const float* x_nchw, const float* sc_nchw, int cx, int np, const float* wp, const float* bias, const float* res,
+                      float* y, int ldy, double* seg, int B, int S, int n, int k, hipStream_t s);
 
 // ---- linear attention, dim_head = 64 (kernels_linattn.hip).  q | k | v are column slices of one [B][H][W][3 inner] map
 constexpr int LA_CHUNK = 64;   // tokens per chunk of the k-softmax partials
@@ -355,10 +362,16 @@ int launch_upsample_scale_conv3x3(const float* x, int ldx, const float* ab, cons
 // ---- final conv to the image's `ch` = 1 .. 4 channels (kernels_final.hip)
 int final_gemm_cols(int ch);   // width of P: the 9 ch (output, tap) columns padded for the 1x1 GEMM (32; 48 at ch = 4)
 int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, hipStream_t s);
+// (ks: the conv's kernel size, 1 | 3 | 5 | 7)
 int launch_final_static(const float* lowres, const float* w_oihw, const float* bias, float* stat, int Ctot, int c0,
-                        int ch, int B, int H, int W, hipStream_t s);
+                        int ch, int B, int H, int W, hipStream_t s, int ks = 3);
 int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int ch, int B, int H, int W,
                         hipStream_t s);
+// the same for final_conv_kernel_size = k (1 | 5 | 7; k = 3 forwards to the functions above): ch (k^2 rounded up to 4) columns n = o kp + tap
+int final_gemm_cols_k(int ch, int k);
+int launch_pack_final_k(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, int k, hipStream_t s);
+int launch_final_gather_k(const float* P, const float* stat, const float* bias, float* out, int ch, int k, int B, int H, int W,
+                          hipStream_t s);
 
 // ---- text conditioning helpers (kernels_text.hip)
 int launch_text_select(const float* tok, const float* mask, const float* null_embed, float* out, int B, int L, int P,

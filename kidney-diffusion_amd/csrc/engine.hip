@@ -284,6 +284,13 @@ struct kd_unet {
   int combine_upsample_fmaps = 0;
   // Unet(layer_attns_depth=...) (kd_unet_ext3_t): (attention, feed-forward) pairs of level l's TransformerBlocks, >= 1
   int attn_depth[KD_MAX_LEVELS] = {1, 1, 1, 1, 1, 1, 1, 1};
+  // the first and the last layer's structural switches (kd_unet_ext4_t), normalised: init_plain: one Conv2d of init_ks[0];
+  // else a CrossEmbedLayer of the n_init_ks ascending sizes init_ks; final_ks: final_conv's kernel size; no_final_res:
+  // final_conv reads the concat itself; skip_scale: 2^-1/2, or 1 with scale_skip_connection=False (then no scale pass runs)
+  int init_plain = 0, n_init_ks = 3, init_ks[4] = {3, 7, 15, 0};
+  int final_ks = 3, no_final_res = 0;
+  int init_generic = 0;   // A/B: the init conv's per-step share on the generic conv path even where a one-kernel form applies
+  float skip_scale = 0.70710678118654752440f;
   // per-call I/O (read by the ops at run time)
   const float *in_x = nullptr, *in_lowres = nullptr, *in_cond = nullptr, *in_log_snr = nullptr,
               *in_lowres_log_snr = nullptr, *in_text_tokens = nullptr, *in_text_hiddens = nullptr;
@@ -1509,6 +1516,9 @@ struct Builder {
   // skip_c0 >= 0: x is a concat whose channels [skip_c0, ..) hold an UNSCALED skip tensor that the layer must see
   // scaled by skip_scale: the GroupNorm gets it through the partials' scale (SegPart), the 1x1 skip conv through
   // weights whose columns were scaled at plan build.
+  // false while unet_build.inc emits the last producer in front of a final conv that reads it directly (final_resnet_block=False):
+  // no GroupNorm normalises that output, so its ResnetBlock / upsample does not leave partials
+  bool out_seg = true;
   T resnet(const T& x, const std::string& pre, int dim_out, const T* ctx, bool use_gca, const T* ct = nullptr,
            const T* out_slot = nullptr, int skip_c0 = -1, float skip_scale = 1.0f) {
     bool has_cross = has(pre + ".cross_attn.to_q.weight");
@@ -1545,7 +1555,7 @@ struct Builder {
         ConvOpt o;
         o.gate_src = &h2;
         o.gate = &gate;
-        o.want_seg = true;
+        o.want_seg = out_seg;
         if (ct) o.dst = ct;
         out = conv(x, w_res, P(pre + ".res_conv.bias", dim_out), dim_out, 1, 1, 0, o);
       } else {
@@ -1553,7 +1563,7 @@ struct Builder {
         if (out.C != dim_out) throw std::runtime_error("plan: output slot of the wrong width: " + pre);
         const Ref ar = at(h2), gr = at(gate), rr = at(x), yr = at(out);
         int Bx = x.B, HW = x.HW(), ldr = x.LD(), ldy = out.LD();
-        const bool sg = dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
+        const bool sg = out_seg && dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
         const Ref seg = sg ? seg_at(add_seg(out, 0, dim_out / 16, gate_add_chunks(Bx, HW))) : Ref();
         emit([=](hipStream_t s) {
           return launch_gate_add(ar.f(), gr.f(), rr.f(), ldr, yr.f(), ldy, seg.d(), Bx, HW, dim_out, s);
@@ -1563,7 +1573,7 @@ struct Builder {
     } else {  // res_conv without gca: out = conv1x1(x) + h2
       ConvOpt o;
       o.res = &h2;
-      o.want_seg = true;
+      o.want_seg = out_seg;
       if (ct) o.dst = ct;
       out = conv(x, w_res, P(pre + ".res_conv.bias", dim_out), dim_out, 1, 1, 0, o);
     }
@@ -1720,7 +1730,7 @@ struct Builder {
     ConvOpt o;
     o.act = ACT_SILU;
     o.out_mode = OUT_PIXSHUF;
-    o.want_seg = true;
+    o.want_seg = out_seg;
     if (ct) o.dst = ct;   // straight into the first dim_out channels of the following skip concat
     return conv(x, w, b, 4 * dim_out, 1, 1, 0, o);
   }

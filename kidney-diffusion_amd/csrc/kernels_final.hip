@@ -7,6 +7,14 @@
 // gather-sum below, which also adds the step-invariant contribution of the low-res conditioning planes (`stat`,
 // computed once per sampling call by final_static_kernel) and writes the NCHW prediction the sampler consumes.
 // C <= 3 keeps the 32-column P and the launches of the 3-channel plans; C = 4 is the one width past 32 columns.
+//
+// Unet(final_conv_kernel_size=k), k = 1 | 5 | 7 (the `_k` functions below; k = 3 stays on the launches above, bit for bit):
+// the same two steps with the (output, tap) columns n = o kp + tap, kp = k^2 rounded up to a multiple of 4 (28 | 52: every
+// channel's columns start on a 16-byte boundary; the pad columns have zero weights), the row padded to a multiple of 16 and
+// at least 32 columns (final_gemm_cols_k).  At k = 7 a pixel has up to 208 columns and a gather tile holding all of them
+// would not fit LDS, so the k x k gather is tiled by OUTPUT CHANNEL: a workgroup stages the kp columns of one channel o over
+// its halo patch (16-byte loads; kp + 1 = 29 | 53 floats per pixel in LDS, odd: conflict-free reads) and every lane of the
+// first TW x ROWS threads sums its pixel's k^2 taps.  k = 1 has no taps to gather: out = (stat | bias) + P[pixel][o], no LDS.
 #include "common.h"
 
 namespace kd {
@@ -34,10 +42,11 @@ int launch_pack_final(const float* w, float* out, int Ctot, int C, int ch, hipSt
   return 0;
 }
 
-// stat[b][o][y][x] = bias[o] + sum_{c<ch,taps} lowres[b][c][y+kh-1][x+kw-1] * w[o][c0+c][kh][kw]   (NCHW in/out)
+// stat[b][o][y][x] = bias[o] + sum_{c<ch,taps} lowres[b][c][y+kh-ks/2][x+kw-ks/2] * w[o][c0+c][kh][kw]   (NCHW in/out; ks x ks taps)
 __global__ void final_static_kernel(const float* __restrict__ lowres, const float* __restrict__ w,
                                     const float* __restrict__ bias, float* __restrict__ stat, int Ctot, int c0, int ch,
-                                    int H, int W, int64_t total) {
+                                    int H, int W, int64_t total, int ks) {
+  const int pad = ks >> 1, kk = ks * ks;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     int x = (int)(idx % W);
@@ -48,25 +57,26 @@ __global__ void final_static_kernel(const float* __restrict__ lowres, const floa
     int64_t b = t / ch;
     float acc = bias[o];
     for (int c = 0; c < ch; ++c)
-      for (int kh = 0; kh < 3; ++kh) {
-        int iy = y + kh - 1;
+      for (int kh = 0; kh < ks; ++kh) {
+        int iy = y + kh - pad;
         if (iy < 0 || iy >= H) continue;
-        for (int kw = 0; kw < 3; ++kw) {
-          int ix = x + kw - 1;
+        for (int kw = 0; kw < ks; ++kw) {
+          int ix = x + kw - pad;
           if (ix < 0 || ix >= W) continue;
-          acc += lowres[((b * ch + c) * H + iy) * W + ix] * w[((int64_t)o * Ctot + c0 + c) * 9 + kh * 3 + kw];
+          acc += lowres[((b * ch + c) * H + iy) * W + ix] * w[((int64_t)o * Ctot + c0 + c) * kk + kh * ks + kw];
         }
       }
     stat[idx] = acc;
   }
 }
 int launch_final_static(const float* lowres, const float* w, const float* bias, float* stat, int Ctot, int c0, int ch,
-                        int B, int H, int W, hipStream_t s) {
+                        int B, int H, int W, hipStream_t s, int ks) {
   KD_REQUIRE(ch >= 1 && ch <= 4 && c0 >= 0 && c0 + ch <= Ctot, "final conv: 1 .. 4 low-res planes inside the weights");
+  KD_REQUIRE(ks == 1 || ks == 3 || ks == 5 || ks == 7, "final conv: kernel size 1, 3, 5 or 7");
   int64_t total = (int64_t)B * ch * H * W;
   int64_t blocks = (total + 255) / 256;
   hipLaunchKernelGGL(final_static_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s, lowres, w,
-                     bias, stat, Ctot, c0, ch, H, W, total);
+                     bias, stat, Ctot, c0, ch, H, W, total, ks);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -123,6 +133,127 @@ int launch_final_gather(const float* P, const float* stat, const float* bias, fl
     case 3: hipLaunchKernelGGL(final_gather_kernel<3>, grid, block, 0, s, P, stat, bias, out, H, W); break;
     default: hipLaunchKernelGGL(final_gather_kernel<4>, grid, block, 0, s, P, stat, bias, out, H, W); break;
   }
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---- k x k final conv, k = 1 | 5 | 7 (k = 3: the functions above)
+static bool final_k_ok(int k) { return k == 1 || k == 5 || k == 7; }
+static int final_kp(int k) { return k == 1 ? 1 : (k * k + 3) & ~3; }   // columns per output channel
+int final_gemm_cols_k(int ch, int k) {
+  if (k == 3) return final_gemm_cols(ch);
+  const int n = (final_kp(k) * ch + 15) / 16 * 16;
+  return n < 32 ? 32 : n;
+}
+
+// w_oihw [ch][Ctot][k][k] -> packed [nf][C] rows n = o kp + tap for channels [0, C); rows with tap >= k^2 or o >= ch zero
+__global__ void pack_final_k_kernel(const float* __restrict__ w, float* __restrict__ out, int Ctot, int C, int ch, int nf, int kk,
+                                    int kp) {
+  int total = nf * C;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+    int c = idx % C, n = idx / C;
+    int o = n / kp, tap = n - o * kp;
+    float v = 0.f;
+    if (o < ch && tap < kk) v = w[((int64_t)o * Ctot + c) * kk + tap];
+    out[idx] = v;
+  }
+}
+int launch_pack_final_k(const float* w, float* out, int Ctot, int C, int ch, int k, hipStream_t s) {
+  if (k == 3) return launch_pack_final(w, out, Ctot, C, ch, s);
+  KD_REQUIRE(ch >= 1 && ch <= 4 && C >= 1 && C <= Ctot && final_k_ok(k), "final conv: 1 .. 4 image channels, kernel size 1, 3, 5 or 7");
+  const int nf = final_gemm_cols_k(ch, k);
+  hipLaunchKernelGGL(pack_final_k_kernel, dim3((nf * C + 255) / 256), dim3(256), 0, s, w, out, Ctot, C, ch, nf, k * k,
+                     final_kp(k));
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// k = 1: out[b][o][y][x] = (stat ? stat : bias[o]) + P[b][y][x][o]
+__global__ void final_cols_kernel(const float* __restrict__ P, const float* __restrict__ stat, const float* __restrict__ bias,
+                                  float* __restrict__ out, int ch, int nf, int64_t hw, int64_t total) {
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t pix = idx % hw, t = idx / hw;
+    const int o = (int)(t % ch);
+    const int64_t b = t / ch;
+    out[idx] = (stat ? stat[idx] : bias[o]) + P[(b * hw + pix) * nf + o];
+  }
+}
+
+// out[b][o][y][x] = (stat ? stat[b][o][y][x] : bias[o]) + sum_tap P[b][y+kh-K/2][x+kw-K/2][o KP + tap], one output channel
+// and one TW x ROWS pixel tile per workgroup of NT >= TW ROWS threads (all stage, the first TW ROWS sum); tile
+// [(ROWS + K - 1)][(TW + K - 1)][KP + 1] floats of dynamic LDS
+template <int K, int TW, int ROWS, int NT>
+__global__ __launch_bounds__(NT) void final_gather_k_kernel(const float* __restrict__ P, const float* __restrict__ stat,
+                                                            const float* __restrict__ bias, float* __restrict__ out, int CH, int NF,
+                                                            int H, int W) {
+  constexpr int KP = (K * K + 3) & ~3, Q = KP / 4, LD = KP + 1, PW = TW + K - 1, PH = ROWS + K - 1, PAD = K / 2;
+  static_assert((LD & 1) && NT >= TW * ROWS, "an odd pixel stride reads LDS free of bank conflicts");
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  extern __shared__ __attribute__((aligned(16))) float fk_tile[];
+  const int segs = (W + TW - 1) / TW, rgs = (H + ROWS - 1) / ROWS;
+  int t = blockIdx.x;
+  const int seg = t % segs;
+  t /= segs;
+  const int rg = t % rgs;
+  t /= rgs;
+  const int o = t % CH, b = t / CH;
+  const int x0 = seg * TW, y0 = rg * ROWS;
+  const float* Po = P + (int64_t)b * H * W * NF + o * KP;   // 16-byte aligned: NF % 4 == 0, KP % 4 == 0
+#pragma unroll 4
+  for (int idx = threadIdx.x; idx < PH * PW * Q; idx += NT) {
+    const int q = idx % Q, pp = idx / Q;
+    const int px = pp % PW, r = pp / PW;
+    const int iy = y0 + r - PAD, ix = x0 + px - PAD;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = *(const f32x4*)(Po + ((int64_t)iy * W + ix) * NF + q * 4);
+    float* d = fk_tile + pp * LD + q * 4;
+    d[0] = v[0];
+    d[1] = v[1];
+    d[2] = v[2];
+    d[3] = v[3];
+  }
+  __syncthreads();
+  if (threadIdx.x >= TW * ROWS) return;
+  const int lx = threadIdx.x % TW, ly = threadIdx.x / TW;
+  const int x = x0 + lx, y = y0 + ly;
+  if (x >= W || y >= H) return;
+  const int64_t oi = (((int64_t)b * CH + o) * H + y) * W + x;
+  float acc = stat ? stat[oi] : bias[o];
+#pragma unroll
+  for (int kh = 0; kh < K; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < K; ++kw) acc += fk_tile[((ly + kh) * PW + lx + kw) * LD + kh * K + kw];
+  out[oi] = acc;
+}
+template <int K, int TW, int ROWS, int NT>
+static int launch_final_gather_kt(const float* P, const float* stat, const float* bias, float* out, int ch, int nf, int B, int H,
+                                  int W, hipStream_t s) {
+  constexpr size_t smem = (size_t)(ROWS + K - 1) * (TW + K - 1) * (((K * K + 3) & ~3) + 1) * sizeof(float);
+  static_assert(smem <= 160 * 1024, "final gather: the tile must fit LDS");
+  const int64_t blocks = (int64_t)B * ch * ((H + ROWS - 1) / ROWS) * ((W + TW - 1) / TW);
+  KD_REQUIRE(blocks < 0x7fffffff && nf % 4 == 0 && ((uintptr_t)P & 15) == 0, "final conv: too many tiles for one launch, or P not 16-byte aligned");
+  KD_HIP_CHECK(hipFuncSetAttribute((const void*)final_gather_k_kernel<K, TW, ROWS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)smem));
+  hipLaunchKernelGGL((final_gather_k_kernel<K, TW, ROWS, NT>), dim3((unsigned)blocks), dim3(NT), smem, s, P, stat, bias, out, ch, nf,
+                     H, W);
+  return 0;
+}
+int launch_final_gather_k(const float* P, const float* stat, const float* bias, float* out, int ch, int k, int B, int H, int W,
+                          hipStream_t s) {
+  if (k == 3) return launch_final_gather(P, stat, bias, out, ch, B, H, W, s);
+  KD_REQUIRE(ch >= 1 && ch <= 4 && final_k_ok(k) && B >= 1 && H >= 1 && W >= 1, "final conv: 1 .. 4 image channels, kernel size 1, 3, 5 or 7");
+  const int nf = final_gemm_cols_k(ch, k);
+  int rc = 0;
+  if (k == 1) {
+    const int64_t total = (int64_t)B * ch * H * W, blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(final_cols_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, s, P, stat, bias, out, ch,
+                       nf, (int64_t)H * W, total);
+  } else if (k == 5) {
+    rc = launch_final_gather_kt<5, 64, 4, 256>(P, stat, bias, out, ch, nf, B, H, W, s);
+  } else {
+    rc = launch_final_gather_kt<7, 32, 8, 512>(P, stat, bias, out, ch, nf, B, H, W, s);
+  }
+  if (rc) return rc;
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -438,4 +438,197 @@ int launch_init_conv(const float* x, const float* sc, int cx, int np, const floa
   return 0;
 }
 
+// ---- Unet(init_cross_embed=False): the per-step share of ONE k x k conv (k = 3 | 5 | 7) of the NP per-step planes to all
+// n <= 128 output channels, in the shape of init_conv_kernel: persistent workgroups with the packed weights [rows][ic_ldk(k, NP)]
+// resident in LDS, 32 x 8 output pixels at a time from a (32 + k - 1) x (8 + k - 1) x NP halo patch read straight from the NCHW
+// planes (fetched one tile ahead), K over whole kernel rows on v_mfma_f32_32x32x2_f32, wave w = row w of the tile and one
+// 32-channel tile after the other, the same epilogue (bias | step-invariant residual, NHWC into a channel slice, 16-channel
+// GroupNorm partials).  LDS: rows x ic_ldk floats + patch + 32 KiB of epilogue scratch within 160 KiB - dim 128 at k = 7:
+// 128 x 155 floats (77.5 KiB) at NP = 3 fits, 128 x 295 (147.5 KiB) at NP = 6 does not (init_plain_ok; the plan then takes
+// the generic conv).
+__host__ __device__ constexpr int ip_patch(int k, int np) { return (IC_TH + k - 1) * (IC_TW + k - 1) * np + 8; }
+static size_t init_plain_lds_floats(int n, int k, int np) {
+  return (size_t)ic_rows(n) * ic_ldk(k, np) + ip_patch(k, np) + IC_SCRATCH;
+}
+size_t init_plain_weight_floats(int n, int k, int np) { return (size_t)ic_rows(n) * ic_ldk(k, np); }
+bool init_plain_ok(int S, int n, int k, int np) {
+  if (!ic_np_ok(np) || (k != 3 && k != 5 && k != 7) || n < 4 || n > 128 || n % 4) return false;
+  return S >= IC_TW && S % IC_TW == 0 && S % IC_TH == 0 && init_plain_lds_floats(n, k, np) * sizeof(float) <= (size_t)IC_LDS_BYTES;
+}
+int launch_init_plain_pack(const float* w, float* out, int n, int Itot, int c0, int np, int k, hipStream_t s) {
+  KD_REQUIRE(ic_np_ok(np) && (k == 3 || k == 5 || k == 7) && c0 >= 0 && c0 + np <= Itot,
+             "plain init conv pack: 1, 2, 3, 4, 6 or 8 planes inside the weights, kernel size 3, 5 or 7");
+  hipLaunchKernelGGL(init_conv_pack_kernel, dim3(64), dim3(256), 0, s, w, out, n, Itot, c0, np, k, ic_run(k, np), ic_ldk(k, np),
+                     ic_rows(n), 0);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+struct InitPlainParams {
+  const float* x;      // NCHW [B][cx][S][S]
+  const float* sc;     // NP = 2 cx: the self-conditioning planes NCHW [B][cx][S][S] (nullptr: zeros)
+  const float* wp;     // init_plain_weight_floats packed weights
+  const float* bias;   // [n] or nullptr
+  const float* res;    // dense NHWC [B][S][S][n] step-invariant share, or nullptr
+  float* y;            // NHWC, row stride ldy, first channel at y
+  double* seg;         // GroupNorm partials [B][n/16][S*S/32][2] or nullptr
+  int B, S, ldy, n, cx;
+};
+
+template <int KS, int NP>
+__global__ __launch_bounds__(512, 1) void init_plain_kernel(InitPlainParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int RUN = ic_run(KS, NP), LDK = ic_ldk(KS, NP), PATCH = ip_patch(KS, NP);
+  constexpr int PW = IC_TW + KS - 1, PH = IC_TH + KS - 1, PAD = KS / 2;
+  const int rows = ic_rows(p.n);
+  float* Wl = lds;
+  float* patch = Wl + rows * LDK;
+  float* scratch = patch + PATCH + (threadIdx.x >> 6) * 1024;   // 4 KB per wave (epilogue.h)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < rows * LDK; i += 512) lds[i] = p.wp[i];
+  for (int i = tid; i < 8; i += 512) patch[PATCH - 8 + i] = 0.f;
+
+  const int S = p.S, tx_n = S / IC_TW, ty_n = S / IC_TH;
+  const int ntiles = p.B * tx_n * ty_n;
+  const int C = p.n;
+  const int frow = lane & 31, khalf = lane >> 5;
+  const int64_t plane = (int64_t)S * S;
+  const int cx = (NP & 1) ? NP : NP == 6 ? 3 : NP == 8 ? 4 : p.cx;
+
+  constexpr int NPV = (PH * PW * NP + 511) / 512;
+  float pv[NPV];
+  auto fetch = [&](int tile) {
+    const int b = tile / (tx_n * ty_n);
+    const int rem = tile - b * tx_n * ty_n;
+    const int y0 = (rem / tx_n) * IC_TH, x0 = (rem % tx_n) * IC_TW;
+#pragma unroll
+    for (int q = 0; q < NPV; ++q) {
+      const int i = tid + q * 512;
+      const int c = i / (PH * PW), r = i - c * (PH * PW);
+      const int py = r / PW, px = r - py * PW;
+      const int iy = y0 - PAD + py, ix = x0 - PAD + px;
+      float v = 0.f;
+      if (i < PH * PW * NP && iy >= 0 && iy < S && ix >= 0 && ix < S) {
+        if ((NP & 1) || c < cx)
+          v = p.x[((int64_t)b * cx + c) * plane + (int64_t)iy * S + ix];
+        else if (p.sc)
+          v = p.sc[((int64_t)b * cx + c - cx) * plane + (int64_t)iy * S + ix];
+      }
+      pv[q] = v;
+    }
+  };
+  if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int b = tile / (tx_n * ty_n);
+    const int rem = tile - b * tx_n * ty_n;
+    const int y0 = (rem / tx_n) * IC_TH, x0 = (rem % tx_n) * IC_TW;
+    __syncthreads();   // the previous tile's MFMA reads of the patch are done (and the weights have landed)
+#pragma unroll
+    for (int q = 0; q < NPV; ++q) {
+      const int i = tid + q * 512;
+      if (i < PH * PW * NP) {
+        const int c = i / (PH * PW), r = i - c * (PH * PW);
+        patch[r * NP + c] = pv[q];
+      }
+    }
+    __syncthreads();
+    if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
+
+    const int row = wave;
+    const int64_t pix0 = ((int64_t)b * S + y0 + row) * S + x0;
+    const int64_t chunk = ((int64_t)(y0 + row) * S + x0) >> 5;   // 32-pixel run index inside the image
+    const float* pa = patch + (row * PW + frow) * NP + khalf;
+    for (int j = 0; j * 32 < p.n; ++j) {   // one 32-channel tile after the other: one set of accumulators live
+      const int ch0 = j * 32, nreal = p.n - ch0;
+      WideEpilogue e;
+      e.y = p.y + pix0 * p.ldy + ch0;
+      e.ldy = p.ldy;
+      e.bias = p.bias ? p.bias + ch0 : nullptr;
+      e.res = p.res ? p.res + pix0 * C + ch0 : nullptr;
+      e.ldres = C;
+      e.gate_src = nullptr;
+      e.ldgs = 0;
+      e.gate = nullptr;
+      e.rows = 32;
+      e.cols = nreal < 32 ? nreal : 32;
+      e.act = ACT_NONE;
+      ep_f32x4 rp[4];
+      wide_prefetch_res(e, rp);   // the step-invariant share arrives under the MFMAs
+      const float* pb = Wl + (ch0 + frow) * LDK + khalf;
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+      for (int ky = 0; ky < KS; ++ky)
+#pragma unroll
+        for (int kk = 0; kk < RUN / 2; ++kk)
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[ky * PW * NP + 2 * kk], pb[ky * RUN + 2 * kk], acc, 0, 0, 0);
+      double s1, s2;
+      if (p.seg) {   // wave-uniform
+        store_tile32_wide_pre<true>(acc, scratch, e, rp, s1, s2);
+        reduce_tile32_stats(s1, s2);
+        const int n = ch0 + 4 * (lane & 7);   // lane 0: columns 0-15, lane 4: columns 16-31
+        if ((lane & ~4) == 0 && 4 * (lane & 7) < nreal) {
+          double* o = p.seg + (((int64_t)b * (C >> 4) + (n >> 4)) * (plane >> 5) + chunk) * 2;
+          o[0] = s1;
+          o[1] = s2;
+        }
+      } else {
+        store_tile32_wide_pre<false>(acc, scratch, e, rp, s1, s2);
+      }
+    }
+  }
+}
+
+template <int KS, int NP>
+static int launch_init_plain_knp(const InitPlainParams& p, size_t smem, int grid, hipStream_t s) {
+  KD_HIP_CHECK(hipFuncSetAttribute((const void*)init_plain_kernel<KS, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL((init_plain_kernel<KS, NP>), dim3(grid), dim3(512), smem, s, p);
+  return 0;
+}
+template <int KS>
+static int launch_init_plain_k(const InitPlainParams& p, int np, size_t smem, int grid, hipStream_t s) {
+  switch (np) {
+    case 1: return launch_init_plain_knp<KS, 1>(p, smem, grid, s);
+    case 2: return launch_init_plain_knp<KS, 2>(p, smem, grid, s);
+    case 3: return launch_init_plain_knp<KS, 3>(p, smem, grid, s);
+    case 4: return launch_init_plain_knp<KS, 4>(p, smem, grid, s);
+    case 6: return launch_init_plain_knp<KS, 6>(p, smem, grid, s);
+    case 8: return launch_init_plain_knp<KS, 8>(p, smem, grid, s);
+  }
+  return 1;
+}
+
+int launch_init_plain(const float* x, const float* sc, int cx, int np, const float* wp, const float* bias, const float* res, float* y,
+                      int ldy, double* seg, int B, int S, int n, int k, hipStream_t s) {
+  KD_REQUIRE(init_plain_ok(S, n, k, np), "plain init conv kernel: kernel size 3 | 5 | 7, image size % 32, weights must fit LDS");
+  KD_REQUIRE(B >= 1 && (int64_t)B * (S / IC_TW) * (S / IC_TH) < 0x7fffffff, "plain init conv kernel: batch out of range");
+  KD_REQUIRE(ldy % 4 == 0 && ldy >= n && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
+                 ((uintptr_t)wp & 15) == 0,
+             "plain init conv kernel: 16-byte aligned output / residual / bias rows");
+  KD_REQUIRE(!seg || n % 16 == 0, "plain init conv partials: 16-channel segments");
+  KD_REQUIRE(cx >= 1 && (np == cx || np == 2 * cx), "plain init conv kernel: planes = channels (x) or 2 channels (x | self_cond)");
+  InitPlainParams p{x, np == 2 * cx ? sc : nullptr, wp, bias, res, y, seg, B, S, ldy, n, cx};
+  const size_t smem = init_plain_lds_floats(n, k, np) * sizeof(float);
+  const int ntiles = B * (S / IC_TW) * (S / IC_TH);
+  static int cus = 0;
+  if (!cus) {
+    hipDeviceProp_t prop;
+    int dev = 0;
+    KD_HIP_CHECK(hipGetDevice(&dev));
+    KD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  const int grid = ntiles < cus ? ntiles : cus;   // persistent: one workgroup per CU keeps the weights in LDS
+  int rc = 1;
+  switch (k) {
+    case 3: rc = launch_init_plain_k<3>(p, np, smem, grid, s); break;
+    case 5: rc = launch_init_plain_k<5>(p, np, smem, grid, s); break;
+    case 7: rc = launch_init_plain_k<7>(p, np, smem, grid, s); break;
+  }
+  if (rc) return 1;
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace kd

@@ -61,11 +61,16 @@ void Builder::build() {
 
   // Buffers that are written once per sampling call (static_ops) and read by every step are allocated
   // FIRST and stay live to the end of the build, so the arena can never hand their space to a per-step tensor.
-  const int fin_c = dim + (cfg.lowres_cond ? Ci : 0), fin_n = final_gemm_cols(Ci);
-  const float* wfin = P("final_conv.weight", (int64_t)Ci * fin_c * 9);
+  // (final_resnet_block=False: final_conv reads the concat in front of it, fin_w channels; final_conv_kernel_size = fks: the
+  // fks^2 Ci (output, tap) columns - kernels_final.hip, whose `_k` functions are the 3x3 ones at fks = 3)
+  const int fks = u->final_ks;
+  const bool final_res = u->no_final_res == 0;
+  const int fin_w = final_res ? dim : combine ? cat_w : dim + (cfg.init_conv_to_final_conv_residual ? dim : 0);
+  const int fin_c = fin_w + (cfg.lowres_cond ? Ci : 0), fin_n = final_gemm_cols_k(Ci, fks);
+  const float* wfin = P("final_conv.weight", (int64_t)Ci * fin_c * fks * fks);
   const float* bfin = P("final_conv.bias", Ci);
-  float* wfin_p = cached("final_conv_gemm", (size_t)fin_n * dim,
-                         [&](float* dst) { KD_THROW_IF(launch_pack_final(wfin, dst, fin_c, dim, Ci, 0)); });
+  float* wfin_p = cached("final_conv_gemm", (size_t)fin_n * fin_w,
+                         [&](float* dst) { KD_THROW_IF(launch_pack_final_k(wfin, dst, fin_c, fin_w, Ci, fks, 0)); });
   T fin_static;
   const bool fin_has_static = cfg.lowres_cond != 0;
   if (fin_has_static) {
@@ -77,7 +82,7 @@ void Builder::build() {
         set_error("lowres_cond_img must be given iff the UNet has lowres_cond");
         return 1;
       }
-      return launch_final_static(io->in_lowres, wfin, bfin, fr.f(), fin_c, dim, Ci, Bx, S, S, s);
+      return launch_final_static(io->in_lowres, wfin, bfin, fr.f(), fin_c, fin_w, Ci, Bx, S, S, s, fks);
     });
   }
 
@@ -135,8 +140,21 @@ void Builder::build() {
   const int NPs = u->self_cond ? 2 * Ci : Ci;
   const int init_ch = Cc + NPs + Cl, Cs = Cc + Cl;
   const bool hoist = Cs > 0;
-  const int ks[3] = {3, 7, 15};
-  const int ds[3] = {dim / 2, dim / 4, dim - dim / 2 - dim / 4};
+  // init_cross_embed_kernel_sizes: n_ic convs of the sizes ks, widths dim / 2, dim / 4, .., the rest (the library's rule);
+  // init_cross_embed=False: ONE conv of size ks[0] to all dim channels, parameters init_conv.{weight,bias}
+  const bool init_plain = u->init_plain != 0;
+  const int n_ic = init_plain ? 1 : u->n_init_ks;
+  int ks[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
+  bool ds16 = true;   // every conv's slice is whole 16-channel segments: the convs can leave the GroupNorm partials
+  for (int i = 0, left = dim; i < n_ic; ++i) {
+    ks[i] = u->init_ks[i];
+    ds[i] = i + 1 < n_ic ? dim >> (i + 1) : left;
+    left -= ds[i];
+    if (ds[i] < 4 || ds[i] % 4) throw std::runtime_error("init conv: every conv's width must be a multiple of 4");
+    ds16 = ds16 && ds[i] % 16 == 0;
+  }
+  const bool ks_default = !init_plain && n_ic == 3 && ks[0] == 3 && ks[1] == 7 && ks[2] == 15;
+  auto init_pre = [&](int i) { return init_plain ? std::string("init_conv") : "init_conv.convs." + std::to_string(i); };
   T init_static;
   {
     auto check_inputs = [=]() {
@@ -162,8 +180,8 @@ void Builder::build() {
       });
       init_static = alloc(B, S, S, dim);
       int off = 0;
-      for (int i = 0; i < 3; ++i) {
-        std::string pre = "init_conv.convs." + std::to_string(i);
+      for (int i = 0; i < n_ic; ++i) {
+        std::string pre = init_pre(i);
         ConvOpt o;
         o.dst = &init_static;
         o.yoff = off;
@@ -188,9 +206,27 @@ void Builder::build() {
     } else {
       xt = alloc(B, S, S, dim);
     }
-    const bool fused_init = init_conv_fused_ok(S, ds[0], ds[1], ds[2], NPs) &&
+    const bool fused_init = ks_default && !u->init_generic && init_conv_fused_ok(S, ds[0], ds[1], ds[2], NPs) &&
                             kd_switch("KD_INIT_FUSED", 1) != 0;   // A/B, read per plan
-    if (fused_init) {
+    // the plain conv's per-step share in one kernel of the same form where k is 3 | 5 | 7 and its weights fit LDS
+    const bool fused_plain = init_plain && !u->init_generic && init_plain_ok(S, dim, ks[0], NPs) &&
+                             kd_switch("KD_INIT_FUSED", 1) != 0;
+    if (fused_plain) {
+      const int k = ks[0], np = NPs, Itot = init_ch, c0 = Cc;
+      const float* w = raw("init_conv.weight", (int64_t)dim * init_ch * k * k);
+      float* wp = cached("init_conv_plain" + std::to_string(np), init_plain_weight_floats(dim, k, np),
+                         [&](float* dst) { KD_THROW_IF(launch_init_plain_pack(w, dst, dim, Itot, c0, np, k, 0)); });
+      const float* biasp = hoist ? nullptr : P("init_conv.bias", dim);   // (hoisted: the step-invariant share carries the bias)
+      const Ref seg = dim % 16 == 0 ? seg_at(add_seg(xt, 0, dim / 16, S * S / 32)) : Ref();
+      const Ref yr = at(xt), rr = hoist ? at(init_static) : Ref();
+      const int ldy = xt.LD();
+      const int64_t m = (int64_t)B * S * S * np * k * k * dim;
+      emit([=](hipStream_t s) {
+        if (check_inputs()) return 1;
+        return launch_init_plain(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, dim, k, s);
+      }, "init conv plain fused k" + std::to_string(k) + " S" + std::to_string(S) + " C" + std::to_string(dim) + (u->self_cond ? " self-cond" : ""), m);
+      count_macs(m, (int64_t)B * S * S * k * (((k * np + 1) / 2) * 2) * ((dim + 31) / 32 * 32));
+    } else if (fused_init) {
       // x's (| self_cond's) share of the three convs in ONE persistent kernel straight from the NCHW planes (kernels_init.hip)
       const float* w3 = raw("init_conv.convs.0.weight", (int64_t)ds[0] * init_ch * 9);
       const float* w7 = raw("init_conv.convs.1.weight", (int64_t)ds[1] * init_ch * 49);
@@ -234,14 +270,14 @@ void Builder::build() {
         return launch_pack_init(nullptr, 0, io->in_x, Ci, sc, sc ? Ci : 0, ir.f(), ipad, Bx, HW, s);
       });
       int off = 0;
-      for (int i = 0; i < 3; ++i) {
-        std::string pre = "init_conv.convs." + std::to_string(i);
+      for (int i = 0; i < n_ic; ++i) {
+        std::string pre = init_pre(i);
         ConvOpt o;
         o.dst = &xt;
         o.yoff = off;
         o.cin_logical = np;
         o.rowrun = true;  // K runs over whole kernel rows (ks*ipad contiguous floats)
-        o.want_seg = true;  // the three slices fill one partial buffer: GroupNorm of init_resnet_block / the tail
+        o.want_seg = ds16;  // the slices fill one partial buffer: GroupNorm of init_resnet_block / the tail
         o.seg_c0 = 0;
         o.seg_cn = dim;
         if (hoist) {
@@ -353,7 +389,7 @@ void Builder::build() {
   step(resnet(x, "mid_block2", mid, &c, false));
 
   // ---- up path
-  const float skip_scale = 0.70710678118654752440f;  // scale_skip_connection: 2^-0.5
+  const float skip_scale = u->skip_scale;  // scale_skip_connection: 2^-0.5; 1 without it, and then no scale pass is emitted
   // A producer that is directly followed by a skip concat (a ResnetBlock ending in its 1x1 skip conv, an
   // upsample conv) writes its channels straight into the concat buffer (`ct`), and add_skip then only copies
   // the scaled skip half.  KD_CONCAT_INPLACE=0 keeps the full copy (A/B, read per plan).
@@ -407,6 +443,7 @@ void Builder::build() {
       // scale 2^-1/2 of the skip half: folded into the consumer where it reads statistics and weights that can
       // carry it (block1's 3x3 conv on the paths conv3x3_choice names + the 1x1 skip conv), else applied in place
       move_seg(skip, full, Ca, skip_scale, skip_scale);
+      if (skip_scale == 1.0f) return -1;   // scale_skip_connection=False: nothing to fold, nothing to scale
       SegPart sp[2];
       int nsp = 0;
       // (round 5: the F(4x4,3x3) layers too - their input transform takes the factor into its affine; nine in-place scale
@@ -461,16 +498,23 @@ void Builder::build() {
     auto took_head = [&]() {   // the ResnetBlock wrote into the concat: x is its first dim channels
       if (head_resnet && x.off == cat_buf.off) x = head_slot;
     };
+    // final_resnet_block=False: the final conv reads the last producer's output itself - a ResnetBlock (no attention behind it, no
+    // upsample, and not an UpsampleCombiner map, whose Block normalises it) or the last upsample: no GroupNorm partials asked for
+    const bool last_is_resnet = is_last && !final_res && !ups && !attn && !lin && !combine;
     int sc0 = add_skip(dim_out);
+    out_seg = !(last_is_resnet && nb == 0);
     step(resnet(x, pre + ".0", dim_out, cfg.layer_cross_attns[l] || u->lin_cross[l] ? &c : nullptr, false,
                 nb > 0 ? offer_ct(x.B, x.H, x.W, dim_out) : head_resnet ? &cat_buf : nullptr, nullptr, sc0, skip_scale));
+    out_seg = true;
     if (nb == 0) took_head();
     for (int n = 0; n < nb; ++n) {
       sc0 = add_skip(dim_out);
       const bool next_is_skip = n + 1 < nb || (!attn && !lin && !ups && !is_last);
+      out_seg = !(last_is_resnet && n == nb - 1);
       step(resnet(x, pre + ".1." + std::to_string(n), dim_out, nullptr, cfg.use_gca != 0,
                   next_is_skip ? offer_ct(x.B, x.H, x.W, dim_out) : head_resnet && n == nb - 1 ? &cat_buf : nullptr, nullptr, sc0,
                   skip_scale));
+      out_seg = true;
       if (n == nb - 1) took_head();
     }
     if (attn) step(transformer(x, pre + ".2", &c, head_here ? &head_slot : nullptr, false, u->attn_depth[l]));
@@ -490,7 +534,9 @@ void Builder::build() {
         fin = whole(init_residual);   // the last upsample writes the first half of the concat in front of final_res_block
         target = &fin;
       }
+      out_seg = !(is_last && !final_res);
       step(upsample(x, pre + ".3", dim_in, target));
+      out_seg = true;
     }
   }
   if (have_ct) throw std::runtime_error("plan: concat buffer offered but never consumed");
@@ -527,7 +573,8 @@ void Builder::build() {
       step(y);
     }
   }
-  step(resnet(x, "final_res_block", dim, nullptr, true));
+  if (final_res) step(resnet(x, "final_res_block", dim, nullptr, true));
+  if (x.C != fin_w) throw std::runtime_error("plan: final conv input of the wrong width");
   free(c);
   if (tmlp_total > 0) free(t_ss);
 
@@ -536,12 +583,12 @@ void Builder::build() {
   // step-invariant and computed once per sampling call.
   {
     ConvOpt o;
-    o.macs_override = (int64_t)B * S * S * Ci * fin_c * 9;
+    o.macs_override = (int64_t)B * S * S * Ci * fin_c * fks * fks;
     T pm = conv(x, wfin_p, nullptr, fin_n, 1, 1, 0, o);
     const Ref pr = at(pm), fr = fin_has_static ? at(fin_static) : Ref();
     emit([=](hipStream_t s) {
-      return launch_final_gather(pr.f(), fr.f(), bfin, io->out, Ci, Bx, S, S, s);
-    }, "final gather");
+      return launch_final_gather_k(pr.f(), fr.f(), bfin, io->out, Ci, fks, Bx, S, S, s);
+    }, fks == 3 ? std::string("final gather") : "final gather k" + std::to_string(fks));
     free(pm);
   }
   free(x);

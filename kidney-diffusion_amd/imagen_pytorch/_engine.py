@@ -130,6 +130,12 @@ class kd_unet_ext3_t(C.Structure):
     _fields_ = [("layer_attns_depth", C.c_int * KD_MAX_LEVELS)]
 
 
+class kd_unet_ext4_t(C.Structure):
+    _fields_ = [("init_plain", C.c_int), ("init_kernel_size", C.c_int), ("init_kernel_sizes", C.c_int * 4),
+                ("n_init_kernel_sizes", C.c_int), ("final_kernel_size", C.c_int), ("no_final_resnet_block", C.c_int),
+                ("no_skip_scale", C.c_int), ("init_generic", C.c_int)]
+
+
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
 SIGNATURES = {
     "kd_last_error": (C.c_char_p, []),
@@ -150,6 +156,9 @@ SIGNATURES = {
     "kd_unet_create_ext3": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
                                       C.POINTER(kd_unet_ext_t), C.POINTER(kd_unet_ext2_t), C.POINTER(kd_unet_ext3_t),
                                       C.POINTER(C.c_void_p)]),
+    "kd_unet_create_ext4": (C.c_int, [C.POINTER(kd_unet_config_t), C.POINTER(kd_param_t), C.c_int, C.c_void_p,
+                                      C.POINTER(kd_unet_ext_t), C.POINTER(kd_unet_ext2_t), C.POINTER(kd_unet_ext3_t),
+                                      C.POINTER(kd_unet_ext4_t), C.POINTER(C.c_void_p)]),
     "kd_unet_weight_bytes": (C.c_int64, [C.c_void_p]),
     "kd_unet_macs": (C.c_int64, [C.c_void_p]),
     "kd_unet_mfma_macs": (C.c_int64, [C.c_void_p]),
@@ -216,6 +225,9 @@ SIGNATURES = {
     "kd_init_conv_planes_c_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6 +
                                    [C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "kd_final_conv_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
+    "kd_final_conv_k_nchw": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "kd_init_conv_plain_nchw": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] +
+                                [C.c_int] * 6 + [C.POINTER(C.c_float), C.c_void_p]),
     "kd_groupnorm_silu_nhwc": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
     "kd_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "kd_layernorm_ex": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

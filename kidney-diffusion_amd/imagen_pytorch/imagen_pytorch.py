@@ -304,8 +304,8 @@ class Unet(nn.Module):
         channels_out=None, attn_dim_head=64, attn_heads=8, ff_mult=2.0, lowres_cond=False, layer_attns=True,
         layer_attns_depth=1, attend_at_middle=True, layer_cross_attns=True, use_linear_attn=False,
         use_linear_cross_attn=False, cond_on_text=True, max_text_len=256, resnet_groups=8,
-        init_cross_embed=True, init_cross_embed_kernel_sizes=(3, 7, 15), cross_embed_downsample=False,
-        cross_embed_downsample_kernel_sizes=(2, 4),
+        init_conv_kernel_size=7, init_cross_embed=True, init_cross_embed_kernel_sizes=(3, 7, 15),
+        cross_embed_downsample=False, cross_embed_downsample_kernel_sizes=(2, 4),
         attn_pool_text=True, attn_pool_num_latents=32, dropout=0.0, memory_efficient=False,
         init_conv_to_final_conv_residual=False, use_global_context_attn=True, scale_skip_connection=True,
         final_resnet_block=True, final_conv_kernel_size=3, self_cond=False, pixel_shuffle_upsample=True,
@@ -321,15 +321,31 @@ class Unet(nn.Module):
         when the incoming keys contain `q_scale` - so the first real checkpoint decides the variant."""
         super().__init__()
         self._locals = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
-        required = dict(init_cross_embed=init_cross_embed, scale_skip_connection=scale_skip_connection,
-                        final_resnet_block=final_resnet_block)
-        bad = [k for k, v in required.items() if not v]
         if tuple(cross_embed_downsample_kernel_sizes) != (2, 4):
             raise NotImplementedError("cross_embed_downsample_kernel_sizes: the engine plans the library's default (2, 4) only")
-        if bad or final_conv_kernel_size != 3 or tuple(init_cross_embed_kernel_sizes) != (3, 7, 15) \
-                or channels not in (1, 2, 3, 4):
+        if channels not in (1, 2, 3, 4):
             raise NotImplementedError(
-                f"Unet option outside what the reference's configs use and the HIP engine plans: {bad or 'see kwargs'}")
+                f"Unet option outside what the reference's configs use and the HIP engine plans: channels={channels}")
+        # the structural switches of the first and the last layer: every value the engine cannot plan is refused here by name
+        init_cross_embed, final_resnet_block = bool(init_cross_embed), bool(final_resnet_block)
+        scale_skip_connection = bool(scale_skip_connection)
+        odd_to_15 = lambda k: isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= 15 and k % 2 == 1
+        if not init_cross_embed and not odd_to_15(init_conv_kernel_size):
+            raise NotImplementedError(f"init_conv_kernel_size={init_conv_kernel_size}: the engine plans odd sizes from 1 to 15")
+        init_cross_embed_kernel_sizes = tuple(init_cross_embed_kernel_sizes)
+        if init_cross_embed:
+            ks = init_cross_embed_kernel_sizes
+            if not 1 <= len(ks) <= 4 or not all(odd_to_15(k) for k in ks):
+                raise NotImplementedError(f"init_cross_embed_kernel_sizes={ks}: the engine plans one to four odd sizes "
+                                          "from 1 to 15")
+            # the library's widths: dim / 2, dim / 4, .., the rest; every conv writes a slice of the NHWC map in 16-byte steps
+            widths = [int(dim / 2 ** (i + 1)) for i in range(len(ks) - 1)]
+            widths.append(dim - sum(widths))
+            if any(w < 4 or w % 4 for w in widths):
+                raise NotImplementedError(f"init_cross_embed_kernel_sizes={ks} with dim={dim}: the width split {widths} "
+                                          "has a conv of a width that is no multiple of 4")
+        if final_conv_kernel_size not in (1, 3, 5, 7) or isinstance(final_conv_kernel_size, bool):
+            raise NotImplementedError(f"final_conv_kernel_size={final_conv_kernel_size}: the engine plans 1, 3, 5 and 7")
         if attn_dim_head not in (32, 64, 128):
             raise NotImplementedError(f"attn_dim_head={attn_dim_head}: the attention kernels are built for 32, 64 and 128")
         if channels != 3 and channels_out is not None and channels_out != channels:
@@ -373,7 +389,9 @@ class Unet(nn.Module):
         self.self_cond = bool(self_cond)
         init_channels = channels * (1 + int(lowres_cond) + int(self.self_cond)) + cond_images_channels
 
-        self.init_conv = CrossEmbedLayer(init_channels, init_cross_embed_kernel_sizes, dim, stride=1)
+        # init_cross_embed=False: the library's plain Conv2d(init_channels, dim, init_conv_kernel_size), keys init_conv.{weight,bias}
+        self.init_conv = CrossEmbedLayer(init_channels, init_cross_embed_kernel_sizes, dim, stride=1) if init_cross_embed \
+            else nn.Conv2d(init_channels, dim, init_conv_kernel_size, padding=init_conv_kernel_size // 2)
         dims = [dim, *[dim * m for m in dim_mults]]
         in_out = list(zip(dims[:-1], dims[1:]))
         L = len(in_out)
@@ -432,7 +450,8 @@ class Unet(nn.Module):
         for d_in, d_out in in_out:
             cur = d_out if memory_efficient else d_in
             gn_widths |= {cur, d_out, d_out + cur}                # the level's down blocks; its up blocks behind the skip concat
-        gn_widths |= {dim, dim * (1 + int(bool(init_conv_to_final_conv_residual)) + (L if combine_upsample_fmaps else 0))}
+        if final_resnet_block:                                    # (without it no GroupNorm reads the concat in front of final_conv)
+            gn_widths |= {dim, dim * (1 + int(bool(init_conv_to_final_conv_residual)) + (L if combine_upsample_fmaps else 0))}
         self._gn_widths = sorted(gn_widths)
         bad_w = sorted(w for w in gn_widths if groups[0] < 1 or w % (4 * groups[0]))
         if bad_w:
@@ -446,7 +465,11 @@ class Unet(nn.Module):
                           groups=groups[0], attend_at_middle=attend_at_middle, use_gca=use_global_context_attn,
                           cross_embed_downsample=self.cross_embed_downsample,
                           upsample_nearest=not self.pixel_shuffle_upsample,
-                          combine_upsample_fmaps=self.combine_upsample_fmaps)
+                          combine_upsample_fmaps=self.combine_upsample_fmaps,
+                          init_cross_embed=init_cross_embed, init_conv_kernel_size=init_conv_kernel_size,
+                          init_cross_embed_kernel_sizes=tuple(sorted(init_cross_embed_kernel_sizes)),
+                          final_conv_kernel_size=final_conv_kernel_size, final_resnet_block=final_resnet_block,
+                          scale_skip_connection=scale_skip_connection)
 
         self.init_resnet_block = ResnetBlock(dim, dim, time_cond_dim=tcd, groups=groups[0],
                                              use_gca=use_global_context_attn, **ak) if memory_efficient else None
@@ -522,8 +545,11 @@ class Unet(nn.Module):
         if self.combine_upsample_fmaps:   # Block's own default of 8 groups, not resnet_groups; up level i works at dims[L - i]
             self.upsample_combiner = UpsampleCombiner(tuple(dims[L - i] for i in range(L)), dim)
             fin += dim * L
-        self.final_res_block = ResnetBlock(fin, dim, time_cond_dim=tcd, groups=groups[0], use_gca=True)
-        self.final_conv = nn.Conv2d(dim + (channels if lowres_cond else 0), self.channels_out, 3, padding=1)
+        # final_resnet_block=False: no final_res_block, final_conv reads the concat itself
+        self.final_res_block = ResnetBlock(fin, dim, time_cond_dim=tcd, groups=groups[0], use_gca=True) \
+            if final_resnet_block else None
+        self.final_conv = nn.Conv2d((dim if final_resnet_block else fin) + (channels if lowres_cond else 0), self.channels_out,
+                                    final_conv_kernel_size, padding=final_conv_kernel_size // 2)
         nn.init.zeros_(self.final_conv.weight)
         nn.init.zeros_(self.final_conv.bias)
 
@@ -697,7 +723,9 @@ class Unet(nn.Module):
         x3 = int(getattr(self, "gemm_bf16x3", 0))           # engine extension: bf16x3 position GEMMs (0 = default on, < 0 = fp32 MFMA)
         x3lin = int(getattr(self, "x3_linear", 0))          # engine extension: token GEMMs / 1x1 convs on bf16x3 (0 = default: K >= 512, < 0 = never)
         w4img = int(getattr(self, "wino4_max_images", 0))   # engine extension: F(4x4,3x3) layers in sets of at most n images (0 = default)
+        init_generic = int(bool(getattr(self, "init_conv_generic", 0)))   # engine extension (A/B): init conv on the generic conv path
         key = (batch, image_size, device.index, bool(with_text), conv_algo, self.attn_qk_norm, slice_mb, w43, x3, x3lin, w4img) + \
+            ((("init_generic",),) if init_generic else ()) + \
             ((replica,) if replica else ())   # (the structural forks drop every plan when they change)
         if self._engines:
             fp = self._weights_fingerprint()
@@ -765,7 +793,24 @@ class Unet(nn.Module):
             ext.upsample_nearest = int(p["upsample_nearest"])
             ext2 = E.kd_unet_ext2_t()
             ext2.combine_upsample_fmaps = int(p["combine_upsample_fmaps"])
-            if any(d != 1 for d in p["layer_attns_depth"]):
+            ext4 = E.kd_unet_ext4_t()
+            ext4.init_plain = int(not p["init_cross_embed"])
+            ext4.init_kernel_size = int(p["init_conv_kernel_size"]) if ext4.init_plain else 0
+            if p["init_cross_embed"] and p["init_cross_embed_kernel_sizes"] != (3, 7, 15):
+                ext4.n_init_kernel_sizes = len(p["init_cross_embed_kernel_sizes"])
+                for i, k in enumerate(p["init_cross_embed_kernel_sizes"]):
+                    ext4.init_kernel_sizes[i] = int(k)
+            ext4.final_kernel_size = 0 if p["final_conv_kernel_size"] == 3 else int(p["final_conv_kernel_size"])
+            ext4.no_final_resnet_block = int(not p["final_resnet_block"])
+            ext4.no_skip_scale = int(not p["scale_skip_connection"])
+            ext4.init_generic = init_generic
+            if any(bytes(ext4)):   # one of the first / last layer's structural switches
+                ext3 = E.kd_unet_ext3_t()
+                for i in range(L):
+                    ext3.layer_attns_depth[i] = int(p["layer_attns_depth"][i])
+                E.check(lib.kd_unet_create_ext4(C.byref(cfg), arr, len(names), share, C.byref(ext), C.byref(ext2), C.byref(ext3),
+                                                C.byref(ext4), C.byref(handle)))
+            elif any(d != 1 for d in p["layer_attns_depth"]):
                 ext3 = E.kd_unet_ext3_t()
                 for i in range(L):
                     ext3.layer_attns_depth[i] = int(p["layer_attns_depth"][i])
