@@ -56,7 +56,8 @@ const char* kd_last_error(void);
  *      kd_unet_create_ext4 with its struct kd_unet_ext4_t for the first and the last layer's structural switches
  *      (`init_cross_embed`, `init_conv_kernel_size`, `init_cross_embed_kernel_sizes`, `final_conv_kernel_size`,
  *      `final_resnet_block`, `scale_skip_connection`) - kd_unet_create_ext3 is that call with ext4 = NULL - and
- *      kd_final_conv_k_nchw, kd_init_conv_plain_nchw added */
+ *      kd_final_conv_k_nchw, kd_init_conv_plain_nchw added; kd_tiles_gather and kd_tiles_fuse_update added (fused-tile
+ *      canvas sampling) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -807,6 +808,40 @@ int kd_philox_normal_rows(float* d_out, int B, int64_t n, const uint64_t* seeds,
  * k_begin = skip_steps. */
 int kd_sample_start(float* d_x, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* d_noise,
                     const float* d_init, int Hs, int Ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Fused-tile canvas sampling (an engine extension; MultiDiffusion / Mixture of Diffusers).  An alternative to the
+ * reference's sequential outpainting (outpainting.py:146-157, sample_ultra_res.py:183-195): the canvas of a stage is one
+ * noisy image d_x [C,Hc,Wc]; at every schedule step every tile of an ny x nx lattice - tile size S, stride st,
+ * Hc = (ny - 1) st + S, Wc = (nx - 1) st + S - is denoised by itself (kd_solver_sample_steps(k, k + 1) on gathered tiles,
+ * its x0 estimate and thresholds read with kd_sample_last), and one call of kd_tiles_fuse_update averages the thresholded
+ * estimates where tiles overlap and runs the solver update on the canvas.  S and st are multiples of 4, so every tile
+ * origin and Wc are: all accesses are 16-byte loads and stores.  The Python package: Imagen.sample_tiled.
+ * ---------------------------------------------------------------------------------------- */
+/* d_tiles[b] = d_canvas[:, y0_b : y0_b + S, x0_b : x0_b + S] for b < B; d_canvas [C,Hc,Wc], d_tiles [B,C,S,S].
+ * `origins_yx` is a HOST array [B][2] of (y0, x0), read before the call returns (the origins travel as kernel arguments);
+ * origins may repeat and come in any order.  Needs S % 4 == 0, Wc % 4 == 0, every x0 % 4 == 0, every tile inside the
+ * canvas and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
+int kd_tiles_gather(const float* d_canvas, float* d_tiles, int B, int C, int Hc, int Wc, int S, const int* origins_yx,
+                    void* stream);
+/* The canvas step in one pass, in place on d_x and d_x0bar [C,Hc,Wc].  Per pixel, over the present tiles t that cover it
+ * in ascending (row, column) order of their slots:
+ *     x0c_t = clamp(x0_t, -s_t, s_t) / s_t,  s_t = max(d_thr[t], 1)  (d_thr == NULL: s_t = 1, the static threshold)
+ *     x0bar = (sum w_t x0c_t) / (sum w_t)
+ *     x <- A x + B x0bar [+ P hist] [+ Sn z];  hist <- x0bar          (hist: what d_x0bar held on entry)
+ * without contraction, the expression and op order of the solver step (kd_solver_sample_steps).  A term whose coefficient
+ * is 0 is left out and its operand is not read: P == 0 leaves d_x0bar unread, Sn == 0 draws nothing.  A pixel that no
+ * present tile covers is left untouched in both buffers.
+ *   d_x0_tiles [N,C,S,S]  the x0 estimates BEFORE the threshold (kd_sample_last which = 1), d_thr [N] (which = 2)
+ *   d_tile_of  [ny][nx]   tile index of the slot, or -1: no tile there (entries outside 0 .. N - 1 count as -1)
+ *   ramp       0: w = 1.  != 0: w(y, x) = r(y) r(x), r(i) = min(i + 1, S - i, ov) / ov, ov = max(S - st, 1), inside the tile
+ *   z          d_noise [C,Hc,Wc], or, when it is NULL, element (c Hc + y) Wc + x of Philox stream `stream_id` under `seed`:
+ *              the bits kd_philox_normal writes over C Hc Wc elements - a property of the canvas, not of the tiling.
+ * Needs S % 4 == 0, st % 4 == 0, 4 <= st <= S <= 3 st (at most 3 tiles per axis, 9 in all, cover a pixel), 1 <= N <= ny nx
+ * and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
+int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, const float* d_thr, const int* d_tile_of, int N,
+                         int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn,
+                         const float* d_noise, uint64_t seed, uint64_t stream_id, void* stream);
 
 #ifdef __cplusplus
 }

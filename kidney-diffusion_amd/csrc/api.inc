@@ -1196,4 +1196,15 @@ int kd_sample_start(float* d_x, int B, int C, int S, float scale, uint64_t seed,
   return launch_sample_start(d_x, B, C, S, scale, seed, seeds, d_noise, d_init, Hs, Ws, (hipStream_t)stream);
 }
 
+int kd_tiles_gather(const float* d_canvas, float* d_tiles, int B, int C, int Hc, int Wc, int S, const int* origins_yx,
+                    void* stream) {
+  return launch_tiles_gather(d_canvas, d_tiles, B, C, Hc, Wc, S, origins_yx, (hipStream_t)stream);
+}
+int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, const float* d_thr, const int* d_tile_of, int N,
+                         int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn,
+                         const float* d_noise, uint64_t seed, uint64_t stream_id, void* stream) {
+  return launch_tiles_fuse_update(d_x, d_x0bar, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P, Sn, d_noise,
+                                  seed, stream_id, (hipStream_t)stream);
+}
+
 }  // extern "C"

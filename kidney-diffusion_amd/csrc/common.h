@@ -449,4 +449,12 @@ int launch_philox_normal_rows(float* out, int B, int64_t n, const uint64_t* seed
 int launch_sample_start(float* out, int B, int C, int S, float scale, uint64_t seed, const uint64_t* seeds, const float* noise,
                         const float* init, int Hs, int Ws, hipStream_t s);
 
+// fused-tile canvas sampling (kernels_tiles.hip): tiles[b] = canvas[:, y0_b : y0_b + S, x0_b : x0_b + S], origins_yx a host
+// array [B][2]; and the canvas step x <- A x + B x0bar + P hist + Sn z over the weighted mean x0bar of the covering tiles
+int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc, int Wc, int S, const int* origins_yx,
+                        hipStream_t s);
+int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, const float* thr, const int* tile_of, int N, int C,
+                             int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn, const float* noise,
+                             uint64_t seed, uint64_t stream_id, hipStream_t s);
+
 }  // namespace kd

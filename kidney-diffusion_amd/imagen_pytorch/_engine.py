@@ -256,6 +256,9 @@ SIGNATURES = {
     "kd_philox_normal_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "kd_sample_start": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(C.c_uint64),
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "kd_tiles_gather": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int), C.c_void_p]),
+    "kd_tiles_fuse_update": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_void_p, C.c_uint64, C.c_uint64,
+                                                                                          C.c_void_p]),
 }
 
 

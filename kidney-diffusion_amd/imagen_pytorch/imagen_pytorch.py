@@ -1054,6 +1054,96 @@ def normalize_sampler(sampler, sampler_eta, sample_steps, num_unets):
     return out
 
 
+TILE_WEIGHTS = ("uniform", "ramp")
+TILE_COVER = 3   # kd_tiles_fuse_update visits at most this many tile slots per axis
+
+
+def normalize_tiling(image_sizes, grid, overlap=0.25, present=None, tile_weights="uniform"):
+    """``sample_tiled(grid=..., overlap=..., present=..., tile_weights=...)`` as the per-stage geometry of a fused-tile
+    canvas.  The canvas of stage s is a lattice of ``ny x nx`` tile slots of size ``S`` (the stage's image size) at stride
+    ``st = int(S * (1 - overlap))``; ``present[ny][nx]`` (None: all) marks the slots that hold a tile, and tiles are numbered
+    in row-major order over the present slots.  Returns one dict per stage: ``S, st, ny, nx, Hc, Wc`` (canvas size
+    ``(n - 1) st + S``), ``ov = max(S - st, 1)``, ``origins`` [(y0, x0)] per tile, ``tile_of`` [ny][nx] (tile index or -1),
+    ``weights``.  Raises ValueError for a tile size or stride that is no multiple of 4 (the kernels move 16 bytes), a
+    stride outside 1 .. S, a pixel covered by more than 3 tiles per axis, no present slot, and stages whose lattices are
+    not images of one another (``st_s S_{s-1} != st_{s-1} S_s``: the canvas of stage s - 1 must resize onto the canvas of
+    stage s exactly).  Needs no GPU."""
+    import numbers
+
+    if tile_weights not in TILE_WEIGHTS:
+        raise ValueError(f"tile_weights must be one of {TILE_WEIGHTS}, got {tile_weights!r}")
+    if (not isinstance(grid, (tuple, list)) or len(grid) != 2
+            or any(not isinstance(g, numbers.Integral) or isinstance(g, bool) or int(g) < 1 for g in grid)):
+        raise ValueError(f"grid must be (ny, nx), two ints >= 1, got {grid!r}")
+    ny, nx = int(grid[0]), int(grid[1])
+    if not isinstance(overlap, numbers.Real) or isinstance(overlap, bool):
+        raise ValueError(f"overlap must be a number, got {overlap!r}")
+    if present is None:
+        rows = [[True] * nx for _ in range(ny)]
+    else:
+        rows = present.tolist() if torch.is_tensor(present) else [list(r) for r in present]
+        if len(rows) != ny or any(len(r) != nx for r in rows):
+            raise ValueError(f"present must be [ny={ny}][nx={nx}], got {len(rows)} rows of lengths {[len(r) for r in rows]}")
+        rows = [[bool(v) for v in r] for r in rows]
+    if not any(any(r) for r in rows):
+        raise ValueError(f"present marks no slot of the {ny} x {nx} lattice: a canvas needs at least one tile")
+    out = []
+    for i, S in enumerate(image_sizes):
+        num, S = i + 1, int(S)
+        st = int(S * (1 - overlap))
+        if S % 4 != 0:
+            raise ValueError(f"tile size S={S} of unet {num} must be a multiple of 4")
+        if st < 1:
+            raise ValueError(f"tile stride st={st} of unet {num} (S={S}, overlap={overlap}) must be at least 1")
+        if st > S:
+            raise ValueError(f"tile stride st={st} of unet {num} must not exceed the tile size S={S}")
+        if st % 4 != 0:
+            raise ValueError(f"tile stride st={st} of unet {num} (S={S}, overlap={overlap}) must be a multiple of 4")
+        if S > TILE_COVER * st:
+            raise ValueError(f"tile stride st={st} of unet {num} lets more than {TILE_COVER} tiles per axis cover a pixel "
+                             f"(S={S} > {TILE_COVER} st)")
+        if out and st * out[-1]["S"] != out[-1]["st"] * S:
+            raise ValueError(f"the lattices of unets {num - 1} and {num} are not images of one another: "
+                             f"st={st} * S={out[-1]['S']} != st={out[-1]['st']} * S={S}")
+        tile_of, origins = [[-1] * nx for _ in range(ny)], []
+        for r in range(ny):
+            for q in range(nx):
+                if rows[r][q]:
+                    tile_of[r][q] = len(origins)
+                    origins.append((r * st, q * st))
+        out.append(dict(S=S, st=st, ny=ny, nx=nx, Hc=(ny - 1) * st + S, Wc=(nx - 1) * st + S, ov=max(S - st, 1),
+                        origins=origins, tile_of=tile_of, weights=tile_weights))
+    return out
+
+
+def tile_weight(S, st, weights="uniform"):
+    """The weight of a tile's pixels in the fused estimate, fp32 [S, S]: ``"uniform"`` is 1; ``"ramp"`` is separable,
+    ``w(y, x) = r(y) r(x)`` with ``r(i) = min(i + 1, S - i, ov) / ov``, ``ov = max(S - st, 1)`` - strictly positive, 1 in the
+    interior, falling linearly over the overlap strip.  What kd_tiles_fuse_update forms per pixel."""
+    if weights not in TILE_WEIGHTS:
+        raise ValueError(f"tile_weights must be one of {TILE_WEIGHTS}, got {weights!r}")
+    if weights == "uniform":
+        return torch.ones(S, S, dtype=torch.float32)
+    ov = max(S - st, 1)
+    i = torch.arange(S)
+    r = torch.minimum(torch.minimum(i + 1, S - i), torch.tensor(ov)).to(torch.float32) / float(ov)
+    return r[:, None] * r[None, :]
+
+
+def canvas_tables(step_tables, sampler, eta=0.0):
+    """Coefficients of the canvas step  x <- A x + B x0bar + P hist + S z  of fused-tile sampling, as solver_tables gives
+    them (``coef_x, coef_x0, coef_prev, coef_noise``).  ``"ddim"`` and ``"dpmpp_2m"`` are solver_tables' as they are;
+    ``"ddpm"`` is the ancestral step in the same linear form, ``A = alpha_next (1 - c) / alpha``, ``B = alpha_next c``,
+    ``P = 0``, ``S = noise_scale``, formed in float64 from the fp32 step tables and rounded once."""
+    if sampler != "ddpm":
+        return solver_tables(step_tables, sampler, eta=eta)
+    if eta != 0:
+        raise ValueError(f"canvas_tables: eta={eta} needs sampler 'ddim', got 'ddpm'")
+    a, an, c = (step_tables[n].to(torch.float64) for n in ("alpha", "alpha_next", "c"))
+    vals = (an * (1 - c) / a, an * c, torch.zeros_like(a), step_tables["noise_scale"].to(torch.float64))
+    return {n: v.to(torch.float32).contiguous() for n, v in zip(("coef_x", "coef_x0", "coef_prev", "coef_noise"), vals)}
+
+
 def resize_image_to(image, target_image_size, mode="nearest"):
     if image.shape[-1] == target_image_size:
         return image
@@ -1424,6 +1514,233 @@ class Imagen(nn.Module):
             img = img.clone()  # the stable buffer is overwritten by the next call (stream-ordered copy)
         return img
 
+    # ------------------------------------------------------------------ fused-tile canvas sampling
+    @torch.no_grad()
+    def sample_tiled(self, grid, overlap=0.25, present=None, tile_batch=16, tile_weights="uniform", cond_images=None,
+                     text_embeds=None, text_masks=None, cond_scale=1.0, sampler=None, sampler_eta=0.0, sample_steps=None,
+                     seed: Optional[int] = None, noise_fn: Optional[Callable] = None, use_graph: bool = True,
+                     start_at_unet_number=1, stop_at_unet_number=None, start_image_or_video=None,
+                     return_all_unet_outputs=False, lowres_sample_noise_level=None, device=None, inpaint_images=None,
+                     inpaint_masks=None, inpaint_resample_times=None, init_images=None, skip_steps=None):
+        """A canvas of overlapping tiles denoised jointly (MultiDiffusion / Mixture of Diffusers; an engine extension, the
+        alternative to sequential outpainting).  The canvas of a stage is ONE noisy image over the ``grid = (ny, nx)``
+        lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
+        tiles per UNet forward, their thresholded x0 estimates are averaged where tiles overlap (``tile_weights``) and the
+        update of ``sampler`` (None / ``"ddpm"``, ``"ddim"`` with ``sampler_eta``, ``"dpmpp_2m"``; ``sample_steps`` as in
+        ``sample``) runs once, on the canvas, with canvas-level noise (kd_tiles_fuse_update).  There is no inpainting, no
+        resampling and no order among the tiles, and the canvas does not depend on ``tile_batch`` beyond the rounding of
+        plans of different batch sizes.
+
+        ``cond_images`` [N, Cc, h, w] holds one image per tile (row-major over the present slots); ``text_embeds`` /
+        ``text_masks`` hold ONE row, given to every tile; ``seed`` is an int (None: drawn from torch's generator);
+        ``noise_fn(tag, shape)`` injects the draws: ``("init", stage)`` and ``("lowres", stage)`` of the canvas shape, and
+        ``("step", stage, k, 0)`` only for the steps whose update adds noise.  The low-res conditioning of a stage is the
+        previous canvas resized to this stage's canvas and augmented ONCE, so overlapping tiles see the same conditioning on
+        shared pixels; ``start_image_or_video`` is a canvas.  Returns the canvas [1, C, Hc, Wc] in [0, 1] (a list of the
+        stages' canvases with ``return_all_unet_outputs``); pixels that no tile covers are 0."""
+        for name, v in dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
+                            inpaint_resample_times=inpaint_resample_times).items():
+            if exists(v):
+                raise NotImplementedError(f"sample_tiled({name}=...): a fused canvas holds no inpainting - its tiles are "
+                                          "denoised together")
+        for name, v in dict(init_images=init_images, skip_steps=skip_steps).items():
+            if exists(v):
+                raise NotImplementedError(f"sample_tiled({name}=...) is not provided: a canvas starts from noise at step 0")
+        import numbers
+
+        if exists(seed) and (not isinstance(seed, numbers.Integral) or isinstance(seed, bool)):
+            raise ValueError(f"sample_tiled(seed=...) takes one int for the canvas (per-image seed lists belong to sample()), "
+                             f"got {type(seed).__name__}")
+        if not isinstance(tile_batch, numbers.Integral) or isinstance(tile_batch, bool) or int(tile_batch) < 1:
+            raise ValueError(f"tile_batch must be an int >= 1, got {tile_batch!r}")
+        n = len(self.unets)
+        solvers = self._solver_args(sampler, sampler_eta, sample_steps)
+        tiling = normalize_tiling(self.image_sizes, grid, overlap, present, tile_weights)
+        n_tiles = len(tiling[0]["origins"])
+        if exists(cond_images) and (cond_images.dim() != 4 or cond_images.shape[0] != n_tiles):
+            raise ValueError(f"cond_images must be [tiles {n_tiles}, Cc, h, w], one per present tile, got {tuple(cond_images.shape)}")
+        if exists(text_embeds) and (text_embeds.dim() != 3 or text_embeds.shape[0] != 1):
+            raise ValueError(f"text_embeds must hold one row [1, L, D] for the whole canvas, got {tuple(text_embeds.shape)}")
+        if not 1 <= start_at_unet_number <= n:
+            raise ValueError(f"start_at_unet_number={start_at_unet_number} is outside 1 .. {n}")
+        E.require_gpu()
+        device = torch.device(default(device, self.device))
+        if device.type != "cuda":
+            raise E.EngineUnavailable(f"sampling runs on the HIP engine only; got device {device}")
+        self.eval()
+        assert not (self.condition_on_text and not exists(text_embeds)), "text or text encodings must be passed into imagen if specified"
+        assert not (not self.condition_on_text and exists(text_embeds)), "imagen specified not to be conditioned on text, yet it is presented"
+        assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
+            f"invalid text embedding dimension being passed in (should be {self.text_embed_dim})"
+        if exists(text_embeds):
+            text_masks = default(text_masks, lambda: torch.any(text_embeds != 0.0, dim=-1))
+        lowres_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
+        cond_scale = cast_tuple(cond_scale, n)
+        if exists(cond_images) and cond_images.dtype == torch.uint8:
+            cond_images = cond_images.float() / 255.0
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
+        canvas = None
+        if start_at_unet_number > 1:
+            assert exists(start_image_or_video), "starting image or video must be supplied if only doing upscaling"
+            g = tiling[start_at_unet_number - 2]
+            canvas = F.interpolate(f32(start_image_or_video), (g["Hc"], g["Wc"]), mode="nearest")
+        outputs = []
+        for num, unet, geo, sched, obj, dyn, cs, (solver, eta, steps) in zip(
+                range(1, n + 1), self.unets, tiling, self.noise_schedulers, self.pred_objectives, self.dynamic_thresholding,
+                cond_scale, solvers):
+            if num < start_at_unet_number:
+                continue
+            assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
+            assert not (cs != 1.0 and not self.condition_on_text), \
+                "imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)"
+            if exists(steps):
+                sched = sched.with_timesteps(steps)
+            canvas = self._tiled_stage(unet, num, geo, sched, obj, dyn, device, canvas, cond_images, lowres_level, noise_fn,
+                                       int(seed), use_graph, int(tile_batch), text_embeds=text_embeds, text_masks=text_masks,
+                                       cond_scale=float(cs), solver=(solver, eta))
+            outputs.append(canvas)
+            if exists(stop_at_unet_number) and stop_at_unet_number == num:
+                break
+        return outputs if return_all_unet_outputs else outputs[-1]
+
+    def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
+                     lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
+                     solver=("ddpm", 0.0)):
+        """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  Per schedule step k and chunk of at
+        most `tile_batch` tiles: gather the chunk out of the canvas into the plan's stable buffers, one iteration
+        kd_solver_sample_steps(k, k + 1) with DDIM(0) coefficients (first order: no history, no draw; its tile-level
+        update is discarded), the x0 estimates and thresholds into the tile store; then ONE kd_tiles_fuse_update with the
+        canvas sampler's coefficients of step k.  A ragged last chunk runs the plan of its own batch size."""
+        lib = E.load()
+        Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
+        origins = geo["origins"]
+        N = len(origins)
+        shape = (1, Cn, Hc, Wc)
+        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
+        stage_seed = (seed + STAGE_SEED_STRIDE * stage) % (2 ** 64)
+        stream = E.current_stream
+
+        def gauss(tag, sid):
+            if exists(noise_fn):
+                return f32(noise_fn(tag, shape))
+            out = torch.empty(shape, device=device, dtype=torch.float32)
+            E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), stage_seed, sid, stream()))
+            return out
+
+        T = sched.num_timesteps
+        tables = sched.step_tables()
+        name, eta = solver
+        coefs = canvas_tables(tables, name, eta)
+        tile_tables = {k: tables[k] for k in ("log_snr", "alpha", "sigma", "rn_a", "rn_b")}
+        tile_tables.update(solver_tables(tables, "ddim", eta=0.0))   # the tiles' own iteration: first order, no draw
+        sc = E.kd_solver_schedule_t()
+        sc.T = T
+        for k, v in tile_tables.items():
+            setattr(sc, k, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
+
+        with torch.cuda.device(device):
+            x = gauss(("init", stage), (16 << 32) | 2)
+            x0bar = torch.zeros(shape, device=device, dtype=torch.float32)
+            store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
+            thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
+            tile_of = torch.tensor(geo["tile_of"], dtype=torch.int32).to(device).contiguous()
+            lowres = ls = None
+            if unet.lowres_cond:
+                ls = self.lowres_noise_schedule.log_snr(torch.full((1,), lowres_level, dtype=torch.float32))
+                a, s = log_snr_to_alpha_sigma(ls)
+                lowres = F.interpolate(prev_canvas, (Hc, Wc), mode="nearest") * 2 - 1
+                lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), (16 << 32) | 1)).contiguous()
+            cond = None
+            if exists(cond_images):
+                assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
+                cond = f32(resize_image_to(f32(cond_images), S))
+            with_text = exists(text_embeds) and unet.cond_on_text
+
+            def gather(src, dst, n0, b):   # dst [b, C, S, S] <- tiles n0 .. n0 + b - 1 of the canvas-shaped src
+                yx = (C.c_int * (2 * b))(*[v for o in origins[n0:n0 + b] for v in o])
+                E.check(lib.kd_tiles_gather(E.ptr(src), E.ptr(dst), b, Cn, Hc, Wc, S, yx, stream()))
+
+            # one plan, one set of stable buffers and one argument struct per batch size (the full chunks' and the ragged one's)
+            plans = {}
+            for b in sorted({min(tile_batch, N - n0) for n0 in range(0, N, tile_batch)}):
+                io = unet._io_buffers.setdefault((b, S, device.index), {})
+
+                def buf(key, shp, io=io):
+                    t = io.get(key)
+                    if t is None or tuple(t.shape) != tuple(shp):
+                        t = io[key] = torch.empty(shp, device=device, dtype=torch.float32)
+                    return t
+
+                args = E.kd_sample_args_t()
+                args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
+                args.dynamic_threshold = int(bool(dynamic_threshold))
+                args.percentile = self.dynamic_thresholding_percentile
+                args.resample_times = 1
+                args.seed = stage_seed   # (DDIM(0) draws nothing)
+                args.use_graph = int(bool(use_graph))
+                args.cond_table = int(getattr(self, "cond_table", 0))
+                p = dict(img=buf("img", (b, Cn, S, S)), args=args)
+                if unet.lowres_cond:
+                    p["lowres"] = buf("lowres", (b, Cn, S, S))
+                    lls = buf("lowres_log_snr", (b,))
+                    lls.copy_(ls.to(device).expand(b))
+                    args.d_lowres, args.d_lowres_log_snr = E.ptr(p["lowres"]), E.ptr(lls)
+                    args.lowres_log_snr_uniform = 1
+                    args.lowres_log_snr_value = float(ls[0])
+                if exists(cond):
+                    p["cond"] = buf("cond", (b,) + tuple(cond.shape[1:]))
+                    args.d_cond_images = E.ptr(p["cond"])
+                if unet.self_cond:
+                    p["self_cond"] = buf("tile_self_cond", (b, Cn, S, S))
+                h = p["h"] = unet.engine(b, S, device, with_text=with_text)
+                if with_text:   # one row for the canvas, given to every tile of the chunk
+                    rows = lambda t: None if t is None else t.expand(b, *t.shape[1:])
+                    for drop, keys in ((False, ("text_tokens", "text_hiddens")), (True, ("null_text_tokens", "null_text_hiddens"))):
+                        if drop and cond_scale == 1.0:
+                            continue
+                        tok, hid = unet.text_cond(h, rows(text_embeds), rows(text_masks), drop=drop, device=device)
+                        bt, bh = buf(keys[0], tok.shape), buf(keys[1], hid.shape)
+                        bt.copy_(tok)
+                        bh.copy_(hid)
+                        if drop:
+                            args.d_null_text_tokens, args.d_null_text_hiddens = E.ptr(bt), E.ptr(bh)
+                        else:
+                            args.d_text_tokens, args.d_text_hiddens = E.ptr(bt), E.ptr(bh)
+                    args.cond_scale = cond_scale
+                plans[b] = p
+
+            for k in range(T):
+                for n0 in range(0, N, tile_batch):
+                    b = min(tile_batch, N - n0)
+                    p = plans[b]
+                    gather(x, p["img"], n0, b)
+                    if unet.lowres_cond:
+                        gather(lowres, p["lowres"], n0, b)
+                    if exists(cond):
+                        p["cond"].copy_(cond[n0:n0 + b])
+                    if unet.self_cond and k > 0:   # the carry is the FUSED estimate of step k - 1 (step 0 starts from zeros)
+                        gather(x0bar, p["self_cond"], n0, b)
+                        E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
+                    E.check(lib.kd_solver_sample_steps(p["h"], C.byref(sc), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1,
+                                                       stream()))
+                    E.check(lib.kd_sample_last(p["h"], 1, E.ptr(store[n0:n0 + b]), stream()))
+                    if dynamic_threshold:
+                        E.check(lib.kd_sample_last(p["h"], 2, E.ptr(thr[n0:n0 + b]), stream()))
+                A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
+                z = f32(noise_fn(("step", stage, k, 0), shape)) if Sn != 0.0 and exists(noise_fn) else None
+                # (z: memory of torch's current stream, handed on only behind this launch)
+                E.check(lib.kd_tiles_fuse_update(E.ptr(x), E.ptr(x0bar), E.ptr(store), E.ptr(thr), C.c_void_p(tile_of.data_ptr()),
+                                                 N, Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z),
+                                                 stage_seed, (1 << 32) | k, stream()))
+            covered = torch.zeros(Hc, Wc, dtype=torch.bool)
+            for y0, x0 in origins:
+                covered[y0:y0 + S, x0:x0 + S] = True
+            out = (x.clamp(-1.0, 1.0) + 1) * 0.5
+            out = torch.where(covered.to(device), out, torch.zeros_like(out))
+        return out
+
     def _num_steps(self):
         """Schedule steps of every UNet's sampler: what skip_steps is checked against."""
         return [s.num_timesteps for s in self.noise_schedulers]
@@ -1560,6 +1877,10 @@ class ElucidatedImagen(Imagen):
         """x = sigma_0 * N(0,1) (+ the init image): the first sigma of the full schedule, whatever skip_steps is; a python
         float of the fp32 value, so the kernel's product is the library's fp32 tensor product."""
         return float(self.step_tables(stage)["init_sigma"])
+
+    def sample_tiled(self, *args, **kwargs):
+        raise NotImplementedError("ElucidatedImagen.sample_tiled: fused-tile canvas sampling runs the DDPM-trained samplers of "
+                                  "Imagen (ancestral, DDIM, DPM-Solver++(2M)); the EDM Heun sampler has no canvas step")
 
     def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
                     self_cond=False, solver=None):
