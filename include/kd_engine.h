@@ -57,7 +57,8 @@ const char* kd_last_error(void);
  *      (`init_cross_embed`, `init_conv_kernel_size`, `init_cross_embed_kernel_sizes`, `final_conv_kernel_size`,
  *      `final_resnet_block`, `scale_skip_connection`) - kd_unet_create_ext3 is that call with ext4 = NULL - and
  *      kd_final_conv_k_nchw, kd_init_conv_plain_nchw added; kd_tiles_gather and kd_tiles_fuse_update added (fused-tile
- *      canvas sampling) */
+ *      canvas sampling); kd_tiles_cond_gather, kd_tiles_gather_lowres and kd_tiles_finalize added (a fused-tile stage at the
+ *      sizes of a magnification level) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -842,6 +843,38 @@ int kd_tiles_gather(const float* d_canvas, float* d_tiles, int B, int C, int Hc,
 int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, const float* d_thr, const int* d_tile_of, int N,
                          int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn,
                          const float* d_noise, uint64_t seed, uint64_t stream_id, void* stream);
+
+/* A stage at the sizes of a magnification level (the mag-2 canvas is 3 x 40960 x 40960): three memory-bound kernels that
+ * stream what would otherwise be materialised per tile or per canvas.  The Python package: Imagen.sample_tiled(streamed=,
+ * cond_crops=, into=), ultra_res.tiled.fused_level. */
+/* The conditioning tiles of a chunk straight from the level above: d_src [Cs,W,W] -> d_tiles [B,Cs,S,S], or [B,2 Cs,S,S]
+ * when d_centre_of is given.  Per axis, for output coordinate p of a tile with shift sh (`shifts_yx`: a HOST array [B][2]
+ * of (sy, sx), read before the call returns): w = map[p] is a coordinate of the window that starts at `top`, g = top + w;
+ * the coordinate is filled when sh > 0 ? g < sh : g >= (W + sh) % W (sh == 0 fills everything: the reference's `[shift:]`
+ * slice), else it reads source index (g - sh) mod W.  A pixel is `fill` if either axis is filled, else d_src[c, ry, rx].
+ * Channels c < Cs go through d_win_of [S], channels Cs + c (the `v2` centre crop) through d_centre_of [S]; both maps are
+ * DEVICE arrays (imagen_pytorch.cond_crop_maps builds them) with entries in [0, W - top) - an entry outside is clamped
+ * into that range, so nothing is read outside d_src.  Data movement only: bit-equal to
+ * resize_image_to(cond_images_for_grid(...), S) where W >= window.  Needs S % 4 == 0, |sh| < W, 0 <= top < W and a 16-byte
+ * aligned d_tiles (refused with an error, nothing launched, otherwise). */
+int kd_tiles_cond_gather(const float* d_src, int Cs, int W, float* d_tiles, int B, int S, const int* shifts_yx, int top,
+                         const int* d_win_of, const int* d_centre_of, float fill, void* stream);
+/* The low-res conditioning tiles of a chunk straight from the previous stage's canvas d_prev [C,Hp,Wp]:
+ *     d_tiles[b,c,y,x] = a (2 d_prev[c,iy,ix] - 1) + s z[(c Hc + y0_b + y) Wc + x0_b + x]
+ * iy = min((int)floorf((float)(y0_b + y) * ((float)Hp / (float)Hc)), Hp - 1), ix likewise (kd_sample_start's rule, torch's
+ * nearest); op order 2 v, - 1, a *, s z, the sum.  z is read from d_noise [C,Hc,Wc] or, when it is NULL, is the element
+ * of Philox stream `stream_id` under `seed` - the bits of kd_philox_normal over C Hc Wc elements: overlapping tiles see
+ * one conditioning on shared pixels and no canvas-sized buffer exists.  s == 0 leaves the term out, operand unread.
+ * `origins_yx` and the preconditions are kd_tiles_gather's. */
+int kd_tiles_gather_lowres(const float* d_prev, int Hp, int Wp, float* d_tiles, int B, int C, int Hc, int Wc, int S,
+                           const int* origins_yx, float a, float s, const float* d_noise, uint64_t seed, uint64_t stream_id,
+                           void* stream);
+/* The end of a stage: for every pixel of the canvas d_x [C,Hc,Wc] covered by a present tile (kd_tiles_fuse_update's cover
+ * test over d_tile_of [ny][nx]), d_out[c, oy + y, ox + x] = (clamp(x, -1, 1) + 1) * 0.5; every other element of d_out
+ * [C,Ho,Wo] is left untouched.  Needs the lattice preconditions of kd_tiles_fuse_update, ox % 4 == 0, Wo % 4 == 0, the
+ * canvas inside d_out and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
+int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
+                      int Wo, int oy, int ox, void* stream);
 
 #ifdef __cplusplus
 }

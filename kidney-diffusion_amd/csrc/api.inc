@@ -1206,5 +1206,19 @@ int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, co
   return launch_tiles_fuse_update(d_x, d_x0bar, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P, Sn, d_noise,
                                   seed, stream_id, (hipStream_t)stream);
 }
+int kd_tiles_cond_gather(const float* d_src, int Cs, int W, float* d_tiles, int B, int S, const int* shifts_yx, int top,
+                         const int* d_win_of, const int* d_centre_of, float fill, void* stream) {
+  return launch_tiles_cond_gather(d_src, Cs, W, d_tiles, B, S, shifts_yx, top, d_win_of, d_centre_of, fill, (hipStream_t)stream);
+}
+int kd_tiles_gather_lowres(const float* d_prev, int Hp, int Wp, float* d_tiles, int B, int C, int Hc, int Wc, int S,
+                           const int* origins_yx, float a, float s, const float* d_noise, uint64_t seed, uint64_t stream_id,
+                           void* stream) {
+  return launch_tiles_gather_lowres(d_prev, Hp, Wp, d_tiles, B, C, Hc, Wc, S, origins_yx, a, s, d_noise, seed, stream_id,
+                                    (hipStream_t)stream);
+}
+int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
+                      int Wo, int oy, int ox, void* stream) {
+  return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -456,5 +456,15 @@ int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc,
 int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, const float* thr, const int* tile_of, int N, int C,
                              int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn, const float* noise,
                              uint64_t seed, uint64_t stream_id, hipStream_t s);
+// a stage at the sizes of a magnification level: conditioning tiles [B, Cs | 2 Cs, S, S] out of the level above src [Cs, W, W]
+// (shifts_yx a host array [B][2], the maps [S] in device memory); low-res conditioning tiles a (2 nearest(prev) - 1) + s z
+// out of the previous canvas [C, Hp, Wp]; and (clamp(x, -1, 1) + 1) / 2 of the covered pixels into out [C, Ho, Wo] at (oy, ox)
+int launch_tiles_cond_gather(const float* src, int Cs, int W, float* tiles, int B, int S, const int* shifts_yx, int top,
+                             const int* win_of, const int* centre_of, float fill, hipStream_t s);
+int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, int B, int C, int Hc, int Wc, int S,
+                               const int* origins_yx, float a, float s, const float* noise, uint64_t seed, uint64_t stream_id,
+                               hipStream_t st);
+int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
+                          int Wo, int oy, int ox, hipStream_t s);
 
 }  // namespace kd

@@ -1,7 +1,10 @@
 // Fused-tile canvas sampling (MultiDiffusion / Mixture of Diffusers): the canvas of a stage is ONE noisy image
 // [C, Hc, Wc]; at every schedule step every tile of an ny x nx lattice (tile size S, stride st, Hc = (ny - 1) st + S) is
 // denoised by itself, the thresholded x0 estimates are averaged where tiles overlap and the solver update runs once, on the
-// canvas.  Two kernels, both bound by memory: the gather canvas -> tiles, and the whole canvas step in one pass.
+// canvas.  Two kernels, both bound by memory: the gather canvas -> tiles, and the whole canvas step in one pass.  Three
+// more make a stage stream at the sizes of a magnification level (canvas 40960^2): the conditioning tiles of a chunk cut
+// straight out of the level above, the low-res conditioning tiles cut straight out of the previous stage's canvas, and
+// the end of a stage written in place into a larger canvas - none of them leaves a canvas-sized temporary.
 //
 // S, st and hence every tile origin and Wc are multiples of 4: a float4 of a canvas row never straddles a tile edge, so
 // every access below is one 16-byte load or store.
@@ -155,6 +158,212 @@ int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, cons
   const int64_t rows = (int64_t)C * Hc;
   hipLaunchKernelGGL(tiles_fuse_update_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
                      dim3(256), 0, s, x, x0bar, x0_tiles, thr, tile_of, g, A, B, P, Sn, noise, seed, sid);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- conditioning tiles from the level above
+// The conditioning image of a tile is a window of the level above, `src` [Cs, W, W]: the image rolled by the tile's shift
+// (sy, sx), filled where the roll wraps, cropped to the window at `top` and resized to S (ultra_res.grid
+// .cond_images_for_grid, then resize_image_to).  Per axis, output coordinate p of a tile with shift sh:
+//   w = map[p] (window coordinate), g = top + w;  filled = sh > 0 ? g < sh : g >= (W + sh) % W   (sh == 0: everything)
+//   source index (g - sh) mod W
+// Channels c < Cs read through `win_of`; channels Cs + c (the v2 centre crop, `centre_of` != nullptr) through `centre_of`.
+// Data movement only.  The source x wraps and is unaligned: scalar loads, one 16-byte store.  A block row is one output
+// row: filled_y is uniform over the block and a filled row stores `fill` without loading.  The maps live in device
+// memory, where the host cannot check them: a map entry is clamped into [0, W - top - 1], so no entry reads outside src.
+__global__ __launch_bounds__(256) void tiles_cond_gather_kernel(const float* __restrict__ src, int Cs, int W,
+                                                                float* __restrict__ tiles, int S, int Ct, TileOrigins sh, int top,
+                                                                const int* __restrict__ win_of,
+                                                                const int* __restrict__ centre_of, float fill) {
+  const int S4 = S / 4;
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  if (xq >= S4) return;
+  const int b = blockIdx.z;
+  const int sy = sh.y0[b], sx = sh.x0[b];
+  const int wmax = W - top - 1;
+  const int edge_x = sx > 0 ? sx : (W + sx) % W, edge_y = sy > 0 ? sy : (W + sy) % W;
+  // the four source columns of this thread under either map
+  int rx[2][4];
+  bool fx[2][4];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const int* map = m ? centre_of : win_of;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int g = top + (map ? min(max(map[4 * xq + e], 0), wmax) : 0);
+      fx[m][e] = sx > 0 ? g < edge_x : g >= edge_x;
+      int r = g - sx;
+      r = r < 0 ? r + W : (r >= W ? r - W : r);
+      rx[m][e] = r;
+    }
+  }
+  const int rows = Ct * S;
+  float* dst = tiles + (int64_t)b * rows * S;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int c = row / S, y = row - c * S;
+    const int m = c >= Cs ? 1 : 0;
+    const int g = top + min(max((m ? centre_of : win_of)[y], 0), wmax);
+    const bool fy = sy > 0 ? g < edge_y : g >= edge_y;
+    f32x4 o = {fill, fill, fill, fill};
+    if (!fy) {
+      int ry = g - sy;
+      ry = ry < 0 ? ry + W : (ry >= W ? ry - W : ry);
+      const float* line = src + ((int64_t)(c - m * Cs) * W + ry) * W;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (!fx[m][e]) o[e] = line[rx[m][e]];
+    }
+    *(f32x4*)(dst + (int64_t)row * S + 4 * xq) = o;
+  }
+}
+int launch_tiles_cond_gather(const float* src, int Cs, int W, float* tiles, int B, int S, const int* shifts_yx, int top,
+                             const int* win_of, const int* centre_of, float fill, hipStream_t s) {
+  KD_REQUIRE(src && tiles && shifts_yx && win_of, "tiles cond gather: null argument");
+  KD_REQUIRE(B >= 1 && Cs >= 1 && Cs <= 512 && S >= 4 && S % 4 == 0 && S <= (1 << 20),
+             "tiles cond gather: needs B, Cs >= 1 and a tile size S % 4 == 0");
+  KD_REQUIRE(W >= 1 && W <= (1 << 20) && top >= 0 && top < W, "tiles cond gather: source width or window offset out of range");
+  const int Ct = centre_of ? 2 * Cs : Cs;
+  KD_REQUIRE((int64_t)Ct * S * S < (1ll << 31), "tiles cond gather: a tile must hold fewer than 2^31 elements");
+  KD_REQUIRE(((uintptr_t)tiles & 15) == 0, "tiles cond gather: tiles must be 16-byte aligned");
+  for (int b = 0; b < B; ++b) {
+    const int sy = shifts_yx[2 * b], sx = shifts_yx[2 * b + 1];
+    KD_REQUIRE(sy > -W && sy < W && sx > -W && sx < W, "tiles cond gather: a shift must lie inside (-W, W)");
+  }
+  const int S4 = S / 4, rows = Ct * S;
+  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
+    const int nb = std::min(B - b0, (int)TILE_CHUNK);
+    TileOrigins sh{};
+    for (int b = 0; b < nb; ++b) {
+      sh.y0[b] = shifts_yx[2 * (b0 + b)];
+      sh.x0[b] = shifts_yx[2 * (b0 + b) + 1];
+    }
+    hipLaunchKernelGGL(tiles_cond_gather_kernel, dim3((unsigned)((S4 + 255) / 256), (unsigned)std::min(rows, 8192), (unsigned)nb),
+                       dim3(256), 0, s, src, Cs, W, tiles + (int64_t)b0 * rows * S, S, Ct, sh, top, win_of, centre_of, fill);
+  }
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- low-res conditioning tiles from the previous canvas
+// tiles[b, c, y, x] = a (2 prev[c, iy, ix] - 1) + s z[(c Hc + y0 + y) Wc + x0 + x]: the previous stage's canvas resized
+// (nearest, the rule of sample_start_kernel: min((int)floorf(dst * ((float)in / (float)out)), in - 1), the ratios divided
+// in fp32 by the host) to this stage's canvas [C, Hc, Wc], normalised and augmented - cut per tile without the canvas
+// ever existing.  z is a property of the canvas element (read from `noise`, or the element of Philox stream `sid` under
+// `seed`: x0 and Wc are multiples of 4, so a thread's four x are one float4 of the stream), so overlapping tiles see one
+// conditioning on shared pixels.  Op order: 2 v, - 1, a *, s z, the sum; s == 0 leaves the term out, operand unread.
+__global__ __launch_bounds__(256) void tiles_gather_lowres_kernel(const float* __restrict__ prev, int Hp, int Wp, float ry,
+                                                                  float rx, float* __restrict__ tiles, int C, int Hc, int Wc,
+                                                                  int S, TileOrigins org, float a, float s,
+                                                                  const float* __restrict__ noise, uint64_t seed, uint64_t sid) {
+  const int b = blockIdx.y;
+  const int S4 = S / 4;
+  const int per4 = C * S * S4;   // (< 2^31: checked by the host)
+  const int y0 = org.y0[b], x0 = org.x0[b];
+  float* dst = tiles + (int64_t)b * per4 * 4;
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < per4; j += gridDim.x * 256) {
+    const int row = j / S4, xq = j - row * S4;   // row = c * S + y
+    const int c = row / S, y = row - c * S;
+    const int iy = min((int)floorf((float)(y0 + y) * ry), Hp - 1);
+    const float* line = prev + ((int64_t)c * Hp + iy) * Wp;
+    const int64_t at = ((int64_t)c * Hc + y0 + y) * Wc + x0 + 4 * xq;   // canvas element of the float4's first x
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int ix = min((int)floorf((float)(x0 + 4 * xq + e) * rx), Wp - 1);
+      float t = 2.0f * line[ix];
+      t = t - 1.0f;
+      o[e] = a * t;
+    }
+    if (s != 0.0f) {
+      const f32x4 z = noise ? *(const f32x4*)(noise + at) : philox_normal4(seed, sid, (uint64_t)(at / 4));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = o[e] + s * z[e];
+    }
+    *(f32x4*)(dst + (int64_t)j * 4) = o;
+  }
+}
+int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, int B, int C, int Hc, int Wc, int S,
+                               const int* origins_yx, float a, float s, const float* noise, uint64_t seed, uint64_t sid,
+                               hipStream_t st) {
+  KD_REQUIRE(prev && tiles && origins_yx, "tiles gather lowres: null argument");
+  KD_REQUIRE(B >= 1 && C >= 1 && C <= 1024 && S >= 4 && S % 4 == 0, "tiles gather lowres: needs B, C >= 1 and a tile size S % 4 == 0");
+  KD_REQUIRE(Hc >= S && Wc >= S && Wc % 4 == 0 && Hc <= (1 << 20) && Wc <= (1 << 20),
+             "tiles gather lowres: canvas smaller than a tile, or Wc % 4 != 0");
+  KD_REQUIRE(Hp >= 1 && Wp >= 1 && Hp <= (1 << 20) && Wp <= (1 << 20), "tiles gather lowres: previous canvas out of range");
+  KD_REQUIRE((int64_t)C * S * S < (1ll << 31), "tiles gather lowres: a tile must hold fewer than 2^31 elements");
+  KD_REQUIRE((((uintptr_t)tiles | (uintptr_t)noise) & 15) == 0, "tiles gather lowres: tiles and noise must be 16-byte aligned");
+  for (int b = 0; b < B; ++b) {
+    const int y0 = origins_yx[2 * b], x0 = origins_yx[2 * b + 1];
+    KD_REQUIRE(y0 >= 0 && y0 + S <= Hc && x0 >= 0 && x0 + S <= Wc && x0 % 4 == 0,
+               "tiles gather lowres: a tile origin lies outside the canvas or its x0 is no multiple of 4");
+  }
+  const float ry = (float)Hp / (float)Hc, rx = (float)Wp / (float)Wc;
+  const int per4 = C * S * (S / 4);
+  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
+    const int nb = std::min(B - b0, (int)TILE_CHUNK);
+    TileOrigins org{};
+    for (int b = 0; b < nb; ++b) {
+      org.y0[b] = origins_yx[2 * (b0 + b)];
+      org.x0[b] = origins_yx[2 * (b0 + b) + 1];
+    }
+    const int gx = std::max(1, std::min((per4 + 255) / 256, 8192 / nb));
+    hipLaunchKernelGGL(tiles_gather_lowres_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, st, prev, Hp, Wp, ry, rx,
+                       tiles + (int64_t)b0 * per4 * 4, C, Hc, Wc, S, org, a, s, noise, seed, sid);
+  }
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- the end of a stage
+// out[c, oy + y, ox + x] = (clamp(x[c, y, x], -1, 1) + 1) * 0.5 for every canvas pixel that a present tile covers (the
+// cover test of tiles_fuse_update_kernel); every other element of out [C, Ho, Wo] keeps its bits.  One pass, no mask.
+__global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
+                                                             TileGeom g, float* __restrict__ out, int Ho, int Wo, int oy, int ox) {
+  const int W4 = g.Wc / 4;
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  if (xq >= W4) return;
+  const int xx = 4 * xq;
+  const int q_hi = min(xx / g.st, g.nx - 1), q_lo = xx < g.S ? 0 : (xx - g.S) / g.st + 1;
+  const int rows = g.C * g.Hc;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int c = row / g.Hc, y = row - c * g.Hc;
+    const int r_hi = min(y / g.st, g.ny - 1), r_lo = y < g.S ? 0 : (y - g.S) / g.st + 1;
+    bool covered = false;
+    for (int r = r_lo; r <= r_hi; ++r)
+      for (int q = q_lo; q <= q_hi; ++q) {
+        const int t = tile_of[r * g.nx + q];
+        covered = covered || (t >= 0 && t < g.N);
+      }
+    if (!covered) continue;
+    const f32x4 v = *(const f32x4*)(x + ((int64_t)row * W4 + xq) * 4);
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float cl = v[e] < -1.0f ? -1.0f : (v[e] > 1.0f ? 1.0f : v[e]);
+      o[e] = (cl + 1.0f) * 0.5f;
+    }
+    *(f32x4*)(out + ((int64_t)c * Ho + oy + y) * Wo + ox + xx) = o;
+  }
+}
+int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
+                          int Wo, int oy, int ox, hipStream_t s) {
+  KD_REQUIRE(x && tile_of && out, "tiles finalize: null argument");
+  KD_REQUIRE(N >= 1 && C >= 1 && C <= 1024 && ny >= 1 && nx >= 1 && N <= (int64_t)ny * nx, "tiles finalize: needs 1 <= N <= ny nx tiles and C >= 1");
+  KD_REQUIRE(S >= 4 && S % 4 == 0 && st >= 4 && st % 4 == 0 && st <= S, "tiles finalize: needs S % 4 == 0, st % 4 == 0 and 4 <= st <= S");
+  KD_REQUIRE(S <= TILE_COVER * st, "tiles finalize: more than 3 tiles per axis cover a pixel (S > 3 st)");
+  const int64_t Hc = (int64_t)(ny - 1) * st + S, Wc = (int64_t)(nx - 1) * st + S;
+  KD_REQUIRE(Hc <= (1 << 20) && Wc <= (1 << 20) && (int64_t)C * Hc < (1ll << 31) && (int64_t)ny * nx < (1ll << 31),
+             "tiles finalize: canvas out of range");
+  KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
+             "tiles finalize: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
+  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo, "tiles finalize: the canvas at (oy, ox) lies outside the output");
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize: x and out must be 16-byte aligned");
+  TileGeom g{C, S, st, ny, nx, (int)Hc, (int)Wc, 0, std::max(S - st, 1), N};
+  const int W4 = (int)Wc / 4;
+  const int64_t rows = (int64_t)C * Hc;
+  hipLaunchKernelGGL(tiles_finalize_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
+                     dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -259,6 +259,12 @@ SIGNATURES = {
     "kd_tiles_gather": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int), C.c_void_p]),
     "kd_tiles_fuse_update": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_void_p, C.c_uint64, C.c_uint64,
                                                                                           C.c_void_p]),
+    "kd_tiles_cond_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "kd_tiles_gather_lowres": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int), C.c_float,
+                                                                                                      C.c_float, C.c_void_p, C.c_uint64,
+                                                                                                      C.c_uint64, C.c_void_p]),
+    "kd_tiles_finalize": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
 }
 
 

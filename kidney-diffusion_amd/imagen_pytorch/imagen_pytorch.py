@@ -1150,6 +1150,73 @@ def resize_image_to(image, target_image_size, mode="nearest"):
     return F.interpolate(image, target_image_size, mode=mode)
 
 
+def cond_crop_maps(window, S, centre_width=None):
+    """The index maps of kd_tiles_cond_gather for a conditioning window of ``window`` pixels seen at tile size ``S``:
+    ``win_of`` int32 [S], the window coordinate that output coordinate p shows, and ``centre_of`` int32 [S] (None without
+    ``centre_width``), the same for the `v2` centre channels.  An index ramp is pushed through the very functions the
+    materialised path uses - ``resize_image_to`` for the window, ``ultra_res.grid.center_crop``, ``F.interpolate(...,
+    "nearest")`` to the window and ``resize_image_to`` for the centre crop - so the maps are torch's own rounding, whatever
+    it is, and one map serves both axes (every step is separable and square).  Needs no GPU."""
+    from ultra_res import grid as G
+
+    window, S = int(window), int(S)
+    if window < 1 or S < 1 or window >= 2 ** 24:
+        raise ValueError(f"cond_crop_maps: window={window} and S={S} must be positive (window below 2^24: the ramp is fp32)")
+    ramp = torch.arange(window, dtype=torch.float32).expand(1, 1, window, window)
+    read = lambda img: img[0, 0, 0].to(torch.int32).contiguous()
+    win_of = read(resize_image_to(ramp, S))
+    centre_of = None
+    if centre_width is not None:
+        if not 1 <= int(centre_width) <= window:
+            raise ValueError(f"cond_crop_maps: centre_width={centre_width} must lie in 1 .. window={window}")
+        centre = G.center_crop(ramp[0], int(centre_width))
+        centre = F.interpolate(centre.unsqueeze(0), window, mode="nearest")
+        centre_of = read(resize_image_to(centre, S))
+    return win_of, centre_of
+
+
+class TileCondCrops:
+    """``sample_tiled(cond_crops=...)``: the conditioning images of a canvas' tiles as windows of ONE image of the level
+    above, never materialised - what ``ultra_res.grid.cond_images_for_grid`` builds, described instead of built.
+    ``image`` [1, Cs, W, W] (fp32 in [0, 1], or uint8); ``shifts`` [N][2], the roll (sy, sx) of each present tile in
+    row-major order; ``window``: width of the centre window that is cut after the roll (it starts at
+    ``center_crop_offset(W, window)``); ``fill``: the value of the pixels the roll wraps; ``centre_width``: when given,
+    the centre crop of that width, enlarged (nearest) to the window, follows as Cs more channels (`v2`)."""
+
+    def __init__(self, image, shifts, window, fill, centre_width=None):
+        self.image, self.window, self.fill, self.centre_width = image, window, fill, centre_width
+        self.shifts = shifts.tolist() if torch.is_tensor(shifts) else shifts
+
+    def checked(self, n_tiles):
+        """(Cs, W, channels of a tile, top, shifts as a list of int pairs); ValueError by name for what the kernel cannot
+        take.  Needs no GPU."""
+        import numbers
+
+        from ultra_res import grid as G
+
+        isint = lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        img = self.image
+        if not torch.is_tensor(img) or img.dim() != 4 or img.shape[0] != 1 or img.shape[2] != img.shape[3]:
+            raise ValueError(f"cond_crops.image must be one square image [1, Cs, W, W], got "
+                             f"{tuple(img.shape) if torch.is_tensor(img) else type(img).__name__}")
+        Cs, W = int(img.shape[1]), int(img.shape[3])
+        if not isint(self.window) or self.window < 1:
+            raise ValueError(f"cond_crops.window must be an int >= 1, got {self.window!r}")
+        if W < self.window:
+            raise ValueError(f"cond_crops: the image is W={W} wide, narrower than window={self.window}: that branch of "
+                             "cond_images_for_grid (roll, fill, zero padding) stays on the materialised path (cond_images=)")
+        shifts = self.shifts
+        if (not isinstance(shifts, (list, tuple)) or len(shifts) != n_tiles
+                or any(not isinstance(s, (list, tuple)) or len(s) != 2 or not all(isint(v) for v in s) for s in shifts)):
+            raise ValueError(f"cond_crops.shifts must be [tiles {n_tiles}][2] ints (sy, sx), one pair per present tile")
+        shifts = [(int(sy), int(sx)) for sy, sx in shifts]
+        if any(abs(v) >= W for s in shifts for v in s):
+            raise ValueError(f"cond_crops.shifts must lie inside (-W, W) = (-{W}, {W})")
+        if self.centre_width is not None and (not isint(self.centre_width) or not 1 <= self.centre_width <= self.window):
+            raise ValueError(f"cond_crops.centre_width={self.centre_width!r} must be an int in 1 .. window={self.window}")
+        return Cs, W, Cs * (2 if self.centre_width is not None else 1), G.center_crop_offset(W, int(self.window)), shifts
+
+
 STAGE_SEED_STRIDE = 0x9E3779B97F4A7C15   # stage s of a cascade draws under (seed + STAGE_SEED_STRIDE * s) mod 2^64
 
 
@@ -1521,7 +1588,8 @@ class Imagen(nn.Module):
                      seed: Optional[int] = None, noise_fn: Optional[Callable] = None, use_graph: bool = True,
                      start_at_unet_number=1, stop_at_unet_number=None, start_image_or_video=None,
                      return_all_unet_outputs=False, lowres_sample_noise_level=None, device=None, inpaint_images=None,
-                     inpaint_masks=None, inpaint_resample_times=None, init_images=None, skip_steps=None):
+                     inpaint_masks=None, inpaint_resample_times=None, init_images=None, skip_steps=None, streamed=False,
+                     cond_crops=None, into=None):
         """A canvas of overlapping tiles denoised jointly (MultiDiffusion / Mixture of Diffusers; an engine extension, the
         alternative to sequential outpainting).  The canvas of a stage is ONE noisy image over the ``grid = (ny, nx)``
         lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
@@ -1537,7 +1605,17 @@ class Imagen(nn.Module):
         ``("step", stage, k, 0)`` only for the steps whose update adds noise.  The low-res conditioning of a stage is the
         previous canvas resized to this stage's canvas and augmented ONCE, so overlapping tiles see the same conditioning on
         shared pixels; ``start_image_or_video`` is a canvas.  Returns the canvas [1, C, Hc, Wc] in [0, 1] (a list of the
-        stages' canvases with ``return_all_unet_outputs``); pixels that no tile covers are 0."""
+        stages' canvases with ``return_all_unet_outputs``); pixels that no tile covers are 0.
+
+        Three arguments carry a stage to the sizes of a magnification level (a 40960 x 40960 canvas of 1024-pixel tiles);
+        a call without them keeps its code path and its bits.  ``streamed=True``: the low-res conditioning tiles are cut
+        straight out of the previous canvas (kd_tiles_gather_lowres: no resized, augmented canvas is built) and the stage
+        ends in one pass into a zero canvas (kd_tiles_finalize: no host mask, no temporaries) - bit-equal to
+        ``streamed=False``.  ``cond_crops``: a ``TileCondCrops`` in the place of ``cond_images`` - the tiles'
+        conditioning images are windows of one image, cut per chunk by kd_tiles_cond_gather, bit-equal to
+        ``cond_images=cond_images_for_grid(...)``.  ``into=(canvas, oy, ox)`` (needs ``streamed``): the last sampled stage
+        writes its covered pixels into ``canvas`` [1, C, Ho, Wo] (fp32, contiguous, on the device) at row ``oy``, column
+        ``ox`` (multiples of 4) in place, leaves every other pixel of it alone and returns it."""
         for name, v in dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
                             inpaint_resample_times=inpaint_resample_times).items():
             if exists(v):
@@ -1563,6 +1641,37 @@ class Imagen(nn.Module):
             raise ValueError(f"text_embeds must hold one row [1, L, D] for the whole canvas, got {tuple(text_embeds.shape)}")
         if not 1 <= start_at_unet_number <= n:
             raise ValueError(f"start_at_unet_number={start_at_unet_number} is outside 1 .. {n}")
+        last = stop_at_unet_number if exists(stop_at_unet_number) and start_at_unet_number <= stop_at_unet_number <= n else n
+        crops = None
+        if exists(cond_crops):
+            if exists(cond_images):
+                raise ValueError("sample_tiled takes cond_images or cond_crops, one of them: cond_crops describes the same "
+                                 "images as windows of one image")
+            if not isinstance(cond_crops, TileCondCrops):
+                raise ValueError(f"cond_crops must be a TileCondCrops, got {type(cond_crops).__name__}")
+            crops = (cond_crops,) + cond_crops.checked(n_tiles)
+        if exists(into):
+            if not streamed:
+                raise ValueError("sample_tiled(into=...) needs streamed=True: only kd_tiles_finalize writes a stage in place")
+            if not isinstance(into, (tuple, list)) or len(into) != 3 or not torch.is_tensor(into[0]):
+                raise ValueError("into must be (canvas [1, C, Ho, Wo], oy, ox)")
+            dst, oy, ox = into
+            g = tiling[last - 1]
+            if dst.dtype != torch.float32:
+                raise ValueError(f"into: the canvas must be float32, got {dst.dtype}")
+            if dst.dim() != 4 or dst.shape[0] != 1 or dst.shape[1] != self.channels or not dst.is_contiguous():
+                raise ValueError(f"into: the canvas must be a contiguous [1, {self.channels}, Ho, Wo], got shape {tuple(dst.shape)}")
+            if any(not isinstance(v, numbers.Integral) or isinstance(v, bool) for v in (oy, ox)):
+                raise ValueError(f"into: the offset (oy, ox) must be two ints, got ({oy!r}, {ox!r})")
+            if oy % 4 != 0 or ox % 4 != 0 or dst.shape[3] % 4 != 0:
+                raise ValueError(f"into: the offset (oy, ox) = ({oy}, {ox}) and the canvas width {dst.shape[3]} must be multiples "
+                                 "of 4 (the kernels move 16 bytes)")
+            if oy < 0 or ox < 0 or oy + g["Hc"] > dst.shape[2] or ox + g["Wc"] > dst.shape[3]:
+                raise ValueError(f"into: the {g['Hc']} x {g['Wc']} canvas of unet {last} at ({oy}, {ox}) is out of bounds of the "
+                                 f"{dst.shape[2]} x {dst.shape[3]} canvas")
+            if not dst.is_cuda:
+                raise ValueError(f"into: the canvas must live on the device, got {dst.device}")
+            into = (dst, int(oy), int(ox))
         E.require_gpu()
         device = torch.device(default(device, self.device))
         if device.type != "cuda":
@@ -1599,7 +1708,8 @@ class Imagen(nn.Module):
                 sched = sched.with_timesteps(steps)
             canvas = self._tiled_stage(unet, num, geo, sched, obj, dyn, device, canvas, cond_images, lowres_level, noise_fn,
                                        int(seed), use_graph, int(tile_batch), text_embeds=text_embeds, text_masks=text_masks,
-                                       cond_scale=float(cs), solver=(solver, eta))
+                                       cond_scale=float(cs), solver=(solver, eta), streamed=bool(streamed), crops=crops,
+                                       into=into if num == last else None)
             outputs.append(canvas)
             if exists(stop_at_unet_number) and stop_at_unet_number == num:
                 break
@@ -1607,12 +1717,15 @@ class Imagen(nn.Module):
 
     def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
                      lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
-                     solver=("ddpm", 0.0)):
+                     solver=("ddpm", 0.0), streamed=False, crops=None, into=None):
         """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  Per schedule step k and chunk of at
         most `tile_batch` tiles: gather the chunk out of the canvas into the plan's stable buffers, one iteration
         kd_solver_sample_steps(k, k + 1) with DDIM(0) coefficients (first order: no history, no draw; its tile-level
         update is discarded), the x0 estimates and thresholds into the tile store; then ONE kd_tiles_fuse_update with the
-        canvas sampler's coefficients of step k.  A ragged last chunk runs the plan of its own batch size."""
+        canvas sampler's coefficients of step k.  A ragged last chunk runs the plan of its own batch size.
+        `streamed`: the chunk's low-res tiles come from the previous canvas (kd_tiles_gather_lowres) and the stage ends
+        with kd_tiles_finalize, into `into = (canvas, oy, ox)` or a zero canvas; `crops`: (TileCondCrops, Cs, W, tile
+        channels, top, shifts) - the chunk's conditioning tiles come from its image (kd_tiles_cond_gather)."""
         lib = E.load()
         Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
         origins = geo["origins"]
@@ -1646,21 +1759,46 @@ class Imagen(nn.Module):
             store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
             thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
             tile_of = torch.tensor(geo["tile_of"], dtype=torch.int32).to(device).contiguous()
-            lowres = ls = None
+            lowres = ls = lowres_z = None
             if unet.lowres_cond:
                 ls = self.lowres_noise_schedule.log_snr(torch.full((1,), lowres_level, dtype=torch.float32))
                 a, s = log_snr_to_alpha_sigma(ls)
-                lowres = F.interpolate(prev_canvas, (Hc, Wc), mode="nearest") * 2 - 1
-                lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), (16 << 32) | 1)).contiguous()
-            cond = None
+                if streamed:   # no canvas is built: every chunk is cut out of prev_canvas (injected noise stays a canvas)
+                    prev_canvas = f32(prev_canvas)
+                    assert prev_canvas.dim() == 4 and tuple(prev_canvas.shape[:2]) == (1, Cn), "the previous canvas must be [1, C, H, W]"
+                    lowres_z = f32(noise_fn(("lowres", stage), shape)) if exists(noise_fn) else None
+                else:
+                    lowres = F.interpolate(prev_canvas, (Hc, Wc), mode="nearest") * 2 - 1
+                    lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), (16 << 32) | 1)).contiguous()
+            cond = cond_shape = None
             if exists(cond_images):
                 assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
                 cond = f32(resize_image_to(f32(cond_images), S))
+                cond_shape = tuple(cond.shape[1:])
+            elif exists(crops):
+                cc, Cs, W, Ct, top, shifts = crops
+                assert Ct == unet.cond_images_channels, "invalid number of channels in conditioning image"
+                src = cc.image
+                src = f32(src.float() / 255.0 if src.dtype == torch.uint8 else src)   # moved once; stays for the stage
+                win_of, centre_of = (None if m is None else m.to(device) for m in cond_crop_maps(cc.window, S, cc.centre_width))
+                cond_shape = (Ct, S, S)
             with_text = exists(text_embeds) and unet.cond_on_text
 
             def gather(src, dst, n0, b):   # dst [b, C, S, S] <- tiles n0 .. n0 + b - 1 of the canvas-shaped src
                 yx = (C.c_int * (2 * b))(*[v for o in origins[n0:n0 + b] for v in o])
                 E.check(lib.kd_tiles_gather(E.ptr(src), E.ptr(dst), b, Cn, Hc, Wc, S, yx, stream()))
+
+            def gather_lowres(dst, n0, b):   # dst [b, C, S, S] <- a (2 nearest(prev_canvas) - 1) + s z over tiles n0 ..
+                yx = (C.c_int * (2 * b))(*[v for o in origins[n0:n0 + b] for v in o])
+                E.check(lib.kd_tiles_gather_lowres(E.ptr(prev_canvas), prev_canvas.shape[2], prev_canvas.shape[3], E.ptr(dst), b,
+                                                   Cn, Hc, Wc, S, yx, float(a), float(s), E.ptr(lowres_z), stage_seed,
+                                                   (16 << 32) | 1, stream()))
+
+            def gather_cond(dst, n0, b):   # dst [b, Ct, S, S] <- the conditioning windows of tiles n0 .. n0 + b - 1
+                yx = (C.c_int * (2 * b))(*[v for sh in shifts[n0:n0 + b] for v in sh])
+                E.check(lib.kd_tiles_cond_gather(E.ptr(src), Cs, W, E.ptr(dst), b, S, yx, top, C.c_void_p(win_of.data_ptr()),
+                                                 C.c_void_p(centre_of.data_ptr()) if exists(centre_of) else None, float(cc.fill),
+                                                 stream()))
 
             # one plan, one set of stable buffers and one argument struct per batch size (the full chunks' and the ragged one's)
             plans = {}
@@ -1689,8 +1827,8 @@ class Imagen(nn.Module):
                     args.d_lowres, args.d_lowres_log_snr = E.ptr(p["lowres"]), E.ptr(lls)
                     args.lowres_log_snr_uniform = 1
                     args.lowres_log_snr_value = float(ls[0])
-                if exists(cond):
-                    p["cond"] = buf("cond", (b,) + tuple(cond.shape[1:]))
+                if exists(cond_shape):
+                    p["cond"] = buf("cond", (b,) + cond_shape)
                     args.d_cond_images = E.ptr(p["cond"])
                 if unet.self_cond:
                     p["self_cond"] = buf("tile_self_cond", (b, Cn, S, S))
@@ -1716,10 +1854,14 @@ class Imagen(nn.Module):
                     b = min(tile_batch, N - n0)
                     p = plans[b]
                     gather(x, p["img"], n0, b)
-                    if unet.lowres_cond:
+                    if unet.lowres_cond and streamed:
+                        gather_lowres(p["lowres"], n0, b)
+                    elif unet.lowres_cond:
                         gather(lowres, p["lowres"], n0, b)
                     if exists(cond):
                         p["cond"].copy_(cond[n0:n0 + b])
+                    elif exists(crops):
+                        gather_cond(p["cond"], n0, b)
                     if unet.self_cond and k > 0:   # the carry is the FUSED estimate of step k - 1 (step 0 starts from zeros)
                         gather(x0bar, p["self_cond"], n0, b)
                         E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
@@ -1734,6 +1876,12 @@ class Imagen(nn.Module):
                 E.check(lib.kd_tiles_fuse_update(E.ptr(x), E.ptr(x0bar), E.ptr(store), E.ptr(thr), C.c_void_p(tile_of.data_ptr()),
                                                  N, Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z),
                                                  stage_seed, (1 << 32) | k, stream()))
+            if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
+                out, oy, ox = into if exists(into) else (torch.zeros(shape, device=device, dtype=torch.float32), 0, 0)
+                assert out.device == x.device, f"into: the canvas lives on {out.device}, the stage runs on {x.device}"
+                E.check(lib.kd_tiles_finalize(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
+                                              out.shape[2], out.shape[3], oy, ox, stream()))
+                return out
             covered = torch.zeros(Hc, Wc, dtype=torch.bool)
             for y0, x0 in origins:
                 covered[y0:y0 + S, x0:x0 + S] = True

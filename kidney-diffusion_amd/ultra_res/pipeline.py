@@ -106,3 +106,42 @@ def generate_all_levels(sample_fns: Dict[int, Callable], overlap: float = 0.25, 
         out.append(generate_high_res_image(sample_fns[level], out[-1], level, overlap=overlap, version=version,
                                            ignore_unet_1=ignore_unet_1, group=group, device=device, patch_pos=pos))
     return tuple(out)
+
+
+def generate_high_res_image_fused(load_imagen: Callable, zoomed_image: torch.Tensor, mag_level: int, overlap: float = 0.25,
+                                  version: str = "ultra", patch_pos: Optional[Sequence[G.Pos]] = None,
+                                  **fused_kw) -> torch.Tensor:
+    """`generate_high_res_image` by fused-tile sampling: `level_patches` (every position at mag 1, the tissue set at
+    mag 2; `patch_pos` overrides it) and `tiled.fused_level` over them.  `load_imagen(stage)` returns the Imagen of that
+    stage, as for `tiled.fused_canvas`; `fused_kw` are `fused_level`'s keywords (`stages`, `tile_batch`, `sampler`,
+    `sample_steps`, `seed`, `noise_fn`, `fill_color`, `background`, `device`, ...).  (1,3,W,W) on the device."""
+    from . import tiled as UT
+
+    geom, pos = level_patches(zoomed_image, mag_level, overlap, version)
+    if patch_pos is not None:
+        pos = list(patch_pos)
+    return UT.fused_level(load_imagen, zoomed_image, geom, pos, overlap=overlap, version=version, **fused_kw)
+
+
+def generate_all_levels_fused(load_imagens: Dict[int, Callable], overlap: float = 0.25, version: str = "ultra",
+                              patch_filter: Optional[Callable[[int, List[G.Pos]], List[G.Pos]]] = None,
+                              **fused_kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`generate_all_levels` by fused-tile sampling: mag 0 is `tiled.fused_canvas(grid=(1, 1))` - one tile, the
+    unconditional sample - and mag 1 and mag 2 are `generate_high_res_image_fused` over the level before.
+    `load_imagens[level](stage)` returns the Imagen of that level and stage; `patch_filter` as in `generate_all_levels`;
+    `fused_kw` as in `generate_high_res_image_fused` (mag 0 takes those of them that `fused_canvas` knows).  With an int
+    `seed`, level L runs under `seed + L`.  Returns the three images, each (1,3,W,W) on the device."""
+    from . import tiled as UT
+
+    seed = fused_kw.pop("seed", None)
+    level_seed = lambda level: None if seed is None else int(seed) + level
+    canvas_kw = {k: v for k, v in fused_kw.items() if k in ("stages", "tile_batch", "sampler", "sampler_eta", "sample_steps",
+                                                            "tile_weights", "use_graph", "noise_fn", "device")}
+    out = [UT.fused_canvas(load_imagens[0], grid=(1, 1), overlap=overlap, seed=level_seed(0), **canvas_kw)]
+    for level in (1, 2):
+        pos = None
+        if patch_filter is not None:
+            pos = patch_filter(level, level_patches(out[-1], level, overlap, version)[1])
+        out.append(generate_high_res_image_fused(load_imagens[level], out[-1], level, overlap=overlap, version=version,
+                                                 patch_pos=pos, seed=level_seed(level), **fused_kw))
+    return tuple(out)

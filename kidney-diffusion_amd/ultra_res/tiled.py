@@ -1,10 +1,15 @@
 """Fused-tile canvas driver: the counterpart of `distributed.outpaint_canvas` in which the tiles of a canvas are denoised
 together (`Imagen.sample_tiled`: MultiDiffusion / Mixture of Diffusers) instead of one after the other with inpainted overlap
 strips (reference: outpainting.py:173-243, sample_ultra_res.py:183-195).  No inpainting, no resampling, no waves: every
-schedule step runs all tiles in full batches and one canvas update."""
+schedule step runs all tiles in full batches and one canvas update.  `fused_level` is the counterpart of
+`pipeline.generate_high_res_image`: one magnification level - conditioning windows of the level above, a sparse tile
+set, the paste over the enlarged level above - at the pipeline's real sizes."""
 from typing import Callable, Optional, Sequence
 
 import torch
+import torch.nn.functional as F
+
+from . import grid as G
 
 
 def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None, grid: Optional[Sequence[int]] = None,
@@ -52,4 +57,100 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
                                      sampler_eta=per_unet(sampler_eta, 0.0), sample_steps=per_unet(sample_steps, None),
                                      seed=seed, noise_fn=noise_fn, use_graph=use_graph, start_at_unet_number=stage,
                                      stop_at_unet_number=stage, start_image_or_video=canvas, device=device)
+    return canvas
+
+
+def level_box(positions: Sequence[G.Pos]):
+    """The lattice of a (sparse) position set: its bounding box.  Returns (r0, c0, grid = (rows, columns), present
+    [rows][columns], tiles): `tiles` are the positions without repeats in row-major order, the order in which
+    `normalize_tiling` numbers the present slots."""
+    tiles = sorted({(int(i), int(j)) for i, j in positions})
+    if not tiles:
+        raise ValueError("level_box: no positions")
+    r0, r1 = min(p[0] for p in tiles), max(p[0] for p in tiles)
+    c0, c1 = min(p[1] for p in tiles), max(p[1] for p in tiles)
+    present = [[False] * (c1 - c0 + 1) for _ in range(r1 - r0 + 1)]
+    for i, j in tiles:
+        present[i - r0][j - c0] = True
+    return r0, c0, (r1 - r0 + 1, c1 - c0 + 1), present, tiles
+
+
+def level_background(zoomed_image: torch.Tensor, width: int) -> torch.Tensor:
+    """`zoomed_image` enlarged bilinearly to `width`, exactly as `grid.stitch_canvas` builds its background."""
+    if zoomed_image.shape[1] * width * width >= 2 ** 31 - 1:
+        return G.bilinear_resize_large(zoomed_image, width)
+    return F.interpolate(zoomed_image, size=(width, width), mode="bilinear", align_corners=False)
+
+
+def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridGeometry, positions: Sequence[G.Pos], *,
+                overlap: float = 0.25, version: str = "ultra", fill_color: Optional[float] = None, window: int = G.PATCH_SIZE,
+                stages: Sequence[int] = (1, 2, 3), tile_batch: int = 16, tile_weights: str = "uniform", sampler=None,
+                sampler_eta=0.0, sample_steps=None, seed: Optional[int] = None, noise_fn: Optional[Callable] = None,
+                use_graph: bool = True, background: bool = True, device: Optional[torch.device] = None) -> torch.Tensor:
+    """One magnification level by fused-tile sampling, with the semantics of `pipeline.generate_high_res_image`: the
+    tiles at `positions` (grid positions (i, j) of `geom`; all of them at mag 1, the tissue set at mag 2) are conditioned
+    on windows of `zoomed_image` [1, 3, W, W], the level above, denoised together through `stages`, and written over the
+    bilinearly enlarged `zoomed_image` (`background=False`: zeros).  Returns the canvas [1, 3, canvas_width, canvas_width]
+    on the device.  No positions: the enlarged background alone.
+
+    The lattice is the bounding box of `positions` with `present` marking them (`level_box`), so a sparse tissue set pays
+    for its box only: the stage canvases, the fused estimate and the noise span the box.  THE CANVAS NOISE IS KEYED BY THE
+    ELEMENT OF THE BOX CANVAS - x_T, the low-res augmentation and the step noise of a pixel follow its offset from the
+    box' corner, so the same tile set inside another box (a position added far away) draws other noise.
+
+    Nothing canvas-sized is materialised beside the result: the conditioning images are described, not built
+    (`TileCondCrops` with `cond_images_for_grid`'s shifts `W // 2 - (i patch_dist + patch_width // 2)`, the window at
+    `center_crop_offset(W, window)`, the `v2` centre channels with `version == "v2"`), every stage runs `streamed`, and the
+    last one writes its covered pixels `into` the full canvas at the box' corner.  `fill_color` None: 0 for 'airs', else
+    0.95.  `geom.out_patch_dist` and `geom.canvas_width` must be the stride and the full lattice of the last stage
+    (ValueError otherwise).  `load_imagen`, `stages` (from 1), `sampler`, `sampler_eta`, `sample_steps`: as `fused_canvas`."""
+    from imagen_pytorch.imagen_pytorch import TileCondCrops, normalize_tiling
+
+    stages = tuple(int(s) for s in stages)
+    if not stages or stages[0] != 1 or any(b != a + 1 for a, b in zip(stages, stages[1:])):
+        raise ValueError(f"stages must be consecutive unet numbers from 1 in ascending order, got {stages}")
+    if zoomed_image.dim() != 4 or zoomed_image.shape[0] != 1 or zoomed_image.shape[2] != zoomed_image.shape[3]:
+        raise ValueError(f"zoomed_image must be one square image [1, C, W, W], got {tuple(zoomed_image.shape)}")
+    width = int(geom.canvas_width)
+    positions = list(positions)
+    if not positions:   # nothing to generate (a mag-2 canvas without tissue)
+        dev = zoomed_image.device if device is None else torch.device(device)
+        full = level_background(zoomed_image.to(dev), width)
+        return full if background else torch.zeros_like(full)
+    n = int(geom.num_patches_width)
+    if any(not (0 <= i < n and 0 <= j < n) for i, j in positions):
+        raise ValueError(f"positions must lie inside the {n} x {n} grid of geom")
+    r0, c0, grid, present, tiles = level_box(positions)
+    W = int(zoomed_image.shape[3])
+    half = geom.patch_width // 2
+    shifts = [(W // 2 - (i * geom.patch_dist + half), W // 2 - (j * geom.patch_dist + half)) for i, j in tiles]
+    if fill_color is None:
+        fill_color = 0.0 if version == "airs" else 0.95  # sample_ultra_res.py:374-377
+    crops = TileCondCrops(zoomed_image, shifts, int(window), float(fill_color),
+                          centre_width=geom.patch_width if version == "v2" else None)
+    device = torch.device(device if device is not None else "cuda")
+    full = canvas = None
+    for stage in stages:
+        imagen = load_imagen(stage)
+        n_unets = len(imagen.unets)
+        if stage == stages[0]:   # the geometry is checked before anything moves to the device
+            if stages[-1] > n_unets:
+                raise ValueError(f"stages={stages} name unet {stages[-1]}, the Imagen holds {n_unets}")
+            last = normalize_tiling(imagen.image_sizes, grid, overlap, present, tile_weights)[stages[-1] - 1]
+            S, st = last["S"], last["st"]
+            if geom.out_patch_dist != st or width != (n - 1) * st + S:
+                raise ValueError(f"geom (out_patch_dist={geom.out_patch_dist}, canvas_width={width}, {n} patches wide) is not the "
+                                 f"lattice of unet {stages[-1]}: stride st={st}, canvas (n - 1) st + S = {(n - 1) * st + S}")
+            crops.checked(len(tiles))
+            crops.image = zoomed_image = zoomed_image.to(device)   # moved once, for the background and every stage
+            full = level_background(zoomed_image.float(), width) if background else \
+                torch.zeros(1, zoomed_image.shape[1], width, width, device=device, dtype=torch.float32)
+        per_unet = lambda v, d: tuple(v.get(s, d) for s in range(1, n_unets + 1)) if isinstance(v, dict) else v
+        imagen = imagen.to(device)
+        canvas = imagen.sample_tiled(grid, overlap=overlap, present=present, tile_batch=tile_batch, tile_weights=tile_weights,
+                                     cond_crops=crops, sampler=per_unet(sampler, None), sampler_eta=per_unet(sampler_eta, 0.0),
+                                     sample_steps=per_unet(sample_steps, None), seed=seed, noise_fn=noise_fn,
+                                     use_graph=use_graph, start_at_unet_number=stage, stop_at_unet_number=stage,
+                                     start_image_or_video=canvas, device=device, streamed=True,
+                                     into=(full, r0 * st, c0 * st) if stage == stages[-1] else None)
     return canvas
