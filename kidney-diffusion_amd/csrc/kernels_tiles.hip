@@ -23,6 +23,32 @@ struct TileOrigins {
   int y0[TILE_CHUNK];
   int x0[TILE_CHUNK];
 };
+// Host side of the gathers.  `who` is the launcher's prefix in the requirement messages.
+// The tile set of kd_tiles_gather / kd_tiles_gather_lowres: B tiles [C, S, S] at origins_yx [B][2] inside a canvas [C, Hc, Wc].
+static int check_tile_origins(const std::string& who, const int* origins_yx, int B, int C, int Hc, int Wc, int S) {
+  KD_REQUIRE(B >= 1 && C >= 1 && C <= 1024 && S >= 4 && S % 4 == 0, who + ": needs B, C >= 1 and a tile size S % 4 == 0");
+  KD_REQUIRE(Hc >= S && Wc >= S && Wc % 4 == 0 && Hc <= (1 << 20) && Wc <= (1 << 20), who + ": canvas smaller than a tile, or Wc % 4 != 0");
+  KD_REQUIRE((int64_t)C * S * S < (1ll << 31), who + ": a tile must hold fewer than 2^31 elements");
+  for (int b = 0; b < B; ++b) {
+    const int y0 = origins_yx[2 * b], x0 = origins_yx[2 * b + 1];
+    KD_REQUIRE(y0 >= 0 && y0 + S <= Hc && x0 >= 0 && x0 + S <= Wc && x0 % 4 == 0,
+               who + ": a tile origin lies outside the canvas or its x0 is no multiple of 4");
+  }
+  return 0;
+}
+// launch(b0, nb, org) for every pack of at most TILE_CHUNK of the B pairs yx [B][2]; org holds the pack's pairs.
+template <class Launch>
+static void for_tile_chunks(const int* yx, int B, Launch launch) {
+  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
+    const int nb = std::min(B - b0, (int)TILE_CHUNK);
+    TileOrigins org{};
+    for (int b = 0; b < nb; ++b) {
+      org.y0[b] = yx[2 * (b0 + b)];
+      org.x0[b] = yx[2 * (b0 + b) + 1];
+    }
+    launch(b0, nb, org);
+  }
+}
 __global__ __launch_bounds__(256) void tiles_gather_kernel(const float* __restrict__ canvas, float* __restrict__ tiles, int C,
                                                            int Hc, int Wc, int S, TileOrigins org) {
   const int b = blockIdx.y;
@@ -39,27 +65,14 @@ __global__ __launch_bounds__(256) void tiles_gather_kernel(const float* __restri
 int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc, int Wc, int S, const int* origins_yx,
                         hipStream_t s) {
   KD_REQUIRE(canvas && tiles && origins_yx, "tiles gather: null argument");
-  KD_REQUIRE(B >= 1 && C >= 1 && C <= 1024 && S >= 4 && S % 4 == 0, "tiles gather: needs B, C >= 1 and a tile size S % 4 == 0");
-  KD_REQUIRE(Hc >= S && Wc >= S && Wc % 4 == 0 && Hc <= (1 << 20) && Wc <= (1 << 20), "tiles gather: canvas smaller than a tile, or Wc % 4 != 0");
-  KD_REQUIRE((int64_t)C * S * S < (1ll << 31), "tiles gather: a tile must hold fewer than 2^31 elements");
+  if (check_tile_origins("tiles gather", origins_yx, B, C, Hc, Wc, S)) return 1;
   KD_REQUIRE((((uintptr_t)canvas | (uintptr_t)tiles) & 15) == 0, "tiles gather: canvas and tiles must be 16-byte aligned");
-  for (int b = 0; b < B; ++b) {
-    const int y0 = origins_yx[2 * b], x0 = origins_yx[2 * b + 1];
-    KD_REQUIRE(y0 >= 0 && y0 + S <= Hc && x0 >= 0 && x0 + S <= Wc && x0 % 4 == 0,
-               "tiles gather: a tile origin lies outside the canvas or its x0 is no multiple of 4");
-  }
   const int per4 = C * S * (S / 4);
-  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
-    const int nb = std::min(B - b0, (int)TILE_CHUNK);
-    TileOrigins org{};
-    for (int b = 0; b < nb; ++b) {
-      org.y0[b] = origins_yx[2 * (b0 + b)];
-      org.x0[b] = origins_yx[2 * (b0 + b) + 1];
-    }
+  for_tile_chunks(origins_yx, B, [&](int b0, int nb, const TileOrigins& org) {
     const int gx = std::max(1, std::min((per4 + 255) / 256, 8192 / nb));
     hipLaunchKernelGGL(tiles_gather_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, s, canvas,
                        tiles + (int64_t)b0 * per4 * 4, C, Hc, Wc, S, org);
-  }
+  });
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -81,6 +94,17 @@ struct TileGeom {
   int N;          // tiles in x0_tiles
 };
 __device__ __forceinline__ float ramp_weight(int i, int S, int ov) { return (float)min(min(i + 1, S - i), ov) / (float)ov; }
+// Host side of the canvas step and of the end of a stage: the lattice checked and as the kernels take it.
+static int tile_lattice(const std::string& who, int N, int C, int S, int st, int ny, int nx, int ramp, TileGeom* g) {
+  KD_REQUIRE(N >= 1 && C >= 1 && C <= 1024 && ny >= 1 && nx >= 1 && N <= (int64_t)ny * nx, who + ": needs 1 <= N <= ny nx tiles and C >= 1");
+  KD_REQUIRE(S >= 4 && S % 4 == 0 && st >= 4 && st % 4 == 0 && st <= S, who + ": needs S % 4 == 0, st % 4 == 0 and 4 <= st <= S");
+  KD_REQUIRE(S <= TILE_COVER * st, who + ": more than 3 tiles per axis cover a pixel (S > 3 st)");
+  const int64_t Hc = (int64_t)(ny - 1) * st + S, Wc = (int64_t)(nx - 1) * st + S;
+  KD_REQUIRE(Hc <= (1 << 20) && Wc <= (1 << 20) && (int64_t)C * Hc < (1ll << 31) && (int64_t)ny * nx < (1ll << 31),
+             who + ": canvas out of range");
+  *g = TileGeom{C, S, st, ny, nx, (int)Hc, (int)Wc, ramp != 0, std::max(S - st, 1), N};
+  return 0;
+}
 
 __global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, float* __restrict__ x0bar,
                                                                 const float* __restrict__ x0_tiles,
@@ -145,17 +169,12 @@ int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, cons
                              int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn, const float* noise,
                              uint64_t seed, uint64_t sid, hipStream_t s) {
   KD_REQUIRE(x && x0bar && x0_tiles && tile_of, "tiles fuse: null argument");
-  KD_REQUIRE(N >= 1 && C >= 1 && C <= 1024 && ny >= 1 && nx >= 1 && N <= (int64_t)ny * nx, "tiles fuse: needs 1 <= N <= ny nx tiles and C >= 1");
-  KD_REQUIRE(S >= 4 && S % 4 == 0 && st >= 4 && st % 4 == 0 && st <= S, "tiles fuse: needs S % 4 == 0, st % 4 == 0 and 4 <= st <= S");
-  KD_REQUIRE(S <= TILE_COVER * st, "tiles fuse: more than 3 tiles per axis cover a pixel (S > 3 st)");
-  const int64_t Hc = (int64_t)(ny - 1) * st + S, Wc = (int64_t)(nx - 1) * st + S;
-  KD_REQUIRE(Hc <= (1 << 20) && Wc <= (1 << 20) && (int64_t)C * Hc < (1ll << 31) && (int64_t)ny * nx < (1ll << 31),
-             "tiles fuse: canvas out of range");
+  TileGeom g;
+  if (tile_lattice("tiles fuse", N, C, S, st, ny, nx, ramp, &g)) return 1;
   KD_REQUIRE((((uintptr_t)x | (uintptr_t)x0bar | (uintptr_t)x0_tiles | (uintptr_t)noise) & 15) == 0,
              "tiles fuse: x, x0bar, x0_tiles and noise must be 16-byte aligned");
-  TileGeom g{C, S, st, ny, nx, (int)Hc, (int)Wc, ramp != 0, std::max(S - st, 1), N};
-  const int W4 = (int)Wc / 4;
-  const int64_t rows = (int64_t)C * Hc;
+  const int W4 = g.Wc / 4;
+  const int64_t rows = (int64_t)C * g.Hc;
   hipLaunchKernelGGL(tiles_fuse_update_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
                      dim3(256), 0, s, x, x0bar, x0_tiles, thr, tile_of, g, A, B, P, Sn, noise, seed, sid);
   KD_HIP_CHECK(hipGetLastError());
@@ -231,16 +250,10 @@ int launch_tiles_cond_gather(const float* src, int Cs, int W, float* tiles, int 
     KD_REQUIRE(sy > -W && sy < W && sx > -W && sx < W, "tiles cond gather: a shift must lie inside (-W, W)");
   }
   const int S4 = S / 4, rows = Ct * S;
-  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
-    const int nb = std::min(B - b0, (int)TILE_CHUNK);
-    TileOrigins sh{};
-    for (int b = 0; b < nb; ++b) {
-      sh.y0[b] = shifts_yx[2 * (b0 + b)];
-      sh.x0[b] = shifts_yx[2 * (b0 + b) + 1];
-    }
+  for_tile_chunks(shifts_yx, B, [&](int b0, int nb, const TileOrigins& sh) {
     hipLaunchKernelGGL(tiles_cond_gather_kernel, dim3((unsigned)((S4 + 255) / 256), (unsigned)std::min(rows, 8192), (unsigned)nb),
                        dim3(256), 0, s, src, Cs, W, tiles + (int64_t)b0 * rows * S, S, Ct, sh, top, win_of, centre_of, fill);
-  }
+  });
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -287,30 +300,16 @@ int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, 
                                const int* origins_yx, float a, float s, const float* noise, uint64_t seed, uint64_t sid,
                                hipStream_t st) {
   KD_REQUIRE(prev && tiles && origins_yx, "tiles gather lowres: null argument");
-  KD_REQUIRE(B >= 1 && C >= 1 && C <= 1024 && S >= 4 && S % 4 == 0, "tiles gather lowres: needs B, C >= 1 and a tile size S % 4 == 0");
-  KD_REQUIRE(Hc >= S && Wc >= S && Wc % 4 == 0 && Hc <= (1 << 20) && Wc <= (1 << 20),
-             "tiles gather lowres: canvas smaller than a tile, or Wc % 4 != 0");
+  if (check_tile_origins("tiles gather lowres", origins_yx, B, C, Hc, Wc, S)) return 1;
   KD_REQUIRE(Hp >= 1 && Wp >= 1 && Hp <= (1 << 20) && Wp <= (1 << 20), "tiles gather lowres: previous canvas out of range");
-  KD_REQUIRE((int64_t)C * S * S < (1ll << 31), "tiles gather lowres: a tile must hold fewer than 2^31 elements");
   KD_REQUIRE((((uintptr_t)tiles | (uintptr_t)noise) & 15) == 0, "tiles gather lowres: tiles and noise must be 16-byte aligned");
-  for (int b = 0; b < B; ++b) {
-    const int y0 = origins_yx[2 * b], x0 = origins_yx[2 * b + 1];
-    KD_REQUIRE(y0 >= 0 && y0 + S <= Hc && x0 >= 0 && x0 + S <= Wc && x0 % 4 == 0,
-               "tiles gather lowres: a tile origin lies outside the canvas or its x0 is no multiple of 4");
-  }
   const float ry = (float)Hp / (float)Hc, rx = (float)Wp / (float)Wc;
   const int per4 = C * S * (S / 4);
-  for (int b0 = 0; b0 < B; b0 += TILE_CHUNK) {
-    const int nb = std::min(B - b0, (int)TILE_CHUNK);
-    TileOrigins org{};
-    for (int b = 0; b < nb; ++b) {
-      org.y0[b] = origins_yx[2 * (b0 + b)];
-      org.x0[b] = origins_yx[2 * (b0 + b) + 1];
-    }
+  for_tile_chunks(origins_yx, B, [&](int b0, int nb, const TileOrigins& org) {
     const int gx = std::max(1, std::min((per4 + 255) / 256, 8192 / nb));
     hipLaunchKernelGGL(tiles_gather_lowres_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, st, prev, Hp, Wp, ry, rx,
                        tiles + (int64_t)b0 * per4 * 4, C, Hc, Wc, S, org, a, s, noise, seed, sid);
-  }
+  });
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -349,19 +348,15 @@ __global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __rest
 int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
                           int Wo, int oy, int ox, hipStream_t s) {
   KD_REQUIRE(x && tile_of && out, "tiles finalize: null argument");
-  KD_REQUIRE(N >= 1 && C >= 1 && C <= 1024 && ny >= 1 && nx >= 1 && N <= (int64_t)ny * nx, "tiles finalize: needs 1 <= N <= ny nx tiles and C >= 1");
-  KD_REQUIRE(S >= 4 && S % 4 == 0 && st >= 4 && st % 4 == 0 && st <= S, "tiles finalize: needs S % 4 == 0, st % 4 == 0 and 4 <= st <= S");
-  KD_REQUIRE(S <= TILE_COVER * st, "tiles finalize: more than 3 tiles per axis cover a pixel (S > 3 st)");
-  const int64_t Hc = (int64_t)(ny - 1) * st + S, Wc = (int64_t)(nx - 1) * st + S;
-  KD_REQUIRE(Hc <= (1 << 20) && Wc <= (1 << 20) && (int64_t)C * Hc < (1ll << 31) && (int64_t)ny * nx < (1ll << 31),
-             "tiles finalize: canvas out of range");
+  TileGeom g;
+  if (tile_lattice("tiles finalize", N, C, S, st, ny, nx, 0, &g)) return 1;
+  const int64_t Hc = g.Hc, Wc = g.Wc;   // (oy + Hc, ox + Wc: no overflow for any int offset)
   KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
              "tiles finalize: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
   KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo, "tiles finalize: the canvas at (oy, ox) lies outside the output");
   KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize: x and out must be 16-byte aligned");
-  TileGeom g{C, S, st, ny, nx, (int)Hc, (int)Wc, 0, std::max(S - st, 1), N};
-  const int W4 = (int)Wc / 4;
-  const int64_t rows = (int64_t)C * Hc;
+  const int W4 = g.Wc / 4;
+  const int64_t rows = C * Hc;
   hipLaunchKernelGGL(tiles_finalize_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
                      dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox);
   KD_HIP_CHECK(hipGetLastError());

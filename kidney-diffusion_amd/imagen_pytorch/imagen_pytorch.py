@@ -1294,6 +1294,146 @@ def normalize_init_images(init_images, skip_steps, *, steps, batch_size, channel
     return out
 
 
+# ============================================================================ one stage on the engine (host side)
+_OBJECTIVES = {"noise": 0, "v": 1, "x_start": 2}
+
+
+def _f32(t, device):
+    return None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
+
+
+class _StepSchedule:
+    """The host tables of one stage's sampler together with the ctypes struct the engine reads them through:
+    ``kd_schedule_t`` for ``"ddpm"`` (the arrays of ``step_tables()``), ``kd_solver_schedule_t`` for ``"ddim"`` /
+    ``"dpmpp_2m"`` (five of them plus ``solver_tables``), ``kd_edm_schedule_t`` through ``_StepSchedule.edm``.  ``steps`` and
+    ``loop`` name the library entries that take the struct, ``T`` is the number of steps.
+
+    Pointer lifetime: the struct's pointers point into the memory of the tensors in ``self.tables`` and nothing else keeps
+    that memory alive, so ``struct`` is valid exactly as long as this object is.  Hold the object over every call that is
+    given ``byref(struct)``; the engine copies the arrays into its own staging buffer inside the call, so nothing has to
+    outlive it."""
+
+    def __init__(self, step_tables, sampler="ddpm", eta=0.0, skip=0):
+        if sampler == "ddpm":
+            self._own(E.kd_schedule_t(), step_tables, "kd_sample")
+        else:   # the solver's coefficients in place of the ancestral step's; its own entries, tables and step graph
+            self._own(E.kd_solver_schedule_t(), {**step_tables, **solver_tables(step_tables, sampler, eta=eta, skip=skip)},
+                      "kd_solver_sample")
+        self.struct.T = self.T = int(step_tables["alpha"].numel())
+
+    @classmethod
+    def edm(cls, edm_tables, S_noise):
+        self = cls.__new__(cls)
+        self._own(E.kd_edm_schedule_t(), edm_tables, "kd_edm_sample")
+        self.struct.N = self.T = int(edm_tables["sigma"].numel())
+        self.struct.S_noise = float(S_noise)
+        return self
+
+    def _own(self, struct, tables, entry):
+        self.struct, self.steps, self.loop, self.tables = struct, entry + "_steps", entry + "_loop", {}
+        for name, ctype in struct._fields_:
+            if ctype is C.POINTER(C.c_float):   # (ctypes caches pointer types: one object per pointee)
+                t = self.tables[name] = tables[name]
+                assert t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda, f"schedule table {name}: fp32 on the host"
+                setattr(struct, name, t.numpy().ctypes.data_as(C.POINTER(C.c_float)))
+
+
+def _walk(lib, sc, h, args, img, *, skip=0, trace=None, self_cond=False):
+    """Steps ``skip .. T - 1`` of the schedule ``sc`` (a _StepSchedule) on the plan ``h``, in place on ``img`` (x at step
+    ``skip`` in, the unnormalised sample out).  A self-conditioned plan starts step ``skip`` > 0 from zeros, as step 0
+    does by itself.  ``trace`` receives a copy of the state behind every step walked (one step per call)."""
+    steps, stream = getattr(lib, sc.steps), E.current_stream
+    if skip > 0 and self_cond:
+        E.check(lib.kd_sample_set_self_cond(h, None, stream()))
+    if exists(trace):
+        for k in range(skip, sc.T):
+            E.check(steps(h, C.byref(sc.struct), C.byref(args), E.ptr(img), k, k + 1, stream()))
+            trace.append(img.clone())
+        E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), stream()))
+    elif skip > 0:
+        E.check(steps(h, C.byref(sc.struct), C.byref(args), E.ptr(img), skip, sc.T, stream()))
+        E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), stream()))
+    else:
+        E.check(getattr(lib, sc.loop)(h, C.byref(sc.struct), C.byref(args), E.ptr(img), stream()))
+
+
+def _stage_noise(lib, noise_fn, seed, stage, device):
+    """The Gaussian draws of one stage: ``(gauss, key, keys)``.  An int ``seed`` gives the stage's Philox key ``key`` and
+    ``keys = None``; a list of per-image seeds (normalize_seed) gives ``key = 0`` and ``keys``, the host array of one key
+    per image, each derived per stage like the int.  ``gauss(tag, shape, sid)`` is ``noise_fn(tag, shape)`` when noise is
+    injected, else Philox stream ``sid`` under ``key`` - with ``keys``, row b is the batch-1 draw under image b's key."""
+    derive = lambda s: (s + STAGE_SEED_STRIDE * stage) % (2 ** 64)
+    key, keys = (0, E.seed_array([derive(s) for s in seed])) if isinstance(seed, list) else (derive(seed), None)
+
+    def gauss(tag, shape, sid):
+        if exists(noise_fn):
+            return _f32(noise_fn(tag, tuple(shape)), device)
+        out = torch.empty(tuple(shape), device=device, dtype=torch.float32)
+        if exists(keys):
+            E.check(lib.kd_philox_normal_rows(E.ptr(out), shape[0], out.numel() // shape[0], keys, sid, E.current_stream()))
+        else:
+            E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), key, sid, E.current_stream()))
+        return out
+
+    return gauss, key, keys
+
+
+class _StageIO:
+    """The inputs of one plan (UNet, batch, size, device) at stable addresses, and the kd_sample_args_t that names them.
+    The engine caches the captured step graph keyed on the device addresses it was captured with.  Per-call tensors are
+    therefore copied into per-(batch, size, device) buffers of the UNet that keep their address, so that e.g. the 64
+    patches of an ultra-res grid replay one graph per stage instead of re-capturing it for every patch; sample() and
+    sample_tiled() share them by name.  The object owns everything ``args`` points into: the buffers, and ``keys``, the
+    host array of per-image Philox keys."""
+
+    def __init__(self, imagen, unet, batch, size, device, *, dynamic_threshold, use_graph, key, keys=None, resample_times=1):
+        self.unet, self.batch, self.device, self.keys = unet, batch, device, keys
+        self._io = unet._io_buffers.setdefault((batch, size, device.index), {})
+        args = self.args = E.kd_sample_args_t()
+        args.dynamic_threshold = int(bool(dynamic_threshold))
+        args.percentile = imagen.dynamic_thresholding_percentile
+        args.resample_times = resample_times
+        args.seed = key
+        if exists(keys):
+            args.seeds = keys
+        args.use_graph = int(bool(use_graph))
+        args.cond_table = int(getattr(imagen, "cond_table", 0))   # engine extension: < 0 switches the table off
+
+    def buf(self, name, shape):
+        """The stable fp32 buffer of this name and shape (allocated on first use and when the shape changes)."""
+        t = self._io.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = self._io[name] = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
+        return t
+
+    def put(self, name, t):
+        """`t` copied into its stable buffer (stream-ordered); None stays None."""
+        if t is None:
+            return None
+        b = self.buf(name, t.shape)
+        b.copy_(t)
+        return b
+
+    def lowres_level(self, log_snr):
+        """One augmentation level for the whole batch (the library's sample() has no other form): lets the engine table the
+        time conditioning per schedule step."""
+        self.args.d_lowres_log_snr = E.ptr(self.put("lowres_log_snr", log_snr.to(self.device).expand(self.batch)))
+        self.args.lowres_log_snr_uniform = 1
+        self.args.lowres_log_snr_value = float(log_snr[0])
+
+    def text(self, h, text_embeds, text_masks, cond_scale):
+        """Step-invariant: pooled text tokens + text hiddens, once per stage; with guidance, their null twins for the second
+        forward."""
+        args = self.args
+        tok, hid = self.unet.text_cond(h, text_embeds, text_masks, drop=False, device=self.device)
+        args.d_text_tokens, args.d_text_hiddens = E.ptr(self.put("text_tokens", tok)), E.ptr(self.put("text_hiddens", hid))
+        args.cond_scale = cond_scale
+        if cond_scale != 1.0:
+            tok, hid = self.unet.text_cond(h, text_embeds, text_masks, drop=True, device=self.device)
+            args.d_null_text_tokens = E.ptr(self.put("null_text_tokens", tok))
+            args.d_null_text_hiddens = E.ptr(self.put("null_text_hiddens", hid))
+
+
 # ============================================================================ Imagen
 class Imagen(nn.Module):
     def __init__(self, unets, *, image_sizes, text_encoder_name=None, text_embed_dim=None, channels=3,
@@ -1393,61 +1533,31 @@ class Imagen(nn.Module):
                                        batch_size=n_images,
                                        channels=self.channels, start_at_unet_number=start_at_unet_number,
                                        stop_at_unet_number=stop_at_unet_number)
-        E.require_gpu()
-        device = torch.device(default(device, self.device))
-        if device.type != "cuda":
-            raise E.EngineUnavailable(f"sampling runs on the HIP engine only; got device {device}")
-        self.eval()
-
-        if not self.unconditional:
-            assert exists(text_embeds), "text must be passed in if the network was not trained without text `condition_on_text` must be set to `False` when training"
-            text_masks = default(text_masks, lambda: torch.any(text_embeds != 0.0, dim=-1))
-            batch_size = text_embeds.shape[0]
+        device, text_masks, cond_images, seed, cond_scale, lowres_sample_noise_level, img = self._sampling_setup(
+            device, text_embeds, text_masks, cond_images, seed, cond_scale, lowres_sample_noise_level, start_at_unet_number,
+            start_image_or_video)
+        # with the text asserts passed (text_embeds given exactly when the model is conditioned on text), the library's
+        # batch size - text_embeds' rows, else an unconditional batch of 1 follows inpaint_images - is n_images as settled above
+        batch_size = n_images
         if exists(inpaint_images):
-            if self.unconditional and batch_size == 1:
-                batch_size = inpaint_images.shape[0]
             assert inpaint_images.shape[0] == batch_size, \
                 "number of inpainting images must be equal to the specified batch size on sample `sample(batch_size=<int>)``"
-        assert not (self.condition_on_text and not exists(text_embeds)), "text or text encodings must be passed into imagen if specified"
-        assert not (not self.condition_on_text and exists(text_embeds)), "imagen specified not to be conditioned on text, yet it is presented"
-        assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
-            f"invalid text embedding dimension being passed in (should be {self.text_embed_dim})"
         assert not (exists(inpaint_images) ^ exists(inpaint_masks)), "inpaint images and masks must be both passed in to do inpainting"
-        lowres_sample_noise_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
-        n = len(self.unets)
-        cond_scale = cast_tuple(cond_scale, n)
-        if exists(cond_images) and cond_images.dtype == torch.uint8:
-            cond_images = cond_images.float() / 255.0
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-
-        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        img = None
         if start_at_unet_number > 1:
-            assert start_at_unet_number <= n, "must start a unet that is less than the total number of unets"
+            assert start_at_unet_number <= len(self.unets), "must start a unet that is less than the total number of unets"
             assert not exists(stop_at_unet_number) or start_at_unet_number <= stop_at_unet_number
-            assert exists(start_image_or_video), "starting image or video must be supplied if only doing upscaling"
-            img = resize_image_to(f32(start_image_or_video), self.image_sizes[start_at_unet_number - 2])
+            img = resize_image_to(img, self.image_sizes[start_at_unet_number - 2])
 
         outputs = []
-        for num, unet, size, sched, obj, dyn, cs, (init_image, skip), (solver, eta, steps) in zip(
-                range(1, n + 1), self.unets, self.image_sizes, self.noise_schedulers, self.pred_objectives,
-                self.dynamic_thresholding, cond_scale, starts, solvers):
-            if num < start_at_unet_number:
-                continue
-            assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
-            assert not (cs != 1.0 and not self.condition_on_text), \
-                "imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)"
-            if exists(steps):
-                sched = sched.with_timesteps(steps)
+        for num, unet, sched, obj, dyn, cs, solver in self._stages(solvers, cond_scale, start_at_unet_number,
+                                                                  stop_at_unet_number):
+            init_image, skip = starts[num - 1]
             img = self._p_sample_loop(
-                unet, num, size, sched, obj, dyn, batch_size, device, img, cond_images, inpaint_images,
+                unet, num, self.image_sizes[num - 1], sched, obj, dyn, batch_size, device, img, cond_images, inpaint_images,
                 inpaint_masks, inpaint_resample_times, lowres_sample_noise_level, noise_fn, seed, use_graph, trace,
-                text_embeds=text_embeds, text_masks=text_masks, cond_scale=float(cs), init_image=init_image, skip=skip,
-                solver=(solver, eta))
+                text_embeds=text_embeds, text_masks=text_masks, cond_scale=cs, init_image=init_image, skip=skip,
+                solver=solver)
             outputs.append(img)
-            if exists(stop_at_unet_number) and stop_at_unet_number == num:
-                break
 
         out = outputs if return_all_unet_outputs else outputs[-1]
         if not return_pil_images:
@@ -1461,107 +1571,91 @@ class Imagen(nn.Module):
 
         return [to_pil(o) for o in out] if return_all_unet_outputs else to_pil(out)
 
+    def _sampling_setup(self, device, text_embeds, text_masks, cond_images, seed, cond_scale, lowres_level,
+                        start_at_unet_number, start_image):
+        """What sample() and sample_tiled() share behind their own argument refusals: the GPU and device check, eval mode,
+        the library's text asserts, and the defaults.  Returns (device, text_masks, cond_images as floats, seed, cond_scale
+        per UNet, low-res noise level, the start image as fp32 on the device - None when sampling starts at UNet 1)."""
+        E.require_gpu()
+        device = torch.device(default(device, self.device))
+        if device.type != "cuda":
+            raise E.EngineUnavailable(f"sampling runs on the HIP engine only; got device {device}")
+        self.eval()
+        assert not (self.condition_on_text and not exists(text_embeds)), "text or text encodings must be passed into imagen if specified"
+        assert not (not self.condition_on_text and exists(text_embeds)), "imagen specified not to be conditioned on text, yet it is presented"
+        assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
+            f"invalid text embedding dimension being passed in (should be {self.text_embed_dim})"
+        if exists(text_embeds):
+            text_masks = default(text_masks, lambda: torch.any(text_embeds != 0.0, dim=-1))
+        if exists(cond_images) and cond_images.dtype == torch.uint8:
+            cond_images = cond_images.float() / 255.0
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if start_at_unet_number > 1:
+            assert exists(start_image), "starting image or video must be supplied if only doing upscaling"
+            start_image = _f32(start_image, device)
+        else:
+            start_image = None
+        return (device, text_masks, cond_images, seed, cast_tuple(cond_scale, len(self.unets)),
+                default(lowres_level, self.lowres_sample_noise_level), start_image)
+
+    def _stages(self, solvers, cond_scale, start_at_unet_number=1, stop_at_unet_number=None):
+        """The UNets a sampling call walks, ``start_at_unet_number .. stop_at_unet_number``: per stage ``(number, unet,
+        schedule, objective, dynamic-threshold flag, cond_scale, (solver, eta))``, the schedule already on the stage's
+        ``sample_steps``.  ``solvers`` as ``_solver_args`` gives them, ``cond_scale`` one entry per UNet."""
+        for num, (unet, sched, obj, dyn, cs, (solver, eta, steps)) in enumerate(
+                zip(self.unets, self.noise_schedulers, self.pred_objectives, self.dynamic_thresholding, cond_scale, solvers), 1):
+            if num < start_at_unet_number:
+                continue
+            assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
+            assert not (cs != 1.0 and not self.condition_on_text), \
+                "imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)"
+            yield num, unet, sched.with_timesteps(steps) if exists(steps) else sched, obj, dyn, float(cs), (solver, eta)
+            if exists(stop_at_unet_number) and stop_at_unet_number == num:
+                break
+
     def _p_sample_loop(self, unet, stage, size, sched, objective, dynamic_threshold, batch, device, prev_img,
                        cond_images, inpaint_images, inpaint_masks, resample_times, lowres_level, noise_fn, seed,
                        use_graph, trace, text_embeds=None, text_masks=None, cond_scale=1.0, init_image=None, skip=0,
                        solver=("ddpm", 0.0)):
         lib = E.load()
         shape = (batch, self.channels, size, size)
-        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        per_image = isinstance(seed, list)   # normalize_seed: one key per image, each derived per stage like the int
-        if per_image:
-            stage_seeds = E.seed_array([(s + STAGE_SEED_STRIDE * stage) % (2 ** 64) for s in seed])
-            stage_seed = 0
-        else:
-            stage_seed = (seed + STAGE_SEED_STRIDE * stage) % (2 ** 64)
-
-        def gauss(tag, shp, sid):
-            if exists(noise_fn):
-                return f32(noise_fn(tag, tuple(shp)))
-            out = torch.empty(shp, device=device, dtype=torch.float32)
-            if per_image:   # row b is the batch-1 draw under image b's key
-                E.check(lib.kd_philox_normal_rows(E.ptr(out), shp[0], out.numel() // shp[0], stage_seeds, sid,
-                                                  E.current_stream()))
-            else:
-                E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), stage_seed, sid, E.current_stream()))
-            return out
-
-        # The engine caches the captured step graph keyed on the device addresses it was captured with.
-        # Per-call tensors are therefore copied into per-(batch, size) buffers that keep their address,
-        # so that e.g. the 64 patches of an ultra-res grid replay one graph per stage instead of
-        # re-capturing it for every patch.
-        io = unet._io_buffers.setdefault((batch, size, device.index), {})
-
-        def stable(name, t):
-            if t is None:
-                return None
-            buf = io.get(name)
-            if buf is None or buf.shape != t.shape:
-                buf = io[name] = torch.empty_like(t)
-            buf.copy_(t)
-            return buf
-
+        f32 = lambda t: _f32(t, device)
+        gauss, key, keys = _stage_noise(lib, noise_fn, seed, stage, device)
+        has_inpaint = exists(inpaint_images) and exists(inpaint_masks)
+        R = resample_times if has_inpaint else 1
+        io = _StageIO(self, unet, batch, size, device, dynamic_threshold=dynamic_threshold, use_graph=use_graph, key=key,
+                      keys=keys, resample_times=R)
+        args = io.args
         with torch.cuda.device(device):
-            lowres = lowres_log_snr = None
             if unet.lowres_cond:
-                t_lr = torch.full((batch,), lowres_level, dtype=torch.float32)
-                ls = self.lowres_noise_schedule.log_snr(t_lr)
+                ls = self.lowres_noise_schedule.log_snr(torch.full((batch,), lowres_level, dtype=torch.float32))
                 a, s = log_snr_to_alpha_sigma(ls)
                 lowres = resize_image_to(prev_img, size) * 2 - 1
                 lowres = (a.to(device)[:, None, None, None] * lowres
                           + s.to(device)[:, None, None, None] * gauss(("lowres", stage), lowres.shape, (16 << 32) | 1))
-                lowres = stable("lowres", lowres.contiguous())
-                lowres_log_snr = stable("lowres_log_snr", ls.to(device))
-            cond = None
+                args.d_lowres = E.ptr(io.put("lowres", lowres.contiguous()))
+                io.lowres_level(ls)
             if exists(cond_images):
                 assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
-                cond = stable("cond", f32(resize_image_to(f32(cond_images), size)))
-            has_inpaint = exists(inpaint_images) and exists(inpaint_masks)
-            R = resample_times if has_inpaint else 1
-            inp = msk = None
+                args.d_cond_images = E.ptr(io.put("cond", f32(resize_image_to(f32(cond_images), size))))
             if has_inpaint:
-                inp = stable("inpaint", f32(resize_image_to(f32(inpaint_images) * 2 - 1, size)))
-                msk = stable("mask", f32(resize_image_to(f32(inpaint_masks)[:, None], size).bool().float()))
-            args = E.kd_sample_args_t()
-            args.dynamic_threshold = int(bool(dynamic_threshold))
-            args.percentile = self.dynamic_thresholding_percentile
-            args.resample_times = R
-            args.d_lowres, args.d_lowres_log_snr, args.d_cond_images = E.ptr(lowres), E.ptr(lowres_log_snr), E.ptr(cond)
-            args.d_inpaint_images, args.d_inpaint_masks = E.ptr(inp), E.ptr(msk)
-            args.seed = stage_seed
-            if per_image:
-                args.seeds = stage_seeds
-            args.use_graph = int(bool(use_graph))
-            if unet.lowres_cond:   # one augmentation level for the whole batch (the library's sample() has no other form):
-                args.lowres_log_snr_uniform = 1          # lets the engine table the time conditioning per schedule step
-                args.lowres_log_snr_value = float(ls[0])
-            args.cond_table = int(getattr(self, "cond_table", 0))   # engine extension: < 0 switches the table off
+                args.d_inpaint_images = E.ptr(io.put("inpaint", f32(resize_image_to(f32(inpaint_images) * 2 - 1, size))))
+                args.d_inpaint_masks = E.ptr(io.put("mask", f32(resize_image_to(f32(inpaint_masks)[:, None], size).bool().float())))
             keep = []
             # x_T = scale * z + (2 * nearest(init_image) - 1), written into the stable buffer by one engine call: z drawn in
             # the kernel (stream (16 << 32) | 2 under the stage's key or keys) or read from the injected tensor
-            img = io.get("img")
-            if img is None or img.shape != shape:
-                img = io["img"] = torch.empty(shape, device=device, dtype=torch.float32)
+            img = io.buf("img", shape)
             z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
             init_image = f32(init_image)
             hs, ws = init_image.shape[2:] if exists(init_image) else (0, 0)
-            E.check(lib.kd_sample_start(E.ptr(img), batch, self.channels, size, self._start_scale(stage), stage_seed,
-                                        stage_seeds if per_image else None, E.ptr(z), E.ptr(init_image), hs, ws,
-                                        E.current_stream()))
+            E.check(lib.kd_sample_start(E.ptr(img), batch, self.channels, size, self._start_scale(stage), key, keys, E.ptr(z),
+                                        E.ptr(init_image), hs, ws, E.current_stream()))
             keep += [z, init_image]
             with_text = exists(text_embeds) and unet.cond_on_text
             h = unet.engine(batch, size, device, with_text=with_text)
-            if with_text:  # step-invariant: pooled text tokens + text hiddens, once per stage
-                tok, hid = unet.text_cond(h, text_embeds, text_masks, drop=False, device=device)
-                tok, hid = stable("text_tokens", tok), stable("text_hiddens", hid)
-                keep += [tok, hid]
-                args.d_text_tokens, args.d_text_hiddens = E.ptr(tok), E.ptr(hid)
-                args.cond_scale = cond_scale
-                if cond_scale != 1.0:  # classifier-free guidance: null conditioning for the second forward
-                    ntok, nhid = unet.text_cond(h, text_embeds, text_masks, drop=True, device=device)
-                    ntok, nhid = stable("null_text_tokens", ntok), stable("null_text_hiddens", nhid)
-                    keep += [ntok, nhid]
-                    args.d_null_text_tokens, args.d_null_text_hiddens = E.ptr(ntok), E.ptr(nhid)
+            if with_text:
+                io.text(h, text_embeds, text_masks, cond_scale)
 
             def stack(kind, T):   # injected noise of every iteration, [T*R, *shape], indexed k*R + (R-1-r)
                 ts = [noise_fn((kind, stage, k, r), shape) for k in range(skip, T) for r in reversed(range(R))]
@@ -1672,47 +1766,20 @@ class Imagen(nn.Module):
             if not dst.is_cuda:
                 raise ValueError(f"into: the canvas must live on the device, got {dst.device}")
             into = (dst, int(oy), int(ox))
-        E.require_gpu()
-        device = torch.device(default(device, self.device))
-        if device.type != "cuda":
-            raise E.EngineUnavailable(f"sampling runs on the HIP engine only; got device {device}")
-        self.eval()
-        assert not (self.condition_on_text and not exists(text_embeds)), "text or text encodings must be passed into imagen if specified"
-        assert not (not self.condition_on_text and exists(text_embeds)), "imagen specified not to be conditioned on text, yet it is presented"
-        assert not (exists(text_embeds) and text_embeds.shape[-1] != self.text_embed_dim), \
-            f"invalid text embedding dimension being passed in (should be {self.text_embed_dim})"
-        if exists(text_embeds):
-            text_masks = default(text_masks, lambda: torch.any(text_embeds != 0.0, dim=-1))
-        lowres_level = default(lowres_sample_noise_level, self.lowres_sample_noise_level)
-        cond_scale = cast_tuple(cond_scale, n)
-        if exists(cond_images) and cond_images.dtype == torch.uint8:
-            cond_images = cond_images.float() / 255.0
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        canvas = None
-        if start_at_unet_number > 1:
-            assert exists(start_image_or_video), "starting image or video must be supplied if only doing upscaling"
+        device, text_masks, cond_images, seed, cond_scale, lowres_level, canvas = self._sampling_setup(
+            device, text_embeds, text_masks, cond_images, seed, cond_scale, lowres_sample_noise_level, start_at_unet_number,
+            start_image_or_video)
+        if exists(canvas):
             g = tiling[start_at_unet_number - 2]
-            canvas = F.interpolate(f32(start_image_or_video), (g["Hc"], g["Wc"]), mode="nearest")
+            canvas = F.interpolate(canvas, (g["Hc"], g["Wc"]), mode="nearest")
         outputs = []
-        for num, unet, geo, sched, obj, dyn, cs, (solver, eta, steps) in zip(
-                range(1, n + 1), self.unets, tiling, self.noise_schedulers, self.pred_objectives, self.dynamic_thresholding,
-                cond_scale, solvers):
-            if num < start_at_unet_number:
-                continue
-            assert not isinstance(unet, NullUnet), "one cannot sample from null / placeholder unets"
-            assert not (cs != 1.0 and not self.condition_on_text), \
-                "imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)"
-            if exists(steps):
-                sched = sched.with_timesteps(steps)
-            canvas = self._tiled_stage(unet, num, geo, sched, obj, dyn, device, canvas, cond_images, lowres_level, noise_fn,
-                                       int(seed), use_graph, int(tile_batch), text_embeds=text_embeds, text_masks=text_masks,
-                                       cond_scale=float(cs), solver=(solver, eta), streamed=bool(streamed), crops=crops,
-                                       into=into if num == last else None)
+        for num, unet, sched, obj, dyn, cs, solver in self._stages(solvers, cond_scale, start_at_unet_number,
+                                                                  stop_at_unet_number):
+            canvas = self._tiled_stage(unet, num, tiling[num - 1], sched, obj, dyn, device, canvas, cond_images, lowres_level,
+                                       noise_fn, int(seed), use_graph, int(tile_batch), text_embeds=text_embeds,
+                                       text_masks=text_masks, cond_scale=cs, solver=solver, streamed=bool(streamed),
+                                       crops=crops, into=into if num == last else None)
             outputs.append(canvas)
-            if exists(stop_at_unet_number) and stop_at_unet_number == num:
-                break
         return outputs if return_all_unet_outputs else outputs[-1]
 
     def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
@@ -1731,30 +1798,17 @@ class Imagen(nn.Module):
         origins = geo["origins"]
         N = len(origins)
         shape = (1, Cn, Hc, Wc)
-        f32 = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        stage_seed = (seed + STAGE_SEED_STRIDE * stage) % (2 ** 64)
+        f32 = lambda t: _f32(t, device)
+        gauss, stage_seed, _ = _stage_noise(lib, noise_fn, seed, stage, device)
         stream = E.current_stream
 
-        def gauss(tag, sid):
-            if exists(noise_fn):
-                return f32(noise_fn(tag, shape))
-            out = torch.empty(shape, device=device, dtype=torch.float32)
-            E.check(lib.kd_philox_normal(E.ptr(out), out.numel(), stage_seed, sid, stream()))
-            return out
-
-        T = sched.num_timesteps
         tables = sched.step_tables()
-        name, eta = solver
-        coefs = canvas_tables(tables, name, eta)
-        tile_tables = {k: tables[k] for k in ("log_snr", "alpha", "sigma", "rn_a", "rn_b")}
-        tile_tables.update(solver_tables(tables, "ddim", eta=0.0))   # the tiles' own iteration: first order, no draw
-        sc = E.kd_solver_schedule_t()
-        sc.T = T
-        for k, v in tile_tables.items():
-            setattr(sc, k, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
+        coefs = canvas_tables(tables, *solver)
+        sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
+        T, tile_steps = sc.T, getattr(lib, sc.steps)
 
         with torch.cuda.device(device):
-            x = gauss(("init", stage), (16 << 32) | 2)
+            x = gauss(("init", stage), shape, (16 << 32) | 2)
             x0bar = torch.zeros(shape, device=device, dtype=torch.float32)
             store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
             thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
@@ -1769,7 +1823,7 @@ class Imagen(nn.Module):
                     lowres_z = f32(noise_fn(("lowres", stage), shape)) if exists(noise_fn) else None
                 else:
                     lowres = F.interpolate(prev_canvas, (Hc, Wc), mode="nearest") * 2 - 1
-                    lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), (16 << 32) | 1)).contiguous()
+                    lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), shape, (16 << 32) | 1)).contiguous()
             cond = cond_shape = None
             if exists(cond_images):
                 assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
@@ -1803,51 +1857,24 @@ class Imagen(nn.Module):
             # one plan, one set of stable buffers and one argument struct per batch size (the full chunks' and the ragged one's)
             plans = {}
             for b in sorted({min(tile_batch, N - n0) for n0 in range(0, N, tile_batch)}):
-                io = unet._io_buffers.setdefault((b, S, device.index), {})
-
-                def buf(key, shp, io=io):
-                    t = io.get(key)
-                    if t is None or tuple(t.shape) != tuple(shp):
-                        t = io[key] = torch.empty(shp, device=device, dtype=torch.float32)
-                    return t
-
-                args = E.kd_sample_args_t()
-                args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
-                args.dynamic_threshold = int(bool(dynamic_threshold))
-                args.percentile = self.dynamic_thresholding_percentile
-                args.resample_times = 1
-                args.seed = stage_seed   # (DDIM(0) draws nothing)
-                args.use_graph = int(bool(use_graph))
-                args.cond_table = int(getattr(self, "cond_table", 0))
-                p = dict(img=buf("img", (b, Cn, S, S)), args=args)
+                io = _StageIO(self, unet, b, S, device, dynamic_threshold=dynamic_threshold, use_graph=use_graph,
+                              key=stage_seed)   # (DDIM(0) draws nothing)
+                args = io.args
+                args.objective = _OBJECTIVES[objective]
+                p = plans[b] = dict(io=io, args=args, img=io.buf("img", (b, Cn, S, S)))
                 if unet.lowres_cond:
-                    p["lowres"] = buf("lowres", (b, Cn, S, S))
-                    lls = buf("lowres_log_snr", (b,))
-                    lls.copy_(ls.to(device).expand(b))
-                    args.d_lowres, args.d_lowres_log_snr = E.ptr(p["lowres"]), E.ptr(lls)
-                    args.lowres_log_snr_uniform = 1
-                    args.lowres_log_snr_value = float(ls[0])
+                    p["lowres"] = io.buf("lowres", (b, Cn, S, S))
+                    args.d_lowres = E.ptr(p["lowres"])
+                    io.lowres_level(ls)
                 if exists(cond_shape):
-                    p["cond"] = buf("cond", (b,) + cond_shape)
+                    p["cond"] = io.buf("cond", (b,) + cond_shape)
                     args.d_cond_images = E.ptr(p["cond"])
                 if unet.self_cond:
-                    p["self_cond"] = buf("tile_self_cond", (b, Cn, S, S))
+                    p["self_cond"] = io.buf("tile_self_cond", (b, Cn, S, S))
                 h = p["h"] = unet.engine(b, S, device, with_text=with_text)
                 if with_text:   # one row for the canvas, given to every tile of the chunk
                     rows = lambda t: None if t is None else t.expand(b, *t.shape[1:])
-                    for drop, keys in ((False, ("text_tokens", "text_hiddens")), (True, ("null_text_tokens", "null_text_hiddens"))):
-                        if drop and cond_scale == 1.0:
-                            continue
-                        tok, hid = unet.text_cond(h, rows(text_embeds), rows(text_masks), drop=drop, device=device)
-                        bt, bh = buf(keys[0], tok.shape), buf(keys[1], hid.shape)
-                        bt.copy_(tok)
-                        bh.copy_(hid)
-                        if drop:
-                            args.d_null_text_tokens, args.d_null_text_hiddens = E.ptr(bt), E.ptr(bh)
-                        else:
-                            args.d_text_tokens, args.d_text_hiddens = E.ptr(bt), E.ptr(bh)
-                    args.cond_scale = cond_scale
-                plans[b] = p
+                    io.text(h, rows(text_embeds), rows(text_masks), cond_scale)
 
             for k in range(T):
                 for n0 in range(0, N, tile_batch):
@@ -1865,8 +1892,7 @@ class Imagen(nn.Module):
                     if unet.self_cond and k > 0:   # the carry is the FUSED estimate of step k - 1 (step 0 starts from zeros)
                         gather(x0bar, p["self_cond"], n0, b)
                         E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
-                    E.check(lib.kd_solver_sample_steps(p["h"], C.byref(sc), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1,
-                                                       stream()))
+                    E.check(tile_steps(p["h"], C.byref(sc.struct), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1, stream()))
                     E.check(lib.kd_sample_last(p["h"], 1, E.ptr(store[n0:n0 + b]), stream()))
                     if dynamic_threshold:
                         E.check(lib.kd_sample_last(p["h"], 2, E.ptr(thr[n0:n0 + b]), stream()))
@@ -1907,41 +1933,17 @@ class Imagen(nn.Module):
         p_sample_loop over the steps skip .. T - 1, its update the ancestral one or that of `solver` = (name, eta).
         `stack(kind, T)` gives the injected noise of a kind (None: on-device Philox).  A self-conditioned plan starts step
         `skip` > 0 from zeros, as step 0 does by itself."""
-        T = sched.num_timesteps
-        tables = sched.step_tables()
         name, eta = solver
-        if name == "ddpm":
-            sc = E.kd_schedule_t()
-            steps_fn, loop_fn = lib.kd_sample_steps, lib.kd_sample_loop
-        else:   # the solver's coefficients in place of the ancestral step's; its own entries, tables and step graph
-            coefs = solver_tables(tables, name, eta=eta, skip=skip)
-            tables = {n: tables[n] for n in ("log_snr", "alpha", "sigma", "rn_a", "rn_b")}
-            tables.update(coefs)
-            sc = E.kd_solver_schedule_t()
-            steps_fn, loop_fn = lib.kd_solver_sample_steps, lib.kd_solver_sample_loop
-        sc.T = T
-        for n, v in tables.items():
-            setattr(sc, n, v.numpy().ctypes.data_as(C.POINTER(C.c_float)))
-        args.objective = {"noise": 0, "v": 1, "x_start": 2}[objective]
+        sc = _StepSchedule(sched.step_tables(), name, eta, skip)
+        args.objective = _OBJECTIVES[objective]
         if exists(stack):
             if name == "ddpm" or (name == "ddim" and eta > 0):   # DDIM(0) and 2M draw nothing in the step
-                args.d_noise_step = stack("step", T)
+                args.d_noise_step = stack("step", sc.T)
             if has_inpaint:
-                args.d_noise_inpaint = stack("inpaint", T)
+                args.d_noise_inpaint = stack("inpaint", sc.T)
                 if R > 1:
-                    args.d_noise_renoise = stack("renoise", T)
-        if skip > 0 and self_cond:
-            E.check(lib.kd_sample_set_self_cond(h, None, E.current_stream()))
-        if exists(trace):
-            for k in range(skip, T):
-                E.check(steps_fn(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
-                trace.append(img.clone())
-            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
-        elif skip > 0:
-            E.check(steps_fn(h, C.byref(sc), C.byref(args), E.ptr(img), skip, T, E.current_stream()))
-            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
-        else:
-            E.check(loop_fn(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
+                    args.d_noise_renoise = stack("renoise", sc.T)
+        _walk(lib, sc, h, args, img, skip=skip, trace=trace, self_cond=self_cond)
 
 
 # ============================================================================ ElucidatedImagen (EDM)
@@ -2036,25 +2038,9 @@ class ElucidatedImagen(Imagen):
         kd_sample_start wrote it: per step skip .. N - 1 churn, a preconditioned forward and the Euler step, and (not on
         the last step) a second forward and the Heun correction; RePaint re-noise between resamples.  Noise tags
         ("churn" | "renoise", stage, k, r)."""
-        tab = self.step_tables(stage)
-        N = self.hparams[stage - 1]["num_sample_steps"]
-        sc = E.kd_edm_schedule_t()
-        sc.N, sc.S_noise = N, float(self.hparams[stage - 1]["S_noise"])
-        for name, _ in E.kd_edm_schedule_t._fields_[2:]:
-            setattr(sc, name, tab[name].numpy().ctypes.data_as(C.POINTER(C.c_float)))
+        sc = _StepSchedule.edm(self.step_tables(stage), self.hparams[stage - 1]["S_noise"])
         if exists(stack):
-            args.d_noise_step = stack("churn", N)
+            args.d_noise_step = stack("churn", sc.T)
             if has_inpaint and R > 1:
-                args.d_noise_renoise = stack("renoise", N)
-        if skip > 0 and self_cond:
-            E.check(lib.kd_sample_set_self_cond(h, None, E.current_stream()))
-        if exists(trace):
-            for k in range(skip, N):
-                E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), k, k + 1, E.current_stream()))
-                trace.append(img.clone())
-            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
-        elif skip > 0:
-            E.check(lib.kd_edm_sample_steps(h, C.byref(sc), C.byref(args), E.ptr(img), skip, N, E.current_stream()))
-            E.check(lib.kd_sample_finalize(h, C.byref(args), E.ptr(img), E.current_stream()))
-        else:
-            E.check(lib.kd_edm_sample_loop(h, C.byref(sc), C.byref(args), E.ptr(img), E.current_stream()))
+                args.d_noise_renoise = stack("renoise", sc.T)
+        _walk(lib, sc, h, args, img, skip=skip, trace=trace, self_cond=self_cond)

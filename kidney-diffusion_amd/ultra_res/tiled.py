@@ -12,6 +12,37 @@ import torch.nn.functional as F
 from . import grid as G
 
 
+def _check_stages(stages, from_one):   # -> a tuple of ints: consecutive unet numbers, ascending, from 1 with `from_one`
+    stages = tuple(int(s) for s in stages)
+    if not stages or (stages[0] != 1 if from_one else stages[0] < 1) or any(b != a + 1 for a, b in zip(stages, stages[1:])):
+        raise ValueError(f"stages must be consecutive unet numbers {'from 1 ' if from_one else ''}in ascending order, got {stages}")
+    return stages
+
+
+def _per_unet(v, default, n):   # {stage: value} -> one entry per unet 1 .. n (`default` where left out); anything else as it is
+    return tuple(v.get(s, default) for s in range(1, n + 1)) if isinstance(v, dict) else v
+
+
+def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, **kw):
+    """`canvas` through `stages`, one `sample_tiled(**kw)` call of `load_imagen(stage)` each; `solver = (sampler, sampler_eta,
+    sample_steps)`; `first_stage(geometry of the last stage, device)` returns the last stage's `into`."""
+    from imagen_pytorch.imagen_pytorch import normalize_tiling
+    device = torch.device(device if device is not None else "cuda")
+    for stage in stages:
+        imagen = load_imagen(stage)
+        n = len(imagen.unets)
+        if stage == stages[0]:   # the geometry is checked before anything moves to the device
+            if stages[-1] > n:
+                raise ValueError(f"stages={stages} name unet {stages[-1]}, the Imagen holds {n}")
+            tiling = normalize_tiling(imagen.image_sizes, kw["grid"], kw["overlap"], kw["present"], kw["tile_weights"])
+            into = first_stage(tiling[stages[-1] - 1], device) if first_stage else None
+        sampler, eta, steps = (_per_unet(v, d, n) for v, d in zip(solver, (None, 0.0, None)))
+        canvas = imagen.to(device).sample_tiled(sampler=sampler, sampler_eta=eta, sample_steps=steps, start_at_unet_number=stage,
+                                                stop_at_unet_number=stage, start_image_or_video=canvas, device=device,
+                                                into=into if stage == stages[-1] else None, **kw)
+    return canvas
+
+
 def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None, grid: Optional[Sequence[int]] = None,
                  overlap: float = 0.25, stages: Sequence[int] = (1, 2, 3), tile_batch: int = 16, sampler=None, sampler_eta=0.0,
                  sample_steps=None, seed: Optional[int] = None, cond_images: Optional[torch.Tensor] = None, present=None,
@@ -29,35 +60,16 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
     A single process: the tiles of one canvas meet in every schedule step (the fused estimate needs all of them), so
     spreading them over ranks would take an exchange per step - out of scope here.  Independent canvases can run on
     different ranks as they are."""
-    from imagen_pytorch.imagen_pytorch import normalize_tiling
-
     if (num_patches_width is None) == (grid is None):
         raise ValueError(f"fused_canvas takes num_patches_width or grid, one of them; got num_patches_width={num_patches_width!r}, "
                          f"grid={grid!r}")
     grid = (num_patches_width, num_patches_width) if grid is None else tuple(grid)
-    stages = tuple(int(s) for s in stages)
-    if not stages or stages[0] < 1 or any(b != a + 1 for a, b in zip(stages, stages[1:])):
-        raise ValueError(f"stages must be consecutive unet numbers in ascending order, got {stages}")
+    stages = _check_stages(stages, from_one=False)
     if stages[0] > 1 and start_canvas is None:
         raise ValueError(f"stages={stages} begin at unet {stages[0]}: start_canvas, the canvas of unet {stages[0] - 1}, is needed")
-    device = torch.device(device if device is not None else "cuda")
-    cache = {}
-    canvas = start_canvas
-    for stage in stages:
-        imagen = cache[stage] = load_imagen(stage)
-        n = len(imagen.unets)
-        if stage == stages[0]:   # the geometry is checked before anything moves to the device
-            if stages[-1] > n:
-                raise ValueError(f"stages={stages} name unet {stages[-1]}, the Imagen holds {n}")
-            normalize_tiling(imagen.image_sizes, grid, overlap, present, tile_weights)
-        per_unet = lambda v, d: tuple(v.get(s, d) for s in range(1, n + 1)) if isinstance(v, dict) else v
-        imagen = cache[stage] = imagen.to(device)
-        canvas = imagen.sample_tiled(grid, overlap=overlap, present=present, tile_batch=tile_batch, tile_weights=tile_weights,
-                                     cond_images=cond_images, sampler=per_unet(sampler, None),
-                                     sampler_eta=per_unet(sampler_eta, 0.0), sample_steps=per_unet(sample_steps, None),
-                                     seed=seed, noise_fn=noise_fn, use_graph=use_graph, start_at_unet_number=stage,
-                                     stop_at_unet_number=stage, start_image_or_video=canvas, device=device)
-    return canvas
+    return _run_stages(load_imagen, stages, device, start_canvas, (sampler, sampler_eta, sample_steps), grid=grid, overlap=overlap,
+                       present=present, tile_batch=tile_batch, tile_weights=tile_weights, cond_images=cond_images, seed=seed,
+                       noise_fn=noise_fn, use_graph=use_graph)
 
 
 def level_box(positions: Sequence[G.Pos]):
@@ -104,11 +116,9 @@ def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridG
     last one writes its covered pixels `into` the full canvas at the box' corner.  `fill_color` None: 0 for 'airs', else
     0.95.  `geom.out_patch_dist` and `geom.canvas_width` must be the stride and the full lattice of the last stage
     (ValueError otherwise).  `load_imagen`, `stages` (from 1), `sampler`, `sampler_eta`, `sample_steps`: as `fused_canvas`."""
-    from imagen_pytorch.imagen_pytorch import TileCondCrops, normalize_tiling
+    from imagen_pytorch.imagen_pytorch import TileCondCrops
 
-    stages = tuple(int(s) for s in stages)
-    if not stages or stages[0] != 1 or any(b != a + 1 for a, b in zip(stages, stages[1:])):
-        raise ValueError(f"stages must be consecutive unet numbers from 1 in ascending order, got {stages}")
+    stages = _check_stages(stages, from_one=True)
     if zoomed_image.dim() != 4 or zoomed_image.shape[0] != 1 or zoomed_image.shape[2] != zoomed_image.shape[3]:
         raise ValueError(f"zoomed_image must be one square image [1, C, W, W], got {tuple(zoomed_image.shape)}")
     width = int(geom.canvas_width)
@@ -128,29 +138,18 @@ def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridG
         fill_color = 0.0 if version == "airs" else 0.95  # sample_ultra_res.py:374-377
     crops = TileCondCrops(zoomed_image, shifts, int(window), float(fill_color),
                           centre_width=geom.patch_width if version == "v2" else None)
-    device = torch.device(device if device is not None else "cuda")
-    full = canvas = None
-    for stage in stages:
-        imagen = load_imagen(stage)
-        n_unets = len(imagen.unets)
-        if stage == stages[0]:   # the geometry is checked before anything moves to the device
-            if stages[-1] > n_unets:
-                raise ValueError(f"stages={stages} name unet {stages[-1]}, the Imagen holds {n_unets}")
-            last = normalize_tiling(imagen.image_sizes, grid, overlap, present, tile_weights)[stages[-1] - 1]
-            S, st = last["S"], last["st"]
-            if geom.out_patch_dist != st or width != (n - 1) * st + S:
-                raise ValueError(f"geom (out_patch_dist={geom.out_patch_dist}, canvas_width={width}, {n} patches wide) is not the "
-                                 f"lattice of unet {stages[-1]}: stride st={st}, canvas (n - 1) st + S = {(n - 1) * st + S}")
-            crops.checked(len(tiles))
-            crops.image = zoomed_image = zoomed_image.to(device)   # moved once, for the background and every stage
-            full = level_background(zoomed_image.float(), width) if background else \
-                torch.zeros(1, zoomed_image.shape[1], width, width, device=device, dtype=torch.float32)
-        per_unet = lambda v, d: tuple(v.get(s, d) for s in range(1, n_unets + 1)) if isinstance(v, dict) else v
-        imagen = imagen.to(device)
-        canvas = imagen.sample_tiled(grid, overlap=overlap, present=present, tile_batch=tile_batch, tile_weights=tile_weights,
-                                     cond_crops=crops, sampler=per_unet(sampler, None), sampler_eta=per_unet(sampler_eta, 0.0),
-                                     sample_steps=per_unet(sample_steps, None), seed=seed, noise_fn=noise_fn,
-                                     use_graph=use_graph, start_at_unet_number=stage, stop_at_unet_number=stage,
-                                     start_image_or_video=canvas, device=device, streamed=True,
-                                     into=(full, r0 * st, c0 * st) if stage == stages[-1] else None)
-    return canvas
+
+    def first_stage(last, device):
+        S, st = last["S"], last["st"]
+        if geom.out_patch_dist != st or width != (n - 1) * st + S:
+            raise ValueError(f"geom (out_patch_dist={geom.out_patch_dist}, canvas_width={width}, {n} patches wide) is not the "
+                             f"lattice of unet {stages[-1]}: stride st={st}, canvas (n - 1) st + S = {(n - 1) * st + S}")
+        crops.checked(len(tiles))
+        crops.image = zoomed = zoomed_image.to(device)   # moved once, for the background and every stage
+        full = level_background(zoomed.float(), width) if background else \
+            torch.zeros(1, zoomed.shape[1], width, width, device=device, dtype=torch.float32)
+        return full, r0 * st, c0 * st
+
+    return _run_stages(load_imagen, stages, device, None, (sampler, sampler_eta, sample_steps), first_stage, grid=grid,
+                       overlap=overlap, present=present, tile_batch=tile_batch, tile_weights=tile_weights, cond_crops=crops,
+                       seed=seed, noise_fn=noise_fn, use_graph=use_graph, streamed=True)
