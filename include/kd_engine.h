@@ -58,7 +58,9 @@ const char* kd_last_error(void);
  *      `final_resnet_block`, `scale_skip_connection`) - kd_unet_create_ext3 is that call with ext4 = NULL - and
  *      kd_final_conv_k_nchw, kd_init_conv_plain_nchw added; kd_tiles_gather and kd_tiles_fuse_update added (fused-tile
  *      canvas sampling); kd_tiles_cond_gather, kd_tiles_gather_lowres and kd_tiles_finalize added (a fused-tile stage at the
- *      sizes of a magnification level) */
+ *      sizes of a magnification level); kd_tiles_start, kd_tiles_fuse_update_known and kd_tiles_finalize_known with their
+ *      structs kd_tiles_image_t and kd_tiles_mask_t added (a fused-tile canvas that keeps known pixels or starts from an image);
+ *      kd_sample_args_t gained `keep_self_cond` at its end (zero = the reset at step 0 of before) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -375,6 +377,10 @@ typedef struct kd_sample_args {
    * image, so it draws bit for bit what a batch-1 call with seed = seeds[b] draws; `seed` is then not read.  Keys and
    * mode live in device memory: the captured step graph serves an int seed, a seed list and any values of either. */
   const uint64_t* seeds;
+  /* != 0: a kd_*_sample_steps call that begins at step 0 keeps the self-conditioning carry the plan holds (what
+   * kd_sample_set_self_cond left) instead of starting from zeros - a caller that walks the resample slots of step 0 one
+   * call each.  0 (a zero-initialised struct): step 0 starts from zeros, as before. */
+  int keep_self_cond;
 } kd_sample_args_t;
 
 /* Philox stream ids (the `stream_id` of kd_philox_normal; what the sampler draws when a d_noise_* pointer is NULL):
@@ -875,6 +881,61 @@ int kd_tiles_gather_lowres(const float* d_prev, int Hp, int Wp, float* d_tiles, 
  * canvas inside d_out and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
 int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
                       int Wo, int oy, int ox, void* stream);
+
+/* A canvas that keeps known pixels (RePaint mixing at the level of the canvas) or starts from an image: three
+ * memory-bound kernels in the conventions of the ones above.  The Python package: Imagen.sample_tiled(known_image=,
+ * known_mask=, known_resample_times=, init_canvas=, init_skip_steps=), ultra_res.tiled.fused_level(canvas=, keep=).
+ * A source - the known image, the init image, the mask - is described, not copied: base, size and strides in ELEMENTS, so a
+ * window of a larger canvas is passed as it lies.  It is seen at the canvas' size [Hc, Wc] through torch's nearest rule as
+ * kd_sample_start states it, sy = min((int)floorf((float)y * ((float)H / (float)Hc)), H - 1).  Where H == Hc, W == Wc, the
+ * strides are multiples of 4 and the base is aligned (16 bytes the image, 4 the mask) a thread's four x are one load;
+ * otherwise they are gathered one by one.  row_stride >= W and plane_stride >= 0 are required; that base and strides stay
+ * inside the caller's allocation is the caller's to see to. */
+typedef struct kd_tiles_image {   /* [C, H, W] fp32 */
+  const float* d;
+  int H, W;
+  int64_t row_stride, plane_stride;
+} kd_tiles_image_t;
+typedef struct kd_tiles_mask {   /* [H, W] uint8, non-zero = known */
+  const unsigned char* d;
+  int H, W;
+  int64_t row_stride;
+} kd_tiles_mask_t;
+/* The mix of one resample slot, x = m ? a (2 kn - 1) + s z : x, with a, s = alpha, sigma of the slot's step; op order 2 v,
+ * - 1, a *, s z, the sum, without contraction; s == 0 leaves the term out, operand unread.  z is read from d_mix_noise
+ * [C,Hc,Wc] or, when it is NULL, is the canvas element of Philox stream mix_stream_id under `seed`; a float4 whose four
+ * mask bytes are clear draws none.  `known` and `mask` come together; both NULL: no mix. */
+/* x of a stage in one launch over a rectangular canvas d_x [C,Hc,Wc] (kd_sample_start is square and per batch row):
+ *     x = scale z [+ (2 nearest(init) - 1)],  then [the mix]
+ * z is read from d_noise or is the canvas element of Philox stream (16 << 32) | 2 under `seed`; with init, known and mask
+ * NULL and scale 1 the bits of kd_philox_normal over C Hc Wc elements.  Needs Wc % 4 == 0 and 16-byte aligned d_x and
+ * noise tensors (refused with an error, nothing launched, otherwise). */
+int kd_tiles_start(float* d_x, int C, int Hc, int Wc, float scale, const float* d_noise, uint64_t seed,
+                   const kd_tiles_image_t* init, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a,
+                   float mix_s, const float* d_mix_noise, uint64_t mix_stream_id, void* stream);
+/* kd_tiles_fuse_update and, on the same pixel in the same pass, [the re-noise x = x rn_a + z rn_b] (renoise != 0; z from
+ * d_rn_noise or Philox stream rn_stream_id) then [the mix of the NEXT slot]: a step with known pixels stays one canvas pass.
+ * Bit for bit kd_tiles_fuse_update followed by the two expressions; with renoise == 0 and no mask, kd_tiles_fuse_update's
+ * bits.  d_hist (read only when P != 0) and d_x0bar_out are given apart and may be one buffer (kd_tiles_fuse_update's in-place
+ * form); DPM-Solver++(2M) under resampling keeps them apart, the history taking a step's estimate in its last slot only.
+ * A zero coefficient leaves its operand unread.  A float4 whose four mask bytes are all set is known after the mix
+ * whatever the update gives: d_x is not read and the update draws nothing there; d_x0bar_out is written all the same.  A
+ * pixel that no present tile covers is left untouched in every buffer.  Preconditions: kd_tiles_fuse_update's, d_x apart
+ * from d_hist and d_x0bar_out. */
+int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_out, const float* d_x0_tiles, const float* d_thr,
+                               const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                               float P, float Sn, const float* d_noise, uint64_t seed, uint64_t stream_id, int renoise,
+                               float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
+                               const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
+                               const float* d_mix_noise, uint64_t mix_stream_id, void* stream);
+/* kd_tiles_finalize with the paste: d_out[c, oy + y, ox + x] = m ? kn : (clamp(x, -1, 1) + 1) * 0.5 on covered pixels,
+ * every other element of d_out untouched.  A known pixel is the known image's value copied, not round-tripped through
+ * 2 v - 1.  `known` may be the window of d_out that is written (base d_out + oy Wo + ox, size [Hc, Wc], strides Wo and
+ * Ho Wo): every thread then reads and writes the same element.  A known image that overlaps d_out in any other way is
+ * refused.  Preconditions: kd_tiles_finalize's. */
+int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
+                            int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
+                            void* stream);
 
 #ifdef __cplusplus
 }

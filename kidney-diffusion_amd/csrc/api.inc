@@ -1220,5 +1220,45 @@ int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int 
                       int Wo, int oy, int ox, void* stream) {
   return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, (hipStream_t)stream);
 }
+// the C structs of the canvas sources as the launchers take them; a NULL source stays NULL
+static const TileImage* tile_image_of(const kd_tiles_image_t* in, TileImage* out) {
+  if (!in) return nullptr;
+  *out = TileImage{in->d, in->H, in->W, in->row_stride, in->plane_stride};
+  return out;
+}
+static const TileMask* tile_mask_of(const kd_tiles_mask_t* in, TileMask* out) {
+  if (!in) return nullptr;
+  *out = TileMask{in->d, in->H, in->W, in->row_stride};
+  return out;
+}
+int kd_tiles_start(float* d_x, int C, int Hc, int Wc, float scale, const float* d_noise, uint64_t seed,
+                   const kd_tiles_image_t* init, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a,
+                   float mix_s, const float* d_mix_noise, uint64_t mix_stream_id, void* stream) {
+  TileImage in, kn;
+  TileMask mk;
+  const TileMix mix{tile_image_of(known, &kn), tile_mask_of(mask, &mk), mix_a, mix_s, d_mix_noise, mix_stream_id};
+  return launch_tiles_start(d_x, C, Hc, Wc, scale, d_noise, seed, tile_image_of(init, &in), mix, (hipStream_t)stream);
+}
+int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_out, const float* d_x0_tiles, const float* d_thr,
+                               const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                               float P, float Sn, const float* d_noise, uint64_t seed, uint64_t stream_id, int renoise,
+                               float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
+                               const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
+                               const float* d_mix_noise, uint64_t mix_stream_id, void* stream) {
+  TileImage kn;
+  TileMask mk;
+  const TileMix mix{tile_image_of(known, &kn), tile_mask_of(mask, &mk), mix_a, mix_s, d_mix_noise, mix_stream_id};
+  return launch_tiles_fuse_update_known(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
+                                        Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
+                                        (hipStream_t)stream);
+}
+int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
+                            int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
+                            void* stream) {
+  TileImage kn;
+  TileMask mk;
+  return launch_tiles_finalize_known(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
+                                     tile_mask_of(mask, &mk), (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -466,5 +466,38 @@ int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, 
                                hipStream_t st);
 int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
                           int Wo, int oy, int ox, hipStream_t s);
+// a canvas that keeps known pixels or starts from an image.  A source is seen at the canvas' size through torch's nearest
+// rule (launch_sample_start's); strides in elements, so a window of a larger tensor is passed without a copy.
+struct TileImage {   // [C, H, W] fp32
+  const float* d;
+  int H, W;
+  int64_t row, plane;
+};
+struct TileMask {   // [H, W] uint8, non-zero = known
+  const unsigned char* d;
+  int H, W;
+  int64_t row;
+};
+// the mix x = m ? a (2 kn - 1) + s z : x  (known == nullptr: none); z from `noise` or Philox stream `sid` by canvas element
+struct TileMix {
+  const TileImage* known;
+  const TileMask* mask;
+  float a, s;
+  const float* noise;
+  uint64_t sid;
+};
+// x [C, Hc, Wc] = scale z [+ (2 init - 1)], then the mix; z from `noise` or stream (16 << 32) | 2 under `seed`
+int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float* noise, uint64_t seed, const TileImage* init,
+                       const TileMix& mix, hipStream_t s);
+// launch_tiles_fuse_update with hist (read when P != 0) and x0bar_out apart (they may alias), then on the same pixel
+// [x = x rn_a + z rn_b] (renoise != 0) and [the mix]
+int launch_tiles_fuse_update_known(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
+                                   const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                                   float P, float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise,
+                                   float rn_a, float rn_b, const float* rn_noise, uint64_t rn_sid, const TileMix& mix,
+                                   hipStream_t s);
+// launch_tiles_finalize with the paste: out = m ? kn : (clamp(x, -1, 1) + 1) / 2 on covered pixels
+int launch_tiles_finalize_known(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out,
+                                int Ho, int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s);
 
 }  // namespace kd

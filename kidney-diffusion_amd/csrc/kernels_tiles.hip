@@ -106,6 +106,64 @@ static int tile_lattice(const std::string& who, int N, int C, int S, int st, int
   return 0;
 }
 
+// The covering slots of the float4 at (y, xx): rows r_lo .. r_hi, columns q_lo .. q_hi of the lattice.
+struct TileCover {
+  int r_lo, r_hi, q_lo, q_hi;
+};
+__device__ __forceinline__ TileCover tile_cover(const TileGeom& g, int y, int xx) {
+  return TileCover{y < g.S ? 0 : (y - g.S) / g.st + 1, min(y / g.st, g.ny - 1), xx < g.S ? 0 : (xx - g.S) / g.st + 1,
+                   min(xx / g.st, g.nx - 1)};
+}
+// x0bar of the float4 at (c, y, xx) into xb; false when no present tile covers it (xb is then not written).
+__device__ __forceinline__ bool fuse_tiles(const float* __restrict__ x0_tiles, const float* __restrict__ thr,
+                                           const int* __restrict__ tile_of, const TileGeom& g, int c, int y, int xx, f32x4& xb) {
+  const TileCover cv = tile_cover(g, y, xx);
+  const int64_t tile_plane = (int64_t)g.S * g.S;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f}, wsum = {0.f, 0.f, 0.f, 0.f};
+  bool covered = false;
+  for (int r = cv.r_lo; r <= cv.r_hi; ++r) {
+    const int ly = y - r * g.st;
+    const float wy = g.ramp ? ramp_weight(ly, g.S, g.ov) : 1.0f;
+    for (int q = cv.q_lo; q <= cv.q_hi; ++q) {
+      const int t = tile_of[r * g.nx + q];
+      if (t < 0 || t >= g.N) continue;
+      covered = true;
+      const int lx = xx - q * g.st;
+      const float s = thr ? fmaxf(thr[t], 1.0f) : 1.0f;
+      const f32x4 v = *(const f32x4*)(x0_tiles + ((int64_t)t * g.C + c) * tile_plane + (int64_t)ly * g.S + lx);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xs = fminf(fmaxf(v[e], -s), s) / s;
+        const float w = g.ramp ? wy * ramp_weight(lx + e, g.S, g.ov) : 1.0f;
+        acc[e] = acc[e] + w * xs;
+        wsum[e] = wsum[e] + w;
+      }
+    }
+  }
+  if (!covered) return false;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) xb[e] = acc[e] / wsum[e];
+  return true;
+}
+// The update of the float4 j4: A x + B x0bar [+ P hist] [+ Sn z].
+__device__ __forceinline__ f32x4 canvas_update(const f32x4& xv, const f32x4& xb, const float* hist, int64_t j4, float A, float B,
+                                               float P, float Sn, const float* __restrict__ noise, uint64_t seed, uint64_t sid) {
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = A * xv[e] + B * xb[e];
+  if (P != 0.0f) {
+    const f32x4 hv = *(const f32x4*)(hist + j4 * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = o[e] + P * hv[e];
+  }
+  if (Sn != 0.0f) {
+    const f32x4 z = noise ? *(const f32x4*)(noise + j4 * 4) : philox_normal4(seed, sid, (uint64_t)j4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = o[e] + Sn * z[e];
+  }
+  return o;
+}
+
 __global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, float* __restrict__ x0bar,
                                                                 const float* __restrict__ x0_tiles,
                                                                 const float* __restrict__ thr, const int* __restrict__ tile_of,
@@ -115,52 +173,13 @@ __global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restric
   const int xq = blockIdx.x * 256 + threadIdx.x;
   if (xq >= W4) return;
   const int xx = 4 * xq;
-  // covering slot columns: q st <= xx < q st + S
-  const int q_hi = min(xx / g.st, g.nx - 1), q_lo = xx < g.S ? 0 : (xx - g.S) / g.st + 1;
   const int rows = g.C * g.Hc;
-  const int64_t tile_plane = (int64_t)g.S * g.S;
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int c = row / g.Hc, y = row - c * g.Hc;
-    const int r_hi = min(y / g.st, g.ny - 1), r_lo = y < g.S ? 0 : (y - g.S) / g.st + 1;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, wsum = {0.f, 0.f, 0.f, 0.f};
-    bool covered = false;
-    for (int r = r_lo; r <= r_hi; ++r) {
-      const int ly = y - r * g.st;
-      const float wy = g.ramp ? ramp_weight(ly, g.S, g.ov) : 1.0f;
-      for (int q = q_lo; q <= q_hi; ++q) {
-        const int t = tile_of[r * g.nx + q];
-        if (t < 0 || t >= g.N) continue;
-        covered = true;
-        const int lx = xx - q * g.st;
-        const float s = thr ? fmaxf(thr[t], 1.0f) : 1.0f;
-        const f32x4 v = *(const f32x4*)(x0_tiles + ((int64_t)t * g.C + c) * tile_plane + (int64_t)ly * g.S + lx);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float xs = fminf(fmaxf(v[e], -s), s) / s;
-          const float w = g.ramp ? wy * ramp_weight(lx + e, g.S, g.ov) : 1.0f;
-          acc[e] = acc[e] + w * xs;
-          wsum[e] = wsum[e] + w;
-        }
-      }
-    }
-    if (!covered) continue;
+    f32x4 xb;
+    if (!fuse_tiles(x0_tiles, thr, tile_of, g, c, y, xx, xb)) continue;
     const int64_t j4 = (int64_t)row * W4 + xq;
-    f32x4 xv = *(const f32x4*)(x + j4 * 4), xb, o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      xb[e] = acc[e] / wsum[e];
-      o[e] = A * xv[e] + B * xb[e];
-    }
-    if (P != 0.0f) {
-      const f32x4 hv = *(const f32x4*)(x0bar + j4 * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = o[e] + P * hv[e];
-    }
-    if (Sn != 0.0f) {
-      const f32x4 z = noise ? *(const f32x4*)(noise + j4 * 4) : philox_normal4(seed, sid, (uint64_t)j4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = o[e] + Sn * z[e];
-    }
+    const f32x4 o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, x0bar, j4, A, B, P, Sn, noise, seed, sid);
     *(f32x4*)(x + j4 * 4) = o;
     *(f32x4*)(x0bar + j4 * 4) = xb;
   }
@@ -359,6 +378,289 @@ int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int 
   const int64_t rows = C * Hc;
   hipLaunchKernelGGL(tiles_finalize_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
                      dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- known pixels and an image start
+// A canvas that keeps known pixels (RePaint at the level of the canvas) or starts from an image.  The known image, the init
+// image and the mask are read at the canvas' size through the nearest rule of tiles_gather_lowres_kernel; a source is a
+// base with strides, so a window of a level is read in place.  `vec`: source and canvas sizes agree and base and strides
+// are aligned - the thread's four x are one 16-byte (image) or 4-byte (mask) load; otherwise scalar gathers.
+struct ImgSrc {
+  const float* d;
+  int H, W;
+  int64_t row, plane;
+  float ry, rx;
+  int vec;
+};
+struct MaskSrc {
+  const unsigned char* d;
+  int H, W;
+  int64_t row;
+  float ry, rx;
+  int vec;
+};
+__device__ __forceinline__ f32x4 src_image4(const ImgSrc& s, int c, int y, int xx) {
+  if (s.vec) return *(const f32x4*)(s.d + (int64_t)c * s.plane + (int64_t)y * s.row + xx);
+  const int sy = min((int)floorf((float)y * s.ry), s.H - 1);
+  const float* line = s.d + (int64_t)c * s.plane + (int64_t)sy * s.row;
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = line[min((int)floorf((float)(xx + e) * s.rx), s.W - 1)];
+  return v;
+}
+// byte e of the word: the mask of x = xx + e
+__device__ __forceinline__ uint32_t src_mask4(const MaskSrc& m, int y, int xx) {
+  if (m.vec) return *(const uint32_t*)(m.d + (int64_t)y * m.row + xx);
+  const int sy = min((int)floorf((float)y * m.ry), m.H - 1);
+  const unsigned char* line = m.d + (int64_t)sy * m.row;
+  uint32_t w = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) w |= (uint32_t)line[min((int)floorf((float)(xx + e) * m.rx), m.W - 1)] << (8 * e);
+  return w;
+}
+__device__ __forceinline__ bool mask_at(uint32_t w, int e) { return ((w >> (8 * e)) & 0xffu) != 0; }
+__device__ __forceinline__ bool mask_all(uint32_t w) { return mask_at(w, 0) && mask_at(w, 1) && mask_at(w, 2) && mask_at(w, 3); }
+// The mix of one slot: x = m ? a (2 kn - 1) + s z : x; op order 2 v, - 1, a *, s z, the sum; s == 0 leaves z unread.
+struct MixArgs {
+  int on;
+  ImgSrc kn;
+  MaskSrc mk;
+  float a, s;
+  const float* noise;
+  uint64_t sid;
+};
+// the known elements (mask word mw != 0) of the float4 j4 at (c, y, xx) replaced in o
+__device__ __forceinline__ void mix_known(const MixArgs& m, uint32_t mw, int c, int y, int xx, int64_t j4, uint64_t seed, f32x4& o) {
+  const f32x4 kv = src_image4(m.kn, c, y, xx);
+  f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  if (m.s != 0.0f) z = m.noise ? *(const f32x4*)(m.noise + j4 * 4) : philox_normal4(seed, m.sid, (uint64_t)j4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float t = 2.0f * kv[e];
+    t = t - 1.0f;
+    float v = m.a * t;
+    if (m.s != 0.0f) v = v + m.s * z[e];
+    if (mask_at(mw, e)) o[e] = v;
+  }
+}
+// Host side: a source as the kernels take it.  Hc, Wc: the canvas it is seen at; `align`: bytes of the vector load.
+template <class Src, class Dev>
+static int tile_source(const std::string& who, const Src* in, int Hc, int Wc, int64_t plane, int align, Dev* out) {
+  KD_REQUIRE(in->d != nullptr && in->H >= 1 && in->W >= 1 && in->H <= (1 << 20) && in->W <= (1 << 20),
+             who + ": null base or size out of range");
+  KD_REQUIRE(in->row >= in->W && plane >= 0, who + ": a row stride below the width, or a negative plane stride");
+  out->d = in->d;
+  out->H = in->H;
+  out->W = in->W;
+  out->row = in->row;
+  out->ry = (float)in->H / (float)Hc;
+  out->rx = (float)in->W / (float)Wc;
+  out->vec = in->H == Hc && in->W == Wc && in->row % 4 == 0 && plane % 4 == 0 && ((uintptr_t)in->d & (align - 1)) == 0;
+  return 0;
+}
+static int tile_image(const std::string& who, const TileImage* in, int Hc, int Wc, ImgSrc* out) {
+  if (tile_source(who, in, Hc, Wc, in->plane, 16, out)) return 1;
+  out->plane = in->plane;
+  return 0;
+}
+static int tile_mix(const std::string& who, const TileMix& mix, int Hc, int Wc, MixArgs* m) {
+  *m = MixArgs{};
+  KD_REQUIRE((mix.known != nullptr) == (mix.mask != nullptr), who + ": the known image and the mask come together");
+  if (!mix.known) return 0;
+  KD_REQUIRE(((uintptr_t)mix.noise & 15) == 0, who + ": the mix noise must be 16-byte aligned");
+  if (tile_image(who + " known image", mix.known, Hc, Wc, &m->kn)) return 1;
+  if (tile_source(who + " mask", mix.mask, Hc, Wc, 0, 4, &m->mk)) return 1;
+  m->on = 1;
+  m->a = mix.a;
+  m->s = mix.s;
+  m->noise = mix.noise;
+  m->sid = mix.sid;
+  return 0;
+}
+
+// x of a stage in one launch: x = scale z [+ (2 init - 1)], then [the mix of the first slot].  z: `noise`, or element
+// (c Hc + y) Wc + x of stream `sid` - with no image and no mask and scale 1 the bits of kd_philox_normal.  A float4 whose
+// mask bytes are all set draws no z.
+__global__ __launch_bounds__(256) void tiles_start_kernel(float* __restrict__ x, int C, int Hc, int Wc, float scale,
+                                                          const float* __restrict__ noise, uint64_t seed, uint64_t sid,
+                                                          int has_init, ImgSrc init, MixArgs mix) {
+  const int W4 = Wc / 4;
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  if (xq >= W4) return;
+  const int xx = 4 * xq;
+  const int rows = C * Hc;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int c = row / Hc, y = row - c * Hc;
+    const int64_t j4 = (int64_t)row * W4 + xq;
+    const uint32_t mw = mix.on ? src_mask4(mix.mk, y, xx) : 0u;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (!mask_all(mw)) {
+      const f32x4 z = noise ? *(const f32x4*)(noise + j4 * 4) : philox_normal4(seed, sid, (uint64_t)j4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = z[e] * scale;
+      if (has_init) {
+        const f32x4 iv = src_image4(init, c, y, xx);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float t = 2.0f * iv[e];
+          t = t - 1.0f;
+          o[e] = o[e] + t;
+        }
+      }
+    }
+    if (mw != 0u) mix_known(mix, mw, c, y, xx, j4, seed, o);
+    *(f32x4*)(x + j4 * 4) = o;
+  }
+}
+int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float* noise, uint64_t seed, const TileImage* init,
+                       const TileMix& mix, hipStream_t s) {
+  KD_REQUIRE(x != nullptr, "tiles start: null output");
+  KD_REQUIRE(C >= 1 && C <= 1024 && Hc >= 1 && Wc >= 4 && Wc % 4 == 0 && Hc <= (1 << 20) && Wc <= (1 << 20) &&
+                 (int64_t)C * Hc < (1ll << 31),
+             "tiles start: canvas out of range, or Wc % 4 != 0");
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)noise) & 15) == 0, "tiles start: x and noise must be 16-byte aligned");
+  ImgSrc in{};
+  if (init && tile_image("tiles start init image", init, Hc, Wc, &in)) return 1;
+  MixArgs m;
+  if (tile_mix("tiles start", mix, Hc, Wc, &m)) return 1;
+  const int W4 = Wc / 4;
+  const int64_t rows = (int64_t)C * Hc;
+  const uint64_t sid = (16ull << 32) | 2;   // the caller's x_T stream, as launch_sample_start (include/kd_engine.h)
+  hipLaunchKernelGGL(tiles_start_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256),
+                     0, s, x, C, Hc, Wc, scale, noise, seed, sid, init ? 1 : 0, in, m);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// The canvas step of tiles_fuse_update_kernel and, on the same pixel in the same pass, [the re-noise x = x rn_a + z rn_b]
+// then [the mix of the NEXT slot]: bit for bit the three passes one after the other.  hist (read when P != 0) and
+// x0bar_out may be one buffer: a thread reads and writes its own element.  A float4 whose mask bytes are all set is known
+// after the mix whatever the update gives: x is not read, nothing is drawn for the update; x0bar is written all the same.
+__global__ __launch_bounds__(256) void tiles_fuse_update_known_kernel(float* __restrict__ x, const float* hist, float* x0bar_out,
+                                                                      const float* __restrict__ x0_tiles,
+                                                                      const float* __restrict__ thr,
+                                                                      const int* __restrict__ tile_of, TileGeom g, float A,
+                                                                      float B, float P, float Sn, const float* __restrict__ noise,
+                                                                      uint64_t seed, uint64_t sid, int renoise, float rn_a,
+                                                                      float rn_b, const float* __restrict__ rn_noise,
+                                                                      uint64_t rn_sid, MixArgs mix) {
+  const int W4 = g.Wc / 4;
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  if (xq >= W4) return;
+  const int xx = 4 * xq;
+  const int rows = g.C * g.Hc;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int c = row / g.Hc, y = row - c * g.Hc;
+    f32x4 xb;
+    if (!fuse_tiles(x0_tiles, thr, tile_of, g, c, y, xx, xb)) continue;
+    const int64_t j4 = (int64_t)row * W4 + xq;
+    const uint32_t mw = mix.on ? src_mask4(mix.mk, y, xx) : 0u;
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (!mask_all(mw)) {
+      o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, hist, j4, A, B, P, Sn, noise, seed, sid);
+      if (renoise) {
+        const f32x4 z = rn_noise ? *(const f32x4*)(rn_noise + j4 * 4) : philox_normal4(seed, rn_sid, (uint64_t)j4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = o[e] * rn_a + z[e] * rn_b;
+      }
+    }
+    if (mw != 0u) mix_known(mix, mw, c, y, xx, j4, seed, o);
+    *(f32x4*)(x + j4 * 4) = o;
+    *(f32x4*)(x0bar_out + j4 * 4) = xb;
+  }
+}
+int launch_tiles_fuse_update_known(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
+                                   const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                                   float P, float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise,
+                                   float rn_a, float rn_b, const float* rn_noise, uint64_t rn_sid, const TileMix& mix,
+                                   hipStream_t s) {
+  KD_REQUIRE(x && x0bar_out && x0_tiles && tile_of && (hist || P == 0.0f), "tiles fuse known: null argument");
+  TileGeom g;
+  if (tile_lattice("tiles fuse known", N, C, S, st, ny, nx, ramp, &g)) return 1;
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)hist | (uintptr_t)x0bar_out | (uintptr_t)x0_tiles | (uintptr_t)noise |
+               (uintptr_t)rn_noise) & 15) == 0,
+             "tiles fuse known: x, hist, x0bar_out, x0_tiles and the noise tensors must be 16-byte aligned");
+  KD_REQUIRE(x != hist && x != x0bar_out, "tiles fuse known: x must not be the history or the estimate");
+  MixArgs m;
+  if (tile_mix("tiles fuse known", mix, g.Hc, g.Wc, &m)) return 1;
+  const int W4 = g.Wc / 4;
+  const int64_t rows = (int64_t)C * g.Hc;
+  hipLaunchKernelGGL(tiles_fuse_update_known_kernel,
+                     dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, s, x, hist,
+                     x0bar_out, x0_tiles, thr, tile_of, g, A, B, P, Sn, noise, seed, stream_id, renoise != 0, rn_a, rn_b, rn_noise,
+                     rn_sid, m);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// tiles_finalize_kernel with the paste: out = m ? kn : (clamp(x, -1, 1) + 1) * 0.5 on covered pixels - the known value
+// copied, not round-tripped.  kn may be the window of `out` that is written (the host checks that an overlapping source
+// is exactly that window): a thread then reads and writes the same element.
+__global__ __launch_bounds__(256) void tiles_finalize_known_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
+                                                                   TileGeom g, float* out, int Ho, int Wo, int oy, int ox,
+                                                                   ImgSrc kn, MaskSrc mk) {
+  const int W4 = g.Wc / 4;
+  const int xq = blockIdx.x * 256 + threadIdx.x;
+  if (xq >= W4) return;
+  const int xx = 4 * xq;
+  const int rows = g.C * g.Hc;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int c = row / g.Hc, y = row - c * g.Hc;
+    const TileCover cv = tile_cover(g, y, xx);
+    bool covered = false;
+    for (int r = cv.r_lo; r <= cv.r_hi; ++r)
+      for (int q = cv.q_lo; q <= cv.q_hi; ++q) {
+        const int t = tile_of[r * g.nx + q];
+        covered = covered || (t >= 0 && t < g.N);
+      }
+    if (!covered) continue;
+    const uint32_t mw = src_mask4(mk, y, xx);
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    if (!mask_all(mw)) {
+      const f32x4 v = *(const f32x4*)(x + ((int64_t)row * W4 + xq) * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float cl = v[e] < -1.0f ? -1.0f : (v[e] > 1.0f ? 1.0f : v[e]);
+        o[e] = (cl + 1.0f) * 0.5f;
+      }
+    }
+    if (mw != 0u) {
+      const f32x4 kv = src_image4(kn, c, y, xx);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (mask_at(mw, e)) o[e] = kv[e];
+    }
+    *(f32x4*)(out + ((int64_t)c * Ho + oy + y) * Wo + ox + xx) = o;
+  }
+}
+int launch_tiles_finalize_known(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out,
+                                int Ho, int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s) {
+  KD_REQUIRE(x && tile_of && out && known && mask, "tiles finalize known: null argument");
+  TileGeom g;
+  if (tile_lattice("tiles finalize known", N, C, S, st, ny, nx, 0, &g)) return 1;
+  const int64_t Hc = g.Hc, Wc = g.Wc;
+  KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
+             "tiles finalize known: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
+  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo,
+             "tiles finalize known: the canvas at (oy, ox) lies outside the output");
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize known: x and out must be 16-byte aligned");
+  ImgSrc kn;
+  MaskSrc mk;
+  if (tile_image("tiles finalize known image", known, g.Hc, g.Wc, &kn)) return 1;
+  if (tile_source("tiles finalize known mask", mask, g.Hc, g.Wc, 0, 4, &mk)) return 1;
+  // a source inside the output must be the window written: every thread then reads the element it writes, and no other
+  const uintptr_t kn0 = (uintptr_t)known->d, out0 = (uintptr_t)out;
+  const uintptr_t kn1 = kn0 + 4 * (uintptr_t)((int64_t)(C - 1) * known->plane + (int64_t)(known->H - 1) * known->row + known->W);
+  if (kn0 < out0 + 4 * (uintptr_t)((int64_t)C * Ho * Wo) && kn1 > out0)
+    KD_REQUIRE(known->d == out + (int64_t)oy * Wo + ox && known->H == g.Hc && known->W == g.Wc && known->row == Wo &&
+                   (C == 1 || known->plane == (int64_t)Ho * Wo),
+               "tiles finalize known: a known image inside the output must be the window at (oy, ox) that is written");
+  const int W4 = g.Wc / 4;
+  const int64_t rows = C * Hc;
+  hipLaunchKernelGGL(tiles_finalize_known_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
+                     dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox, kn, mk);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -318,7 +318,7 @@ static int sample_steps(kd_unet* u, const kd_schedule_t* sc, const kd_sample_arg
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= ctx.T, "step range out of bounds");
   if (ctx.R > 1) KD_REQUIRE(sc->rn_a && sc->rn_b, "re-noise tables are required when resampling");
   Sampler& m = u->smp;
-  if (k_begin == 0 && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
+  if (k_begin == 0 && !a->keep_self_cond && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
   if (sampler_cond_table(u, m.ddpm_tab.host, a, ctx, k_begin, k_end, s)) return 1;
   if (launch_iter_set(m.iter, k_begin * ctx.R, s)) return 1;
   const int n_iter = (k_end - k_begin) * ctx.R;
@@ -381,7 +381,7 @@ static int solver_sample_steps(kd_unet* u, const kd_solver_schedule_t* sc, const
     KD_HIP_CHECK(hipMemsetAsync(m.hist, 0, image_bytes(u), s));
   }
   float* hist = keeps ? m.hist : nullptr;
-  if (k_begin == 0 && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
+  if (k_begin == 0 && !a->keep_self_cond && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
   const std::vector<float> cond_key(m.solver_tab.host.begin(), m.solver_tab.host.begin() + ctx.T);
   if (sampler_cond_table(u, cond_key, a, ctx, k_begin, k_end, s)) return 1;
   if (launch_iter_set(m.iter, k_begin * ctx.R, s)) return 1;
@@ -480,7 +480,7 @@ static int edm_sample_steps(kd_unet* u, const kd_edm_schedule_t* sc, const kd_sa
   ctx.tb.log_snr = tb.c_noise_hat;
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= N, "step range out of bounds");
   Sampler& m = u->smp;
-  if (k_begin == 0 && self_cond_reset(u, s)) return 1;
+  if (k_begin == 0 && !a->keep_self_cond && self_cond_reset(u, s)) return 1;
   // rows k of both halves for the steps walked (the rows in between come along; each row is built once per schedule)
   if (sampler_cond_table(u, m.edm_tab.host, a, ctx, k_begin, k_end > k_begin ? N + k_end : k_begin, s)) return 1;
   if (launch_iter_set(m.iter, k_begin * ctx.R, s)) return 1;

@@ -97,6 +97,7 @@ class kd_sample_args_t(C.Structure):
         ("cond_table", C.c_int),
         ("cond_table_max_mb", C.c_int),
         ("seeds", C.POINTER(C.c_uint64)),   # host array of B per-image keys, or NULL: `seed` keys the whole batch
+        ("keep_self_cond", C.c_int),        # != 0: a steps call from step 0 keeps the carry kd_sample_set_self_cond left
     ]
 
 
@@ -134,6 +135,41 @@ class kd_unet_ext4_t(C.Structure):
     _fields_ = [("init_plain", C.c_int), ("init_kernel_size", C.c_int), ("init_kernel_sizes", C.c_int * 4),
                 ("n_init_kernel_sizes", C.c_int), ("final_kernel_size", C.c_int), ("no_final_resnet_block", C.c_int),
                 ("no_skip_scale", C.c_int), ("init_generic", C.c_int)]
+
+
+class kd_tiles_image_t(C.Structure):
+    _fields_ = [("d", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("row_stride", C.c_int64), ("plane_stride", C.c_int64)]
+
+
+class kd_tiles_mask_t(C.Structure):
+    _fields_ = [("d", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("row_stride", C.c_int64)]
+
+
+def tiles_image(t):
+    """kd_tiles_image_t of a device fp32 view [C, H, W] or [1, C, H, W] with unit x stride, used in place (None stays
+    None).  The struct holds an address only: keep the tensor alive over the call."""
+    import torch
+
+    if t is None:
+        return None
+    t = t[0] if t.dim() == 4 else t
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.stride(2) == 1, "canvas source: fp32 [C, H, W] on device, unit x stride"
+    return kd_tiles_image_t(t.data_ptr(), t.shape[1], t.shape[2], t.stride(1), t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def tiles_mask(t):
+    """kd_tiles_mask_t of a device bool / uint8 view [H, W] with unit x stride, used in place (None stays None)."""
+    import torch
+
+    if t is None:
+        return None
+    assert t.is_cuda and t.dtype in (torch.uint8, torch.bool) and t.dim() == 2 and t.stride(1) == 1, "canvas mask: uint8 / bool [H, W] on device, unit x stride"
+    return kd_tiles_mask_t(t.data_ptr(), t.shape[0], t.shape[1], t.stride(0))
+
+
+def ref(struct):
+    """byref of a ctypes struct, None for None."""
+    return None if struct is None else C.byref(struct)
 
 
 # symbol -> (restype, argtypes); tests/test_cpu.py::test_library_loads_and_exports_every_symbol_the_header_declares checks it against include/kd_engine.h
@@ -265,6 +301,18 @@ SIGNATURES = {
                                                                                                       C.c_float, C.c_void_p, C.c_uint64,
                                                                                                       C.c_uint64, C.c_void_p]),
     "kd_tiles_finalize": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "kd_tiles_start": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_uint64,
+                                 C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_float,
+                                 C.c_float, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kd_tiles_fuse_update_known": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_void_p, C.c_uint64, C.c_uint64,
+                                                                                                C.c_int, C.c_float, C.c_float,
+                                                                                                C.c_void_p, C.c_uint64,
+                                                                                                C.POINTER(kd_tiles_image_t),
+                                                                                                C.POINTER(kd_tiles_mask_t), C.c_float,
+                                                                                                C.c_float, C.c_void_p, C.c_uint64,
+                                                                                                C.c_void_p]),
+    "kd_tiles_finalize_known": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 +
+                                [C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_void_p]),
 }
 
 

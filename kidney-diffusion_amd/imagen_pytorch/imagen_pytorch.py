@@ -1130,13 +1130,14 @@ def tile_weight(S, st, weights="uniform"):
     return r[:, None] * r[None, :]
 
 
-def canvas_tables(step_tables, sampler, eta=0.0):
+def canvas_tables(step_tables, sampler, eta=0.0, skip=0):
     """Coefficients of the canvas step  x <- A x + B x0bar + P hist + S z  of fused-tile sampling, as solver_tables gives
-    them (``coef_x, coef_x0, coef_prev, coef_noise``).  ``"ddim"`` and ``"dpmpp_2m"`` are solver_tables' as they are;
-    ``"ddpm"`` is the ancestral step in the same linear form, ``A = alpha_next (1 - c) / alpha``, ``B = alpha_next c``,
-    ``P = 0``, ``S = noise_scale``, formed in float64 from the fp32 step tables and rounded once."""
+    them (``coef_x, coef_x0, coef_prev, coef_noise``).  ``"ddim"`` and ``"dpmpp_2m"`` are solver_tables' as they are
+    (``skip``: the first step walked, first order for 2M); ``"ddpm"`` is the ancestral step in the same linear form,
+    ``A = alpha_next (1 - c) / alpha``, ``B = alpha_next c``, ``P = 0``, ``S = noise_scale``, formed in float64 from the fp32
+    step tables and rounded once."""
     if sampler != "ddpm":
-        return solver_tables(step_tables, sampler, eta=eta)
+        return solver_tables(step_tables, sampler, eta=eta, skip=skip)
     if eta != 0:
         raise ValueError(f"canvas_tables: eta={eta} needs sampler 'ddim', got 'ddpm'")
     a, an, c = (step_tables[n].to(torch.float64) for n in ("alpha", "alpha_next", "c"))
@@ -1292,6 +1293,70 @@ def normalize_init_images(init_images, skip_steps, *, steps, batch_size, channel
                 raise ValueError(f"init_images of unet {num} must be of a floating dtype or uint8, got {init.dtype}")
         out.append((init, int(skip)))
     return out
+
+
+def normalize_known(known_image, known_mask, known_resample_times=1, *, channels):
+    """``sample_tiled(known_image=..., known_mask=..., known_resample_times=...)``: the pixels a canvas keeps.
+    ``known_image`` is ONE image [1, channels, Hk, Wk] with values in [0, 1] - float32 (any view with unit x stride: a
+    window of a larger canvas is used in place) or uint8 (divided by 255 once); ``known_mask`` is [Hk, Wk] or [1, Hk, Wk],
+    non-zero = keep - bool / uint8 (a view with unit x stride, used in place) or floating (``!= 0``, converted once);
+    ``known_resample_times`` is an int >= 1, more than 1 only with a mask.  Returns ``(image, mask [Hk, Wk], R)``, or
+    ``(None, None, 1)`` without the pair.  Anything else raises ValueError by name.  Needs no GPU."""
+    import numbers
+
+    R = known_resample_times
+    if not isinstance(R, numbers.Integral) or isinstance(R, bool) or int(R) < 1:
+        raise ValueError(f"known_resample_times must be an int >= 1, got {R!r}")
+    if exists(known_image) != exists(known_mask):
+        raise ValueError("known_image and known_mask come together: "
+                         f"{'known_mask' if exists(known_image) else 'known_image'} is missing")
+    if not exists(known_image):
+        if int(R) != 1:
+            raise ValueError(f"known_resample_times={int(R)} needs known_image and known_mask: without known pixels nothing is resampled")
+        return None, None, 1
+    img, mask = known_image, known_mask
+    if not torch.is_tensor(img) or img.dim() != 4 or img.shape[0] != 1 or img.shape[1] != channels or 0 in img.shape[2:]:
+        raise ValueError(f"known_image must be one image [1, channels {channels}, Hk, Wk], got "
+                         f"{tuple(img.shape) if torch.is_tensor(img) else type(img).__name__}")
+    if not torch.is_tensor(mask) or mask.dim() not in (2, 3) or (mask.dim() == 3 and mask.shape[0] != 1):
+        raise ValueError(f"known_mask must be [Hk, Wk] or [1, Hk, Wk], got "
+                         f"{tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
+    mask = mask[0] if mask.dim() == 3 else mask
+    if tuple(mask.shape) != tuple(img.shape[2:]):
+        raise ValueError(f"known_image is {tuple(img.shape[2:])} and known_mask {tuple(mask.shape)}: the sizes must agree")
+    if img.dtype == torch.uint8:
+        img = img.float() / 255.0
+    elif not img.dtype.is_floating_point:
+        raise ValueError(f"known_image must be of a floating dtype or uint8, got {img.dtype}")
+    elif img.dtype != torch.float32:
+        img = img.float()
+    elif img.stride(3) != 1:
+        raise ValueError(f"known_image must have unit x stride (it is used in place), got strides {tuple(img.stride())}")
+    if mask.dtype.is_floating_point:
+        mask = (mask != 0).to(torch.uint8)
+    elif mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"known_mask must be bool, uint8 or floating, got {mask.dtype}")
+    elif mask.stride(1) != 1:
+        raise ValueError(f"known_mask must have unit x stride (it is used in place), got strides {tuple(mask.stride())}")
+    return img, mask, int(R)
+
+
+def normalize_init_canvas(init_canvas, init_skip_steps, *, steps, channels, start_at_unet_number=1, stop_at_unet_number=None):
+    """``sample_tiled(init_canvas=..., init_skip_steps=...)`` cast per UNet, the canvas-level ``normalize_init_images``:
+    ``init_canvas`` is None, one canvas-shaped image [1, channels, H, W] (float32 with unit x stride, used in place; uint8
+    divided by 255) for every UNet sampled, or one entry per UNet; ``init_skip_steps`` None (0), an int, or one entry per
+    UNet, each in 0 .. steps[i] - 1.  Returns ``[(image or None, skip)]``; ValueError by name otherwise.  Needs no GPU."""
+    try:
+        out = normalize_init_images(init_canvas, init_skip_steps, steps=steps, batch_size=1, channels=channels,
+                                    start_at_unet_number=start_at_unet_number, stop_at_unet_number=stop_at_unet_number)
+    except ValueError as e:   # the same rules under the canvas-level names
+        raise ValueError(str(e).replace("init_images", "init_canvas").replace("skip_steps", "init_skip_steps")
+                         .replace("[batch 1,", "[1,")) from None
+    for i, (init, _) in enumerate(out):
+        if exists(init) and init.dtype == torch.float32 and init.stride(3) != 1:
+            raise ValueError(f"init_canvas of unet {i + 1} must have unit x stride (it is used in place), got strides "
+                             f"{tuple(init.stride())}")
+    return [(None if init is None else init.float(), skip) for init, skip in out]
 
 
 # ============================================================================ one stage on the engine (host side)
@@ -1683,7 +1748,8 @@ class Imagen(nn.Module):
                      start_at_unet_number=1, stop_at_unet_number=None, start_image_or_video=None,
                      return_all_unet_outputs=False, lowres_sample_noise_level=None, device=None, inpaint_images=None,
                      inpaint_masks=None, inpaint_resample_times=None, init_images=None, skip_steps=None, streamed=False,
-                     cond_crops=None, into=None):
+                     cond_crops=None, into=None, known_image=None, known_mask=None, known_resample_times=1, init_canvas=None,
+                     init_skip_steps=None):
         """A canvas of overlapping tiles denoised jointly (MultiDiffusion / Mixture of Diffusers; an engine extension, the
         alternative to sequential outpainting).  The canvas of a stage is ONE noisy image over the ``grid = (ny, nx)``
         lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
@@ -1709,7 +1775,24 @@ class Imagen(nn.Module):
         conditioning images are windows of one image, cut per chunk by kd_tiles_cond_gather, bit-equal to
         ``cond_images=cond_images_for_grid(...)``.  ``into=(canvas, oy, ox)`` (needs ``streamed``): the last sampled stage
         writes its covered pixels into ``canvas`` [1, C, Ho, Wo] (fp32, contiguous, on the device) at row ``oy``, column
-        ``ox`` (multiples of 4) in place, leaves every other pixel of it alone and returns it."""
+        ``ox`` (multiples of 4) in place, leaves every other pixel of it alone and returns it.
+
+        A canvas that keeps known pixels or starts from an image (canvas-level; the per-tile ``inpaint_*`` / ``init_images``
+        / ``skip_steps`` of ``sample`` stay refused - a canvas holds no image per tile).  ``known_image`` [1, C, Hk, Wk] in
+        [0, 1], ``known_mask`` [Hk, Wk] (non-zero = keep) and ``known_resample_times = R`` (``normalize_known``): RePaint
+        mixing on the canvas.  Every stage reads both at its own canvas size (nearest); before each of the R resample
+        slots of step k the known pixels become ``alpha_k (2 kn - 1) + sigma_k z``, after every slot but a step's last the
+        canvas is re-noised to step k (``rn_a``, ``rn_b``), and the result holds the known image's values, copied.  The
+        draws are canvas-level like x_T: ``noise_fn`` tags ``("inpaint" | "renoise" | "step", stage, k, r)``, r counting
+        down from R - 1, or Philox purposes 2, 3 and 1 at iteration ``k R + (R - 1 - r)`` - ``sample``'s, so a 1 x 1 lattice
+        draws what ``sample(batch_size=1, inpaint_images=...)`` draws.  2M keeps the fused estimate of a step's last slot as
+        its history; a self-conditioned UNet carries the previous slot's.  ``init_canvas`` (one image, or one per UNet)
+        and ``init_skip_steps`` (``normalize_init_canvas``; counted in ``sample_steps`` where given): the stage starts from
+        ``z + nearest(2 init - 1)`` and walks steps ``skip .. T - 1``; a step keeps its index - table row, streams, tags -
+        and 2M is first order on the first step walked.  With any of them the stage starts through kd_tiles_start, steps
+        through kd_tiles_fuse_update_known (update, re-noise and the next slot's mix in the one canvas pass) and, with a
+        mask, ends through kd_tiles_finalize_known (``streamed``) or the same paste in torch.  ``known_image`` may be a
+        window of the ``into`` canvas itself."""
         for name, v in dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
                             inpaint_resample_times=inpaint_resample_times).items():
             if exists(v):
@@ -1766,6 +1849,11 @@ class Imagen(nn.Module):
             if not dst.is_cuda:
                 raise ValueError(f"into: the canvas must live on the device, got {dst.device}")
             into = (dst, int(oy), int(ox))
+        known = normalize_known(known_image, known_mask, known_resample_times, channels=self.channels)
+        starts = normalize_init_canvas(init_canvas, init_skip_steps,
+                                       steps=[default(st, T) for (_, _, st), T in zip(solvers, self._num_steps())],
+                                       channels=self.channels, start_at_unet_number=start_at_unet_number,
+                                       stop_at_unet_number=stop_at_unet_number)
         device, text_masks, cond_images, seed, cond_scale, lowres_level, canvas = self._sampling_setup(
             device, text_embeds, text_masks, cond_images, seed, cond_scale, lowres_sample_noise_level, start_at_unet_number,
             start_image_or_video)
@@ -1778,13 +1866,13 @@ class Imagen(nn.Module):
             canvas = self._tiled_stage(unet, num, tiling[num - 1], sched, obj, dyn, device, canvas, cond_images, lowres_level,
                                        noise_fn, int(seed), use_graph, int(tile_batch), text_embeds=text_embeds,
                                        text_masks=text_masks, cond_scale=cs, solver=solver, streamed=bool(streamed),
-                                       crops=crops, into=into if num == last else None)
+                                       crops=crops, into=into if num == last else None, known=known, start=starts[num - 1])
             outputs.append(canvas)
         return outputs if return_all_unet_outputs else outputs[-1]
 
     def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
                      lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
-                     solver=("ddpm", 0.0), streamed=False, crops=None, into=None):
+                     solver=("ddpm", 0.0), streamed=False, crops=None, into=None, known=(None, None, 1), start=(None, 0)):
         """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  Per schedule step k and chunk of at
         most `tile_batch` tiles: gather the chunk out of the canvas into the plan's stable buffers, one iteration
         kd_solver_sample_steps(k, k + 1) with DDIM(0) coefficients (first order: no history, no draw; its tile-level
@@ -1792,7 +1880,10 @@ class Imagen(nn.Module):
         canvas sampler's coefficients of step k.  A ragged last chunk runs the plan of its own batch size.
         `streamed`: the chunk's low-res tiles come from the previous canvas (kd_tiles_gather_lowres) and the stage ends
         with kd_tiles_finalize, into `into = (canvas, oy, ox)` or a zero canvas; `crops`: (TileCondCrops, Cs, W, tile
-        channels, top, shifts) - the chunk's conditioning tiles come from its image (kd_tiles_cond_gather)."""
+        channels, top, shifts) - the chunk's conditioning tiles come from its image (kd_tiles_cond_gather).
+        `known = (image, mask, R)` / `start = (init image, skip)`: with any of them the stage walks the R resample slots of
+        the steps skip .. T - 1 - kd_tiles_start, then per slot the tiles and ONE kd_tiles_fuse_update_known that also
+        re-noises and mixes the known pixels for the next slot - and ends with the paste of the known pixels."""
         lib = E.load()
         Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
         origins = geo["origins"]
@@ -1802,13 +1893,33 @@ class Imagen(nn.Module):
         gauss, stage_seed, _ = _stage_noise(lib, noise_fn, seed, stage, device)
         stream = E.current_stream
 
+        kn, km, R = known
+        init, skip = start
+        ext = exists(kn) or exists(init) or skip > 0   # without them: the code path and the bits of before
         tables = sched.step_tables()
-        coefs = canvas_tables(tables, *solver)
+        coefs = canvas_tables(tables, *solver, skip=skip)
         sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
         T, tile_steps = sc.T, getattr(lib, sc.steps)
+        slots = [(k, j) for k in range(skip, T) for j in range(R)]   # slot j of step k is resample r = R - 1 - j
+        inject = lambda kind, k, j: f32(noise_fn((kind, stage, k, R - 1 - j), shape)) if exists(noise_fn) else None
 
         with torch.cuda.device(device):
-            x = gauss(("init", stage), shape, (16 << 32) | 2)
+            if ext:   # the sources stay where they lie: views of the caller's tensors, described to the kernels
+                here = lambda t: t.is_cuda and t.device.index == default(device.index, torch.cuda.current_device())
+                kn, init = (t if t is None or here(t) else f32(t) for t in (kn, init))
+                km = km if km is None or here(km) else km.to(device)
+                kn_s, km_s, init_s = E.tiles_image(kn), E.tiles_mask(km), E.tiles_image(init)
+                mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
+                x = torch.empty(shape, device=device, dtype=torch.float32)
+                z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
+                zm = inject("inpaint", skip, 0) if exists(kn) else None
+                E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
+                                           E.ref(kn_s), E.ref(km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
+                # 2M under resampling: the history takes a step's estimate in its last slot only, the slots before it
+                # leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
+                x0bar_slot = torch.empty(shape, device=device, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
+            else:
+                x = gauss(("init", stage), shape, (16 << 32) | 2)
             x0bar = torch.zeros(shape, device=device, dtype=torch.float32)
             store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
             thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
@@ -1876,7 +1987,8 @@ class Imagen(nn.Module):
                     rows = lambda t: None if t is None else t.expand(b, *t.shape[1:])
                     io.text(h, rows(text_embeds), rows(text_masks), cond_scale)
 
-            for k in range(T):
+            latest = x0bar   # the canvas that holds the fused estimate of the previous slot
+            for i, (k, j) in enumerate(slots):
                 for n0 in range(0, N, tile_batch):
                     b = min(tile_batch, N - n0)
                     p = plans[b]
@@ -1889,29 +2001,56 @@ class Imagen(nn.Module):
                         p["cond"].copy_(cond[n0:n0 + b])
                     elif exists(crops):
                         gather_cond(p["cond"], n0, b)
-                    if unet.self_cond and k > 0:   # the carry is the FUSED estimate of step k - 1 (step 0 starts from zeros)
-                        gather(x0bar, p["self_cond"], n0, b)
+                    if unet.self_cond and i > 0:   # the carry is the FUSED estimate of the slot before (the first starts from zeros)
+                        gather(latest, p["self_cond"], n0, b)
                         E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
+                    elif unet.self_cond and k > 0:   # a first step walked behind step 0: the plan holds another call's carry
+                        E.check(lib.kd_sample_set_self_cond(p["h"], None, stream()))
+                    p["args"].keep_self_cond = int(i > 0)   # (the later slots of step 0 keep the carry just set)
                     E.check(tile_steps(p["h"], C.byref(sc.struct), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1, stream()))
                     E.check(lib.kd_sample_last(p["h"], 1, E.ptr(store[n0:n0 + b]), stream()))
                     if dynamic_threshold:
                         E.check(lib.kd_sample_last(p["h"], 2, E.ptr(thr[n0:n0 + b]), stream()))
                 A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
-                z = f32(noise_fn(("step", stage, k, 0), shape)) if Sn != 0.0 and exists(noise_fn) else None
+                z = inject("step", k, j) if Sn != 0.0 else None
                 # (z: memory of torch's current stream, handed on only behind this launch)
-                E.check(lib.kd_tiles_fuse_update(E.ptr(x), E.ptr(x0bar), E.ptr(store), E.ptr(thr), C.c_void_p(tile_of.data_ptr()),
-                                                 N, Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z),
-                                                 stage_seed, (1 << 32) | k, stream()))
+                if not ext:
+                    E.check(lib.kd_tiles_fuse_update(E.ptr(x), E.ptr(x0bar), E.ptr(store), E.ptr(thr),
+                                                     C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx,
+                                                     int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed,
+                                                     (1 << 32) | k, stream()))
+                    continue
+                it = k * R + j
+                renoise = j < R - 1 and k < T - 1
+                zr = inject("renoise", k, j) if renoise else None
+                nxt = slots[i + 1] if exists(kn) and i + 1 < len(slots) else None   # the last slot mixes nothing: the end pastes
+                zm = inject("inpaint", *nxt) if exists(nxt) else None
+                a_mix, s_mix = mix(nxt[0]) if exists(nxt) else (0.0, 0.0)
+                est = x0bar if j == R - 1 or x0bar_slot is None else x0bar_slot
+                E.check(lib.kd_tiles_fuse_update_known(
+                    E.ptr(x), E.ptr(x0bar), E.ptr(est), E.ptr(store), E.ptr(thr), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st,
+                    ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it), int(renoise),
+                    float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
+                    E.ref(kn_s) if exists(nxt) else None, E.ref(km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
+                    E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0, stream()))
+                latest = est
             if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
                 out, oy, ox = into if exists(into) else (torch.zeros(shape, device=device, dtype=torch.float32), 0, 0)
                 assert out.device == x.device, f"into: the canvas lives on {out.device}, the stage runs on {x.device}"
-                E.check(lib.kd_tiles_finalize(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
-                                              out.shape[2], out.shape[3], oy, ox, stream()))
+                if exists(kn):
+                    E.check(lib.kd_tiles_finalize_known(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
+                                                        out.shape[2], out.shape[3], oy, ox, E.ref(kn_s), E.ref(km_s), stream()))
+                else:
+                    E.check(lib.kd_tiles_finalize(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
+                                                  out.shape[2], out.shape[3], oy, ox, stream()))
                 return out
             covered = torch.zeros(Hc, Wc, dtype=torch.bool)
             for y0, x0 in origins:
                 covered[y0:y0 + S, x0:x0 + S] = True
             out = (x.clamp(-1.0, 1.0) + 1) * 0.5
+            if exists(kn):   # the paste on nearest-resized copies
+                resized = lambda t: t if tuple(t.shape[-2:]) == (Hc, Wc) else F.interpolate(t, (Hc, Wc), mode="nearest")
+                out = torch.where(resized(km[None, None].float()) != 0, resized(kn), out)
             out = torch.where(covered.to(device), out, torch.zeros_like(out))
         return out
 

@@ -114,7 +114,10 @@ def generate_high_res_image_fused(load_imagen: Callable, zoomed_image: torch.Ten
     """`generate_high_res_image` by fused-tile sampling: `level_patches` (every position at mag 1, the tissue set at
     mag 2; `patch_pos` overrides it) and `tiled.fused_level` over them.  `load_imagen(stage)` returns the Imagen of that
     stage, as for `tiled.fused_canvas`; `fused_kw` are `fused_level`'s keywords (`stages`, `tile_batch`, `sampler`,
-    `sample_steps`, `seed`, `noise_fn`, `fill_color`, `background`, `device`, ...).  (1,3,W,W) on the device."""
+    `sample_steps`, `seed`, `noise_fn`, `fill_color`, `background`, `device`, ...).  (1,3,W,W) on the device.
+    Partial regeneration, the fused counterpart of `generate_high_res_image(patch_pos=...)` on a finished level, goes
+    through `fused_kw` as well: `canvas=` (the finished level, written in place), `keep=` (`tiled.level_keep_mask` of the
+    tiles that stay), `known_resample_times=` and `refine_skip_steps=`."""
     from . import tiled as UT
 
     geom, pos = level_patches(zoomed_image, mag_level, overlap, version)
