@@ -60,7 +60,9 @@ const char* kd_last_error(void);
  *      canvas sampling); kd_tiles_cond_gather, kd_tiles_gather_lowres and kd_tiles_finalize added (a fused-tile stage at the
  *      sizes of a magnification level); kd_tiles_start, kd_tiles_fuse_update_known and kd_tiles_finalize_known with their
  *      structs kd_tiles_image_t and kd_tiles_mask_t added (a fused-tile canvas that keeps known pixels or starts from an image);
- *      kd_sample_args_t gained `keep_self_cond` at its end (zero = the reset at step 0 of before) */
+ *      kd_sample_args_t gained `keep_self_cond` at its end (zero = the reset at step 0 of before); kd_tiles_finalize_known
+ *      accepts known = mask = NULL (kd_tiles_finalize's bits) - kd_tiles_fuse_update and kd_tiles_finalize are the _known calls
+ *      with nothing known, no existing entry changed */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -845,7 +847,8 @@ int kd_tiles_gather(const float* d_canvas, float* d_tiles, int B, int C, int Hc,
  *   z          d_noise [C,Hc,Wc], or, when it is NULL, element (c Hc + y) Wc + x of Philox stream `stream_id` under `seed`:
  *              the bits kd_philox_normal writes over C Hc Wc elements - a property of the canvas, not of the tiling.
  * Needs S % 4 == 0, st % 4 == 0, 4 <= st <= S <= 3 st (at most 3 tiles per axis, 9 in all, cover a pixel), 1 <= N <= ny nx
- * and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
+ * and 16-byte aligned pointers (refused with an error, nothing launched, otherwise).
+ * kd_tiles_fuse_update == kd_tiles_fuse_update_known with d_hist = d_x0bar_out = d_x0bar, renoise = 0 and known = mask = NULL. */
 int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, const float* d_thr, const int* d_tile_of, int N,
                          int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn,
                          const float* d_noise, uint64_t seed, uint64_t stream_id, void* stream);
@@ -878,7 +881,8 @@ int kd_tiles_gather_lowres(const float* d_prev, int Hp, int Wp, float* d_tiles, 
 /* The end of a stage: for every pixel of the canvas d_x [C,Hc,Wc] covered by a present tile (kd_tiles_fuse_update's cover
  * test over d_tile_of [ny][nx]), d_out[c, oy + y, ox + x] = (clamp(x, -1, 1) + 1) * 0.5; every other element of d_out
  * [C,Ho,Wo] is left untouched.  Needs the lattice preconditions of kd_tiles_fuse_update, ox % 4 == 0, Wo % 4 == 0, the
- * canvas inside d_out and 16-byte aligned pointers (refused with an error, nothing launched, otherwise). */
+ * canvas inside d_out and 16-byte aligned pointers (refused with an error, nothing launched, otherwise).
+ * kd_tiles_finalize == kd_tiles_finalize_known with known = mask = NULL. */
 int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
                       int Wo, int oy, int ox, void* stream);
 
@@ -932,7 +936,8 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
  * every other element of d_out untouched.  A known pixel is the known image's value copied, not round-tripped through
  * 2 v - 1.  `known` may be the window of d_out that is written (base d_out + oy Wo + ox, size [Hc, Wc], strides Wo and
  * Ho Wo): every thread then reads and writes the same element.  A known image that overlaps d_out in any other way is
- * refused.  Preconditions: kd_tiles_finalize's. */
+ * refused.  `known` and `mask` come together (one without the other is refused); both NULL: no paste, kd_tiles_finalize's
+ * bits.  Preconditions: kd_tiles_finalize's. */
 int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
                             int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
                             void* stream);

@@ -1203,8 +1203,9 @@ int kd_tiles_gather(const float* d_canvas, float* d_tiles, int B, int C, int Hc,
 int kd_tiles_fuse_update(float* d_x, float* d_x0bar, const float* d_x0_tiles, const float* d_thr, const int* d_tile_of, int N,
                          int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn,
                          const float* d_noise, uint64_t seed, uint64_t stream_id, void* stream) {
-  return launch_tiles_fuse_update(d_x, d_x0bar, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P, Sn, d_noise,
-                                  seed, stream_id, (hipStream_t)stream);
+  return kd_tiles_fuse_update_known(d_x, d_x0bar, d_x0bar, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P, Sn,
+                                    d_noise, seed, stream_id, 0, 0.0f, 0.0f, nullptr, 0, nullptr, nullptr, 0.0f, 0.0f, nullptr, 0,
+                                    stream);
 }
 int kd_tiles_cond_gather(const float* d_src, int Cs, int W, float* d_tiles, int B, int S, const int* shifts_yx, int top,
                          const int* d_win_of, const int* d_centre_of, float fill, void* stream) {
@@ -1218,7 +1219,7 @@ int kd_tiles_gather_lowres(const float* d_prev, int Hp, int Wp, float* d_tiles, 
 }
 int kd_tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
                       int Wo, int oy, int ox, void* stream) {
-  return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, (hipStream_t)stream);
+  return kd_tiles_finalize_known(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, nullptr, nullptr, stream);
 }
 // the C structs of the canvas sources as the launchers take them; a NULL source stays NULL
 static const TileImage* tile_image_of(const kd_tiles_image_t* in, TileImage* out) {
@@ -1248,17 +1249,17 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
   TileImage kn;
   TileMask mk;
   const TileMix mix{tile_image_of(known, &kn), tile_mask_of(mask, &mk), mix_a, mix_s, d_mix_noise, mix_stream_id};
-  return launch_tiles_fuse_update_known(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
-                                        Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
-                                        (hipStream_t)stream);
+  return launch_tiles_fuse_update(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
+                                  Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
+                                  (hipStream_t)stream);
 }
 int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
                             int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
                             void* stream) {
   TileImage kn;
   TileMask mk;
-  return launch_tiles_finalize_known(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
-                                     tile_mask_of(mask, &mk), (hipStream_t)stream);
+  return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
+                               tile_mask_of(mask, &mk), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -450,22 +450,17 @@ int launch_sample_start(float* out, int B, int C, int S, float scale, uint64_t s
                         const float* init, int Hs, int Ws, hipStream_t s);
 
 // fused-tile canvas sampling (kernels_tiles.hip): tiles[b] = canvas[:, y0_b : y0_b + S, x0_b : x0_b + S], origins_yx a host
-// array [B][2]; and the canvas step x <- A x + B x0bar + P hist + Sn z over the weighted mean x0bar of the covering tiles
+// array [B][2]
 int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc, int Wc, int S, const int* origins_yx,
                         hipStream_t s);
-int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, const float* thr, const int* tile_of, int N, int C,
-                             int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn, const float* noise,
-                             uint64_t seed, uint64_t stream_id, hipStream_t s);
 // a stage at the sizes of a magnification level: conditioning tiles [B, Cs | 2 Cs, S, S] out of the level above src [Cs, W, W]
 // (shifts_yx a host array [B][2], the maps [S] in device memory); low-res conditioning tiles a (2 nearest(prev) - 1) + s z
-// out of the previous canvas [C, Hp, Wp]; and (clamp(x, -1, 1) + 1) / 2 of the covered pixels into out [C, Ho, Wo] at (oy, ox)
+// out of the previous canvas [C, Hp, Wp]
 int launch_tiles_cond_gather(const float* src, int Cs, int W, float* tiles, int B, int S, const int* shifts_yx, int top,
                              const int* win_of, const int* centre_of, float fill, hipStream_t s);
 int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, int B, int C, int Hc, int Wc, int S,
                                const int* origins_yx, float a, float s, const float* noise, uint64_t seed, uint64_t stream_id,
                                hipStream_t st);
-int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
-                          int Wo, int oy, int ox, hipStream_t s);
 // a canvas that keeps known pixels or starts from an image.  A source is seen at the canvas' size through torch's nearest
 // rule (launch_sample_start's); strides in elements, so a window of a larger tensor is passed without a copy.
 struct TileImage {   // [C, H, W] fp32
@@ -489,15 +484,14 @@ struct TileMix {
 // x [C, Hc, Wc] = scale z [+ (2 init - 1)], then the mix; z from `noise` or stream (16 << 32) | 2 under `seed`
 int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float* noise, uint64_t seed, const TileImage* init,
                        const TileMix& mix, hipStream_t s);
-// launch_tiles_fuse_update with hist (read when P != 0) and x0bar_out apart (they may alias), then on the same pixel
-// [x = x rn_a + z rn_b] (renoise != 0) and [the mix]
-int launch_tiles_fuse_update_known(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
-                                   const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
-                                   float P, float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise,
-                                   float rn_a, float rn_b, const float* rn_noise, uint64_t rn_sid, const TileMix& mix,
-                                   hipStream_t s);
-// launch_tiles_finalize with the paste: out = m ? kn : (clamp(x, -1, 1) + 1) / 2 on covered pixels
-int launch_tiles_finalize_known(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out,
-                                int Ho, int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s);
+// the canvas step x <- A x + B x0bar + P hist + Sn z over the weighted mean x0bar of the covering tiles, hist (read when
+// P != 0) and x0bar_out apart or one buffer; then on the same pixel [x = x rn_a + z rn_b] (renoise != 0) and [the mix]
+int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
+                             const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P,
+                             float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise, float rn_a, float rn_b,
+                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s);
+// out = [m ? kn :] (clamp(x, -1, 1) + 1) / 2 on covered pixels; known and mask both or neither
+int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
+                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s);
 
 }  // namespace kd

@@ -77,17 +77,23 @@ int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc,
   return 0;
 }
 
-// ------------------------------------------------------------------------- the canvas step
+// ------------------------------------------------------------------------- the canvas step: lattice, fusion, update
 // Per canvas pixel, over the present tiles t that cover it, in ascending (row, column) order of their slots:
 //   x0c_t = clamp(x0_t, -s_t, s_t) / s_t, s_t = max(thr_t, 1)          (thr == nullptr: s_t = 1)
 //   x0bar = (sum w_t x0c_t) / (sum w_t)
-//   x <- A x + B x0bar [+ P hist] [+ Sn z] ; hist <- x0bar               (hist: what x0bar held on entry)
+//   x <- A x + B x0bar [+ P hist] [+ Sn z] ; x0bar_out <- x0bar
 // A term whose coefficient is 0 is left out, operand unread.  A pixel that no present tile covers is left alone in both
 // buffers.  z: read from `noise`, or element (c Hc + y) Wc + x of Philox stream `sid` under `seed` - the bits
 // kd_philox_normal writes over C Hc Wc elements, whatever the tiling.
 // Pixel-centric, no atomics: a thread owns four consecutive x of one (c, y); a block row is one canvas row, so the row's
-// slots and weights are uniform over the block.  At most TILE_COVER slots per axis (S <= TILE_COVER st).
+// slots and weights are uniform over the block.  At most TILE_COVER slots per axis (S <= TILE_COVER st).  The kernel
+// itself (tiles_fuse_update_kernel) stands below, behind the sources it mixes in.
 enum { TILE_COVER = 3 };
+// The launch grid of the canvas-shaped kernels (start, step, finish): a thread per float4 of a canvas row [Wc], block row
+// blockIdx.y walks the C Hc rows in strides of gridDim.y.
+static dim3 canvas_grid(int C, int Hc, int Wc) {
+  return dim3((unsigned)((Wc / 4 + 255) / 256), (unsigned)std::min<int64_t>((int64_t)C * Hc, 65535));
+}
 struct TileGeom {
   int C, S, st, ny, nx, Hc, Wc;
   int ramp, ov;   // ramp != 0: w(y, x) = r(y) r(x), r(i) = min(i + 1, S - i, ov) / ov; else w = 1
@@ -113,6 +119,17 @@ struct TileCover {
 __device__ __forceinline__ TileCover tile_cover(const TileGeom& g, int y, int xx) {
   return TileCover{y < g.S ? 0 : (y - g.S) / g.st + 1, min(y / g.st, g.ny - 1), xx < g.S ? 0 : (xx - g.S) / g.st + 1,
                    min(xx / g.st, g.nx - 1)};
+}
+// whether a present tile covers the float4 at (y, xx)
+__device__ __forceinline__ bool tile_covered(const int* __restrict__ tile_of, const TileGeom& g, int y, int xx) {
+  const TileCover cv = tile_cover(g, y, xx);
+  bool covered = false;
+  for (int r = cv.r_lo; r <= cv.r_hi; ++r)
+    for (int q = cv.q_lo; q <= cv.q_hi; ++q) {
+      const int t = tile_of[r * g.nx + q];
+      covered = covered || (t >= 0 && t < g.N);
+    }
+  return covered;
 }
 // x0bar of the float4 at (c, y, xx) into xb; false when no present tile covers it (xb is then not written).
 __device__ __forceinline__ bool fuse_tiles(const float* __restrict__ x0_tiles, const float* __restrict__ thr,
@@ -162,42 +179,6 @@ __device__ __forceinline__ f32x4 canvas_update(const f32x4& xv, const f32x4& xb,
     for (int e = 0; e < 4; ++e) o[e] = o[e] + Sn * z[e];
   }
   return o;
-}
-
-__global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, float* __restrict__ x0bar,
-                                                                const float* __restrict__ x0_tiles,
-                                                                const float* __restrict__ thr, const int* __restrict__ tile_of,
-                                                                TileGeom g, float A, float B, float P, float Sn,
-                                                                const float* __restrict__ noise, uint64_t seed, uint64_t sid) {
-  const int W4 = g.Wc / 4;
-  const int xq = blockIdx.x * 256 + threadIdx.x;
-  if (xq >= W4) return;
-  const int xx = 4 * xq;
-  const int rows = g.C * g.Hc;
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int c = row / g.Hc, y = row - c * g.Hc;
-    f32x4 xb;
-    if (!fuse_tiles(x0_tiles, thr, tile_of, g, c, y, xx, xb)) continue;
-    const int64_t j4 = (int64_t)row * W4 + xq;
-    const f32x4 o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, x0bar, j4, A, B, P, Sn, noise, seed, sid);
-    *(f32x4*)(x + j4 * 4) = o;
-    *(f32x4*)(x0bar + j4 * 4) = xb;
-  }
-}
-int launch_tiles_fuse_update(float* x, float* x0bar, const float* x0_tiles, const float* thr, const int* tile_of, int N, int C,
-                             int S, int st, int ny, int nx, int ramp, float A, float B, float P, float Sn, const float* noise,
-                             uint64_t seed, uint64_t sid, hipStream_t s) {
-  KD_REQUIRE(x && x0bar && x0_tiles && tile_of, "tiles fuse: null argument");
-  TileGeom g;
-  if (tile_lattice("tiles fuse", N, C, S, st, ny, nx, ramp, &g)) return 1;
-  KD_REQUIRE((((uintptr_t)x | (uintptr_t)x0bar | (uintptr_t)x0_tiles | (uintptr_t)noise) & 15) == 0,
-             "tiles fuse: x, x0bar, x0_tiles and noise must be 16-byte aligned");
-  const int W4 = g.Wc / 4;
-  const int64_t rows = (int64_t)C * g.Hc;
-  hipLaunchKernelGGL(tiles_fuse_update_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
-                     dim3(256), 0, s, x, x0bar, x0_tiles, thr, tile_of, g, A, B, P, Sn, noise, seed, sid);
-  KD_HIP_CHECK(hipGetLastError());
-  return 0;
 }
 
 // ------------------------------------------------------------------------- conditioning tiles from the level above
@@ -329,55 +310,6 @@ int launch_tiles_gather_lowres(const float* prev, int Hp, int Wp, float* tiles, 
     hipLaunchKernelGGL(tiles_gather_lowres_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, st, prev, Hp, Wp, ry, rx,
                        tiles + (int64_t)b0 * per4 * 4, C, Hc, Wc, S, org, a, s, noise, seed, sid);
   });
-  KD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------- the end of a stage
-// out[c, oy + y, ox + x] = (clamp(x[c, y, x], -1, 1) + 1) * 0.5 for every canvas pixel that a present tile covers (the
-// cover test of tiles_fuse_update_kernel); every other element of out [C, Ho, Wo] keeps its bits.  One pass, no mask.
-__global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
-                                                             TileGeom g, float* __restrict__ out, int Ho, int Wo, int oy, int ox) {
-  const int W4 = g.Wc / 4;
-  const int xq = blockIdx.x * 256 + threadIdx.x;
-  if (xq >= W4) return;
-  const int xx = 4 * xq;
-  const int q_hi = min(xx / g.st, g.nx - 1), q_lo = xx < g.S ? 0 : (xx - g.S) / g.st + 1;
-  const int rows = g.C * g.Hc;
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int c = row / g.Hc, y = row - c * g.Hc;
-    const int r_hi = min(y / g.st, g.ny - 1), r_lo = y < g.S ? 0 : (y - g.S) / g.st + 1;
-    bool covered = false;
-    for (int r = r_lo; r <= r_hi; ++r)
-      for (int q = q_lo; q <= q_hi; ++q) {
-        const int t = tile_of[r * g.nx + q];
-        covered = covered || (t >= 0 && t < g.N);
-      }
-    if (!covered) continue;
-    const f32x4 v = *(const f32x4*)(x + ((int64_t)row * W4 + xq) * 4);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float cl = v[e] < -1.0f ? -1.0f : (v[e] > 1.0f ? 1.0f : v[e]);
-      o[e] = (cl + 1.0f) * 0.5f;
-    }
-    *(f32x4*)(out + ((int64_t)c * Ho + oy + y) * Wo + ox + xx) = o;
-  }
-}
-int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
-                          int Wo, int oy, int ox, hipStream_t s) {
-  KD_REQUIRE(x && tile_of && out, "tiles finalize: null argument");
-  TileGeom g;
-  if (tile_lattice("tiles finalize", N, C, S, st, ny, nx, 0, &g)) return 1;
-  const int64_t Hc = g.Hc, Wc = g.Wc;   // (oy + Hc, ox + Wc: no overflow for any int offset)
-  KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
-             "tiles finalize: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
-  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo, "tiles finalize: the canvas at (oy, ox) lies outside the output");
-  KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize: x and out must be 16-byte aligned");
-  const int W4 = g.Wc / 4;
-  const int64_t rows = C * Hc;
-  hipLaunchKernelGGL(tiles_finalize_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
-                     dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -525,27 +457,27 @@ int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float
   if (init && tile_image("tiles start init image", init, Hc, Wc, &in)) return 1;
   MixArgs m;
   if (tile_mix("tiles start", mix, Hc, Wc, &m)) return 1;
-  const int W4 = Wc / 4;
-  const int64_t rows = (int64_t)C * Hc;
   const uint64_t sid = (16ull << 32) | 2;   // the caller's x_T stream, as launch_sample_start (include/kd_engine.h)
-  hipLaunchKernelGGL(tiles_start_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256),
-                     0, s, x, C, Hc, Wc, scale, noise, seed, sid, init ? 1 : 0, in, m);
+  hipLaunchKernelGGL(tiles_start_kernel, canvas_grid(C, Hc, Wc), dim3(256), 0, s, x, C, Hc, Wc, scale, noise, seed, sid,
+                     init ? 1 : 0, in, m);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// The canvas step of tiles_fuse_update_kernel and, on the same pixel in the same pass, [the re-noise x = x rn_a + z rn_b]
-// then [the mix of the NEXT slot]: bit for bit the three passes one after the other.  hist (read when P != 0) and
-// x0bar_out may be one buffer: a thread reads and writes its own element.  A float4 whose mask bytes are all set is known
-// after the mix whatever the update gives: x is not read, nothing is drawn for the update; x0bar is written all the same.
-__global__ __launch_bounds__(256) void tiles_fuse_update_known_kernel(float* __restrict__ x, const float* hist, float* x0bar_out,
-                                                                      const float* __restrict__ x0_tiles,
-                                                                      const float* __restrict__ thr,
-                                                                      const int* __restrict__ tile_of, TileGeom g, float A,
-                                                                      float B, float P, float Sn, const float* __restrict__ noise,
-                                                                      uint64_t seed, uint64_t sid, int renoise, float rn_a,
-                                                                      float rn_b, const float* __restrict__ rn_noise,
-                                                                      uint64_t rn_sid, MixArgs mix) {
+// ------------------------------------------------------------------------- the canvas step: the kernel
+// The canvas step and, with KNOWN, on the same pixel in the same pass [the re-noise x = x rn_a + z rn_b] then [the mix of
+// the NEXT slot]: bit for bit the three passes one after the other.  Without KNOWN the re-noise, the mask load and the mix
+// are compiled out.  hist (read when P != 0) and x0bar_out may be one buffer - a thread reads and writes its own element -
+// so neither is restrict.  A float4 whose mask bytes are all set is known after the mix whatever the update gives: x is
+// not read, nothing is drawn for the update; x0bar is written all the same.
+template <bool KNOWN>
+__global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, const float* hist, float* x0bar_out,
+                                                                const float* __restrict__ x0_tiles,
+                                                                const float* __restrict__ thr, const int* __restrict__ tile_of,
+                                                                TileGeom g, float A, float B, float P, float Sn,
+                                                                const float* __restrict__ noise, uint64_t seed, uint64_t sid,
+                                                                int renoise, float rn_a, float rn_b,
+                                                                const float* __restrict__ rn_noise, uint64_t rn_sid, MixArgs mix) {
   const int W4 = g.Wc / 4;
   const int xq = blockIdx.x * 256 + threadIdx.x;
   if (xq >= W4) return;
@@ -556,11 +488,11 @@ __global__ __launch_bounds__(256) void tiles_fuse_update_known_kernel(float* __r
     f32x4 xb;
     if (!fuse_tiles(x0_tiles, thr, tile_of, g, c, y, xx, xb)) continue;
     const int64_t j4 = (int64_t)row * W4 + xq;
-    const uint32_t mw = mix.on ? src_mask4(mix.mk, y, xx) : 0u;
+    const uint32_t mw = KNOWN && mix.on ? src_mask4(mix.mk, y, xx) : 0u;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (!mask_all(mw)) {
       o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, hist, j4, A, B, P, Sn, noise, seed, sid);
-      if (renoise) {
+      if (KNOWN && renoise) {
         const f32x4 z = rn_noise ? *(const f32x4*)(rn_noise + j4 * 4) : philox_normal4(seed, rn_sid, (uint64_t)j4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = o[e] * rn_a + z[e] * rn_b;
@@ -571,36 +503,36 @@ __global__ __launch_bounds__(256) void tiles_fuse_update_known_kernel(float* __r
     *(f32x4*)(x0bar_out + j4 * 4) = xb;
   }
 }
-int launch_tiles_fuse_update_known(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
-                                   const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
-                                   float P, float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise,
-                                   float rn_a, float rn_b, const float* rn_noise, uint64_t rn_sid, const TileMix& mix,
-                                   hipStream_t s) {
-  KD_REQUIRE(x && x0bar_out && x0_tiles && tile_of && (hist || P == 0.0f), "tiles fuse known: null argument");
+int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
+                             const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P,
+                             float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise, float rn_a, float rn_b,
+                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s) {
+  KD_REQUIRE(x && x0bar_out && x0_tiles && tile_of && (hist || P == 0.0f), "tiles fuse: null argument");
   TileGeom g;
-  if (tile_lattice("tiles fuse known", N, C, S, st, ny, nx, ramp, &g)) return 1;
+  if (tile_lattice("tiles fuse", N, C, S, st, ny, nx, ramp, &g)) return 1;
   KD_REQUIRE((((uintptr_t)x | (uintptr_t)hist | (uintptr_t)x0bar_out | (uintptr_t)x0_tiles | (uintptr_t)noise |
                (uintptr_t)rn_noise) & 15) == 0,
-             "tiles fuse known: x, hist, x0bar_out, x0_tiles and the noise tensors must be 16-byte aligned");
-  KD_REQUIRE(x != hist && x != x0bar_out, "tiles fuse known: x must not be the history or the estimate");
+             "tiles fuse: x, hist, x0bar_out, x0_tiles and the noise tensors must be 16-byte aligned");
+  KD_REQUIRE(x != hist && x != x0bar_out, "tiles fuse: x must not be the history or the estimate");
   MixArgs m;
-  if (tile_mix("tiles fuse known", mix, g.Hc, g.Wc, &m)) return 1;
-  const int W4 = g.Wc / 4;
-  const int64_t rows = (int64_t)C * g.Hc;
-  hipLaunchKernelGGL(tiles_fuse_update_known_kernel,
-                     dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, s, x, hist,
-                     x0bar_out, x0_tiles, thr, tile_of, g, A, B, P, Sn, noise, seed, stream_id, renoise != 0, rn_a, rn_b, rn_noise,
-                     rn_sid, m);
+  if (tile_mix("tiles fuse", mix, g.Hc, g.Wc, &m)) return 1;
+  // nothing known and no re-noise: the lean instantiation, whichever entry the call came through
+  const auto kernel = renoise || m.on ? tiles_fuse_update_kernel<true> : tiles_fuse_update_kernel<false>;
+  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, hist, x0bar_out, x0_tiles, thr, tile_of, g, A, B, P, Sn,
+                     noise, seed, stream_id, renoise != 0, rn_a, rn_b, rn_noise, rn_sid, m);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-// tiles_finalize_kernel with the paste: out = m ? kn : (clamp(x, -1, 1) + 1) * 0.5 on covered pixels - the known value
-// copied, not round-tripped.  kn may be the window of `out` that is written (the host checks that an overlapping source
-// is exactly that window): a thread then reads and writes the same element.
-__global__ __launch_bounds__(256) void tiles_finalize_known_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
-                                                                   TileGeom g, float* out, int Ho, int Wo, int oy, int ox,
-                                                                   ImgSrc kn, MaskSrc mk) {
+// ------------------------------------------------------------------------- the end of a stage
+// out[c, oy + y, ox + x] = (clamp(x[c, y, x], -1, 1) + 1) * 0.5 for every canvas pixel that a present tile covers; every
+// other element of out [C, Ho, Wo] keeps its bits.  One pass, no host mask.  With PASTE: out = m ? kn : the same - the known
+// value copied, not round-tripped.  kn may then be the window of `out` that is written (the host checks that an overlapping
+// source is exactly that window): a thread reads and writes the same element, so `out` is not restrict.
+template <bool PASTE>
+__global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
+                                                             TileGeom g, float* out, int Ho, int Wo, int oy, int ox, ImgSrc kn,
+                                                             MaskSrc mk) {
   const int W4 = g.Wc / 4;
   const int xq = blockIdx.x * 256 + threadIdx.x;
   if (xq >= W4) return;
@@ -608,15 +540,8 @@ __global__ __launch_bounds__(256) void tiles_finalize_known_kernel(const float* 
   const int rows = g.C * g.Hc;
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int c = row / g.Hc, y = row - c * g.Hc;
-    const TileCover cv = tile_cover(g, y, xx);
-    bool covered = false;
-    for (int r = cv.r_lo; r <= cv.r_hi; ++r)
-      for (int q = cv.q_lo; q <= cv.q_hi; ++q) {
-        const int t = tile_of[r * g.nx + q];
-        covered = covered || (t >= 0 && t < g.N);
-      }
-    if (!covered) continue;
-    const uint32_t mw = src_mask4(mk, y, xx);
+    if (!tile_covered(tile_of, g, y, xx)) continue;
+    const uint32_t mw = PASTE ? src_mask4(mk, y, xx) : 0u;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (!mask_all(mw)) {
       const f32x4 v = *(const f32x4*)(x + ((int64_t)row * W4 + xq) * 4);
@@ -635,32 +560,32 @@ __global__ __launch_bounds__(256) void tiles_finalize_known_kernel(const float* 
     *(f32x4*)(out + ((int64_t)c * Ho + oy + y) * Wo + ox + xx) = o;
   }
 }
-int launch_tiles_finalize_known(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out,
-                                int Ho, int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s) {
-  KD_REQUIRE(x && tile_of && out && known && mask, "tiles finalize known: null argument");
+int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
+                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s) {
+  KD_REQUIRE(x && tile_of && out, "tiles finalize: null argument");
+  KD_REQUIRE((known != nullptr) == (mask != nullptr), "tiles finalize: the known image and the mask come together");
   TileGeom g;
-  if (tile_lattice("tiles finalize known", N, C, S, st, ny, nx, 0, &g)) return 1;
-  const int64_t Hc = g.Hc, Wc = g.Wc;
+  if (tile_lattice("tiles finalize", N, C, S, st, ny, nx, 0, &g)) return 1;
+  const int64_t Hc = g.Hc, Wc = g.Wc;   // (oy + Hc, ox + Wc: no overflow for any int offset)
   KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
-             "tiles finalize known: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
-  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo,
-             "tiles finalize known: the canvas at (oy, ox) lies outside the output");
-  KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize known: x and out must be 16-byte aligned");
-  ImgSrc kn;
-  MaskSrc mk;
-  if (tile_image("tiles finalize known image", known, g.Hc, g.Wc, &kn)) return 1;
-  if (tile_source("tiles finalize known mask", mask, g.Hc, g.Wc, 0, 4, &mk)) return 1;
-  // a source inside the output must be the window written: every thread then reads the element it writes, and no other
-  const uintptr_t kn0 = (uintptr_t)known->d, out0 = (uintptr_t)out;
-  const uintptr_t kn1 = kn0 + 4 * (uintptr_t)((int64_t)(C - 1) * known->plane + (int64_t)(known->H - 1) * known->row + known->W);
-  if (kn0 < out0 + 4 * (uintptr_t)((int64_t)C * Ho * Wo) && kn1 > out0)
-    KD_REQUIRE(known->d == out + (int64_t)oy * Wo + ox && known->H == g.Hc && known->W == g.Wc && known->row == Wo &&
-                   (C == 1 || known->plane == (int64_t)Ho * Wo),
-               "tiles finalize known: a known image inside the output must be the window at (oy, ox) that is written");
-  const int W4 = g.Wc / 4;
-  const int64_t rows = C * Hc;
-  hipLaunchKernelGGL(tiles_finalize_known_kernel, dim3((unsigned)((W4 + 255) / 256), (unsigned)std::min<int64_t>(rows, 65535)),
-                     dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox, kn, mk);
+             "tiles finalize: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
+  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo, "tiles finalize: the canvas at (oy, ox) lies outside the output");
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize: x and out must be 16-byte aligned");
+  ImgSrc kn{};
+  MaskSrc mk{};
+  if (known) {
+    if (tile_image("tiles finalize known image", known, g.Hc, g.Wc, &kn)) return 1;
+    if (tile_source("tiles finalize known mask", mask, g.Hc, g.Wc, 0, 4, &mk)) return 1;
+    // a source inside the output must be the window written: every thread then reads the element it writes, and no other
+    const uintptr_t kn0 = (uintptr_t)known->d, out0 = (uintptr_t)out;
+    const uintptr_t kn1 = kn0 + 4 * (uintptr_t)((int64_t)(C - 1) * known->plane + (int64_t)(known->H - 1) * known->row + known->W);
+    if (kn0 < out0 + 4 * (uintptr_t)((int64_t)C * Ho * Wo) && kn1 > out0)
+      KD_REQUIRE(known->d == out + (int64_t)oy * Wo + ox && known->H == g.Hc && known->W == g.Wc && known->row == Wo &&
+                     (C == 1 || known->plane == (int64_t)Ho * Wo),
+                 "tiles finalize: a known image inside the output must be the window at (oy, ox) that is written");
+  }
+  const auto kernel = known ? tiles_finalize_kernel<true> : tiles_finalize_kernel<false>;
+  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox, kn, mk);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -1755,7 +1755,7 @@ class Imagen(nn.Module):
         lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
         tiles per UNet forward, their thresholded x0 estimates are averaged where tiles overlap (``tile_weights``) and the
         update of ``sampler`` (None / ``"ddpm"``, ``"ddim"`` with ``sampler_eta``, ``"dpmpp_2m"``; ``sample_steps`` as in
-        ``sample``) runs once, on the canvas, with canvas-level noise (kd_tiles_fuse_update).  There is no inpainting, no
+        ``sample``) runs once, on the canvas, with canvas-level noise (kd_tiles_fuse_update_known).  There is no inpainting, no
         resampling and no order among the tiles, and the canvas does not depend on ``tile_batch`` beyond the rounding of
         plans of different batch sizes.
 
@@ -1768,9 +1768,9 @@ class Imagen(nn.Module):
         stages' canvases with ``return_all_unet_outputs``); pixels that no tile covers are 0.
 
         Three arguments carry a stage to the sizes of a magnification level (a 40960 x 40960 canvas of 1024-pixel tiles);
-        a call without them keeps its code path and its bits.  ``streamed=True``: the low-res conditioning tiles are cut
+        a call without them keeps its bits.  ``streamed=True``: the low-res conditioning tiles are cut
         straight out of the previous canvas (kd_tiles_gather_lowres: no resized, augmented canvas is built) and the stage
-        ends in one pass into a zero canvas (kd_tiles_finalize: no host mask, no temporaries) - bit-equal to
+        ends in one pass into a zero canvas (kd_tiles_finalize_known: no host mask, no temporaries) - bit-equal to
         ``streamed=False``.  ``cond_crops``: a ``TileCondCrops`` in the place of ``cond_images`` - the tiles'
         conditioning images are windows of one image, cut per chunk by kd_tiles_cond_gather, bit-equal to
         ``cond_images=cond_images_for_grid(...)``.  ``into=(canvas, oy, ox)`` (needs ``streamed``): the last sampled stage
@@ -1789,10 +1789,10 @@ class Imagen(nn.Module):
         its history; a self-conditioned UNet carries the previous slot's.  ``init_canvas`` (one image, or one per UNet)
         and ``init_skip_steps`` (``normalize_init_canvas``; counted in ``sample_steps`` where given): the stage starts from
         ``z + nearest(2 init - 1)`` and walks steps ``skip .. T - 1``; a step keeps its index - table row, streams, tags -
-        and 2M is first order on the first step walked.  With any of them the stage starts through kd_tiles_start, steps
-        through kd_tiles_fuse_update_known (update, re-noise and the next slot's mix in the one canvas pass) and, with a
-        mask, ends through kd_tiles_finalize_known (``streamed``) or the same paste in torch.  ``known_image`` may be a
-        window of the ``into`` canvas itself."""
+        and 2M is first order on the first step walked.  Every stage, with or without them, starts through kd_tiles_start,
+        steps through kd_tiles_fuse_update_known (update, re-noise and the next slot's mix in the one canvas pass) and ends
+        through kd_tiles_finalize_known (``streamed``) or the same clamp and paste in torch; a call without them passes
+        NULL sources and keeps its bits.  ``known_image`` may be a window of the ``into`` canvas itself."""
         for name, v in dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
                             inpaint_resample_times=inpaint_resample_times).items():
             if exists(v):
@@ -1873,17 +1873,19 @@ class Imagen(nn.Module):
     def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
                      lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
                      solver=("ddpm", 0.0), streamed=False, crops=None, into=None, known=(None, None, 1), start=(None, 0)):
-        """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  Per schedule step k and chunk of at
-        most `tile_batch` tiles: gather the chunk out of the canvas into the plan's stable buffers, one iteration
-        kd_solver_sample_steps(k, k + 1) with DDIM(0) coefficients (first order: no history, no draw; its tile-level
-        update is discarded), the x0 estimates and thresholds into the tile store; then ONE kd_tiles_fuse_update with the
-        canvas sampler's coefficients of step k.  A ragged last chunk runs the plan of its own batch size.
+        """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  kd_tiles_start writes x_T; then, per
+        resample slot of the schedule steps skip .. T - 1 and chunk of at most `tile_batch` tiles: gather the chunk out of
+        the canvas into the plan's stable buffers, one iteration kd_solver_sample_steps(k, k + 1) with DDIM(0)
+        coefficients (first order: no history, no draw; its tile-level update is discarded), the x0 estimates and
+        thresholds into the tile store; then ONE kd_tiles_fuse_update_known with the canvas sampler's coefficients of
+        step k.  A ragged last chunk runs the plan of its own batch size.
         `streamed`: the chunk's low-res tiles come from the previous canvas (kd_tiles_gather_lowres) and the stage ends
-        with kd_tiles_finalize, into `into = (canvas, oy, ox)` or a zero canvas; `crops`: (TileCondCrops, Cs, W, tile
+        with kd_tiles_finalize_known, into `into = (canvas, oy, ox)` or a zero canvas; `crops`: (TileCondCrops, Cs, W, tile
         channels, top, shifts) - the chunk's conditioning tiles come from its image (kd_tiles_cond_gather).
-        `known = (image, mask, R)` / `start = (init image, skip)`: with any of them the stage walks the R resample slots of
-        the steps skip .. T - 1 - kd_tiles_start, then per slot the tiles and ONE kd_tiles_fuse_update_known that also
-        re-noises and mixes the known pixels for the next slot - and ends with the paste of the known pixels."""
+        `known = (image, mask, R)` / `start = (init image, skip)`: the same three calls carry them - the start adds the init
+        image and the first mix, the canvas step also re-noises and mixes the known pixels for the next slot, the end
+        pastes them.  Without them (R = 1, skip = 0) the sources are NULL, a step has one slot and the calls give the
+        bits of the Philox draw, kd_tiles_fuse_update and kd_tiles_finalize."""
         lib = E.load()
         Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
         origins = geo["origins"]
@@ -1895,7 +1897,6 @@ class Imagen(nn.Module):
 
         kn, km, R = known
         init, skip = start
-        ext = exists(kn) or exists(init) or skip > 0   # without them: the code path and the bits of before
         tables = sched.step_tables()
         coefs = canvas_tables(tables, *solver, skip=skip)
         sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
@@ -1904,22 +1905,21 @@ class Imagen(nn.Module):
         inject = lambda kind, k, j: f32(noise_fn((kind, stage, k, R - 1 - j), shape)) if exists(noise_fn) else None
 
         with torch.cuda.device(device):
-            if ext:   # the sources stay where they lie: views of the caller's tensors, described to the kernels
-                here = lambda t: t.is_cuda and t.device.index == default(device.index, torch.cuda.current_device())
-                kn, init = (t if t is None or here(t) else f32(t) for t in (kn, init))
-                km = km if km is None or here(km) else km.to(device)
-                kn_s, km_s, init_s = E.tiles_image(kn), E.tiles_mask(km), E.tiles_image(init)
-                mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
-                x = torch.empty(shape, device=device, dtype=torch.float32)
-                z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
-                zm = inject("inpaint", skip, 0) if exists(kn) else None
-                E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
-                                           E.ref(kn_s), E.ref(km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
-                # 2M under resampling: the history takes a step's estimate in its last slot only, the slots before it
-                # leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
-                x0bar_slot = torch.empty(shape, device=device, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
-            else:
-                x = gauss(("init", stage), shape, (16 << 32) | 2)
+            # the sources that exist stay where they lie: views of the caller's tensors, described to the kernels
+            here = lambda t: t.is_cuda and t.device.index == default(device.index, torch.cuda.current_device())
+            kn, init = (t if t is None or here(t) else f32(t) for t in (kn, init))
+            km = km if km is None or here(km) else km.to(device)
+            kn_s, km_s, init_s = E.tiles_image(kn), E.tiles_mask(km), E.tiles_image(init)
+            mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
+            x = torch.empty(shape, device=device, dtype=torch.float32)
+            z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
+            zm = inject("inpaint", skip, 0) if exists(kn) else None
+            # (scale 1, no image, no mask: 1.0 * z, the bits of the draw itself)
+            E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
+                                       E.ref(kn_s), E.ref(km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
+            # 2M under resampling: the history takes a step's estimate in its last slot only, the slots before it
+            # leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
+            x0bar_slot = torch.empty(shape, device=device, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
             x0bar = torch.zeros(shape, device=device, dtype=torch.float32)
             store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
             thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
@@ -2014,12 +2014,6 @@ class Imagen(nn.Module):
                 A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
                 z = inject("step", k, j) if Sn != 0.0 else None
                 # (z: memory of torch's current stream, handed on only behind this launch)
-                if not ext:
-                    E.check(lib.kd_tiles_fuse_update(E.ptr(x), E.ptr(x0bar), E.ptr(store), E.ptr(thr),
-                                                     C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx,
-                                                     int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed,
-                                                     (1 << 32) | k, stream()))
-                    continue
                 it = k * R + j
                 renoise = j < R - 1 and k < T - 1
                 zr = inject("renoise", k, j) if renoise else None
@@ -2037,12 +2031,8 @@ class Imagen(nn.Module):
             if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
                 out, oy, ox = into if exists(into) else (torch.zeros(shape, device=device, dtype=torch.float32), 0, 0)
                 assert out.device == x.device, f"into: the canvas lives on {out.device}, the stage runs on {x.device}"
-                if exists(kn):
-                    E.check(lib.kd_tiles_finalize_known(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
-                                                        out.shape[2], out.shape[3], oy, ox, E.ref(kn_s), E.ref(km_s), stream()))
-                else:
-                    E.check(lib.kd_tiles_finalize(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
-                                                  out.shape[2], out.shape[3], oy, ox, stream()))
+                E.check(lib.kd_tiles_finalize_known(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
+                                                    out.shape[2], out.shape[3], oy, ox, E.ref(kn_s), E.ref(km_s), stream()))
                 return out
             covered = torch.zeros(Hc, Wc, dtype=torch.bool)
             for y0, x0 in origins:

@@ -400,7 +400,8 @@ def test_the_known_kernels_refuse_and_launch_nothing(device):
          "come together"),
         (lambda: _finalize_known(x, lat, out, 0, 2, kn, m), "ox % 4"),
         (lambda: _finalize_known(x, lat, out, 16, 0, kn, m), "outside the output"),
-        (lambda: _finalize_known(x, lat, out, 0, 0, None, m), "null argument"),
+        (lambda: _finalize_known(x, lat, out, 0, 0, None, m), "come together"),
+        (lambda: _finalize_known(x, lat, out, 0, 0, kn, None), "come together"),
         (lambda: _finalize_known(x, lat, out, 0, 0, out[:, 4:32, 4:32], m), "must be the window at"),   # inside out, elsewhere
         (lambda: _finalize_known(x, lat, out, 0, 0, out[:, 0:28, 0:36], m), "must be the window at"),   # inside out, another size
     ]
