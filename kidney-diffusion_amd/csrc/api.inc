@@ -988,45 +988,18 @@ int kd_init_conv_plain_nchw(const float* d_x, const float* d_self_cond, const fl
   return 0;
 }
 
-// The final 3x3 conv to the image's channels as the plan runs it (unet_build.inc tail, kernels_final.hip): weight pack,
-// the 1x1 GEMM to the (output, tap) columns, the low-res planes' step-invariant share when d_lowres is given, the gather
-int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
-                       int B, int H, int W, int Cfeat, int channels, void* stream) {
+// The final k x k conv to the image's channels as the plan runs it (unet_build.inc, kernels_final.hip): weight pack, the 1x1
+// GEMM to the (output, tap) columns, the low-res planes' step-invariant share when d_lowres is given, the gather
+static int final_conv_nchw(const std::string& w, const float* d_feat, const float* d_w_oihw, const float* d_bias,
+                           const float* d_lowres, float* d_out, int B, int H, int W, int Cfeat, int channels, int ksize,
+                           void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  KD_REQUIRE(d_feat && d_w_oihw && d_bias && d_out, "kd_final_conv_nchw: null argument");
-  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_final_conv_nchw: 1 to 4 image channels");
-  KD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cfeat >= 4 && Cfeat % 4 == 0 && (int64_t)B * H * W < 0x7fffffff / 48,
-             "kd_final_conv_nchw needs a non-empty map below 2^31 / 48 pixels and Cfeat % 4 == 0");
-  const int Ctot = Cfeat + (d_lowres ? channels : 0), nf = final_gemm_cols(channels);
-  EntryBufs bufs;
-  float *wp = nullptr, *pm = nullptr, *stat = nullptr;
-  if (bufs.get(&wp, (size_t)nf * Cfeat * sizeof(float)) || bufs.get(&pm, (size_t)B * H * W * nf * sizeof(float))) return 1;
-  if (d_lowres && bufs.get(&stat, (size_t)B * channels * H * W * sizeof(float))) return 1;
-  int rc = launch_pack_final(d_w_oihw, wp, Ctot, Cfeat, channels, s);
-  if (!rc && d_lowres) rc = launch_final_static(d_lowres, d_w_oihw, d_bias, stat, Ctot, Cfeat, channels, B, H, W, s);
-  if (!rc) {
-    ConvParams p{};
-    p.x = d_feat; p.w = wp; p.y = pm;
-    p.B = B; p.Hi = H; p.Wi = W; p.Cin = Cfeat; p.ldx = Cfeat;
-    p.Ho = H; p.Wo = W; p.Cout = nf;
-    p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
-    p.out_mode = OUT_NHWC; p.ldy = nf;
-    rc = launch_conv_igemm(p, s);
-  }
-  if (!rc) rc = launch_final_gather(pm, stat, d_bias, d_out, channels, B, H, W, s);
-  return entry_finish(rc, s);
-}
-
-// The same for final_conv_kernel_size = ksize (1 | 3 | 5 | 7): the k x k launches of the plan (ksize = 3: kd_final_conv_nchw)
-int kd_final_conv_k_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
-                         int B, int H, int W, int Cfeat, int channels, int ksize, void* stream) {
-  if (ksize == 3) return kd_final_conv_nchw(d_feat, d_w_oihw, d_bias, d_lowres, d_out, B, H, W, Cfeat, channels, stream);
-  hipStream_t s = (hipStream_t)stream;
-  KD_REQUIRE(d_feat && d_w_oihw && d_bias && d_out, "kd_final_conv_k_nchw: null argument");
-  KD_REQUIRE(channels >= 1 && channels <= 4, "kd_final_conv_k_nchw: 1 to 4 image channels");
-  KD_REQUIRE(ksize == 1 || ksize == 5 || ksize == 7, "kd_final_conv_k_nchw: kernel size 1, 3, 5 or 7");
-  KD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cfeat >= 4 && Cfeat % 4 == 0 && (int64_t)B * H * W < 0x7fffffff / 208,
-             "kd_final_conv_k_nchw needs a non-empty map below 2^31 / 208 pixels and Cfeat % 4 == 0");
+  KD_REQUIRE(d_feat && d_w_oihw && d_bias && d_out, w + ": null argument");
+  KD_REQUIRE(channels >= 1 && channels <= 4, w + ": 1 to 4 image channels");
+  KD_REQUIRE(ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7, w + ": kernel size 1, 3, 5 or 7");
+  const int most = ksize == 3 ? 48 : 208;   // columns of P at 4 channels
+  KD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cfeat >= 4 && Cfeat % 4 == 0 && (int64_t)B * H * W < 0x7fffffff / most,
+             w + " needs a non-empty map below 2^31 / " + std::to_string(most) + " pixels and Cfeat % 4 == 0");
   const int Ctot = Cfeat + (d_lowres ? channels : 0), nf = final_gemm_cols_k(channels, ksize);
   EntryBufs bufs;
   float *wp = nullptr, *pm = nullptr, *stat = nullptr;
@@ -1045,6 +1018,15 @@ int kd_final_conv_k_nchw(const float* d_feat, const float* d_w_oihw, const float
   }
   if (!rc) rc = launch_final_gather_k(pm, stat, d_bias, d_out, channels, ksize, B, H, W, s);
   return entry_finish(rc, s);
+}
+int kd_final_conv_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                       int B, int H, int W, int Cfeat, int channels, void* stream) {
+  return final_conv_nchw("kd_final_conv_nchw", d_feat, d_w_oihw, d_bias, d_lowres, d_out, B, H, W, Cfeat, channels, 3, stream);
+}
+int kd_final_conv_k_nchw(const float* d_feat, const float* d_w_oihw, const float* d_bias, const float* d_lowres, float* d_out,
+                         int B, int H, int W, int Cfeat, int channels, int ksize, void* stream) {
+  return final_conv_nchw("kd_final_conv_k_nchw", d_feat, d_w_oihw, d_bias, d_lowres, d_out, B, H, W, Cfeat, channels, ksize,
+                         stream);
 }
 
 int kd_groupnorm_silu_nhwc(const float* d_x, const float* d_gamma, const float* d_beta, const float* d_scale_shift,

@@ -360,16 +360,12 @@ int launch_upsample_scale_conv3x3(const float* x, int ldx, const float* ab, cons
                                   int yoff, int B, int H, int W, int Cin, int Cout, int scale, hipStream_t s);
 
 // ---- final conv to the image's `ch` = 1 .. 4 channels (kernels_final.hip)
-int final_gemm_cols(int ch);   // width of P: the 9 ch (output, tap) columns padded for the 1x1 GEMM (32; 48 at ch = 4)
-int launch_pack_final(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, hipStream_t s);
-// (ks: the conv's kernel size, 1 | 3 | 5 | 7)
-int launch_final_static(const float* lowres, const float* w_oihw, const float* bias, float* stat, int Ctot, int c0,
-                        int ch, int B, int H, int W, hipStream_t s, int ks = 3);
-int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int ch, int B, int H, int W,
-                        hipStream_t s);
-// the same for final_conv_kernel_size = k (1 | 5 | 7; k = 3 forwards to the functions above): ch (k^2 rounded up to 4) columns n = o kp + tap
+// k: the conv's kernel size, 1 | 3 | 5 | 7.  Width of P: the ch kp (output, tap) columns n = o kp + tap padded for the 1x1
+// GEMM, kp = 9 at k = 3 (32 columns; 48 at ch = 4), else k^2 rounded up to 4
 int final_gemm_cols_k(int ch, int k);
 int launch_pack_final_k(const float* w_oihw, float* w_packed, int Ctot, int C, int ch, int k, hipStream_t s);
+int launch_final_static(const float* lowres, const float* w_oihw, const float* bias, float* stat, int Ctot, int c0,
+                        int ch, int B, int H, int W, hipStream_t s, int ks = 3);
 int launch_final_gather_k(const float* P, const float* stat, const float* bias, float* out, int ch, int k, int B, int H, int W,
                           hipStream_t s);
 

@@ -134,6 +134,7 @@ struct T {  // NHWC tensor in the workspace, or a channel slice of one (a skip t
   int LD() const { return ld ? ld : C; }
   size_t at() const { return off + (size_t)coff * sizeof(float); }  // byte offset of (row 0, channel 0)
   bool dense() const { return LD() == C; }
+  T slice(int c0, int n) const { T s = *this; s.ld = LD(); s.C = n; s.coff = coff + c0; return s; }  // channels [c0, c0 + n)
 };
 
 // ------------------------------------------------------------------------------ sampler state (sampler.inc)
@@ -359,7 +360,6 @@ struct Builder {
   T t_ss;  // [B, tmlp_total] scale|shift rows for all blocks
   // shared scratch
   T gn_stats_t, gn_partial_t;
-  T init_x_;  // output of the init conv (set inside a nested scope of build())
   size_t gn_partial_max = 0;
 
   Builder(kd_unet* u_) : u(u_), cfg(u_->cfg), B(u_->cfg.batch) {}
@@ -661,6 +661,7 @@ struct Builder {
     bool want_seg = false;      // the output feeds a GroupNorm: leave its partials in the epilogue where possible
     int seg_c0 = -1, seg_cn = 0;  // channel range of y the partial buffer spans (default: this launch's own range);
                                   // launches filling slices of one tensor name the same span and share the buffer
+    int* seg_nchunk = nullptr;    // out: chunks per image of the GroupNorm partials the launch leaves, 0 = none
   };
   // What every layer on the bf16x3 kernel's epilogue form (kernels_gemm_bf16x3.hip) must pass: a default-algorithm plan's
   // ordinary step op, whole tiles and at least 64 of them, K of at least min_k where the launch runs whole rounds, and the
@@ -743,7 +744,6 @@ struct Builder {
     u->mfma_bf16_macs += u->op_mfma.back();
     if (sh.needs_sum()) emit([=](hipStream_t s) { return launch(s, true); }, stem + " x3 sum" + shape);
   }
-  int last_seg_nchunk = 0;   // chunks per image of the GroupNorm partials the last conv() / downsample_x3() leaves, 0 = none
   T conv(const T& x, const float* w, const float* bias, int Cout, int K, int stride, int pad, const ConvOpt& o) {
     if (x.x3p && !x3_linear_ok(x, Cout, K, stride, pad, o))
       throw std::runtime_error("plan: a tensor in plane form reached a layer that is not a bf16x3 GEMM");
@@ -822,7 +822,7 @@ struct Builder {
         sego = have ? have->off : add_seg(y, seg_c0, seg_nseg, nchunk);
       }
     }
-    last_seg_nchunk = seg_nseg ? seg_nchunk : 0;
+    if (o.seg_nchunk) *o.seg_nchunk = seg_nseg ? seg_nchunk : 0;
     // ---- token GEMMs / 1x1 convs with K >= 512 as fp32 products on the bf16 matrix pipe (kernels_gemm_bf16x3.hip,
     // epilogue form: bias / residual / gate, strided rows; weights split into planes once per plan, the fp32 activations by
     // the kernel's loader waves; GroupNorm partials of the output where no tile is cut in k).  Layers with an activation
@@ -1212,7 +1212,7 @@ struct Builder {
   // ---- The path of a ResnetBlock 3x3 conv, the `Block` = GroupNorm -> [FiLM] -> SiLU -> conv3x3 (gn_conv3x3): Winograd
   // F(4x4,3x3) as 36 batched GEMMs (wino4_block), F(2x2,3x3) as 16 batched GEMMs (wino_block), the fused F(2x2,3x3) kernel
   // with the GroupNorm folded in (fwino_gn_conv), or gn_silu + the direct conv.  Decided here alone: resnet() dispatches on
-  // it, and add_skip (unet_build.inc) asks it whether the layer takes a skip concat's 2^-1/2 itself - Wino4 through its
+  // it, and SkipStack::pop (unet_build.inc) asks it whether the layer takes a skip concat's 2^-1/2 itself - Wino4 through its
   // input transform's affine, WinoFused through the GroupNorm partials' ab_mul (SegPart); the other two read the skip half
   // scaled in memory.
   enum class Conv3x3 { Wino4, WinoGemm, WinoFused, Direct };
@@ -1308,7 +1308,7 @@ struct Builder {
   }
   // Bx images per set of launches (wino4_images): V and D are one set's, the sets run one after the other.
   // skip_c0 >= 0: channels [skip_c0, ..) of x hold an unscaled skip tensor the layer must see times skip_scale: the input
-  // transform folds the factor into its affine (the statistics come from partials that carry the scale: add_skip)
+  // transform folds the factor into its affine (the statistics come from partials that carry the scale: SkipStack::pop)
   T wino4_block(const T& x, int Bx, const std::string& gn_prefix, int ss_col, const std::string& conv_prefix, int Cout,
                 const T* res, int skip_c0, float skip_scale) {
     const int Cin = x.C, G = cfg.resnet_groups, H = x.H, W = x.W, HW = x.HW(), nset = x.B / Bx;
@@ -1516,15 +1516,19 @@ struct Builder {
   // skip_c0 >= 0: x is a concat whose channels [skip_c0, ..) hold an UNSCALED skip tensor that the layer must see
   // scaled by skip_scale: the GroupNorm gets it through the partials' scale (SegPart), the 1x1 skip conv through
   // weights whose columns were scaled at plan build.
-  // false while unet_build.inc emits the last producer in front of a final conv that reads it directly (final_resnet_block=False):
-  // no GroupNorm normalises that output, so its ResnetBlock / upsample does not leave partials
-  bool out_seg = true;
-  T resnet(const T& x, const std::string& pre, int dim_out, const T* ctx, bool use_gca, const T* ct = nullptr,
-           const T* out_slot = nullptr, int skip_c0 = -1, float skip_scale = 1.0f) {
+  // out_seg: false for the last producer in front of a final conv that reads it directly (final_resnet_block=False): no
+  // GroupNorm normalises that output, so its ResnetBlock / upsample does not leave partials
+  struct ResnetOpt {
+    const T *ct = nullptr, *out_slot = nullptr;
+    int skip_c0 = -1;
+    float skip_scale = 1.0f;
+    bool out_seg = true;
+  };
+  T resnet(const T& x, const std::string& pre, int dim_out, const T* ctx, bool use_gca, const ResnetOpt& ro) {
     bool has_cross = has(pre + ".cross_attn.to_q.weight");
     if (has_cross && !ctx) throw std::runtime_error("cross-attention block without conditioning tokens: " + pre);
     int dim_in = x.C;
-    T h = gn_conv3x3(x, false, pre + ".block1", -1, dim_out, nullptr, skip_c0, skip_scale);
+    T h = gn_conv3x3(x, false, pre + ".block1", -1, dim_out, nullptr, ro.skip_c0, ro.skip_scale);
     if (has_cross) {
       T h2 = lin_cross_pre.count(pre) ? linear_cross_attn(h, pre + ".cross_attn", *ctx) : cross_attn(h, pre + ".cross_attn", *ctx);
       free(h);
@@ -1535,15 +1539,15 @@ struct Builder {
     bool has_res_conv = has(pre + ".res_conv.weight");
     T h2 = gn_conv3x3(h, true, pre + ".block2", ss_col, dim_out, (!use_gca && !has_res_conv) ? &x : nullptr);
     if (!use_gca && !has_res_conv) return h2;
-    if (skip_c0 >= 0 && !has_res_conv) throw std::runtime_error("plan: folded skip scale without a skip conv: " + pre);
+    if (ro.skip_c0 >= 0 && !has_res_conv) throw std::runtime_error("plan: folded skip scale without a skip conv: " + pre);
     const float* w_res = nullptr;
     if (has_res_conv) {
       w_res = P(pre + ".res_conv.weight", (int64_t)dim_out * dim_in);
-      if (skip_c0 >= 0) {   // columns of the skip channels times skip_scale
+      if (ro.skip_c0 >= 0) {   // columns of the skip channels times skip_scale
         const float* src = w_res;
-        w_res = cached("res_conv_skipscaled:" + pre + ":" + std::to_string(skip_c0), (size_t)dim_out * dim_in, [&](float* dst) {
+        w_res = cached("res_conv_skipscaled:" + pre + ":" + std::to_string(ro.skip_c0), (size_t)dim_out * dim_in, [&](float* dst) {
           KD_THROW_IF(launch_copy_scale_rows(src, dim_in, dst, dim_in, dim_in, 1.0f, dim_out, 0));
-          KD_THROW_IF(launch_copy_scale_rows(dst + skip_c0, dim_in, dst + skip_c0, dim_in, dim_in - skip_c0, skip_scale,
+          KD_THROW_IF(launch_copy_scale_rows(dst + ro.skip_c0, dim_in, dst + ro.skip_c0, dim_in, dim_in - ro.skip_c0, ro.skip_scale,
                                              dim_out, 0));
         });
       }
@@ -1555,15 +1559,15 @@ struct Builder {
         ConvOpt o;
         o.gate_src = &h2;
         o.gate = &gate;
-        o.want_seg = out_seg;
-        if (ct) o.dst = ct;
+        o.want_seg = ro.out_seg;
+        if (ro.ct) o.dst = ro.ct;
         out = conv(x, w_res, P(pre + ".res_conv.bias", dim_out), dim_out, 1, 1, 0, o);
       } else {
-        out = out_slot ? *out_slot : alloc(x.B, x.H, x.W, dim_out);
+        out = ro.out_slot ? *ro.out_slot : alloc(x.B, x.H, x.W, dim_out);
         if (out.C != dim_out) throw std::runtime_error("plan: output slot of the wrong width: " + pre);
         const Ref ar = at(h2), gr = at(gate), rr = at(x), yr = at(out);
         int Bx = x.B, HW = x.HW(), ldr = x.LD(), ldy = out.LD();
-        const bool sg = out_seg && dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
+        const bool sg = ro.out_seg && dim_out % 16 == 0;   // GroupNorm partials of `out` for the block that reads it
         const Ref seg = sg ? seg_at(add_seg(out, 0, dim_out / 16, gate_add_chunks(Bx, HW))) : Ref();
         emit([=](hipStream_t s) {
           return launch_gate_add(ar.f(), gr.f(), rr.f(), ldr, yr.f(), ldy, seg.d(), Bx, HW, dim_out, s);
@@ -1573,8 +1577,8 @@ struct Builder {
     } else {  // res_conv without gca: out = conv1x1(x) + h2
       ConvOpt o;
       o.res = &h2;
-      o.want_seg = out_seg;
-      if (ct) o.dst = ct;
+      o.want_seg = ro.out_seg;
+      if (ro.ct) o.dst = ro.ct;
       out = conv(x, w_res, P(pre + ".res_conv.bias", dim_out), dim_out, 1, 1, 0, o);
     }
     free(h2);
@@ -1599,9 +1603,9 @@ struct Builder {
     return x3_epi_layer_ok((int64_t)x.B * (x.H / 2) * (x.W / 2), Cout, 4 * x.C, 256, downsample_x3_epi(x, ldy ? ldy : Cout));
   }
   // dst: write channels [0, Cout) of this map (of dst->C >= Cout channels, whose GroupNorm partials the launch's buffer then
-  // spans: the launches filling the other channels find it under the same span) instead of a new one
+  // spans: the launches filling the other channels find it under the same span) instead of a new one; seg_nchunk: as ConvOpt's
   T downsample_x3(const T& x, const std::string& pre, const float* w_taps /*[tap][O][C]*/, const float* bias, int Cout,
-                  const T* dst = nullptr) {
+                  const T* dst = nullptr, int* seg_nchunk = nullptr) {
     const int C = x.C, K = 4 * C, Ho = x.H / 2, Wo = x.W / 2;
     const int64_t M = (int64_t)x.B * Ho * Wo;
     // B operand [O][K] with k = tap C + c, then its three planes
@@ -1622,8 +1626,9 @@ struct Builder {
     // the output feeds the GroupNorm of the level's first ResnetBlock: partials from the epilogue
     const int span = y.C;   // channels the partial buffer covers
     const bool sg = Cout % 16 == 0 && span % 16 == 0 && (Ho * Wo) % 32 == 0;
-    last_seg_nchunk = sg ? Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows() : 0;
-    const Ref seg = sg ? seg_at(add_seg(y, 0, span / 16, last_seg_nchunk)) : Ref();
+    const int nchunk = sg ? Ho * Wo / gemm_bf16x3_shape(1, (int)M, Cout, K, u->cus).seg_rows() : 0;
+    if (seg_nchunk) *seg_nchunk = nchunk;
+    const Ref seg = sg ? seg_at(add_seg(y, 0, span / 16, nchunk)) : Ref();
     auto epi_of = [=]() {
       X3Epi e = base;
       e.bias = bias;
@@ -1664,18 +1669,20 @@ struct Builder {
     const float* w2 = pack_conv(pre + ".convs.0.weight", d2, C, C, 2);   // [tap = kh 2 + kw][O][C]: downsample()'s tap layout
     const float* b2 = P(pre + ".convs.0.bias", d2);
     T y = alloc(x.B, x.H / 2, x.W / 2, dim_out);
+    int chunks2 = 0, chunks4 = 0;   // of the partials each half leaves
     if (downsample_x3_ok(x, d2, dim_out)) {
-      downsample_x3(x, pre + ".convs.0", w2, b2, d2, &y);
+      downsample_x3(x, pre + ".convs.0", w2, b2, d2, &y, &chunks2);
     } else {
       ConvOpt o2;
+      o2.seg_nchunk = &chunks2;
       o2.dst = &y;
       o2.want_seg = true;
       o2.seg_c0 = 0;
       o2.seg_cn = dim_out;
       conv(x, w2, b2, d2, 2, 2, 0, o2);
     }
-    const int chunks2 = last_seg_nchunk;
     ConvOpt o4;
+    o4.seg_nchunk = &chunks4;
     o4.dst = &y;
     o4.yoff = d2;
     o4.want_seg = true;
@@ -1684,7 +1691,7 @@ struct Builder {
     conv(x, pack_conv(pre + ".convs.1.weight", d4, C, C, 4), P(pre + ".convs.1.bias", d4), d4, 4, 2, 1, o4);
     // one buffer over all dim_out channels, filled by both launches - or none
     auto it = seg_of.find(y.at());
-    if (it != seg_of.end() && (it->second.parts.size() != 1 || chunks2 == 0 || chunks2 != last_seg_nchunk)) {
+    if (it != seg_of.end() && (it->second.parts.size() != 1 || chunks2 == 0 || chunks2 != chunks4)) {
       for (auto& sp : it->second.parts)
         if (sp.owned) arena.release(sp.off);
       seg_of.erase(it);
@@ -1716,7 +1723,7 @@ struct Builder {
     count_macs(m, 4 * M * dim_out * 4 * C);
     return y;
   }
-  T upsample(const T& x, const std::string& pre, int dim_out, const T* ct = nullptr) {  // conv1x1 -> SiLU -> PixelShuffle(2)
+  T upsample(const T& x, const std::string& pre, int dim_out, const T* ct, bool out_seg) {  // conv1x1 -> SiLU -> PixelShuffle(2)
     if (u->upsample_nearest) return upsample_nearest(x, pre, dim_out, ct);
     const float* wsrc = raw(pre + ".net.0.weight", (int64_t)4 * dim_out * x.C);
     const float* bsrc = raw(pre + ".net.0.bias", 4 * dim_out);
@@ -1914,6 +1921,74 @@ struct Builder {
   T linear_attn_block(const T& x, const std::string& pre, const T* ctx, const T* dst = nullptr);
   T linear_cross_attn(const T& x, const std::string& pre, const T& c);
   T feed_forward_tail(const T& x, const T& proj, const std::string& g_out, const std::string& f, const T* dst);
+  // ---- the UNet walk (unet_build.inc): build() is the list of these stages
+  void step(T& x, const T& y) { free(x); x = y; }  // x <- y
+  struct Model {   // the per-model constants, computed once by model()
+    int dim = 0, L = 0, S = 0, tcd = 0, Ci = 0;   // Ci: image channels (x, the self-conditioning and low-res images, the output)
+    std::vector<int> dims;                        // dim, then every level's width
+    bool combine = false, keep_init = false, final_res = true;
+    // cat_w: combine_upsample_fmaps: width of the concat in front of final_res_block, [x: dim | up level 0 (deepest) .. L - 1:
+    // dim each | init conv residual: dim]; fin_w: channels of the map the final conv reads
+    int cat_w = 0, fin_w = 0;
+    float skip_scale = 1.0f;
+  };
+  struct FinalConv {   // prepared by final_conv_setup() at the top, emitted by final_conv() at the bottom
+    int ks = 3, cin = 0, w = 0, n = 0;   // kernel size, weight input channels, channels read from x, GEMM columns
+    const float* bias = nullptr;
+    float* w_packed = nullptr;
+    T stat;   // has_static: the low-res planes' share [B, Ci, S, S], written once per sampling call
+    bool has_static = false;
+  };
+  struct InitConv {
+    T x;      // the init conv's output map
+    T stat;   // hoist: the cond / low-res planes' share, written once per sampling call and released at the end
+    bool hoist = false;
+  };
+  // The skip tensors of the down path and the protocol "a producer may write straight into the concat that follows it"
+  struct SkipStack {
+    Builder& b;
+    std::vector<T> hiddens;
+    T ct;                  // the offer: concat buffer handed to the next producer
+    bool have_ct = false, ct_owned = false;   // ct_owned: allocated by the offer (else it is the skip's own buffer)
+    int ct_ca = 0;         // channels the producer contributes
+    explicit SkipStack(Builder& b_) : b(b_) {}
+    // every hidden of a level is later concatenated behind dim_out channels of the up path: its producer writes it into
+    // channels [dim_out, dim_out + x.C) of that buffer
+    T make_slot(const T& x, int dim_out) { return b.alloc(x.B, x.H, x.W, dim_out + x.C).slice(dim_out, x.C); }
+    void push(const T& x) { b.retain(x); hiddens.push_back(x); }
+    void push(T& x, const T& y, const T* slot);      // x <- y, produced into `slot` or not; then retained
+    void push_copy(const T& x, int dim_out);
+    const T* offer(int Bc, int Hc, int Wc, int Ca);
+    void drop_offer() { if (have_ct && ct_owned) b.free(ct); have_ct = false; }
+    int pop(T& x, int dim_out, float skip_scale);
+    static T whole(T s) { s.C = s.ld; s.ld = 0; s.coff = 0; return s; }   // the buffer a skip slice lives in
+    void finish() const;              // the end-of-walk checks
+  };
+  struct Combiner {
+    Builder& b;
+    const Model& m;
+    T cat, head;           // the concat in front of final_res_block at full width (from the last level on); its channels [0, dim)
+    std::vector<T> maps;   // each level's map after its attention slot
+    bool head_here = false, head_resnet = false;   // the last level's attention block / last ResnetBlock writes the head in place
+    Combiner(Builder& b_, const Model& m_) : b(b_), m(m_) {}
+    void open(const T& x, const T& init_residual, int dim_out, bool ups, bool attn);
+    const T* resnet_target() const { return head_resnet ? &cat : nullptr; }
+    const T* attn_target() const { return head_here ? &head : nullptr; }
+    void took_head(T& x) const { if (head_resnet && x.off == cat.off) x = head; }   // the ResnetBlock wrote into the concat
+    void keep(const T& x) { if (m.combine) { b.retain(x); maps.push_back(x); } }   // the map lives on to the tail, as a skip does
+    void close(T& x);
+  };
+  Model model();
+  void gn_scratch(const Model& m);
+  FinalConv final_conv_setup(const Model& m);
+  T conditioning(const Model& m);
+  InitConv init_conv(const Model& m);
+  void down_path(const Model& m, T& x, const T& c, SkipStack& skips);
+  void middle(const Model& m, T& x, const T& c);
+  void up_path(const Model& m, T& x, const T& c, SkipStack& skips, Combiner& comb, const T& init_residual);
+  void tail(const Model& m, T& x, const T& c, Combiner& comb, const T& init_residual);
+  void final_conv(const Model& m, const FinalConv& f, const T& x);
+  void release(const T& x, const FinalConv& fin, const InitConv& init);
   void build();
   void build_text();
 };

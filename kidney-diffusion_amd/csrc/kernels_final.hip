@@ -3,41 +3,47 @@
 //   out[b][o][y][x] = bias[o] + sum_{c,kh,kw} in[b][y+kh-1][x+kw-1][c] * W[o][c][kh][kw]
 //
 // is evaluated as (1) a 1x1 GEMM on the matrix cores, P[pixel][o*9+tap] = sum_c feat[pixel][c] *
-// W[o][c][tap] (9 C columns: 9 / 18 / 27 padded to 32, 36 padded to 48 - final_gemm_cols), and (2) the 9-tap
+// W[o][c][tap] (9 C columns: 9 / 18 / 27 padded to 32, 36 padded to 48 - final_gemm_cols_k), and (2) the 9-tap
 // gather-sum below, which also adds the step-invariant contribution of the low-res conditioning planes (`stat`,
 // computed once per sampling call by final_static_kernel) and writes the NCHW prediction the sampler consumes.
 // C <= 3 keeps the 32-column P and the launches of the 3-channel plans; C = 4 is the one width past 32 columns.
 //
-// Unet(final_conv_kernel_size=k), k = 1 | 5 | 7 (the `_k` functions below; k = 3 stays on the launches above, bit for bit):
-// the same two steps with the (output, tap) columns n = o kp + tap, kp = k^2 rounded up to a multiple of 4 (28 | 52: every
-// channel's columns start on a 16-byte boundary; the pad columns have zero weights), the row padded to a multiple of 16 and
-// at least 32 columns (final_gemm_cols_k).  At k = 7 a pixel has up to 208 columns and a gather tile holding all of them
-// would not fit LDS, so the k x k gather is tiled by OUTPUT CHANNEL: a workgroup stages the kp columns of one channel o over
-// its halo patch (16-byte loads; kp + 1 = 29 | 53 floats per pixel in LDS, odd: conflict-free reads) and every lane of the
-// first TW x ROWS threads sums its pixel's k^2 taps.  k = 1 has no taps to gather: out = (stat | bias) + P[pixel][o], no LDS.
+// Unet(final_conv_kernel_size=k), k = 1 | 5 | 7 (k = 3 keeps its own gather below, bit for bit): the same two steps with
+// the (output, tap) columns n = o kp + tap, kp = k^2 rounded up to a multiple of 4 (28 | 52: every channel's columns start
+// on a 16-byte boundary; the pad columns have zero weights; k = 3 keeps kp = 9, its gather reads column o 9 + tap), the row
+// padded to a multiple of 16 and at least 32 columns (final_gemm_cols_k).  At k = 7 a pixel has up to 208 columns and a
+// gather tile holding all of them would not fit LDS, so the k x k gather is tiled by OUTPUT CHANNEL: a workgroup stages the kp
+// columns of one channel o over its halo patch (16-byte loads; kp + 1 = 29 | 53 floats per pixel in LDS, odd: conflict-free
+// reads) and every lane of the first TW x ROWS threads sums its pixel's k^2 taps.  k = 1 has no taps to gather: out =
+// (stat | bias) + P[pixel][o], no LDS.
 #include "common.h"
 
 namespace kd {
 
-int final_gemm_cols(int ch) { return ch <= 3 ? 32 : 48; }
+static bool final_k_ok(int k) { return k == 1 || k == 3 || k == 5 || k == 7; }
+static int final_kp(int k) { return k == 1 ? 1 : k == 3 ? 9 : (k * k + 3) & ~3; }   // columns per output channel
+int final_gemm_cols_k(int ch, int k) {   // (k = 3: 32 columns; 48 at ch = 4)
+  const int n = (final_kp(k) * ch + 15) / 16 * 16;
+  return n < 32 ? 32 : n;
+}
 
-// w_oihw [ch][Ctot][3][3] -> packed [nf][C] rows n = o*9 + tap for channels [0, C); rows 9 ch .. nf - 1 zero
-__global__ void pack_final_kernel(const float* __restrict__ w, float* __restrict__ out, int Ctot, int C, int ch, int nf) {
+// w_oihw [ch][Ctot][k][k] -> packed [nf][C] rows n = o kp + tap for channels [0, C); rows with tap >= k^2 or o >= ch zero
+__global__ void pack_final_k_kernel(const float* __restrict__ w, float* __restrict__ out, int Ctot, int C, int ch, int nf, int kk,
+                                    int kp) {
   int total = nf * C;
   for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
     int c = idx % C, n = idx / C;
+    int o = n / kp, tap = n - o * kp;
     float v = 0.f;
-    if (n < 9 * ch) {
-      int o = n / 9, tap = n - o * 9;
-      v = w[((int64_t)o * Ctot + c) * 9 + tap];
-    }
+    if (o < ch && tap < kk) v = w[((int64_t)o * Ctot + c) * kk + tap];
     out[idx] = v;
   }
 }
-int launch_pack_final(const float* w, float* out, int Ctot, int C, int ch, hipStream_t s) {
-  KD_REQUIRE(ch >= 1 && ch <= 4 && C >= 1 && C <= Ctot, "final conv: 1 .. 4 image channels");
-  const int nf = final_gemm_cols(ch);
-  hipLaunchKernelGGL(pack_final_kernel, dim3((nf * C + 255) / 256), dim3(256), 0, s, w, out, Ctot, C, ch, nf);
+int launch_pack_final_k(const float* w, float* out, int Ctot, int C, int ch, int k, hipStream_t s) {
+  KD_REQUIRE(ch >= 1 && ch <= 4 && C >= 1 && C <= Ctot && final_k_ok(k), "final conv: 1 .. 4 image channels, kernel size 1, 3, 5 or 7");
+  const int nf = final_gemm_cols_k(ch, k);
+  hipLaunchKernelGGL(pack_final_k_kernel, dim3((nf * C + 255) / 256), dim3(256), 0, s, w, out, Ctot, C, ch, nf, k * k,
+                     final_kp(k));
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -83,8 +89,8 @@ int launch_final_static(const float* lowres, const float* w, const float* bias, 
 
 // out[b][o][y][x] = (stat ? stat[b][o][y][x] : bias[o]) + sum_tap P[b][y+kh-1][x+kw-1][o*9+tap]
 // One block per 4 rows x 64 pixels (a wave per row): the 6 x 66 pixel rows of P are staged in LDS
-// with 16-B loads - every row of P is read 1.5 times (3 times with the one-row blocks of rounds 1-3: 165 -> ~60 us at
-// the headline shape) -, then every lane sums its pixel's 9 CH values.  CH <= 3: all 32 columns of a row of P are
+// with 16-B loads - every row of P is read 1.5 times (3 times with one-row blocks) -, then every lane sums its pixel's
+// 9 CH values.  CH <= 3: all 32 columns of a row of P are
 // staged (8 loads per pixel); CH = 4: the 36 used ones of its 48 (9 loads) - either way a pixel takes 36 floats of LDS,
 // an odd multiple of 4 (conflict-free 4-B reads), and the tile stays within 64 KB (a row of 52 floats for all 48
 // columns would take 80 KB and the second workgroup off the CU).
@@ -93,7 +99,7 @@ template <int CH>
 __global__ __launch_bounds__(64 * FG_ROWS) void final_gather_kernel(const float* __restrict__ P, const float* __restrict__ stat,
                                                                    const float* __restrict__ bias, float* __restrict__ out,
                                                                    int H, int W) {
-  constexpr int NF = CH <= 3 ? 32 : 48;   // final_gemm_cols(CH)
+  constexpr int NF = CH <= 3 ? 32 : 48;   // final_gemm_cols_k(CH, 3)
   constexpr unsigned NQ = CH <= 3 ? 8 : 9;     // 16-B pieces of a row of P that are staged
   static_assert(4 * NQ <= FG_LD && 9 * CH <= 4 * NQ && 4 * NQ <= NF, "final gather: staged columns");
   __shared__ __attribute__((aligned(16))) float tile[FG_ROWS + 2][66][FG_LD];  // padded rows: conflict-free 4-B reads
@@ -122,8 +128,8 @@ __global__ __launch_bounds__(64 * FG_ROWS) void final_gather_kernel(const float*
     out[oi] = acc;
   }
 }
-int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int ch, int B, int H, int W,
-                        hipStream_t s) {
+static int launch_final_gather(const float* P, const float* stat, const float* bias, float* out, int ch, int B, int H, int W,
+                               hipStream_t s) {
   KD_REQUIRE(ch >= 1 && ch <= 4 && ((uintptr_t)P & 15) == 0, "final conv: 1 .. 4 image channels, 16-byte aligned P");
   const int segs = (W + 63) / 64, rgs = (H + FG_ROWS - 1) / FG_ROWS;
   const dim3 grid((unsigned)((int64_t)B * rgs * segs)), block(64 * FG_ROWS);
@@ -137,37 +143,7 @@ int launch_final_gather(const float* P, const float* stat, const float* bias, fl
   return 0;
 }
 
-// ---- k x k final conv, k = 1 | 5 | 7 (k = 3: the functions above)
-static bool final_k_ok(int k) { return k == 1 || k == 5 || k == 7; }
-static int final_kp(int k) { return k == 1 ? 1 : (k * k + 3) & ~3; }   // columns per output channel
-int final_gemm_cols_k(int ch, int k) {
-  if (k == 3) return final_gemm_cols(ch);
-  const int n = (final_kp(k) * ch + 15) / 16 * 16;
-  return n < 32 ? 32 : n;
-}
-
-// w_oihw [ch][Ctot][k][k] -> packed [nf][C] rows n = o kp + tap for channels [0, C); rows with tap >= k^2 or o >= ch zero
-__global__ void pack_final_k_kernel(const float* __restrict__ w, float* __restrict__ out, int Ctot, int C, int ch, int nf, int kk,
-                                    int kp) {
-  int total = nf * C;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    int c = idx % C, n = idx / C;
-    int o = n / kp, tap = n - o * kp;
-    float v = 0.f;
-    if (o < ch && tap < kk) v = w[((int64_t)o * Ctot + c) * kk + tap];
-    out[idx] = v;
-  }
-}
-int launch_pack_final_k(const float* w, float* out, int Ctot, int C, int ch, int k, hipStream_t s) {
-  if (k == 3) return launch_pack_final(w, out, Ctot, C, ch, s);
-  KD_REQUIRE(ch >= 1 && ch <= 4 && C >= 1 && C <= Ctot && final_k_ok(k), "final conv: 1 .. 4 image channels, kernel size 1, 3, 5 or 7");
-  const int nf = final_gemm_cols_k(ch, k);
-  hipLaunchKernelGGL(pack_final_k_kernel, dim3((nf * C + 255) / 256), dim3(256), 0, s, w, out, Ctot, C, ch, nf, k * k,
-                     final_kp(k));
-  KD_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
+// ---- the gathers of k = 1 | 5 | 7
 // k = 1: out[b][o][y][x] = (stat ? stat : bias[o]) + P[b][y][x][o]
 __global__ void final_cols_kernel(const float* __restrict__ P, const float* __restrict__ stat, const float* __restrict__ bias,
                                   float* __restrict__ out, int ch, int nf, int64_t hw, int64_t total) {

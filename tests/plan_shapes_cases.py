@@ -2,7 +2,7 @@
 every batch a patch grid runs, against the oracle) and of its CPU check in tests/test_plan_shapes.py.  No product imports.
 
 The engine picks its kernels from the static shape - conv3x3_choice / wino4_images / wino4_whole_ok / fwino_ok / gemm_ok
-(csrc/engine.hip), gemm_bf16x3_ok and the k-cut rule (csrc/kernels_gemm_bf16x3.hip), downsample_x3_ok and add_skip
+(csrc/engine.hip), gemm_bf16x3_ok and the k-cut rule (csrc/kernels_gemm_bf16x3.hip), downsample_x3_ok and SkipStack::pop
 (csrc/unet_build.inc) - and `ultra_res/distributed.py::imagen_sample_fn(max_batch=n)` hands it every batch 1 .. n of one
 UNet over one packed-weight store.  SWEEP is those batches at the widths where the fast paths engage (dim 128); EXTRA are
 the cases added so that every label family of test_plan_shapes_gpu.FAMILIES occurs in some plan (plan options through the
