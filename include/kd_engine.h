@@ -62,7 +62,8 @@ const char* kd_last_error(void);
  *      structs kd_tiles_image_t and kd_tiles_mask_t added (a fused-tile canvas that keeps known pixels or starts from an image);
  *      kd_sample_args_t gained `keep_self_cond` at its end (zero = the reset at step 0 of before); kd_tiles_finalize_known
  *      accepts known = mask = NULL (kd_tiles_finalize's bits) - kd_tiles_fuse_update and kd_tiles_finalize are the _known calls
- *      with nothing known, no existing entry changed */
+ *      with nothing known, no existing entry changed; kd_tiles_rows_copy and kd_tiles_finalize_rows added (a fused-tile canvas
+ *      cut into shards over several devices) */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -941,6 +942,31 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
 int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
                             int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
                             void* stream);
+
+/* A canvas cut into shards by lattice rows (Imagen.sample_tiled(devices=...)): every shard holds the whole canvas, steps
+ * the band its own tiles cover and fuses it out of its own tiles' estimates and the overlap strips of its neighbours'
+ * boundary tiles.  Two additions carry that; no entry above changed.
+ *
+ * kd_tiles_rows_copy moves row strips of tiles: for i < n, with (ts, td, row0, rows) = desc[i] (a host array [n][4], free
+ * on return; 32 descriptors per launch travel as a kernel argument),
+ *     dst tile td, rows <- src tile ts, rows          [C, rows, S] each, 16-byte loads and stores, no atomics
+ * Either side is an array of tiles [tiles, C, H, S], H = src_rows / dst_rows: H == S is a tile store and the strip lies at
+ * its rows row0 .. row0 + rows; H < S is a strip buffer and the strip lies at its top (rows <= H).  So one entry packs the
+ * strips of a store into a contiguous buffer, unpacks such a buffer into a store's halo slots, and copies store to store.
+ * d_thr_src / d_thr_dst (both or neither): d_thr_dst[td] = d_thr_src[ts], the tiles' dynamic thresholds.  Elements outside
+ * the strips keep their bits.  Refused with an error, nothing launched: a NULL or misaligned (16 bytes) d_src / d_dst,
+ * d_src == d_dst, S % 4 != 0, a tile index outside [0, tiles), rows outside [0, S] (row0 < 0, rows < 0, row0 + rows > S), a
+ * strip taller than a strip buffer.  The caller sees to it that the two buffers do not overlap and that the destination
+ * strips are disjoint: two descriptors of one call that name the same destination tile with rows in common (or, with
+ * thresholds, the same destination tile at all) would race, the copy having no order among descriptors. */
+int kd_tiles_rows_copy(const float* d_src, int src_tiles, int src_rows, float* d_dst, int dst_tiles, int dst_rows,
+                       const float* d_thr_src, float* d_thr_dst, int n, int C, int S, const int* desc, void* stream);
+/* kd_tiles_finalize_known over the canvas rows y_lo <= y < y_hi alone (0 <= y_lo < y_hi <= Hc): what a shard ends.  oy may
+ * be negative when the output is a band that holds the rows written and not the ones above them: oy + y_lo >= 0 and
+ * oy + y_hi <= Ho are required in the place of kd_tiles_finalize's 0 <= oy, oy + Hc <= Ho. */
+int kd_tiles_finalize_rows(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
+                           int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, int y_lo,
+                           int y_hi, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1241,7 +1241,21 @@ int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C
   TileImage kn;
   TileMask mk;
   return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
-                               tile_mask_of(mask, &mk), (hipStream_t)stream);
+                               tile_mask_of(mask, &mk), 0, -1, (hipStream_t)stream);
+}
+int kd_tiles_finalize_rows(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
+                           int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, int y_lo,
+                           int y_hi, void* stream) {
+  TileImage kn;
+  TileMask mk;
+  KD_REQUIRE(y_hi >= 0, "tiles finalize rows: y_hi must not be negative");
+  return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
+                               tile_mask_of(mask, &mk), y_lo, y_hi, (hipStream_t)stream);
+}
+int kd_tiles_rows_copy(const float* d_src, int src_tiles, int src_rows, float* d_dst, int dst_tiles, int dst_rows,
+                       const float* d_thr_src, float* d_thr_dst, int n, int C, int S, const int* desc, void* stream) {
+  return launch_tiles_rows_copy(d_src, src_tiles, src_rows, d_dst, dst_tiles, dst_rows, d_thr_src, d_thr_dst, n, C, S, desc,
+                                (hipStream_t)stream);
 }
 
 }  // extern "C"

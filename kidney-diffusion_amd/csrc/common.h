@@ -486,8 +486,14 @@ int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, cons
                              const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P,
                              float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise, float rn_a, float rn_b,
                              const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s);
-// out = [m ? kn :] (clamp(x, -1, 1) + 1) / 2 on covered pixels; known and mask both or neither
+// out = [m ? kn :] (clamp(x, -1, 1) + 1) / 2 on covered pixels of the canvas rows [y_lo, y_hi) (y_hi < 0: through Hc); known
+// and mask both or neither
 int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
-                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s);
+                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, int y_lo, int y_hi,
+                          hipStream_t s);
+// row strips of tiles: dst tile desc[i][1] <- src tile desc[i][0], rows desc[i][2] .. + desc[i][3], [C, rows, S] each; a side
+// with fewer than S rows per tile is a strip buffer (the strip at its top); thr_src: the tiles' thresholds travel too
+int launch_tiles_rows_copy(const float* src, int src_tiles, int src_rows, float* dst, int dst_tiles, int dst_rows,
+                           const float* thr_src, float* thr_dst, int n, int C, int S, const int* desc, hipStream_t s);
 
 }  // namespace kd

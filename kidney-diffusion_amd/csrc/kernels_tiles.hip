@@ -528,11 +528,12 @@ int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, cons
 // out[c, oy + y, ox + x] = (clamp(x[c, y, x], -1, 1) + 1) * 0.5 for every canvas pixel that a present tile covers; every
 // other element of out [C, Ho, Wo] keeps its bits.  One pass, no host mask.  With PASTE: out = m ? kn : the same - the known
 // value copied, not round-tripped.  kn may then be the window of `out` that is written (the host checks that an overlapping
-// source is exactly that window): a thread reads and writes the same element, so `out` is not restrict.
+// source is exactly that window): a thread reads and writes the same element, so `out` is not restrict.  Only the canvas
+// rows y_lo <= y < y_hi are written (the whole canvas: 0, Hc): a shard of a canvas ends the rows it owns.
 template <bool PASTE>
 __global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __restrict__ x, const int* __restrict__ tile_of,
                                                              TileGeom g, float* out, int Ho, int Wo, int oy, int ox, ImgSrc kn,
-                                                             MaskSrc mk) {
+                                                             MaskSrc mk, int y_lo, int y_hi) {
   const int W4 = g.Wc / 4;
   const int xq = blockIdx.x * 256 + threadIdx.x;
   if (xq >= W4) return;
@@ -540,7 +541,7 @@ __global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __rest
   const int rows = g.C * g.Hc;
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int c = row / g.Hc, y = row - c * g.Hc;
-    if (!tile_covered(tile_of, g, y, xx)) continue;
+    if (y < y_lo || y >= y_hi || !tile_covered(tile_of, g, y, xx)) continue;
     const uint32_t mw = PASTE ? src_mask4(mk, y, xx) : 0u;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (!mask_all(mw)) {
@@ -561,15 +562,20 @@ __global__ __launch_bounds__(256) void tiles_finalize_kernel(const float* __rest
   }
 }
 int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,
-                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, hipStream_t s) {
+                          int Wo, int oy, int ox, const TileImage* known, const TileMask* mask, int y_lo, int y_hi,
+                          hipStream_t s) {
   KD_REQUIRE(x && tile_of && out, "tiles finalize: null argument");
   KD_REQUIRE((known != nullptr) == (mask != nullptr), "tiles finalize: the known image and the mask come together");
   TileGeom g;
   if (tile_lattice("tiles finalize", N, C, S, st, ny, nx, 0, &g)) return 1;
-  const int64_t Hc = g.Hc, Wc = g.Wc;   // (oy + Hc, ox + Wc: no overflow for any int offset)
+  const int64_t Wc = g.Wc;   // (oy + y_hi, ox + Wc: no overflow for any int offset)
+  if (y_hi < 0) y_hi = g.Hc;   // the whole canvas
+  KD_REQUIRE(y_lo >= 0 && y_lo < y_hi && y_hi <= g.Hc, "tiles finalize: the rows [y_lo, y_hi) must be a non-empty range of the canvas");
   KD_REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= (1 << 20) && Wo <= (1 << 20) && Wo % 4 == 0 && ox % 4 == 0,
              "tiles finalize: needs an output with Wo % 4 == 0 and an offset ox % 4 == 0");
-  KD_REQUIRE(oy >= 0 && ox >= 0 && oy + Hc <= Ho && ox + Wc <= Wo, "tiles finalize: the canvas at (oy, ox) lies outside the output");
+  // (oy < 0 with y_lo > 0: the output is a band that holds the rows written and not the ones above them)
+  KD_REQUIRE((int64_t)oy + y_lo >= 0 && ox >= 0 && (int64_t)oy + y_hi <= Ho && ox + Wc <= Wo,
+             "tiles finalize: the canvas at (oy, ox) lies outside the output");
   KD_REQUIRE((((uintptr_t)x | (uintptr_t)out) & 15) == 0, "tiles finalize: x and out must be 16-byte aligned");
   ImgSrc kn{};
   MaskSrc mk{};
@@ -585,7 +591,71 @@ int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int 
                  "tiles finalize: a known image inside the output must be the window at (oy, ox) that is written");
   }
   const auto kernel = known ? tiles_finalize_kernel<true> : tiles_finalize_kernel<false>;
-  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox, kn, mk);
+  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, tile_of, g, out, Ho, Wo, oy, ox, kn, mk, y_lo, y_hi);
+  KD_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------- row strips of tile estimates
+// A canvas cut into shards by lattice rows: a shard fuses its band out of its own tiles' estimates and the overlap strips of
+// its neighbours' boundary tiles.  One kernel moves them, dst tile d.dst[b] rows <- src tile d.src[b] rows, [C, rows, S] each,
+// ROWS_CHUNK descriptors per launch as a kernel argument.  Either side is an array of tiles [., C, H, S]: H == S is a tile
+// store, the strip lies at its rows row0 .. row0 + rows; H < S is a strip buffer, the strip lies at its top (rows <= H).  So
+// the one kernel packs (store -> buffer), unpacks (buffer -> store) and copies store to store.  With thr_src the threshold
+// of the tile travels too: thr_dst[d.dst[b]] = thr_src[d.src[b]].  Data movement only: 16-byte loads and stores, 64-bit
+// offsets, every element written by one thread.
+enum { ROWS_CHUNK = 32 };
+struct RowStrips {
+  int src[ROWS_CHUNK], dst[ROWS_CHUNK], row0[ROWS_CHUNK], rows[ROWS_CHUNK];
+};
+__global__ __launch_bounds__(256) void tiles_rows_copy_kernel(const float* __restrict__ src, int src_rows, float* __restrict__ dst,
+                                                              int dst_rows, const float* __restrict__ thr_src,
+                                                              float* __restrict__ thr_dst, int C, int S, RowStrips d) {
+  const int b = blockIdx.y;
+  const int S4 = S / 4, rows = d.rows[b];
+  const int per4 = C * rows * S4;   // (< 2^31: checked by the host)
+  const int sr0 = src_rows == S ? d.row0[b] : 0, dr0 = dst_rows == S ? d.row0[b] : 0;
+  const float* from = src + (int64_t)d.src[b] * C * src_rows * S;
+  float* to = dst + (int64_t)d.dst[b] * C * dst_rows * S;
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < per4; j += gridDim.x * 256) {
+    const int row = j / S4, xq = j - row * S4;   // row = c * rows + y
+    const int c = row / rows, y = row - c * rows;
+    *(f32x4*)(to + ((int64_t)c * dst_rows + dr0 + y) * S + 4 * xq) =
+        *(const f32x4*)(from + ((int64_t)c * src_rows + sr0 + y) * S + 4 * xq);
+  }
+  if (thr_src && blockIdx.x == 0 && threadIdx.x == 0) thr_dst[d.dst[b]] = thr_src[d.src[b]];
+}
+int launch_tiles_rows_copy(const float* src, int src_tiles, int src_rows, float* dst, int dst_tiles, int dst_rows,
+                           const float* thr_src, float* thr_dst, int n, int C, int S, const int* desc, hipStream_t s) {
+  KD_REQUIRE(src && dst && desc && src != dst, "tiles rows copy: null argument, or src and dst are one buffer");
+  KD_REQUIRE((thr_src != nullptr) == (thr_dst != nullptr), "tiles rows copy: the thresholds need a source and a destination");
+  KD_REQUIRE(n >= 1 && C >= 1 && C <= 1024 && S >= 4 && S % 4 == 0 && (int64_t)C * S * S < (1ll << 31),
+             "tiles rows copy: needs n, C >= 1 and a tile size S % 4 == 0 with C S S < 2^31");
+  KD_REQUIRE(src_tiles >= 1 && dst_tiles >= 1 && src_rows >= 1 && src_rows <= S && dst_rows >= 1 && dst_rows <= S,
+             "tiles rows copy: a side needs at least one tile and 1 <= rows per tile <= S");
+  KD_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0 && (((uintptr_t)thr_src | (uintptr_t)thr_dst) & 3) == 0,
+             "tiles rows copy: src and dst must be 16-byte aligned");
+  for (int i = 0; i < n; ++i) {   // every descriptor before the first launch
+    const int ts = desc[4 * i], td = desc[4 * i + 1], row0 = desc[4 * i + 2], rows = desc[4 * i + 3];
+    KD_REQUIRE(ts >= 0 && ts < src_tiles && td >= 0 && td < dst_tiles, "tiles rows copy: a tile index lies outside its buffer");
+    KD_REQUIRE(rows >= 0 && rows <= S && row0 >= 0 && row0 <= S - rows, "tiles rows copy: the rows of a strip must lie inside [0, S]");
+    KD_REQUIRE((src_rows == S || rows <= src_rows) && (dst_rows == S || rows <= dst_rows),
+               "tiles rows copy: a strip is taller than the strip buffer");
+  }
+  for (int i0 = 0; i0 < n; i0 += ROWS_CHUNK) {
+    const int nb = std::min(n - i0, (int)ROWS_CHUNK);
+    RowStrips d{};
+    int most = 0;
+    for (int i = 0; i < nb; ++i) {
+      const int* e = desc + 4 * (i0 + i);
+      d.src[i] = e[0], d.dst[i] = e[1], d.row0[i] = e[2], d.rows[i] = e[3];
+      most = std::max(most, e[3]);
+    }
+    const int per4 = C * most * (S / 4);
+    const int gx = std::max(1, std::min((per4 + 255) / 256, 8192 / nb));
+    hipLaunchKernelGGL(tiles_rows_copy_kernel, dim3((unsigned)gx, (unsigned)nb), dim3(256), 0, s, src, src_rows, dst, dst_rows,
+                       thr_src, thr_dst, C, S, d);
+  }
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -313,6 +313,10 @@ SIGNATURES = {
                                                                                                 C.c_void_p]),
     "kd_tiles_finalize_known": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 +
                                 [C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_void_p]),
+    "kd_tiles_rows_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    "kd_tiles_finalize_rows": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 +
+                               [C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_int, C.c_int, C.c_void_p]),
 }
 
 

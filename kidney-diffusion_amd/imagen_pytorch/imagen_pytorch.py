@@ -20,6 +20,7 @@ import ctypes as C
 import math
 import os
 import re
+from types import SimpleNamespace
 from typing import Callable, Optional
 
 import torch
@@ -1116,6 +1117,121 @@ def normalize_tiling(image_sizes, grid, overlap=0.25, present=None, tile_weights
     return out
 
 
+def normalize_devices(devices, noise_fn=None):
+    """``sample_tiled(devices=...)`` as a list of ``torch.device``, one per shard of the canvas (a device may repeat: each
+    shard then owns plans of its own on it); None stays None.  Raises ValueError for ``devices`` that is no sequence or is
+    empty, an entry that is not a device (``torch.device``, a string or an index that names one), a device that is not
+    CUDA, and ``devices`` together with ``noise_fn`` (injected noise lives on one device; a sharded canvas draws Philox
+    noise, keyed by the canvas element, on every device).  Needs no GPU."""
+    import numbers
+
+    if devices is None:
+        return None
+    if isinstance(devices, (str, torch.device)) or not isinstance(devices, (tuple, list)) or len(devices) == 0:
+        raise ValueError(f"devices must be a non-empty sequence of CUDA devices, one per shard, got {devices!r}")
+    out = []
+    for d in devices:
+        if isinstance(d, bool) or not isinstance(d, (torch.device, str, numbers.Integral)):
+            raise ValueError(f"devices: {d!r} is not a device (a torch.device, a string such as 'cuda:0' or an index)")
+        try:
+            dev = torch.device("cuda", int(d)) if isinstance(d, numbers.Integral) else torch.device(d)
+        except (RuntimeError, ValueError) as e:
+            raise ValueError(f"devices: {d!r} is not a device ({e})") from None
+        if dev.type != "cuda":
+            raise ValueError(f"devices: {dev} is not a CUDA device - the shards of a canvas run on the HIP engine only")
+        out.append(dev)
+    if len(out) > 1 and exists(noise_fn):
+        raise ValueError("sample_tiled takes devices or noise_fn, one of them: a sharded canvas draws its noise on every device")
+    return out
+
+
+def normalize_shards(tiling, n_shards, bands=None):
+    """The decomposition of a fused-tile canvas (``tiling``: normalize_tiling's) into ``n_shards`` shards by lattice rows.
+    Returns one dict per stage: ``d`` (the halo depth ``ceil(S / st) - 1`` in lattice rows), ``shards`` and ``exchange``.
+
+    A shard of ``shards`` holds: ``band = (r0, r1)``, a contiguous band of lattice rows - the bands partition the rows and
+    are balanced by the number of PRESENT tiles (the largest band as small as it can be, every band holding at least one;
+    ``bands = [(r0, r1), ...]`` gives them instead); ``own``: the present tiles of those rows (canvas tile numbers,
+    ascending); ``halo``: the present tiles of the ``d`` lattice rows above and below the band; ``strips``: {halo tile: (row0,
+    rows)}, the rows of that tile inside the band's extent; ``extent = (r0 st, (r1 - 1) st + S)``, the canvas rows the own
+    tiles cover; ``owned = (r0 st, r1 st)``, through ``Hc`` for the last band - the canvas rows this shard ends; ``tiles``:
+    own and halo, ascending - the order of the shard's tile store; ``base``: where the own tiles (contiguous) begin in it;
+    ``tile_of`` [ny][nx]: the store slot of every tile of that set, -1 for every other slot of the lattice.
+    ``exchange`` lists, per pair of shards with something to send, ``dict(src, dst, items = [(tile, row0, rows)])``: the
+    strips of ``src``'s own tiles that ``dst`` holds as halo.
+
+    Every tile that covers a pixel of a shard's extent is one of its own or halo tiles, and covers it with a row inside
+    its strip: fusing own and halo over the extent gives the canvas' fused estimate there.
+
+    Raises ValueError for ``n_shards`` that is no int >= 1, more shards than lattice rows that hold a present tile, and
+    ``bands`` that do not partition the rows or hold a band without a present tile.  Needs no GPU."""
+    import numbers
+
+    if not isinstance(n_shards, numbers.Integral) or isinstance(n_shards, bool) or int(n_shards) < 1:
+        raise ValueError(f"n_shards must be an int >= 1, got {n_shards!r}")
+    n = int(n_shards)
+    ny, nx = tiling[0]["ny"], tiling[0]["nx"]
+    count = [sum(1 for t in row if t >= 0) for row in tiling[0]["tile_of"]]   # present tiles per lattice row
+    filled = sum(1 for c in count if c > 0)
+    if n > filled:
+        raise ValueError(f"{n} shards are more than the {filled} lattice rows that hold a present tile: a shard owns at least "
+                         "one row of tiles")
+    if bands is None:
+        # best[i][r]: the smallest largest band when the rows [0, r) make i bands that each hold a tile; the first cut wins ties
+        pre = [0]
+        for c in count:
+            pre.append(pre[-1] + c)
+        INF = float("inf")
+        best = [[INF] * (ny + 1) for _ in range(n + 1)]
+        cut = [[0] * (ny + 1) for _ in range(n + 1)]
+        best[0][0] = 0
+        for i in range(1, n + 1):
+            for r in range(1, ny + 1):
+                for q in range(i - 1, r):
+                    load = pre[r] - pre[q]
+                    if load > 0 and best[i - 1][q] < INF and max(best[i - 1][q], load) < best[i][r]:
+                        best[i][r], cut[i][r] = max(best[i - 1][q], load), q
+        bands, r = [], ny
+        for i in range(n, 0, -1):
+            bands.append((cut[i][r], r))
+            r = cut[i][r]
+        bands.reverse()
+    else:
+        bands = [tuple(int(v) for v in b) for b in bands]
+        if (len(bands) != n or bands[0][0] != 0 or bands[-1][1] != ny or any(a[1] != b[0] for a, b in zip(bands, bands[1:]))
+                or any(r0 >= r1 for r0, r1 in bands)):
+            raise ValueError(f"bands must be {n} ranges [r0, r1) that partition the {ny} lattice rows in order, got {bands}")
+    for r0, r1 in bands:
+        if sum(count[r0:r1]) == 0:
+            raise ValueError(f"the band of lattice rows [{r0}, {r1}) holds no present tile: a shard owns at least one tile")
+    out = []
+    for geo in tiling:
+        S, st, Hc, tile_of = geo["S"], geo["st"], geo["Hc"], geo["tile_of"]
+        d = -(-S // st) - 1
+        row_tiles = lambda a, b: [t for r in range(max(a, 0), min(b, ny)) for t in tile_of[r] if t >= 0]
+        owner, shards = {}, []
+        for i, (r0, r1) in enumerate(bands):
+            own = row_tiles(r0, r1)
+            owner.update({t: i for t in own})
+            extent = (r0 * st, (r1 - 1) * st + S)
+            strips = {}
+            for r in list(range(max(r0 - d, 0), r0)) + list(range(r1, min(r1 + d, ny))):
+                lo, hi = max(extent[0] - r * st, 0), min(extent[1] - r * st, S)
+                strips.update({t: (lo, hi - lo) for t in tile_of[r] if t >= 0})
+            halo = sorted(strips)
+            tiles = sorted(own + halo)
+            slot = {t: j for j, t in enumerate(tiles)}
+            shards.append(dict(band=(r0, r1), own=own, halo=halo, strips=strips, extent=extent,
+                               owned=(r0 * st, r1 * st if i < n - 1 else Hc), tiles=tiles, base=slot[own[0]],
+                               tile_of=[[slot.get(t, -1) for t in row] for row in tile_of]))
+        pairs = {}
+        for j, sh in enumerate(shards):
+            for t in sh["halo"]:
+                pairs.setdefault((owner[t], j), []).append((t,) + sh["strips"][t])
+        out.append(dict(d=d, shards=shards, exchange=[dict(src=a, dst=b, items=items) for (a, b), items in sorted(pairs.items())]))
+    return out
+
+
 def tile_weight(S, st, weights="uniform"):
     """The weight of a tile's pixels in the fused estimate, fp32 [S, S]: ``"uniform"`` is 1; ``"ramp"`` is separable,
     ``w(y, x) = r(y) r(x)`` with ``r(i) = min(i + 1, S - i, ov) / ov``, ``ov = max(S - st, 1)`` - strictly positive, 1 in the
@@ -1451,9 +1567,11 @@ class _StageIO:
     sample_tiled() share them by name.  The object owns everything ``args`` points into: the buffers, and ``keys``, the
     host array of per-image Philox keys."""
 
-    def __init__(self, imagen, unet, batch, size, device, *, dynamic_threshold, use_graph, key, keys=None, resample_times=1):
+    def __init__(self, imagen, unet, batch, size, device, *, dynamic_threshold, use_graph, key, keys=None, resample_times=1,
+                 replica=0):
         self.unet, self.batch, self.device, self.keys = unet, batch, device, keys
-        self._io = unet._io_buffers.setdefault((batch, size, device.index), {})
+        # (`replica` > 0: the buffers of a further plan of the same shape - Unet.engine(replica=) - apart from the first's)
+        self._io = unet._io_buffers.setdefault((batch, size, device.index) + ((replica,) if replica else ()), {})
         args = self.args = E.kd_sample_args_t()
         args.dynamic_threshold = int(bool(dynamic_threshold))
         args.percentile = imagen.dynamic_thresholding_percentile
@@ -1749,7 +1867,7 @@ class Imagen(nn.Module):
                      return_all_unet_outputs=False, lowres_sample_noise_level=None, device=None, inpaint_images=None,
                      inpaint_masks=None, inpaint_resample_times=None, init_images=None, skip_steps=None, streamed=False,
                      cond_crops=None, into=None, known_image=None, known_mask=None, known_resample_times=1, init_canvas=None,
-                     init_skip_steps=None):
+                     init_skip_steps=None, devices=None):
         """A canvas of overlapping tiles denoised jointly (MultiDiffusion / Mixture of Diffusers; an engine extension, the
         alternative to sequential outpainting).  The canvas of a stage is ONE noisy image over the ``grid = (ny, nx)``
         lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
@@ -1792,7 +1910,16 @@ class Imagen(nn.Module):
         and 2M is first order on the first step walked.  Every stage, with or without them, starts through kd_tiles_start,
         steps through kd_tiles_fuse_update_known (update, re-noise and the next slot's mix in the one canvas pass) and ends
         through kd_tiles_finalize_known (``streamed``) or the same clamp and paste in torch; a call without them passes
-        NULL sources and keeps its bits.  ``known_image`` may be a window of the ``into`` canvas itself."""
+        NULL sources and keeps its bits.  ``known_image`` may be a window of the ``into`` canvas itself.
+
+        ``devices``: a sequence of CUDA devices, one per SHARD of the canvas (``normalize_devices``, ``normalize_shards``);
+        None or one device is the call of before, with its bits.  The lattice rows are dealt over the shards in
+        contiguous bands balanced by present tiles; every shard denoises the tiles of its band with plans of its own on
+        its device, the overlap strips of the boundary tiles' estimates cross per step (kd_tiles_rows_copy), and the
+        canvas comes back on ``devices[0]`` (where ``into`` must live) - the canvas of ``devices=None`` bit for bit
+        wherever the chunks of both calls have one batch size, and within the rounding of plans of different batch
+        sizes otherwise.  A device may repeat (``[d, d]``: two shards on one GPU, each with its own plans).  One process,
+        one host thread, no collectives; ``noise_fn`` is refused with more than one shard."""
         for name, v in dict(inpaint_images=inpaint_images, inpaint_masks=inpaint_masks,
                             inpaint_resample_times=inpaint_resample_times).items():
             if exists(v):
@@ -1812,6 +1939,10 @@ class Imagen(nn.Module):
         solvers = self._solver_args(sampler, sampler_eta, sample_steps)
         tiling = normalize_tiling(self.image_sizes, grid, overlap, present, tile_weights)
         n_tiles = len(tiling[0]["origins"])
+        devices = normalize_devices(devices, noise_fn)
+        sharding = normalize_shards(tiling, len(devices)) if exists(devices) and len(devices) > 1 else None
+        if exists(devices):
+            device = devices[0]
         if exists(cond_images) and (cond_images.dim() != 4 or cond_images.shape[0] != n_tiles):
             raise ValueError(f"cond_images must be [tiles {n_tiles}, Cc, h, w], one per present tile, got {tuple(cond_images.shape)}")
         if exists(text_embeds) and (text_embeds.dim() != 3 or text_embeds.shape[0] != 1):
@@ -1860,19 +1991,28 @@ class Imagen(nn.Module):
         if exists(canvas):
             g = tiling[start_at_unet_number - 2]
             canvas = F.interpolate(canvas, (g["Hc"], g["Wc"]), mode="nearest")
+        if exists(sharding):   # every shard's device by its index: two spellings of one device are one device
+            devices = [d if exists(d.index) else torch.device("cuda", torch.cuda.current_device()) for d in devices]
+            if any(d.index >= torch.cuda.device_count() for d in devices):
+                raise ValueError(f"devices={devices} name a device this process does not see ({torch.cuda.device_count()} visible)")
+            device = devices[0]
+            if exists(into) and into[0].device != device:   # before any forward: the stage ends on devices[0]
+                raise ValueError(f"into: with devices=... the canvas must live on devices[0] = {device}, got {into[0].device}")
         outputs = []
         for num, unet, sched, obj, dyn, cs, solver in self._stages(solvers, cond_scale, start_at_unet_number,
                                                                   stop_at_unet_number):
             canvas = self._tiled_stage(unet, num, tiling[num - 1], sched, obj, dyn, device, canvas, cond_images, lowres_level,
                                        noise_fn, int(seed), use_graph, int(tile_batch), text_embeds=text_embeds,
                                        text_masks=text_masks, cond_scale=cs, solver=solver, streamed=bool(streamed),
-                                       crops=crops, into=into if num == last else None, known=known, start=starts[num - 1])
+                                       crops=crops, into=into if num == last else None, known=known, start=starts[num - 1],
+                                       shards=(devices, sharding[num - 1]) if exists(sharding) else None)
             outputs.append(canvas)
         return outputs if return_all_unet_outputs else outputs[-1]
 
     def _tiled_stage(self, unet, stage, geo, sched, objective, dynamic_threshold, device, prev_canvas, cond_images,
                      lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
-                     solver=("ddpm", 0.0), streamed=False, crops=None, into=None, known=(None, None, 1), start=(None, 0)):
+                     solver=("ddpm", 0.0), streamed=False, crops=None, into=None, known=(None, None, 1), start=(None, 0),
+                     shards=None, _poison_halo=False):
         """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  kd_tiles_start writes x_T; then, per
         resample slot of the schedule steps skip .. T - 1 and chunk of at most `tile_batch` tiles: gather the chunk out of
         the canvas into the plan's stable buffers, one iteration kd_solver_sample_steps(k, k + 1) with DDIM(0)
@@ -1885,15 +2025,35 @@ class Imagen(nn.Module):
         `known = (image, mask, R)` / `start = (init image, skip)`: the same three calls carry them - the start adds the init
         image and the first mix, the canvas step also re-noises and mixes the known pixels for the next slot, the end
         pastes them.  Without them (R = 1, skip = 0) the sources are NULL, a step has one slot and the calls give the
-        bits of the Philox draw, kd_tiles_fuse_update and kd_tiles_finalize."""
+        bits of the Philox draw, kd_tiles_fuse_update and kd_tiles_finalize.
+
+        `shards = (devices, normalize_shards' dict of this stage)`: the canvas over several shards, one per entry of
+        `devices`, in this one host thread - every call below is issued under the shard's device on that device's
+        current stream, and the shards meet through events alone (nothing waits on the host inside a step).  Every shard
+        holds the WHOLE canvas - x, the fused estimate, under 2M with resampling the slot's estimate - and a tile store
+        of its own and halo tiles, with a `tile_of` for exactly that set.  It runs kd_tiles_start itself (the bits are a
+        function of the canvas element), denoises its OWN tiles as above with plans of its own (`replica` = its number),
+        then the strips of the boundary tiles' estimates travel with their thresholds - kd_tiles_rows_copy packs them
+        into one buffer per pair of shards, one `copy_` moves it, kd_tiles_rows_copy unpacks it into the receiver's halo
+        slots - and every shard runs the one kd_tiles_fuse_update_known over own and halo.
+        THE INVARIANT: after the canvas step every pixel of a shard's band extent - the canvas rows its own tiles cover -
+        holds the bits of the single-device canvas, in x, in the fused estimate, in the history and so in the
+        self-conditioning carry gathered from it.  Every tile covering such a pixel is an own or a halo tile and covers
+        it inside its strip, the fusion order follows the lattice slot and not the store, the update is pointwise and
+        its noise is keyed by the canvas element; so the next gather of the own tiles, which reads nothing outside the
+        extent, reads only exact pixels.  Outside its extent a shard's canvas holds garbage (fused from halo rows that were
+        never sent) and is never read.  At the end every shard finalises the canvas rows it owns: the first straight into
+        the destination on devices[0], the others into a band of those rows (kd_tiles_finalize_rows) that one copy takes
+        there.  The previous canvas, the conditioning source, the known image, the mask and the init image are copied to
+        each device once per stage; a source already on a shard's device is read in place.
+        `_poison_halo` is for tests alone (no public call passes it): NaN in every halo slot of every shard's store, and in
+        its threshold, before each slot, so that only the received strips hold numbers."""
         lib = E.load()
         Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
         origins = geo["origins"]
-        N = len(origins)
         shape = (1, Cn, Hc, Wc)
-        f32 = lambda t: _f32(t, device)
-        gauss, stage_seed, _ = _stage_noise(lib, noise_fn, seed, stage, device)
         stream = E.current_stream
+        _, stage_seed, _ = _stage_noise(lib, noise_fn, seed, stage, device)
 
         kn, km, R = known
         init, skip = start
@@ -1902,74 +2062,71 @@ class Imagen(nn.Module):
         sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
         T, tile_steps = sc.T, getattr(lib, sc.steps)
         slots = [(k, j) for k in range(skip, T) for j in range(R)]   # slot j of step k is resample r = R - 1 - j
-        inject = lambda kind, k, j: f32(noise_fn((kind, stage, k, R - 1 - j), shape)) if exists(noise_fn) else None
+        mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
+        with_text = exists(text_embeds) and unet.cond_on_text
+        ls = a = s = None
+        if unet.lowres_cond:
+            ls = self.lowres_noise_schedule.log_snr(torch.full((1,), lowres_level, dtype=torch.float32))
+            a, s = log_snr_to_alpha_sigma(ls)
+        if exists(crops):
+            cc, Cs, W, Ct, top, shifts = crops
+            assert Ct == unet.cond_images_channels, "invalid number of channels in conditioning image"
+        if exists(cond_images):
+            assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
 
-        with torch.cuda.device(device):
+        # one shard: the whole lattice on `device`
+        layout = [dict(own=list(range(len(origins))), tiles=list(range(len(origins))), base=0, tile_of=geo["tile_of"], halo=[],
+                       owned=(0, Hc))] if shards is None else shards[1]["shards"]
+        devs = [device] if shards is None else shards[0]
+        exchange = [] if shards is None else shards[1]["exchange"]
+
+        def setup(num, dev, lay):   # the canvas, the store, the sources and the plans of one shard, on its device
+            f32 = lambda t: _f32(t, dev)
+            sh = SimpleNamespace(num=num, dev=dev, own=lay["own"], first=lay["own"][0], base=lay["base"], N=len(lay["tiles"]),
+                                 halo=[lay["tiles"].index(t) for t in lay["halo"]], owned=lay["owned"])
+            gauss = _stage_noise(lib, noise_fn, seed, stage, dev)[0]
+            sh.inject = lambda kind, k, j: f32(noise_fn((kind, stage, k, R - 1 - j), shape)) if exists(noise_fn) else None
             # the sources that exist stay where they lie: views of the caller's tensors, described to the kernels
-            here = lambda t: t.is_cuda and t.device.index == default(device.index, torch.cuda.current_device())
-            kn, init = (t if t is None or here(t) else f32(t) for t in (kn, init))
-            km = km if km is None or here(km) else km.to(device)
-            kn_s, km_s, init_s = E.tiles_image(kn), E.tiles_mask(km), E.tiles_image(init)
-            mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
-            x = torch.empty(shape, device=device, dtype=torch.float32)
+            here = lambda t: t.is_cuda and t.device.index == default(dev.index, torch.cuda.current_device())
+            sh.kn, sh.init = (t if t is None or here(t) else f32(t) for t in (kn, init))
+            sh.km = km if km is None or here(km) else km.to(dev)
+            sh.kn_s, sh.km_s, init_s = E.tiles_image(sh.kn), E.tiles_mask(sh.km), E.tiles_image(sh.init)
+            x = sh.x = torch.empty(shape, device=dev, dtype=torch.float32)
             z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
-            zm = inject("inpaint", skip, 0) if exists(kn) else None
+            zm = sh.inject("inpaint", skip, 0) if exists(kn) else None
             # (scale 1, no image, no mask: 1.0 * z, the bits of the draw itself)
             E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
-                                       E.ref(kn_s), E.ref(km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
+                                       E.ref(sh.kn_s), E.ref(sh.km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
             # 2M under resampling: the history takes a step's estimate in its last slot only, the slots before it
             # leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
-            x0bar_slot = torch.empty(shape, device=device, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
-            x0bar = torch.zeros(shape, device=device, dtype=torch.float32)
-            store = torch.empty((N, Cn, S, S), device=device, dtype=torch.float32)
-            thr = torch.empty((N,), device=device, dtype=torch.float32) if dynamic_threshold else None
-            tile_of = torch.tensor(geo["tile_of"], dtype=torch.int32).to(device).contiguous()
-            lowres = ls = lowres_z = None
+            sh.x0bar_slot = torch.empty(shape, device=dev, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
+            sh.x0bar = torch.zeros(shape, device=dev, dtype=torch.float32)
+            sh.store = torch.empty((sh.N, Cn, S, S), device=dev, dtype=torch.float32)
+            sh.thr = torch.empty((sh.N,), device=dev, dtype=torch.float32) if dynamic_threshold else None
+            sh.tile_of = torch.tensor(lay["tile_of"], dtype=torch.int32).to(dev).contiguous()
+            sh.lowres = sh.lowres_z = sh.prev = sh.cond = sh.src = cond_shape = None
             if unet.lowres_cond:
-                ls = self.lowres_noise_schedule.log_snr(torch.full((1,), lowres_level, dtype=torch.float32))
-                a, s = log_snr_to_alpha_sigma(ls)
                 if streamed:   # no canvas is built: every chunk is cut out of prev_canvas (injected noise stays a canvas)
-                    prev_canvas = f32(prev_canvas)
-                    assert prev_canvas.dim() == 4 and tuple(prev_canvas.shape[:2]) == (1, Cn), "the previous canvas must be [1, C, H, W]"
-                    lowres_z = f32(noise_fn(("lowres", stage), shape)) if exists(noise_fn) else None
+                    sh.prev = f32(prev_canvas)
+                    assert sh.prev.dim() == 4 and tuple(sh.prev.shape[:2]) == (1, Cn), "the previous canvas must be [1, C, H, W]"
+                    sh.lowres_z = f32(noise_fn(("lowres", stage), shape)) if exists(noise_fn) else None
                 else:
-                    lowres = F.interpolate(prev_canvas, (Hc, Wc), mode="nearest") * 2 - 1
-                    lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), shape, (16 << 32) | 1)).contiguous()
-            cond = cond_shape = None
+                    lowres = F.interpolate(prev_canvas.to(dev), (Hc, Wc), mode="nearest") * 2 - 1
+                    sh.lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), shape, (16 << 32) | 1)).contiguous()
             if exists(cond_images):
-                assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
-                cond = f32(resize_image_to(f32(cond_images), S))
-                cond_shape = tuple(cond.shape[1:])
+                sh.cond = f32(resize_image_to(f32(cond_images), S))
+                cond_shape = tuple(sh.cond.shape[1:])
             elif exists(crops):
-                cc, Cs, W, Ct, top, shifts = crops
-                assert Ct == unet.cond_images_channels, "invalid number of channels in conditioning image"
                 src = cc.image
-                src = f32(src.float() / 255.0 if src.dtype == torch.uint8 else src)   # moved once; stays for the stage
-                win_of, centre_of = (None if m is None else m.to(device) for m in cond_crop_maps(cc.window, S, cc.centre_width))
+                sh.src = f32(src.float() / 255.0 if src.dtype == torch.uint8 else src)   # moved once; stays for the stage
+                sh.win_of, sh.centre_of = (None if m is None else m.to(dev) for m in cond_crop_maps(cc.window, S, cc.centre_width))
                 cond_shape = (Ct, S, S)
-            with_text = exists(text_embeds) and unet.cond_on_text
-
-            def gather(src, dst, n0, b):   # dst [b, C, S, S] <- tiles n0 .. n0 + b - 1 of the canvas-shaped src
-                yx = (C.c_int * (2 * b))(*[v for o in origins[n0:n0 + b] for v in o])
-                E.check(lib.kd_tiles_gather(E.ptr(src), E.ptr(dst), b, Cn, Hc, Wc, S, yx, stream()))
-
-            def gather_lowres(dst, n0, b):   # dst [b, C, S, S] <- a (2 nearest(prev_canvas) - 1) + s z over tiles n0 ..
-                yx = (C.c_int * (2 * b))(*[v for o in origins[n0:n0 + b] for v in o])
-                E.check(lib.kd_tiles_gather_lowres(E.ptr(prev_canvas), prev_canvas.shape[2], prev_canvas.shape[3], E.ptr(dst), b,
-                                                   Cn, Hc, Wc, S, yx, float(a), float(s), E.ptr(lowres_z), stage_seed,
-                                                   (16 << 32) | 1, stream()))
-
-            def gather_cond(dst, n0, b):   # dst [b, Ct, S, S] <- the conditioning windows of tiles n0 .. n0 + b - 1
-                yx = (C.c_int * (2 * b))(*[v for sh in shifts[n0:n0 + b] for v in sh])
-                E.check(lib.kd_tiles_cond_gather(E.ptr(src), Cs, W, E.ptr(dst), b, S, yx, top, C.c_void_p(win_of.data_ptr()),
-                                                 C.c_void_p(centre_of.data_ptr()) if exists(centre_of) else None, float(cc.fill),
-                                                 stream()))
-
             # one plan, one set of stable buffers and one argument struct per batch size (the full chunks' and the ragged one's)
-            plans = {}
-            for b in sorted({min(tile_batch, N - n0) for n0 in range(0, N, tile_batch)}):
-                io = _StageIO(self, unet, b, S, device, dynamic_threshold=dynamic_threshold, use_graph=use_graph,
-                              key=stage_seed)   # (DDIM(0) draws nothing)
+            plans, n_own = {}, len(sh.own)
+            sh.plans = plans
+            for b in sorted({min(tile_batch, n_own - n0) for n0 in range(0, n_own, tile_batch)}):
+                io = _StageIO(self, unet, b, S, dev, dynamic_threshold=dynamic_threshold, use_graph=use_graph,
+                              key=stage_seed, replica=num)   # (DDIM(0) draws nothing)
                 args = io.args
                 args.objective = _OBJECTIVES[objective]
                 p = plans[b] = dict(io=io, args=args, img=io.buf("img", (b, Cn, S, S)))
@@ -1982,67 +2139,168 @@ class Imagen(nn.Module):
                     args.d_cond_images = E.ptr(p["cond"])
                 if unet.self_cond:
                     p["self_cond"] = io.buf("tile_self_cond", (b, Cn, S, S))
-                h = p["h"] = unet.engine(b, S, device, with_text=with_text)
+                h = p["h"] = unet.engine(b, S, dev, with_text=with_text, replica=num)
                 if with_text:   # one row for the canvas, given to every tile of the chunk
                     rows = lambda t: None if t is None else t.expand(b, *t.shape[1:])
                     io.text(h, rows(text_embeds), rows(text_masks), cond_scale)
+            sh.latest = sh.x0bar   # the canvas that holds the fused estimate of the previous slot
+            return sh
 
-            latest = x0bar   # the canvas that holds the fused estimate of the previous slot
-            for i, (k, j) in enumerate(slots):
-                for n0 in range(0, N, tile_batch):
-                    b = min(tile_batch, N - n0)
-                    p = plans[b]
-                    gather(x, p["img"], n0, b)
-                    if unet.lowres_cond and streamed:
-                        gather_lowres(p["lowres"], n0, b)
-                    elif unet.lowres_cond:
-                        gather(lowres, p["lowres"], n0, b)
-                    if exists(cond):
-                        p["cond"].copy_(cond[n0:n0 + b])
-                    elif exists(crops):
-                        gather_cond(p["cond"], n0, b)
-                    if unet.self_cond and i > 0:   # the carry is the FUSED estimate of the slot before (the first starts from zeros)
-                        gather(latest, p["self_cond"], n0, b)
-                        E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
-                    elif unet.self_cond and k > 0:   # a first step walked behind step 0: the plan holds another call's carry
-                        E.check(lib.kd_sample_set_self_cond(p["h"], None, stream()))
-                    p["args"].keep_self_cond = int(i > 0)   # (the later slots of step 0 keep the carry just set)
-                    E.check(tile_steps(p["h"], C.byref(sc.struct), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1, stream()))
-                    E.check(lib.kd_sample_last(p["h"], 1, E.ptr(store[n0:n0 + b]), stream()))
-                    if dynamic_threshold:
-                        E.check(lib.kd_sample_last(p["h"], 2, E.ptr(thr[n0:n0 + b]), stream()))
-                A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
-                z = inject("step", k, j) if Sn != 0.0 else None
-                # (z: memory of torch's current stream, handed on only behind this launch)
-                it = k * R + j
-                renoise = j < R - 1 and k < T - 1
-                zr = inject("renoise", k, j) if renoise else None
-                nxt = slots[i + 1] if exists(kn) and i + 1 < len(slots) else None   # the last slot mixes nothing: the end pastes
-                zm = inject("inpaint", *nxt) if exists(nxt) else None
-                a_mix, s_mix = mix(nxt[0]) if exists(nxt) else (0.0, 0.0)
-                est = x0bar if j == R - 1 or x0bar_slot is None else x0bar_slot
-                E.check(lib.kd_tiles_fuse_update_known(
-                    E.ptr(x), E.ptr(x0bar), E.ptr(est), E.ptr(store), E.ptr(thr), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st,
-                    ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it), int(renoise),
-                    float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
-                    E.ref(kn_s) if exists(nxt) else None, E.ref(km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
-                    E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0, stream()))
-                latest = est
-            if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
-                out, oy, ox = into if exists(into) else (torch.zeros(shape, device=device, dtype=torch.float32), 0, 0)
-                assert out.device == x.device, f"into: the canvas lives on {out.device}, the stage runs on {x.device}"
-                E.check(lib.kd_tiles_finalize_known(E.ptr(x), C.c_void_p(tile_of.data_ptr()), N, Cn, S, st, ny, nx, E.ptr(out),
-                                                    out.shape[2], out.shape[3], oy, ox, E.ref(kn_s), E.ref(km_s), stream()))
-                return out
-            covered = torch.zeros(Hc, Wc, dtype=torch.bool)
-            for y0, x0 in origins:
-                covered[y0:y0 + S, x0:x0 + S] = True
-            out = (x.clamp(-1.0, 1.0) + 1) * 0.5
-            if exists(kn):   # the paste on nearest-resized copies
-                resized = lambda t: t if tuple(t.shape[-2:]) == (Hc, Wc) else F.interpolate(t, (Hc, Wc), mode="nearest")
-                out = torch.where(resized(km[None, None].float()) != 0, resized(kn), out)
-            out = torch.where(covered.to(device), out, torch.zeros_like(out))
-        return out
+        def denoise(sh, i, k):   # the own tiles of the shard through slot i (of step k): their estimates into its store
+            def gather(src, dst, t0, b):   # dst [b, C, S, S] <- tiles t0 .. t0 + b - 1 of the canvas-shaped src
+                yx = (C.c_int * (2 * b))(*[v for o in origins[t0:t0 + b] for v in o])
+                E.check(lib.kd_tiles_gather(E.ptr(src), E.ptr(dst), b, Cn, Hc, Wc, S, yx, stream()))
+
+            def gather_lowres(dst, t0, b):   # dst [b, C, S, S] <- a (2 nearest(prev_canvas) - 1) + s z over tiles t0 ..
+                yx = (C.c_int * (2 * b))(*[v for o in origins[t0:t0 + b] for v in o])
+                E.check(lib.kd_tiles_gather_lowres(E.ptr(sh.prev), sh.prev.shape[2], sh.prev.shape[3], E.ptr(dst), b,
+                                                   Cn, Hc, Wc, S, yx, float(a), float(s), E.ptr(sh.lowres_z), stage_seed,
+                                                   (16 << 32) | 1, stream()))
+
+            def gather_cond(dst, t0, b):   # dst [b, Ct, S, S] <- the conditioning windows of tiles t0 .. t0 + b - 1
+                yx = (C.c_int * (2 * b))(*[v for f in shifts[t0:t0 + b] for v in f])
+                E.check(lib.kd_tiles_cond_gather(E.ptr(sh.src), Cs, W, E.ptr(dst), b, S, yx, top, C.c_void_p(sh.win_of.data_ptr()),
+                                                 C.c_void_p(sh.centre_of.data_ptr()) if exists(sh.centre_of) else None,
+                                                 float(cc.fill), stream()))
+
+            n_own = len(sh.own)
+            for n0 in range(0, n_own, tile_batch):
+                b = min(tile_batch, n_own - n0)
+                t0, at = sh.first + n0, sh.base + n0   # the chunk's first tile: its number on the canvas, its slot in the store
+                p = sh.plans[b]
+                gather(sh.x, p["img"], t0, b)
+                if unet.lowres_cond and streamed:
+                    gather_lowres(p["lowres"], t0, b)
+                elif unet.lowres_cond:
+                    gather(sh.lowres, p["lowres"], t0, b)
+                if exists(sh.cond):
+                    p["cond"].copy_(sh.cond[t0:t0 + b])
+                elif exists(crops):
+                    gather_cond(p["cond"], t0, b)
+                if unet.self_cond and i > 0:   # the carry is the FUSED estimate of the slot before (the first starts from zeros)
+                    gather(sh.latest, p["self_cond"], t0, b)
+                    E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
+                elif unet.self_cond and k > 0:   # a first step walked behind step 0: the plan holds another call's carry
+                    E.check(lib.kd_sample_set_self_cond(p["h"], None, stream()))
+                p["args"].keep_self_cond = int(i > 0)   # (the later slots of step 0 keep the carry just set)
+                E.check(tile_steps(p["h"], C.byref(sc.struct), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1, stream()))
+                E.check(lib.kd_sample_last(p["h"], 1, E.ptr(sh.store[at:at + b]), stream()))
+                if dynamic_threshold:
+                    E.check(lib.kd_sample_last(p["h"], 2, E.ptr(sh.thr[at:at + b]), stream()))
+
+        def step(sh, i, k, j):   # the canvas step of slot i = (k, j) on the shard's canvas, over its own and halo tiles
+            A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
+            z = sh.inject("step", k, j) if Sn != 0.0 else None
+            # (z: memory of torch's current stream, handed on only behind this launch)
+            it = k * R + j
+            renoise = j < R - 1 and k < T - 1
+            zr = sh.inject("renoise", k, j) if renoise else None
+            nxt = slots[i + 1] if exists(kn) and i + 1 < len(slots) else None   # the last slot mixes nothing: the end pastes
+            zm = sh.inject("inpaint", *nxt) if exists(nxt) else None
+            a_mix, s_mix = mix(nxt[0]) if exists(nxt) else (0.0, 0.0)
+            est = sh.x0bar if j == R - 1 or sh.x0bar_slot is None else sh.x0bar_slot
+            E.check(lib.kd_tiles_fuse_update_known(
+                E.ptr(sh.x), E.ptr(sh.x0bar), E.ptr(est), E.ptr(sh.store), E.ptr(sh.thr), C.c_void_p(sh.tile_of.data_ptr()), sh.N,
+                Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it),
+                int(renoise), float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
+                E.ref(sh.kn_s) if exists(nxt) else None, E.ref(sh.km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
+                E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0, stream()))
+            sh.latest = est
+
+        def link(e):   # one pair of shards: the strip buffer on either side, the descriptors of the pack and of the unpack
+            src, dst = parts[e["src"]], parts[e["dst"]]
+            rows = max(r for _, _, r in e["items"])
+            n = len(e["items"])
+            slot_of = lambda part, t: layout[part.num]["tiles"].index(t)
+            flat = lambda quads: (C.c_int * (4 * n))(*[v for q in quads for v in q])
+            ln = SimpleNamespace(src=src, dst=dst, n=n, rows=rows, ready=torch.cuda.Event(), freed=torch.cuda.Event(), sent=False,
+                                 pack=flat((slot_of(src, t), m, r0, r) for m, (t, r0, r) in enumerate(e["items"])),
+                                 unpack=flat((m, slot_of(dst, t), r0, r) for m, (t, r0, r) in enumerate(e["items"])))
+            # [n strips of C x rows x S | n thresholds], one allocation: what travels is one contiguous buffer
+            words = n * Cn * rows * S
+            ln.out = torch.empty(words + n, device=src.dev, dtype=torch.float32)
+            ln.inn = torch.empty(words + n, device=dst.dev, dtype=torch.float32)
+            ln.words = words
+            return ln
+
+        def trade(ln):   # the strips of one pair: packed where they were made, moved, unpacked into the halo slots
+            tail = lambda buf: C.c_void_p(buf.data_ptr() + 4 * ln.words) if dynamic_threshold else None
+            with torch.cuda.device(ln.src.dev):
+                if ln.sent:   # the buffer is written again only behind the copy that read it
+                    torch.cuda.current_stream().wait_event(ln.freed)
+                E.check(lib.kd_tiles_rows_copy(E.ptr(ln.src.store), ln.src.N, S, E.ptr(ln.out), ln.n, ln.rows, E.ptr(ln.src.thr),
+                                               tail(ln.out), ln.n, Cn, S, ln.pack, stream()))
+                ln.ready.record()
+            with torch.cuda.device(ln.dst.dev):
+                torch.cuda.current_stream().wait_event(ln.ready)
+                ln.inn.copy_(ln.out, non_blocking=True)
+                ln.freed.record()
+                ln.sent = True
+                E.check(lib.kd_tiles_rows_copy(E.ptr(ln.inn), ln.n, ln.rows, E.ptr(ln.dst.store), ln.dst.N, S, tail(ln.inn),
+                                               E.ptr(ln.dst.thr), ln.n, Cn, S, ln.unpack, stream()))
+
+        parts = []
+        for num, (dev, lay) in enumerate(zip(devs, layout)):
+            with torch.cuda.device(dev):
+                parts.append(setup(num, dev, lay))
+        links = [link(e) for e in exchange]
+        for i, (k, j) in enumerate(slots):
+            for sh in parts:
+                with torch.cuda.device(sh.dev):
+                    if _poison_halo and sh.halo:
+                        sh.store[sh.halo] = float("nan")
+                        if dynamic_threshold:
+                            sh.thr[sh.halo] = float("nan")
+                    denoise(sh, i, k)
+            for ln in links:
+                trade(ln)
+            for sh in parts:
+                with torch.cuda.device(sh.dev):
+                    step(sh, i, k, j)
+
+        head = parts[0]
+        if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
+            with torch.cuda.device(head.dev):
+                out, oy, ox = into if exists(into) else (torch.zeros(shape, device=head.dev, dtype=torch.float32), 0, 0)
+                assert out.device == head.x.device, f"into: the canvas lives on {out.device}, the stage runs on {head.x.device}"
+                if len(parts) == 1:
+                    E.check(lib.kd_tiles_finalize_known(E.ptr(head.x), C.c_void_p(head.tile_of.data_ptr()), head.N, Cn, S, st, ny, nx,
+                                                        E.ptr(out), out.shape[2], out.shape[3], oy, ox, E.ref(head.kn_s),
+                                                        E.ref(head.km_s), stream()))
+                    return out
+            holes = len(origins) < ny * nx   # an uncovered pixel keeps the destination's bits: a band then starts from them
+            for sh in parts:
+                y0, y1 = sh.owned
+                window = out[:, :, oy + y0:oy + y1, ox:ox + Wc]
+                with torch.cuda.device(sh.dev):
+                    if sh is head:
+                        band, Ho, Wo, by, bx = out, out.shape[2], out.shape[3], oy, ox
+                    else:
+                        band = torch.empty((1, Cn, y1 - y0, Wc), device=sh.dev, dtype=torch.float32)
+                        if holes:
+                            band.copy_(window, non_blocking=True)
+                        Ho, Wo, by, bx = y1 - y0, Wc, -y0, 0
+                    E.check(lib.kd_tiles_finalize_rows(E.ptr(sh.x), C.c_void_p(sh.tile_of.data_ptr()), sh.N, Cn, S, st, ny, nx,
+                                                       E.ptr(band), Ho, Wo, by, bx, E.ref(sh.kn_s), E.ref(sh.km_s), y0, y1, stream()))
+                if sh is not head:
+                    with torch.cuda.device(head.dev):
+                        window.copy_(band, non_blocking=True)
+            return out
+        bands = []
+        for sh in parts:   # the same clamp and paste in torch, over the rows the shard owns
+            y0, y1 = sh.owned
+            with torch.cuda.device(sh.dev):
+                covered = torch.zeros(Hc, Wc, dtype=torch.bool)
+                for ty, tx in origins:
+                    covered[ty:ty + S, tx:tx + S] = True
+                out = (sh.x[:, :, y0:y1].clamp(-1.0, 1.0) + 1) * 0.5
+                if exists(kn):   # the paste on nearest-resized copies
+                    resized = lambda t: t if tuple(t.shape[-2:]) == (Hc, Wc) else F.interpolate(t, (Hc, Wc), mode="nearest")
+                    out = torch.where(resized(sh.km[None, None].float())[:, :, y0:y1] != 0, resized(sh.kn)[:, :, y0:y1], out)
+                out = torch.where(covered[y0:y1].to(sh.dev), out, torch.zeros_like(out))
+            bands.append(out)
+        with torch.cuda.device(head.dev):
+            return bands[0] if len(bands) == 1 else torch.cat([b.to(head.dev) for b in bands], dim=2)
 
     def _num_steps(self):
         """Schedule steps of every UNet's sampler: what skip_steps is checked against."""

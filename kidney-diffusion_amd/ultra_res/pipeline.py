@@ -109,7 +109,7 @@ def generate_all_levels(sample_fns: Dict[int, Callable], overlap: float = 0.25, 
 
 
 def generate_high_res_image_fused(load_imagen: Callable, zoomed_image: torch.Tensor, mag_level: int, overlap: float = 0.25,
-                                  version: str = "ultra", patch_pos: Optional[Sequence[G.Pos]] = None,
+                                  version: str = "ultra", patch_pos: Optional[Sequence[G.Pos]] = None, devices=None,
                                   **fused_kw) -> torch.Tensor:
     """`generate_high_res_image` by fused-tile sampling: `level_patches` (every position at mag 1, the tissue set at
     mag 2; `patch_pos` overrides it) and `tiled.fused_level` over them.  `load_imagen(stage)` returns the Imagen of that
@@ -117,24 +117,31 @@ def generate_high_res_image_fused(load_imagen: Callable, zoomed_image: torch.Ten
     `sample_steps`, `seed`, `noise_fn`, `fill_color`, `background`, `device`, ...).  (1,3,W,W) on the device.
     Partial regeneration, the fused counterpart of `generate_high_res_image(patch_pos=...)` on a finished level, goes
     through `fused_kw` as well: `canvas=` (the finished level, written in place), `keep=` (`tiled.level_keep_mask` of the
-    tiles that stay), `known_resample_times=` and `refine_skip_steps=`."""
+    tiles that stay), `known_resample_times=` and `refine_skip_steps=`.  `devices`: the level's canvas over several
+    devices, one shard of lattice rows each (`fused_level(devices=)`); the level comes back on `devices[0]`."""
     from . import tiled as UT
 
     geom, pos = level_patches(zoomed_image, mag_level, overlap, version)
     if patch_pos is not None:
         pos = list(patch_pos)
-    return UT.fused_level(load_imagen, zoomed_image, geom, pos, overlap=overlap, version=version, **fused_kw)
+    return UT.fused_level(load_imagen, zoomed_image, geom, pos, overlap=overlap, version=version, devices=devices, **fused_kw)
 
 
 def generate_all_levels_fused(load_imagens: Dict[int, Callable], overlap: float = 0.25, version: str = "ultra",
-                              patch_filter: Optional[Callable[[int, List[G.Pos]], List[G.Pos]]] = None,
+                              patch_filter: Optional[Callable[[int, List[G.Pos]], List[G.Pos]]] = None, devices=None,
                               **fused_kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """`generate_all_levels` by fused-tile sampling: mag 0 is `tiled.fused_canvas(grid=(1, 1))` - one tile, the
     unconditional sample - and mag 1 and mag 2 are `generate_high_res_image_fused` over the level before.
     `load_imagens[level](stage)` returns the Imagen of that level and stage; `patch_filter` as in `generate_all_levels`;
     `fused_kw` as in `generate_high_res_image_fused` (mag 0 takes those of them that `fused_canvas` knows).  With an int
-    `seed`, level L runs under `seed + L`.  Returns the three images, each (1,3,W,W) on the device."""
+    `seed`, level L runs under `seed + L`.  Returns the three images, each (1,3,W,W) on the device.  `devices`: mag 1 and
+    mag 2 over several devices (`generate_high_res_image_fused(devices=)`); mag 0 is one tile and runs on `devices[0]`."""
     from . import tiled as UT
+    from imagen_pytorch.imagen_pytorch import normalize_devices
+
+    devices = normalize_devices(devices, fused_kw.get("noise_fn"))
+    if devices is not None:
+        fused_kw["device"] = devices[0]
 
     seed = fused_kw.pop("seed", None)
     level_seed = lambda level: None if seed is None else int(seed) + level
@@ -146,5 +153,5 @@ def generate_all_levels_fused(load_imagens: Dict[int, Callable], overlap: float 
         if patch_filter is not None:
             pos = patch_filter(level, level_patches(out[-1], level, overlap, version)[1])
         out.append(generate_high_res_image_fused(load_imagens[level], out[-1], level, overlap=overlap, version=version,
-                                                 patch_pos=pos, seed=level_seed(level), **fused_kw))
+                                                 patch_pos=pos, seed=level_seed(level), devices=devices, **fused_kw))
     return tuple(out)

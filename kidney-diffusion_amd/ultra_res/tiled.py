@@ -25,11 +25,15 @@ def _per_unet(v, default, n):   # {stage: value} -> one entry per unet 1 .. n (`
     return tuple(v.get(s, default) for s in range(1, n + 1)) if isinstance(v, dict) else v
 
 
-def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, **kw):
+def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, devices=None, **kw):
     """`canvas` through `stages`, one `sample_tiled(**kw)` call of `load_imagen(stage)` each; `solver = (sampler, sampler_eta,
     sample_steps)`; `first_stage(geometry of the last stage, device)` returns the last stage's `into` and keywords for
-    every stage's call.  `init_canvas` / `init_skip_steps` in `kw` are a scalar or {stage: value}, like the solver's."""
-    from imagen_pytorch.imagen_pytorch import normalize_tiling
+    every stage's call.  `init_canvas` / `init_skip_steps` in `kw` are a scalar or {stage: value}, like the solver's.
+    `devices`: every stage's canvas over these devices (`sample_tiled(devices=)`), everything else on `devices[0]`."""
+    from imagen_pytorch.imagen_pytorch import normalize_devices, normalize_shards, normalize_tiling
+    devices = normalize_devices(devices, kw.get("noise_fn"))
+    if devices is not None:
+        device = devices[0]
     device = torch.device(device if device is not None else "cuda")
     for stage in stages:
         imagen = load_imagen(stage)
@@ -38,13 +42,16 @@ def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, *
             if stages[-1] > n:
                 raise ValueError(f"stages={stages} name unet {stages[-1]}, the Imagen holds {n}")
             tiling = normalize_tiling(imagen.image_sizes, kw["grid"], kw["overlap"], kw["present"], kw["tile_weights"])
+            if devices is not None and len(devices) > 1:
+                normalize_shards(tiling, len(devices))
             into, more = first_stage(tiling[stages[-1] - 1], device) if first_stage else (None, {})
             kw = dict(kw, **more)
         sampler, eta, steps = (_per_unet(v, d, n) for v, d in zip(solver, (None, 0.0, None)))
         starts = {name: _per_unet(kw[name], None, n) for name in ("init_canvas", "init_skip_steps") if name in kw}
         canvas = imagen.to(device).sample_tiled(sampler=sampler, sampler_eta=eta, sample_steps=steps, start_at_unet_number=stage,
                                                 stop_at_unet_number=stage, start_image_or_video=canvas, device=device,
-                                                into=into if stage == stages[-1] else None, **dict(kw, **starts))
+                                                into=into if stage == stages[-1] else None, devices=devices,
+                                                **dict(kw, **starts))
     return canvas
 
 
@@ -53,7 +60,7 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
                  sample_steps=None, seed: Optional[int] = None, cond_images: Optional[torch.Tensor] = None, present=None,
                  tile_weights: str = "uniform", use_graph: bool = True, noise_fn: Optional[Callable] = None,
                  start_canvas: Optional[torch.Tensor] = None, device: Optional[torch.device] = None, known=None,
-                 known_resample_times: int = 1, init_canvas=None, init_skip_steps=None) -> torch.Tensor:
+                 known_resample_times: int = 1, init_canvas=None, init_skip_steps=None, devices=None) -> torch.Tensor:
     """One canvas through `stages` by fused-tile sampling.  `load_imagen(stage)` returns the Imagen holding the real unet
     of that stage, as for `distributed.imagen_sample_fn` (the reference re-loads one stage at a time; all stay resident
     here).  The lattice is `grid = (ny, nx)` or `num_patches_width` squared, at `overlap`, with `present[ny][nx]` marking
@@ -66,9 +73,11 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
     `init_canvas`, `init_skip_steps`: one value for every stage or {stage: value} - the stage starts from the image at
     that step.
 
-    A single process: the tiles of one canvas meet in every schedule step (the fused estimate needs all of them), so
-    spreading them over ranks would take an exchange per step - out of scope here.  Independent canvases can run on
-    different ranks as they are."""
+    A single process.  `devices` (a sequence of CUDA devices, one per shard; a device may repeat) spreads the canvas of
+    every stage over them by bands of lattice rows, as `sample_tiled(devices=)` describes: the tiles of one canvas meet in
+    every schedule step, so the overlap strips of the boundary tiles' estimates cross per step; the canvas comes back on
+    `devices[0]`, the canvas of `devices=None`.  `torch.distributed` ranks for one canvas stay out of scope; independent
+    canvases can run on different ranks as they are."""
     if (num_patches_width is None) == (grid is None):
         raise ValueError(f"fused_canvas takes num_patches_width or grid, one of them; got num_patches_width={num_patches_width!r}, "
                          f"grid={grid!r}")
@@ -82,7 +91,8 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
     return _run_stages(load_imagen, stages, device, start_canvas, (sampler, sampler_eta, sample_steps), grid=grid, overlap=overlap,
                        present=present, tile_batch=tile_batch, tile_weights=tile_weights, cond_images=cond_images, seed=seed,
                        noise_fn=noise_fn, use_graph=use_graph, known_image=image, known_mask=mask,
-                       known_resample_times=known_resample_times, init_canvas=init_canvas, init_skip_steps=init_skip_steps)
+                       known_resample_times=known_resample_times, init_canvas=init_canvas, init_skip_steps=init_skip_steps,
+                       devices=devices)
 
 
 def level_box(positions: Sequence[G.Pos]):
@@ -128,7 +138,7 @@ def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridG
                 sampler_eta=0.0, sample_steps=None, seed: Optional[int] = None, noise_fn: Optional[Callable] = None,
                 use_graph: bool = True, background: bool = True, device: Optional[torch.device] = None,
                 canvas: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, known_resample_times: int = 1,
-                refine_skip_steps=None) -> torch.Tensor:
+                refine_skip_steps=None, devices=None) -> torch.Tensor:
     """One magnification level by fused-tile sampling, with the semantics of `pipeline.generate_high_res_image`: the
     tiles at `positions` (grid positions (i, j) of `geom`; all of them at mag 1, the tissue set at mag 2) are conditioned
     on windows of `zoomed_image` [1, 3, W, W], the level above, denoised together through `stages`, and written over the
@@ -154,7 +164,10 @@ def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridG
     seam, and every kept pixel keeps its bits.  `refine_skip_steps` (int or {stage: value}): every stage starts from the
     window of `canvas` (or of the enlarged background) at that step instead of from noise.  The known image, the mask
     and the init image are the WINDOWS of `canvas` and `keep` at the box' corner, read in place at every stage's canvas
-    size: no copy of a level is made."""
+    size: no copy of a level is made.
+
+    `devices`: the box' canvas over several devices, a band of its lattice rows each (`sample_tiled(devices=)`); the level,
+    `canvas` and `keep` live on `devices[0]`, every other device takes its copy of the windows once per stage."""
     from imagen_pytorch.imagen_pytorch import TileCondCrops
 
     stages = _check_stages(stages, from_one=True)
@@ -221,4 +234,4 @@ def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridG
 
     return _run_stages(load_imagen, stages, device, None, (sampler, sampler_eta, sample_steps), first_stage, grid=grid,
                        overlap=overlap, present=present, tile_batch=tile_batch, tile_weights=tile_weights, cond_crops=crops,
-                       seed=seed, noise_fn=noise_fn, use_graph=use_graph, streamed=True)
+                       seed=seed, noise_fn=noise_fn, use_graph=use_graph, streamed=True, devices=devices)
