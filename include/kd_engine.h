@@ -63,7 +63,9 @@ const char* kd_last_error(void);
  *      kd_sample_args_t gained `keep_self_cond` at its end (zero = the reset at step 0 of before); kd_tiles_finalize_known
  *      accepts known = mask = NULL (kd_tiles_finalize's bits) - kd_tiles_fuse_update and kd_tiles_finalize are the _known calls
  *      with nothing known, no existing entry changed; kd_tiles_rows_copy and kd_tiles_finalize_rows added (a fused-tile canvas
- *      cut into shards over several devices) */
+ *      cut into shards over several devices); kd_solver3_sample_loop / kd_solver3_sample_steps with their struct
+ *      kd_solver3_schedule_t - DPM-Solver++(3M), the SDE forms of 2M and 3M - and kd_tiles_fuse_update_hist2 added:
+ *      kd_solver_sample_* and kd_tiles_fuse_update_known are those with no second history, no existing entry changed */
 #define KD_ENGINE_ABI_VERSION 2
 int kd_version(void);
 /* sha256 prefix (16 hex digits) of the sources this binary was compiled from (csrc/build_id.py); a build with
@@ -469,6 +471,36 @@ int kd_solver_sample_loop(kd_unet_t* u, const kd_solver_schedule_t* sched, const
  * after kd_sample_steps.  k_begin > 0 continues from the self-conditioning estimate and the history the plan holds. */
 int kd_solver_sample_steps(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
                            int k_begin, int k_end, void* stream);
+
+/* Third order and the SDE forms: DPM-Solver++(3M), and 2M / 3M with noise (the Python package: solver_tables "dpmpp_3m",
+ * "dpmpp_2m_sde", "dpmpp_3m_sde").  The update gains one term,
+ *     x <- coef_x[k] x + coef_x0[k] x0c + coef_prev[k] h1 + coef_prev2[k] h2 + coef_noise[k] N(0,1)
+ * left to right, h1 / h2 the x0c that steps k - 1 / k - 2 kept.  The plan holds the two estimates as a ring indexed by the
+ * step's parity, read on the device from the iteration counter: step k reads h1 in slot (k - 1) & 1 and h2 in slot k & 1 and,
+ * in its last resample slot, writes its own x0c into slot k & 1, each thread behind its own read - one captured step serves
+ * every step and nothing is copied.  Under resampling all R slots of step k read the estimates of steps k - 1 and k - 2.
+ * A zero coefficient leaves its operand unread; step 0 must be first order and step 1 at most second order
+ * (coef_prev[0] == coef_prev2[0] == coef_prev2[1] == 0, checked when k_begin == 0; a caller that starts at k_begin > 0 keeps
+ * the same rule for its first two steps unless it continues a walk), so a call does not depend on what the ring holds.  The
+ * ring's second slot lives in the plan from the first call whose coef_prev2 is not all zero and persists like the first.
+ * coef_prev2 == NULL or all zero IS kd_solver_sample_*: the same launches, arguments, arithmetic and captured step. */
+typedef struct kd_solver3_schedule {
+  int T;
+  const float* log_snr;
+  const float* alpha;
+  const float* sigma;
+  const float* rn_a;
+  const float* rn_b;
+  const float* coef_x;
+  const float* coef_x0;
+  const float* coef_prev;
+  const float* coef_noise;
+  const float* coef_prev2;
+} kd_solver3_schedule_t;
+int kd_solver3_sample_loop(kd_unet_t* u, const kd_solver3_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                           void* stream);
+int kd_solver3_sample_steps(kd_unet_t* u, const kd_solver3_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                            int k_begin, int k_end, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * EDM sampler.  Replaces `ElucidatedImagen.sample` / `one_unet_sample` / `preconditioned_network_forward` of
@@ -933,6 +965,18 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
                                float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
                                const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
                                const float* d_mix_noise, uint64_t mix_stream_id, void* stream);
+/* kd_tiles_fuse_update_known with a second history (the third-order canvas step of DPM-Solver++(3M) and its SDE form):
+ *     x <- A x + B x0bar [+ P hist] [+ P2 hist2] [+ Sn z]
+ * left to right, d_hist2 read only when P2 != 0 (NULL is then allowed).  d_x0bar_out may be d_hist2, as it may be d_hist:
+ * each thread reads its element before it writes it, so a caller keeps three canvases and rotates the pointers - the
+ * estimate of step k overwrites that of step k - 2.  P2 == 0 is kd_tiles_fuse_update_known, bit for bit.  Preconditions:
+ * kd_tiles_fuse_update_known's, d_x apart from d_hist2 too. */
+int kd_tiles_fuse_update_hist2(float* d_x, const float* d_hist, float* d_x0bar_out, const float* d_x0_tiles, const float* d_thr,
+                               const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                               float P, float Sn, const float* d_noise, uint64_t seed, uint64_t stream_id, int renoise,
+                               float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
+                               const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
+                               const float* d_mix_noise, uint64_t mix_stream_id, const float* d_hist2, float P2, void* stream);
 /* kd_tiles_finalize with the paste: d_out[c, oy + y, ox + x] = m ? kn : (clamp(x, -1, 1) + 1) * 0.5 on covered pixels,
  * every other element of d_out untouched.  A known pixel is the known image's value copied, not round-tripped through
  * 2 v - 1.  `known` may be the window of d_out that is written (base d_out + oy Wo + ox, size [Hc, Wc], strides Wo and

@@ -284,6 +284,8 @@ int kd_unet_profile(kd_unet_t* u, int iters, char* buf, size_t buflen, void* str
 //               of a call (a caller that continues with k_begin > 0 seeds it after this call, kd_sample_set_self_cond);
 //               hist (few-step solvers): the first step a call walks is first order and does not read it, and its
 //               last resample slot writes it (a caller that continues with k_begin > 0 poisons before the first call);
+//               hist2 (third-order solvers): with hist a ring - the first two steps a call walks read neither slot
+//               through a non-zero coefficient, and each writes the slot the step behind it reads;
 //               qws: the quantile's QState and histograms are integers - q_init_kernel sets every one of them at the
 //               start of each launch_quantile_abs, before q_hist / q_scan / q_next / q_final index or count with them
 //   left alone - state that outlives a call:
@@ -306,7 +308,7 @@ int kd_unet_poison_scratch(kd_unet_t* u, uint32_t word, int64_t* bytes_filled, v
       {m.pred, img},          {m.pred_null, img},          {m.x0, img},
       {m.thresh, per_b},      {m.time, per_b},             {m.xhat, img},
       {m.d, img},             {m.net_in, img},             {m.self_cond, img},
-      {m.hist, img},
+      {m.hist, img},          {m.hist2, img},
       {m.qws, quantile_ws_bytes(u->cfg.batch)}};
   int64_t total = 0;
   for (const auto& b : bufs) {
@@ -359,7 +361,7 @@ int kd_edm_sample_loop(kd_unet_t* u, const kd_edm_schedule_t* sched, const kd_sa
 
 int kd_solver_sample_steps(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
                            int k_begin, int k_end, void* stream) {
-  return solver_sample_steps(u, sched, args, d_img, k_begin, k_end, (hipStream_t)stream);
+  return solver_sample_steps(u, sched, nullptr, args, d_img, k_begin, k_end, (hipStream_t)stream);
 }
 
 int kd_solver_sample_loop(kd_unet_t* u, const kd_solver_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
@@ -368,7 +370,43 @@ int kd_solver_sample_loop(kd_unet_t* u, const kd_solver_schedule_t* sched, const
     set_error("kd_solver_sample_loop: null schedule");
     return 1;
   }
-  if (solver_sample_steps(u, sched, args, d_img, 0, sched->T, (hipStream_t)stream)) return 1;
+  if (solver_sample_steps(u, sched, nullptr, args, d_img, 0, sched->T, (hipStream_t)stream)) return 1;
+  return kd_sample_finalize(u, args, d_img, stream);
+}
+
+// kd_solver3_schedule_t: kd_solver_schedule_t's fields, then coef_prev2
+static kd_solver_schedule_t solver3_head(const kd_solver3_schedule_t* q) {
+  kd_solver_schedule_t sc{};
+  sc.T = q->T;
+  sc.log_snr = q->log_snr;
+  sc.alpha = q->alpha;
+  sc.sigma = q->sigma;
+  sc.rn_a = q->rn_a;
+  sc.rn_b = q->rn_b;
+  sc.coef_x = q->coef_x;
+  sc.coef_x0 = q->coef_x0;
+  sc.coef_prev = q->coef_prev;
+  sc.coef_noise = q->coef_noise;
+  return sc;
+}
+
+int kd_solver3_sample_steps(kd_unet_t* u, const kd_solver3_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                            int k_begin, int k_end, void* stream) {
+  if (!sched) {
+    set_error("kd_solver3_sample_steps: null schedule");
+    return 1;
+  }
+  const kd_solver_schedule_t sc = solver3_head(sched);
+  return solver_sample_steps(u, &sc, sched->coef_prev2, args, d_img, k_begin, k_end, (hipStream_t)stream);
+}
+
+int kd_solver3_sample_loop(kd_unet_t* u, const kd_solver3_schedule_t* sched, const kd_sample_args_t* args, float* d_img,
+                           void* stream) {
+  if (!sched) {
+    set_error("kd_solver3_sample_loop: null schedule");
+    return 1;
+  }
+  if (kd_solver3_sample_steps(u, sched, args, d_img, 0, sched->T, stream)) return 1;
   return kd_sample_finalize(u, args, d_img, stream);
 }
 
@@ -1234,6 +1272,19 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
   return launch_tiles_fuse_update(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
                                   Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
                                   (hipStream_t)stream);
+}
+int kd_tiles_fuse_update_hist2(float* d_x, const float* d_hist, float* d_x0bar_out, const float* d_x0_tiles, const float* d_thr,
+                               const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
+                               float P, float Sn, const float* d_noise, uint64_t seed, uint64_t stream_id, int renoise,
+                               float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
+                               const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
+                               const float* d_mix_noise, uint64_t mix_stream_id, const float* d_hist2, float P2, void* stream) {
+  TileImage kn;
+  TileMask mk;
+  const TileMix mix{tile_image_of(known, &kn), tile_mask_of(mask, &mk), mix_a, mix_s, d_mix_noise, mix_stream_id};
+  return launch_tiles_fuse_update(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
+                                  Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
+                                  (hipStream_t)stream, d_hist2, P2);
 }
 int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
                             int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,

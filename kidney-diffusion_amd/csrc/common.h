@@ -393,12 +393,15 @@ int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const f
 // Few-step solvers (DDIM, DPM-Solver++(2M)): x = coef_x x + coef_x0 x0c + coef_prev hist + coef_noise N(0,1), device arrays
 // of T floats (kd_solver_schedule_t).  hist: the thresholded estimate the previous step kept, or nullptr when no step of
 // the schedule reads one; it takes this step's in the last resample slot.
+// Third order (kd_solver3_schedule_t with a coef_prev2 != 0): + coef_prev2 h2, and hist / hist2 are the two slots of a ring
+// indexed by the step's parity (kernels_sampler.hip: solver_update_body); both nullptr otherwise.
 struct SolverTables {
   const float *coef_x, *coef_x0, *coef_prev, *coef_noise;
 };
 int launch_solver_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
                          const uint64_t* d_seed, const SolverTables& tb, const int* d_iter, int R, int dynamic_threshold,
-                         int B, int64_t per, hipStream_t s, float* hist, float* sc_out);
+                         int B, int64_t per, hipStream_t s, float* hist, float* sc_out, float* hist2 = nullptr,
+                         const float* coef_prev2 = nullptr);
 int launch_inpaint_mix(float* x, const float* inp, const float* mask, const float* noise, int64_t noise_stride,
                        const uint64_t* d_seed, const StepTables& tb, const int* d_iter, int R, int B, int C, int64_t hw,
                        hipStream_t s);
@@ -481,11 +484,13 @@ struct TileMix {
 int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float* noise, uint64_t seed, const TileImage* init,
                        const TileMix& mix, hipStream_t s);
 // the canvas step x <- A x + B x0bar + P hist + Sn z over the weighted mean x0bar of the covering tiles, hist (read when
-// P != 0) and x0bar_out apart or one buffer; then on the same pixel [x = x rn_a + z rn_b] (renoise != 0) and [the mix]
+// P != 0) and x0bar_out apart or one buffer; then on the same pixel [x = x rn_a + z rn_b] (renoise != 0) and [the mix].
+// hist2 / P2: + P2 hist2 behind the P term (third-order canvas steps), read when P2 != 0; it too may be x0bar_out
 int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
                              const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P,
                              float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise, float rn_a, float rn_b,
-                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s);
+                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s,
+                             const float* hist2 = nullptr, float P2 = 0.0f);
 // out = [m ? kn :] (clamp(x, -1, 1) + 1) / 2 on covered pixels of the canvas rows [y_lo, y_hi) (y_hi < 0: through Hc); known
 // and mask both or neither
 int launch_tiles_finalize(const float* x, const int* tile_of, int N, int C, int S, int st, int ny, int nx, float* out, int Ho,

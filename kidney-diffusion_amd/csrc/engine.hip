@@ -233,16 +233,17 @@ struct Sampler {
   float *xhat = nullptr, *d = nullptr, *net_in = nullptr;
   float* self_cond = nullptr;   // self_cond plans: the thresholded x0 estimate carried to the next forward [B,3,S,S]
   float* hist = nullptr;   // few-step solvers: the thresholded x0 estimate of the previous step [B,C,S,S]; with the first 2M call
+  float* hist2 = nullptr;  // third-order solvers: with hist the two slots of a ring by step parity; with the first 3M call
   int* iter = nullptr;
   uint64_t* seed = nullptr;   // Philox keys [SEED_ROWS + B] (common.h), device-resident so the step graph does not depend on them
   void* qws = nullptr;
   DevBufs mem;
   DeviceTable ddpm_tab;   // 9 x T (kd_schedule_t)
   DeviceTable edm_tab;    // 15 x N (kd_edm_schedule_t), then S_noise
-  DeviceTable solver_tab; // 9 x T (kd_solver_schedule_t)
+  DeviceTable solver_tab; // 9 x T (kd_solver_schedule_t), 10 x T with a coef_prev2 (kd_solver3_schedule_t)
   hipStream_t cap_stream = nullptr;
   StepGraph ddpm_graph, edm_graph[2];   // EDM: one per step kind (0: with the Heun correction, 1: without)
-  StepGraph solver_graph[2];   // few-step solvers: 0 for a schedule that keeps no history (DDIM), 1 for one that does (2M)
+  StepGraph solver_graph[3];   // few-step solvers: 0 for a schedule that keeps no history (DDIM), 1 for one that does (2M), 2: the ring (3M)
   CondTable cond;
   void drop_graphs() {   // the conditioning table moved: every captured iteration holds its address
     ddpm_graph.drop();

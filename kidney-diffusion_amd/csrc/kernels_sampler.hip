@@ -1,6 +1,6 @@
 // Sampler-side kernels: x0 prediction, per-sample 0.95-quantile (radix select), the fused DDPM
 // reverse step (threshold clamp + posterior mean + noise add, noise either from a tensor or
-// from in-kernel Philox4x32-10), the update of the few-step solvers (DDIM, DPM-Solver++(2M)), the RePaint inpaint mix /
+// from in-kernel Philox4x32-10), the update of the few-step solvers (DDIM, DPM-Solver++(2M / 3M) and their SDE forms), the RePaint inpaint mix /
 // re-noise and the final clamp.
 //
 // Every kernel reads the current iteration index from device memory (d_iter) and looks its
@@ -480,23 +480,38 @@ int launch_ddpm_update(float* x, const float* x0, const float* s_thresh, const f
 }
 
 // ------------------------------------------------------------------------- fused few-step solver update
-// DDIM(eta) and DPM-Solver++(2M) in one form:  x = A_k x + B_k x0c + P_k hist + S_k N(0,1), x0c the thresholded estimate
-// of ddpm_update_kernel.  The host puts the solver into the four tables (kd_solver_schedule_t).  A term whose coefficient
-// is 0 is left out, operand unread: no draw for a deterministic step, and no read of `hist` (the estimate the previous
-// step kept) on a first-order step - the first step walked reads nothing an earlier call left.  hist takes this step's
-// x0c in the last resample slot only, so all R resamples of step k read step k-1's; in place, each thread behind its own read.
-__global__ void solver_update_kernel(float* __restrict__ x, const float* __restrict__ x0,
-                                     const float* __restrict__ s_thresh, const float* __restrict__ noise,
-                                     int64_t noise_stride, const uint64_t* __restrict__ d_seed, SolverTables tb,
-                                     const int* __restrict__ d_iter, int R, int dynamic_threshold, int64_t per4,
-                                     float* hist, float* __restrict__ sc_out) {
+// DDIM(eta), DPM-Solver++(2M / 3M) and the SDE forms of 2M and 3M in one form:
+//     x = A_k x + B_k x0c + P_k h1 + Q_k h2 + S_k N(0,1)
+// x0c the thresholded estimate of ddpm_update_kernel, h1 / h2 the x0c that steps k - 1 / k - 2 kept.  The host puts the
+// solver into the tables (kd_solver_schedule_t, kd_solver3_schedule_t).  A term whose coefficient is 0 is left out, operand
+// unread: no draw for a deterministic step, and no read of a history on a step of lower order - the first two steps a call
+// walks read nothing an earlier call left.  A history takes this step's x0c in the last resample slot only, so all R
+// resamples of step k read the estimates of steps k - 1 and k - 2; in place, each thread behind its own read.
+//   RING == false (no Q table): one history `hist`, h1 - today's 2M and DDIM, arguments and arithmetic unchanged.
+//   RING == true: `hist` and `hist2` are the two slots of a ring indexed by the step's parity, read from the iteration
+//   counter - h1 in slot (k - 1) & 1, h2 in slot k & 1, which then takes x0c - so one captured step serves every step.
+template <bool RING>
+__device__ __forceinline__ void solver_update_body(float* __restrict__ x, const float* __restrict__ x0,
+                                                   const float* __restrict__ s_thresh, const float* __restrict__ noise,
+                                                   int64_t noise_stride, const uint64_t* __restrict__ d_seed,
+                                                   const SolverTables& tb, const int* __restrict__ d_iter, int R,
+                                                   int dynamic_threshold, int64_t per4, float* hist, float* hist2,
+                                                   const float* __restrict__ coef_prev2, float* __restrict__ sc_out) {
   const int b = blockIdx.y;
   const NoiseKey key = noise_key(d_seed, b, per4);
   const int it = *d_iter;
   const int k = it / R, ri = it - k * R;
   const float ca = tb.coef_x[k], cb = tb.coef_x0[k], cp = tb.coef_prev[k], cs = tb.coef_noise[k];
-  const bool use_prev = hist != nullptr && cp != 0.0f, use_noise = cs != 0.0f;
-  const bool keep = hist != nullptr && ri == R - 1;
+  const float cq = RING ? coef_prev2[k] : 0.0f;
+  float* h1 = hist;    // the estimate of step k - 1
+  float* h2 = hist2;   // of step k - 2; takes this step's
+  if (RING) {
+    h1 = (k & 1) ? hist : hist2;
+    h2 = (k & 1) ? hist2 : hist;
+  }
+  float* kept = RING ? h2 : h1;
+  const bool use_prev = h1 != nullptr && cp != 0.0f, use_prev2 = RING && cq != 0.0f, use_noise = cs != 0.0f;
+  const bool keep = kept != nullptr && ri == R - 1;
   float s = 1.0f;
   if (dynamic_threshold) s = fmaxf(s_thresh[b], 1.0f);
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < per4; j += (int64_t)gridDim.x * blockDim.x) {
@@ -509,9 +524,14 @@ __global__ void solver_update_kernel(float* __restrict__ x, const float* __restr
       o[e] = ca * xv[e] + cb * xs;
     }
     if (use_prev) {
-      f32x4 hv = *(const f32x4*)(hist + i * 4);
+      f32x4 hv = *(const f32x4*)(h1 + i * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = o[e] + cp * hv[e];
+    }
+    if (use_prev2) {
+      f32x4 hv = *(const f32x4*)(h2 + i * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = o[e] + cq * hv[e];
     }
     if (use_noise) {
       f32x4 z = noise4(noise, noise_stride, key, PURPOSE_STEP, it, i, j);
@@ -519,17 +539,41 @@ __global__ void solver_update_kernel(float* __restrict__ x, const float* __restr
       for (int e = 0; e < 4; ++e) o[e] = o[e] + cs * z[e];
     }
     *(f32x4*)(x + i * 4) = o;
-    if (keep) *(f32x4*)(hist + i * 4) = xsv;
+    if (keep) *(f32x4*)(kept + i * 4) = xsv;
     if (sc_out) *(f32x4*)(sc_out + i * 4) = xsv;   // self-conditioning: the next step's UNet reads this x_start
   }
 }
+__global__ void solver_update_kernel(float* __restrict__ x, const float* __restrict__ x0,
+                                     const float* __restrict__ s_thresh, const float* __restrict__ noise,
+                                     int64_t noise_stride, const uint64_t* __restrict__ d_seed, SolverTables tb,
+                                     const int* __restrict__ d_iter, int R, int dynamic_threshold, int64_t per4,
+                                     float* hist, float* __restrict__ sc_out) {
+  solver_update_body<false>(x, x0, s_thresh, noise, noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per4, hist, nullptr,
+                            nullptr, sc_out);
+}
+__global__ void solver3_update_kernel(float* __restrict__ x, const float* __restrict__ x0,
+                                      const float* __restrict__ s_thresh, const float* __restrict__ noise,
+                                      int64_t noise_stride, const uint64_t* __restrict__ d_seed, SolverTables tb,
+                                      const int* __restrict__ d_iter, int R, int dynamic_threshold, int64_t per4,
+                                      float* hist, float* hist2, const float* __restrict__ coef_prev2,
+                                      float* __restrict__ sc_out) {
+  solver_update_body<true>(x, x0, s_thresh, noise, noise_stride, d_seed, tb, d_iter, R, dynamic_threshold, per4, hist, hist2,
+                           coef_prev2, sc_out);
+}
+// hist2 != nullptr: the ring form (coef_prev2 and hist given too); else today's launch
 int launch_solver_update(float* x, const float* x0, const float* s_thresh, const float* noise, int64_t noise_stride,
                          const uint64_t* d_seed, const SolverTables& tb, const int* d_iter, int R, int dynamic_threshold,
-                         int B, int64_t per, hipStream_t s, float* hist, float* sc_out) {
+                         int B, int64_t per, hipStream_t s, float* hist, float* sc_out, float* hist2, const float* coef_prev2) {
   KD_REQUIRE(per % 4 == 0, "per-sample element count must be a multiple of 4");
   KD_REQUIRE(B >= 1 && B <= 65535, "batch out of range for the per-image grid");
-  hipLaunchKernelGGL(solver_update_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, x0, s_thresh, noise, noise_stride,
-                     d_seed, tb, d_iter, R, dynamic_threshold, per / 4, hist, sc_out);
+  if (hist2) {
+    KD_REQUIRE(hist != nullptr && coef_prev2 != nullptr && hist != hist2, "solver update: the ring needs two histories and coef_prev2");
+    hipLaunchKernelGGL(solver3_update_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, x0, s_thresh, noise, noise_stride,
+                       d_seed, tb, d_iter, R, dynamic_threshold, per / 4, hist, hist2, coef_prev2, sc_out);
+  } else {
+    hipLaunchKernelGGL(solver_update_kernel, grid_rows(per / 4, B), dim3(256), 0, s, x, x0, s_thresh, noise, noise_stride,
+                       d_seed, tb, d_iter, R, dynamic_threshold, per / 4, hist, sc_out);
+  }
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

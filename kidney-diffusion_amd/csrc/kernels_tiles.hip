@@ -81,7 +81,7 @@ int launch_tiles_gather(const float* canvas, float* tiles, int B, int C, int Hc,
 // Per canvas pixel, over the present tiles t that cover it, in ascending (row, column) order of their slots:
 //   x0c_t = clamp(x0_t, -s_t, s_t) / s_t, s_t = max(thr_t, 1)          (thr == nullptr: s_t = 1)
 //   x0bar = (sum w_t x0c_t) / (sum w_t)
-//   x <- A x + B x0bar [+ P hist] [+ Sn z] ; x0bar_out <- x0bar
+//   x <- A x + B x0bar [+ P hist] [+ P2 hist2] [+ Sn z] ; x0bar_out <- x0bar
 // A term whose coefficient is 0 is left out, operand unread.  A pixel that no present tile covers is left alone in both
 // buffers.  z: read from `noise`, or element (c Hc + y) Wc + x of Philox stream `sid` under `seed` - the bits
 // kd_philox_normal writes over C Hc Wc elements, whatever the tiling.
@@ -162,9 +162,10 @@ __device__ __forceinline__ bool fuse_tiles(const float* __restrict__ x0_tiles, c
   for (int e = 0; e < 4; ++e) xb[e] = acc[e] / wsum[e];
   return true;
 }
-// The update of the float4 j4: A x + B x0bar [+ P hist] [+ Sn z].
-__device__ __forceinline__ f32x4 canvas_update(const f32x4& xv, const f32x4& xb, const float* hist, int64_t j4, float A, float B,
-                                               float P, float Sn, const float* __restrict__ noise, uint64_t seed, uint64_t sid) {
+// The update of the float4 j4: A x + B x0bar [+ P hist] [+ P2 hist2] [+ Sn z], left to right.
+__device__ __forceinline__ f32x4 canvas_update(const f32x4& xv, const f32x4& xb, const float* hist, const float* hist2, int64_t j4,
+                                               float A, float B, float P, float P2, float Sn, const float* __restrict__ noise,
+                                               uint64_t seed, uint64_t sid) {
   f32x4 o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = A * xv[e] + B * xb[e];
@@ -172,6 +173,11 @@ __device__ __forceinline__ f32x4 canvas_update(const f32x4& xv, const f32x4& xb,
     const f32x4 hv = *(const f32x4*)(hist + j4 * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = o[e] + P * hv[e];
+  }
+  if (P2 != 0.0f) {
+    const f32x4 hv = *(const f32x4*)(hist2 + j4 * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = o[e] + P2 * hv[e];
   }
   if (Sn != 0.0f) {
     const f32x4 z = noise ? *(const f32x4*)(noise + j4 * 4) : philox_normal4(seed, sid, (uint64_t)j4);
@@ -467,14 +473,15 @@ int launch_tiles_start(float* x, int C, int Hc, int Wc, float scale, const float
 // ------------------------------------------------------------------------- the canvas step: the kernel
 // The canvas step and, with KNOWN, on the same pixel in the same pass [the re-noise x = x rn_a + z rn_b] then [the mix of
 // the NEXT slot]: bit for bit the three passes one after the other.  Without KNOWN the re-noise, the mask load and the mix
-// are compiled out.  hist (read when P != 0) and x0bar_out may be one buffer - a thread reads and writes its own element -
-// so neither is restrict.  A float4 whose mask bytes are all set is known after the mix whatever the update gives: x is
+// are compiled out.  hist (read when P != 0) or hist2 (read when P2 != 0; without HIST2 the term is compiled out) and
+// x0bar_out may be one buffer - a thread reads and writes its own element - so none of them is restrict.  A float4 whose mask bytes are all set is known after the mix whatever the update gives: x is
 // not read, nothing is drawn for the update; x0bar is written all the same.
-template <bool KNOWN>
-__global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, const float* hist, float* x0bar_out,
+template <bool KNOWN, bool HIST2>
+__global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restrict__ x, const float* hist, const float* hist2,
+                                                                float* x0bar_out,
                                                                 const float* __restrict__ x0_tiles,
                                                                 const float* __restrict__ thr, const int* __restrict__ tile_of,
-                                                                TileGeom g, float A, float B, float P, float Sn,
+                                                                TileGeom g, float A, float B, float P, float P2, float Sn,
                                                                 const float* __restrict__ noise, uint64_t seed, uint64_t sid,
                                                                 int renoise, float rn_a, float rn_b,
                                                                 const float* __restrict__ rn_noise, uint64_t rn_sid, MixArgs mix) {
@@ -491,7 +498,7 @@ __global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restric
     const uint32_t mw = KNOWN && mix.on ? src_mask4(mix.mk, y, xx) : 0u;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (!mask_all(mw)) {
-      o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, hist, j4, A, B, P, Sn, noise, seed, sid);
+      o = canvas_update(*(const f32x4*)(x + j4 * 4), xb, hist, hist2, j4, A, B, P, HIST2 ? P2 : 0.0f, Sn, noise, seed, sid);
       if (KNOWN && renoise) {
         const f32x4 z = rn_noise ? *(const f32x4*)(rn_noise + j4 * 4) : philox_normal4(seed, rn_sid, (uint64_t)j4);
 #pragma unroll
@@ -506,20 +513,24 @@ __global__ __launch_bounds__(256) void tiles_fuse_update_kernel(float* __restric
 int launch_tiles_fuse_update(float* x, const float* hist, float* x0bar_out, const float* x0_tiles, const float* thr,
                              const int* tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B, float P,
                              float Sn, const float* noise, uint64_t seed, uint64_t stream_id, int renoise, float rn_a, float rn_b,
-                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s) {
-  KD_REQUIRE(x && x0bar_out && x0_tiles && tile_of && (hist || P == 0.0f), "tiles fuse: null argument");
+                             const float* rn_noise, uint64_t rn_sid, const TileMix& mix, hipStream_t s, const float* hist2,
+                             float P2) {
+  KD_REQUIRE(x && x0bar_out && x0_tiles && tile_of && (hist || P == 0.0f) && (hist2 || P2 == 0.0f), "tiles fuse: null argument");
   TileGeom g;
   if (tile_lattice("tiles fuse", N, C, S, st, ny, nx, ramp, &g)) return 1;
-  KD_REQUIRE((((uintptr_t)x | (uintptr_t)hist | (uintptr_t)x0bar_out | (uintptr_t)x0_tiles | (uintptr_t)noise |
+  KD_REQUIRE((((uintptr_t)x | (uintptr_t)hist | (uintptr_t)hist2 | (uintptr_t)x0bar_out | (uintptr_t)x0_tiles | (uintptr_t)noise |
                (uintptr_t)rn_noise) & 15) == 0,
              "tiles fuse: x, hist, x0bar_out, x0_tiles and the noise tensors must be 16-byte aligned");
-  KD_REQUIRE(x != hist && x != x0bar_out, "tiles fuse: x must not be the history or the estimate");
+  KD_REQUIRE(x != hist && x != hist2 && x != x0bar_out, "tiles fuse: x must not be the history or the estimate");
   MixArgs m;
   if (tile_mix("tiles fuse", mix, g.Hc, g.Wc, &m)) return 1;
   // nothing known and no re-noise: the lean instantiation, whichever entry the call came through
-  const auto kernel = renoise || m.on ? tiles_fuse_update_kernel<true> : tiles_fuse_update_kernel<false>;
-  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, hist, x0bar_out, x0_tiles, thr, tile_of, g, A, B, P, Sn,
-                     noise, seed, stream_id, renoise != 0, rn_a, rn_b, rn_noise, rn_sid, m);
+  // (a second history that is read - P2 != 0 - has its own pair, so the others carry no test for it)
+  const bool known = renoise || m.on;
+  const auto kernel = P2 != 0.0f ? (known ? tiles_fuse_update_kernel<true, true> : tiles_fuse_update_kernel<false, true>)
+                                 : (known ? tiles_fuse_update_kernel<true, false> : tiles_fuse_update_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, canvas_grid(C, g.Hc, g.Wc), dim3(256), 0, s, x, hist, hist2, x0bar_out, x0_tiles, thr, tile_of, g, A, B,
+                     P, P2, Sn, noise, seed, stream_id, renoise != 0, rn_a, rn_b, rn_noise, rn_sid, m);
   KD_HIP_CHECK(hipGetLastError());
   return 0;
 }

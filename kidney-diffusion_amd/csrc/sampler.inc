@@ -241,9 +241,11 @@ static int guided_forward(kd_unet* u, const SamplerCtx& ctx, const kd_sample_arg
   return launch_cfg_combine(m.pred, m.pred_null, m.pred, a->cond_scale, (int64_t)(image_bytes(u) / sizeof(float)), s);
 }
 
-// sv: the update of a few-step solver (its tables; hist = the kept estimate or nullptr) in place of the ancestral one
+// sv: the update of a few-step solver (its tables; hist = the kept estimate or nullptr; hist2 and coef_prev2 = the ring's
+// second slot and the third-order coefficients, or nullptr) in place of the ancestral one
 static int emit_iteration(kd_unet* u, const SamplerCtx& ctx, const kd_sample_args_t* a, float* d_img, hipStream_t s,
-                          const SolverTables* sv = nullptr, float* hist = nullptr) {
+                          const SolverTables* sv = nullptr, float* hist = nullptr, float* hist2 = nullptr,
+                          const float* coef_prev2 = nullptr) {
   Sampler& m = u->smp;
   const int B = u->cfg.batch, S = u->cfg.image_size, R = ctx.R, Ci = u->cfg.channels;
   const int64_t hw = (int64_t)S * S, per = Ci * hw;
@@ -259,7 +261,7 @@ static int emit_iteration(kd_unet* u, const SamplerCtx& ctx, const kd_sample_arg
     if (launch_quantile_abs(m.x0, m.thresh, B, per, a->percentile, m.qws, s)) return 1;
   if (sv) {
     if (launch_solver_update(d_img, m.x0, m.thresh, a->d_noise_step, B * per, m.seed, *sv, m.iter, R, a->dynamic_threshold, B,
-                             per, s, hist, m.self_cond))
+                             per, s, hist, m.self_cond, hist2, coef_prev2))
       return 1;
   } else if (launch_ddpm_update(d_img, m.x0, m.thresh, a->d_noise_step, B * per, m.seed, ctx.tb, m.iter, R,
                                 a->dynamic_threshold, B, per, s, m.self_cond)) {
@@ -330,23 +332,27 @@ static int sample_steps(kd_unet* u, const kd_schedule_t* sc, const kd_sample_arg
   return 0;
 }
 
-// ------------------------------------------------------------------------------ few-step solvers (DDIM, DPM-Solver++(2M))
-// kd_solver_schedule_t -> its tables on the device [9][T]: log_snr, alpha, sigma, rn_a, rn_b, then the four coefficients.
+// ------------------------------------------------------------------------------ few-step solvers (DDIM, DPM-Solver++ 2M / 3M)
+// kd_solver_schedule_t -> its tables on the device [9][T]: log_snr, alpha, sigma, rn_a, rn_b, then the four coefficients;
+// with a coef_prev2 that is not all zero (kd_solver3_schedule_t) a tenth row holds it and *d_prev2 points at it.
 // *keeps: some step reads the previous step's estimate (coef_prev != 0), so the plan carries one.
 static const int SOLVER_NTAB = 9;
-static int solver_prepare(kd_unet* u, const kd_solver_schedule_t* sc, SamplerCtx& ctx, SolverTables& sv, bool* keeps,
-                          hipStream_t s) {
+static int solver_prepare(kd_unet* u, const kd_solver_schedule_t* sc, const float* coef_prev2, SamplerCtx& ctx, SolverTables& sv,
+                          bool* keeps, const float** d_prev2, hipStream_t s) {
   const int T = sc->T;
   KD_REQUIRE(T >= 1, "schedule must have at least one step");
   const float* src[SOLVER_NTAB] = {sc->log_snr, sc->alpha,   sc->sigma,     sc->rn_a,      sc->rn_b,
                                    sc->coef_x,  sc->coef_x0, sc->coef_prev, sc->coef_noise};
-  std::vector<float> host((size_t)SOLVER_NTAB * T, 0.0f);
+  bool ring = false;   // an absent or all-zero coef_prev2 is the nine-row schedule, bit for bit
+  for (int k = 0; coef_prev2 && k < T; ++k) ring = ring || coef_prev2[k] != 0.0f;
+  std::vector<float> host((size_t)(SOLVER_NTAB + (ring ? 1 : 0)) * T, 0.0f);
   for (int i = 0; i < SOLVER_NTAB; ++i) {
     if (i < 3) KD_REQUIRE(src[i] != nullptr, "solver schedule arrays log_snr, alpha and sigma are required");
     if (i >= 5) KD_REQUIRE(src[i] != nullptr, "solver schedule arrays coef_x, coef_x0, coef_prev and coef_noise are required");
     if (src[i]) memcpy(host.data() + (size_t)i * T, src[i], (size_t)T * sizeof(float));
   }
-  *keeps = false;
+  if (ring) memcpy(host.data() + (size_t)SOLVER_NTAB * T, coef_prev2, (size_t)T * sizeof(float));
+  *keeps = ring;
   for (int k = 0; k < T; ++k) *keeps = *keeps || sc->coef_prev[k] != 0.0f;
   if (u->smp.solver_tab.upload(std::move(host), s)) return 1;
   const float* t = u->smp.solver_tab.dev;
@@ -357,38 +363,50 @@ static int solver_prepare(kd_unet* u, const kd_solver_schedule_t* sc, SamplerCtx
   ctx.tb.rn_a = t + 3 * T;
   ctx.tb.rn_b = t + 4 * T;
   sv = SolverTables{t + 5 * T, t + 6 * T, t + 7 * T, t + 8 * T};
+  *d_prev2 = ring ? t + (size_t)SOLVER_NTAB * T : nullptr;
   ctx.T = T;
   return 0;
 }
 
 // As sample_steps, the update being the solver's.  Tables and captured iterations are the solver path's own (solver_tab,
 // solver_graph): a plan that alternates between samplers replays each one's graph.  The conditioning rows are a function
-// of the time inputs alone, so they are keyed on log_snr: DDIM and 2M at any eta share the rows of one N-step schedule.
-static int solver_sample_steps(kd_unet* u, const kd_solver_schedule_t* sc, const kd_sample_args_t* a, float* d_img,
-                               int k_begin, int k_end, hipStream_t s) {
+// of the time inputs alone, so they are keyed on log_snr: every solver at any eta shares the rows of one N-step schedule.
+// coef_prev2 (kd_solver3_*; nullptr from kd_solver_*): the third-order term over the ring of two histories.
+static int solver_sample_steps(kd_unet* u, const kd_solver_schedule_t* sc, const float* coef_prev2, const kd_sample_args_t* a,
+                               float* d_img, int k_begin, int k_end, hipStream_t s) {
   KD_REQUIRE(d_img, "null argument");
   SamplerCtx ctx;
   if (begin_call(u, sc, a, d_img, false, ctx, s)) return 1;
   KD_REQUIRE(a->objective >= 0 && a->objective <= 2, "unknown prediction objective");
   SolverTables sv{};
   bool keeps = false;
-  if (solver_prepare(u, sc, ctx, sv, &keeps, s)) return 1;
+  const float* d_prev2 = nullptr;
+  if (solver_prepare(u, sc, coef_prev2, ctx, sv, &keeps, &d_prev2, s)) return 1;
   KD_REQUIRE(0 <= k_begin && k_begin <= k_end && k_end <= ctx.T, "step range out of bounds");
   if (ctx.R > 1) KD_REQUIRE(sc->rn_a && sc->rn_b, "re-noise tables are required when resampling");
+  // the first two steps of a schedule are of order 1 and at most 2: they read nothing of what the ring holds
+  if (d_prev2 && k_begin == 0)
+    KD_REQUIRE(sc->coef_prev[0] == 0.0f && coef_prev2[0] == 0.0f && (ctx.T < 2 || coef_prev2[1] == 0.0f),
+               "solver schedule: step 0 must be first order and step 1 at most second order (coef_prev[0], coef_prev2[0..1] == 0)");
   Sampler& m = u->smp;
   if (keeps && !m.hist) {   // zeros until a step keeps its estimate: a call that starts at a second-order step reads them
     if (m.mem.get(&m.hist, image_bytes(u))) return 1;
     KD_HIP_CHECK(hipMemsetAsync(m.hist, 0, image_bytes(u), s));
   }
+  if (d_prev2 && !m.hist2) {   // the ring's second slot, with the first third-order call
+    if (m.mem.get(&m.hist2, image_bytes(u))) return 1;
+    KD_HIP_CHECK(hipMemsetAsync(m.hist2, 0, image_bytes(u), s));
+  }
   float* hist = keeps ? m.hist : nullptr;
+  float* hist2 = d_prev2 ? m.hist2 : nullptr;
   if (k_begin == 0 && !a->keep_self_cond && self_cond_reset(u, s)) return 1;   // k_begin > 0 continues from what the plan holds
   const std::vector<float> cond_key(m.solver_tab.host.begin(), m.solver_tab.host.begin() + ctx.T);
   if (sampler_cond_table(u, cond_key, a, ctx, k_begin, k_end, s)) return 1;
   if (launch_iter_set(m.iter, k_begin * ctx.R, s)) return 1;
   const int n_iter = (k_end - k_begin) * ctx.R;
-  auto emit = [&](hipStream_t st) { return emit_iteration(u, ctx, a, d_img, st, &sv, hist); };
+  auto emit = [&](hipStream_t st) { return emit_iteration(u, ctx, a, d_img, st, &sv, hist, hist2, d_prev2); };
   if (a->use_graph)
-    return replay_or_capture(m, m.solver_graph[keeps ? 1 : 0],
+    return replay_or_capture(m, m.solver_graph[d_prev2 ? 2 : keeps ? 1 : 0],
                              graph_key_of(a, d_img, m.solver_tab.dev, ctx.T, ctx.R, ctx.cond_tab), emit, s, n_iter);
   for (int i = 0; i < n_iter; ++i)
     if (emit(s)) return 1;

@@ -117,6 +117,10 @@ class kd_solver_schedule_t(C.Structure):
     ]
 
 
+class kd_solver3_schedule_t(C.Structure):   # kd_solver_schedule_t's fields, then coef_prev2
+    _fields_ = kd_solver_schedule_t._fields_ + [("coef_prev2", C.POINTER(C.c_float))]
+
+
 class kd_unet_ext_t(C.Structure):
     _fields_ = [("self_cond", C.c_int), ("use_linear_attn", C.c_int * KD_MAX_LEVELS),
                 ("use_linear_cross_attn", C.c_int * KD_MAX_LEVELS),
@@ -226,6 +230,10 @@ SIGNATURES = {
                                         C.c_void_p]),
     "kd_solver_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_solver_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
                                          C.c_int, C.c_int, C.c_void_p]),
+    "kd_solver3_sample_loop": (C.c_int, [C.c_void_p, C.POINTER(kd_solver3_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                         C.c_void_p]),
+    "kd_solver3_sample_steps": (C.c_int, [C.c_void_p, C.POINTER(kd_solver3_schedule_t), C.POINTER(kd_sample_args_t), C.c_void_p,
+                                          C.c_int, C.c_int, C.c_void_p]),
     "kd_conv2d_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 10 + [C.c_void_p]),
     "kd_upsample_nearest_conv3x3_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     "kd_upsample_nearest_gn_conv3x3_nhwc": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 8 + [C.c_void_p]),
@@ -311,6 +319,10 @@ SIGNATURES = {
                                                                                                 C.POINTER(kd_tiles_mask_t), C.c_float,
                                                                                                 C.c_float, C.c_void_p, C.c_uint64,
                                                                                                 C.c_void_p]),
+    "kd_tiles_fuse_update_hist2": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_float] * 4 +
+                                   [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_uint64,
+                                    C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_float, C.c_float, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.c_float, C.c_void_p]),
     "kd_tiles_finalize_known": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] + [C.c_int] * 4 +
                                 [C.POINTER(kd_tiles_image_t), C.POINTER(kd_tiles_mask_t), C.c_void_p]),
     "kd_tiles_rows_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -968,13 +968,17 @@ class GaussianDiffusionContinuousTimes(nn.Module):
         return {n: v.to(torch.float32).contiguous() for n, v in zip(names, vals)}
 
 
-SAMPLERS = ("ddpm", "ddim", "dpmpp_2m")
+SAMPLERS = ("ddpm", "ddim", "dpmpp_2m", "dpmpp_3m", "dpmpp_2m_sde", "dpmpp_3m_sde")
+# the multistep solvers of the exponential-integrator form: name -> (order cap, stochastic)
+_MULTISTEP = {"dpmpp_3m": (3, False), "dpmpp_2m_sde": (2, True), "dpmpp_3m_sde": (3, True)}
+SOLVER_COEFS = ("coef_x", "coef_x0", "coef_prev", "coef_noise")
 
 
 def solver_tables(step_tables, sampler, eta=0.0, skip=0):
-    """Coefficients of the few-step solvers' update  x <- coef_x x + coef_x0 x0c + coef_prev hist + coef_noise z  for every
-    step of a schedule (the arrays of kd_solver_schedule_t; DESIGN.md "Few-step solvers").  ``step_tables`` are the fp32
-    entries of ``GaussianDiffusionContinuousTimes.step_tables()``; they are evaluated in float64 and rounded to fp32 once.
+    """Coefficients of the few-step solvers' update  x <- coef_x x + coef_x0 x0c + coef_prev h1 + coef_prev2 h2 + coef_noise z
+    for every step of a schedule (the arrays of kd_solver_schedule_t / kd_solver3_schedule_t; DESIGN.md "Few-step
+    solvers"); h1, h2 the thresholded estimates of steps k - 1 and k - 2.  ``step_tables`` are the fp32 entries of
+    ``GaussianDiffusionContinuousTimes.step_tables()``; they are evaluated in float64 and rounded to fp32 once.
     With a, s = alpha, sigma at t_k, a', s' those at t_{k+1} and c the table's c:
 
     ``"ddim"``, 0 <= eta <= 1: d = eta sqrt(s'^2 c) (the ancestral step's posterior deviation, from the table's c),
@@ -985,18 +989,32 @@ def solver_tables(step_tables, sampler, eta=0.0, skip=0):
     b_k = -a' expm1(-h_k), A = s' / s, S = 0; first-order steps - the first step walked (k == ``skip``) and the last -
     have B = b, P = 0; every other step w = h_k / (2 h_{k-1}), B = b (1 + w), P = -b w.
 
+    ``"dpmpp_3m"`` (eta = 0), ``"dpmpp_2m_sde"``, ``"dpmpp_3m_sde"`` (0 < eta <= 1): the multistep exponential integrator
+    of order up to 3 / 2 / 3 over the same lambda and h_k.  he = h_k (1 + eta), A = (s' / s) exp(-eta h_k),
+    b = -a' expm1(-he), phi2 = expm1(-he) / he + 1, phi3 = phi2 / he - 1/2, S = s' sqrt(-expm1(-2 eta h_k)) (0 on the last
+    step, whose A and B are still formed with eta).  Step k has order o = min(cap, k - skip + 1, N - k):
+    o = 1: B = b, P = Q = 0;  o = 2: r = h_{k-1} / h_k, c = a' phi2 / r, B = b + c, P = -c, Q = 0;
+    o = 3: r0 = h_{k-1} / h_k, r1 = h_{k-2} / h_k, g = r0 / (r0 + r1), c1 = a' phi2, c2 = -a' phi3,
+    u0 = c1 (1 + g) + c2 / (r0 + r1), u1 = -c1 g - c2 / (r0 + r1), B = b + u0 / r0, P = -u0 / r0 + u1 / r1, Q = -u1 / r1.
+    B + P + Q = b at every order.  These three names return a fifth array, ``coef_prev2`` (Q); ``"ddim"`` and
+    ``"dpmpp_2m"`` keep their four.
+
     Pure host arithmetic; needs no GPU."""
-    if sampler not in ("ddim", "dpmpp_2m"):
-        raise ValueError(f"solver_tables: sampler must be 'ddim' or 'dpmpp_2m', got {sampler!r}")
+    if sampler not in ("ddim", "dpmpp_2m") and sampler not in _MULTISTEP:
+        raise ValueError(f"solver_tables: sampler must be 'ddim', 'dpmpp_2m' or one of {tuple(_MULTISTEP)}, got {sampler!r}")
     if not 0.0 <= float(eta) <= 1.0:
         raise ValueError(f"solver_tables: eta={eta} is outside [0, 1]")
-    if eta != 0 and sampler != "ddim":
+    stochastic = sampler == "ddim" or _MULTISTEP.get(sampler, (0, False))[1]
+    if eta != 0 and not stochastic:
         raise ValueError(f"solver_tables: eta={eta} needs sampler 'ddim', got {sampler!r}")
+    if eta == 0 and sampler in _MULTISTEP and stochastic:
+        raise ValueError(f"solver_tables: {sampler!r} needs eta > 0; eta = 0 is {sampler[:-4]!r}")
     t = {n: step_tables[n].to(torch.float64) for n in ("log_snr", "alpha", "sigma", "alpha_next", "sigma_next", "c")}
     a, s, an, sn = t["alpha"], t["sigma"], t["alpha_next"], t["sigma_next"]
     N = a.numel()
     if not 0 <= int(skip) < N:
         raise ValueError(f"solver_tables: skip={skip} is outside 0 .. {N - 1}")
+    skip = int(skip)
     P = torch.zeros(N, dtype=torch.float64)
     S = torch.zeros(N, dtype=torch.float64)
     if sampler == "ddim":
@@ -1005,27 +1023,53 @@ def solver_tables(step_tables, sampler, eta=0.0, skip=0):
         B = an - A * a
         S = d.clone()
         S[N - 1] = 0.0
-    else:
-        lam = t["log_snr"] / 2
-        # log-SNR at t_{k+1}: the next row's entry; behind the last row the tables hold alpha and sigma alone
-        lam_next = torch.cat([lam[1:], torch.log(an[-1:] / sn[-1:])])
-        h = lam_next - lam
+        return {n: v.to(torch.float32).contiguous() for n, v in zip(SOLVER_COEFS, (A, B, P, S))}
+    lam = t["log_snr"] / 2
+    # log-SNR at t_{k+1}: the next row's entry; behind the last row the tables hold alpha and sigma alone
+    lam_next = torch.cat([lam[1:], torch.log(an[-1:] / sn[-1:])])
+    h = lam_next - lam
+    if sampler == "dpmpp_2m":
         b = -an * torch.expm1(-h)
         A = sn / s
         B = b.clone()
-        for k in range(int(skip) + 1, N - 1):
+        for k in range(skip + 1, N - 1):
             w = h[k] / (2 * h[k - 1])
             B[k] = b[k] * (1 + w)
             P[k] = -b[k] * w
-    names = ("coef_x", "coef_x0", "coef_prev", "coef_noise")
-    return {n: v.to(torch.float32).contiguous() for n, v in zip(names, (A, B, P, S))}
+        return {n: v.to(torch.float32).contiguous() for n, v in zip(SOLVER_COEFS, (A, B, P, S))}
+    cap, eta = _MULTISTEP[sampler][0], float(eta)
+    he = h * (1 + eta)
+    A = (sn / s) * torch.exp(-eta * h)
+    b = -an * torch.expm1(-he)
+    phi2 = torch.expm1(-he) / he + 1
+    phi3 = phi2 / he - 0.5
+    if eta != 0:
+        S = sn * torch.sqrt(-torch.expm1(-2 * eta * h))
+        S[N - 1] = 0.0
+    B, Q = b.clone(), torch.zeros(N, dtype=torch.float64)
+    for k in range(skip, N):
+        o = min(cap, k - skip + 1, N - k)
+        if o == 2:
+            c = an[k] * phi2[k] / (h[k - 1] / h[k])
+            B[k], P[k] = b[k] + c, -c
+        elif o == 3:
+            r0, r1 = h[k - 1] / h[k], h[k - 2] / h[k]
+            g = r0 / (r0 + r1)
+            c1, c2 = an[k] * phi2[k], -an[k] * phi3[k]
+            u0 = c1 * (1 + g) + c2 / (r0 + r1)
+            u1 = -c1 * g - c2 / (r0 + r1)
+            B[k], P[k], Q[k] = b[k] + u0 / r0, -u0 / r0 + u1 / r1, -u1 / r1
+    names = SOLVER_COEFS[:3] + ("coef_prev2", "coef_noise")
+    return {n: v.to(torch.float32).contiguous() for n, v in zip(names, (A, B, P, Q, S))}
 
 
 def normalize_sampler(sampler, sampler_eta, sample_steps, num_unets):
     """``sample(sampler=..., sampler_eta=..., sample_steps=...)`` cast per UNet: each is a scalar or a tuple / list with
-    one entry per UNet.  ``sampler``: None or ``"ddpm"`` (the ancestral sampler), ``"ddim"``, ``"dpmpp_2m"``;
-    ``sampler_eta`` in [0, 1], non-zero only with ``"ddim"``; ``sample_steps`` None (the constructor's timesteps) or an
-    int >= 1.  Returns a list of ``(name, eta, steps or None)``.  Anything else raises ValueError.  Needs no GPU."""
+    one entry per UNet.  ``sampler``: None or ``"ddpm"`` (the ancestral sampler), ``"ddim"``, ``"dpmpp_2m"``,
+    ``"dpmpp_3m"``, ``"dpmpp_2m_sde"``, ``"dpmpp_3m_sde"``; ``sampler_eta`` None or in [0, 1]: None is 0 for the
+    deterministic names and ``"ddim"`` and 1 for the ``_sde`` names, a non-zero value needs ``"ddim"`` or an ``_sde``
+    name, and an ``_sde`` name refuses 0; ``sample_steps`` None (the constructor's timesteps) or an int >= 1.  Returns a
+    list of ``(name, eta, steps or None)``.  Anything else raises ValueError.  Needs no GPU."""
     import numbers
 
     def per_unet(v, name):
@@ -1042,11 +1086,14 @@ def normalize_sampler(sampler, sampler_eta, sample_steps, num_unets):
         name = default(name, "ddpm")
         if name not in SAMPLERS:
             raise ValueError(f"sampler of unet {num} must be one of {SAMPLERS} or None, got {name!r}")
-        eta = default(eta, 0.0)
+        sde = name.endswith("_sde")
+        eta = default(eta, 1.0 if sde else 0.0)
         if not isinstance(eta, numbers.Real) or isinstance(eta, bool) or not 0.0 <= float(eta) <= 1.0:
             raise ValueError(f"sampler_eta of unet {num} must be a number in [0, 1], got {eta!r}")
-        if float(eta) != 0.0 and name != "ddim":
+        if float(eta) != 0.0 and name != "ddim" and not sde:
             raise ValueError(f"sampler_eta={eta} of unet {num} needs sampler='ddim', got {name!r}")
+        if float(eta) == 0.0 and sde:
+            raise ValueError(f"sampler_eta=0 of unet {num} makes {name!r} deterministic: use sampler={name[:-4]!r}")
         if exists(steps):
             if not isinstance(steps, numbers.Integral) or isinstance(steps, bool) or int(steps) < 1:
                 raise ValueError(f"sample_steps of unet {num} must be an int >= 1 or None, got {steps!r}")
@@ -1248,8 +1295,9 @@ def tile_weight(S, st, weights="uniform"):
 
 def canvas_tables(step_tables, sampler, eta=0.0, skip=0):
     """Coefficients of the canvas step  x <- A x + B x0bar + P hist + S z  of fused-tile sampling, as solver_tables gives
-    them (``coef_x, coef_x0, coef_prev, coef_noise``).  ``"ddim"`` and ``"dpmpp_2m"`` are solver_tables' as they are
-    (``skip``: the first step walked, first order for 2M); ``"ddpm"`` is the ancestral step in the same linear form,
+    them (``coef_x, coef_x0, coef_prev, coef_noise``; with ``coef_prev2``, the coefficient of the second history, for the
+    names that have one).  Every solver's are solver_tables' as they are (``skip``: the first step walked, first order for
+    the multistep solvers); ``"ddpm"`` is the ancestral step in the same linear form,
     ``A = alpha_next (1 - c) / alpha``, ``B = alpha_next c``, ``P = 0``, ``S = noise_scale``, formed in float64 from the fp32
     step tables and rounded once."""
     if sampler != "ddpm":
@@ -1486,7 +1534,8 @@ def _f32(t, device):
 class _StepSchedule:
     """The host tables of one stage's sampler together with the ctypes struct the engine reads them through:
     ``kd_schedule_t`` for ``"ddpm"`` (the arrays of ``step_tables()``), ``kd_solver_schedule_t`` for ``"ddim"`` /
-    ``"dpmpp_2m"`` (five of them plus ``solver_tables``), ``kd_edm_schedule_t`` through ``_StepSchedule.edm``.  ``steps`` and
+    ``"dpmpp_2m"`` (five of them plus ``solver_tables``), ``kd_solver3_schedule_t`` for the solvers whose tables hold a
+    ``coef_prev2`` (``"dpmpp_3m"`` and the ``_sde`` names), ``kd_edm_schedule_t`` through ``_StepSchedule.edm``.  ``steps`` and
     ``loop`` name the library entries that take the struct, ``T`` is the number of steps.
 
     Pointer lifetime: the struct's pointers point into the memory of the tensors in ``self.tables`` and nothing else keeps
@@ -1498,8 +1547,14 @@ class _StepSchedule:
         if sampler == "ddpm":
             self._own(E.kd_schedule_t(), step_tables, "kd_sample")
         else:   # the solver's coefficients in place of the ancestral step's; its own entries, tables and step graph
-            self._own(E.kd_solver_schedule_t(), {**step_tables, **solver_tables(step_tables, sampler, eta=eta, skip=skip)},
-                      "kd_solver_sample")
+            coefs = solver_tables(step_tables, sampler, eta=eta, skip=skip)
+            if "coef_prev2" in coefs:
+                # the first two steps walked read nothing the plan's history ring holds (the engine checks step 0 itself)
+                assert not coefs["coef_prev"][skip] and not coefs["coef_prev2"][skip:skip + 2].any(), "solver order at the start"
+                self._own(E.kd_solver3_schedule_t(), {**step_tables, **coefs}, "kd_solver3_sample")
+            else:
+                self._own(E.kd_solver_schedule_t(), {**step_tables, **coefs}, "kd_solver_sample")
+            self.draws = bool(coefs["coef_noise"].any())   # some step adds noise: the ancestral step's draw
         self.struct.T = self.T = int(step_tables["alpha"].numel())
 
     @classmethod
@@ -1682,7 +1737,7 @@ class Imagen(nn.Module):
                stop_at_unet_number=None, return_all_unet_outputs=False, return_pil_images=False, device=None,
                use_tqdm=True, use_one_unet_in_gpu=True, *, noise_fn: Optional[Callable] = None,
                seed: Optional[int] = None, use_graph: bool = True, trace: Optional[list] = None,
-               sampler=None, sampler_eta=0.0, sample_steps=None):
+               sampler=None, sampler_eta=None, sample_steps=None):
         """Signature of the library's ``Imagen.sample``.  Extensions (keyword-only):
         ``noise_fn(tag, shape)`` injects every Gaussian draw (parity tests, see oracle/sampler_ref.py
         for the tags); ``seed`` keys the on-device Philox stream when no ``noise_fn`` is given
@@ -1696,10 +1751,12 @@ class Imagen(nn.Module):
         ``noise_fn`` tags, and ``trace`` receives one state per step walked.
         ``sampler`` / ``sampler_eta`` / ``sample_steps`` (a scalar or one entry per UNet, ``normalize_sampler``): few-step
         sampling of the same DDPM-trained weights.  ``sampler`` None or ``"ddpm"`` is the ancestral sampler, ``"ddim"`` is
-        DDIM(``sampler_eta``) and ``"dpmpp_2m"`` DPM-Solver++(2M) with data prediction (``solver_tables``);
+        DDIM(``sampler_eta``), ``"dpmpp_2m"`` / ``"dpmpp_3m"`` DPM-Solver++(2M / 3M) with data prediction and
+        ``"dpmpp_2m_sde"`` / ``"dpmpp_3m_sde"`` their stochastic forms at ``sampler_eta`` (None: 1) (``solver_tables``);
         ``sample_steps=N`` walks the N-step schedule of the UNet's kind instead of the constructor's ``timesteps``, with any
-        sampler, and is what ``skip_steps`` then counts in.  DDIM(eta > 0) draws the ancestral step's noise (``noise_fn`` tag
-        ``("step", stage, k, r)``, Philox purpose 1); DDIM(0) and 2M draw none."""
+        sampler, and is what ``skip_steps`` then counts in.  DDIM(eta > 0) and the ``_sde`` solvers draw the ancestral step's
+        noise (``noise_fn`` tag ``("step", stage, k, r)``, Philox purpose 1) in the steps that add some - the last adds
+        none; DDIM(0), 2M and 3M draw none."""
         for name, v in dict(texts=texts, video_frames=video_frames, cond_video_frames=cond_video_frames,
                             post_cond_video_frames=post_cond_video_frames, inpaint_videos=inpaint_videos).items():
             if exists(v):
@@ -1861,7 +1918,7 @@ class Imagen(nn.Module):
     # ------------------------------------------------------------------ fused-tile canvas sampling
     @torch.no_grad()
     def sample_tiled(self, grid, overlap=0.25, present=None, tile_batch=16, tile_weights="uniform", cond_images=None,
-                     text_embeds=None, text_masks=None, cond_scale=1.0, sampler=None, sampler_eta=0.0, sample_steps=None,
+                     text_embeds=None, text_masks=None, cond_scale=1.0, sampler=None, sampler_eta=None, sample_steps=None,
                      seed: Optional[int] = None, noise_fn: Optional[Callable] = None, use_graph: bool = True,
                      start_at_unet_number=1, stop_at_unet_number=None, start_image_or_video=None,
                      return_all_unet_outputs=False, lowres_sample_noise_level=None, device=None, inpaint_images=None,
@@ -1872,8 +1929,9 @@ class Imagen(nn.Module):
         alternative to sequential outpainting).  The canvas of a stage is ONE noisy image over the ``grid = (ny, nx)``
         lattice of ``normalize_tiling``; at every schedule step every present tile is denoised by itself, ``tile_batch``
         tiles per UNet forward, their thresholded x0 estimates are averaged where tiles overlap (``tile_weights``) and the
-        update of ``sampler`` (None / ``"ddpm"``, ``"ddim"`` with ``sampler_eta``, ``"dpmpp_2m"``; ``sample_steps`` as in
-        ``sample``) runs once, on the canvas, with canvas-level noise (kd_tiles_fuse_update_known).  There is no inpainting, no
+        update of ``sampler`` (None / ``"ddpm"``, ``"ddim"`` with ``sampler_eta``, ``"dpmpp_2m"``, ``"dpmpp_3m"`` and the
+        ``_sde`` names; ``sample_steps`` as in ``sample``) runs once, on the canvas, with canvas-level noise
+        (kd_tiles_fuse_update_known; kd_tiles_fuse_update_hist2 for the third-order names).  There is no inpainting, no
         resampling and no order among the tiles, and the canvas does not depend on ``tile_batch`` beyond the rounding of
         plans of different batch sizes.
 
@@ -1903,8 +1961,8 @@ class Imagen(nn.Module):
         canvas is re-noised to step k (``rn_a``, ``rn_b``), and the result holds the known image's values, copied.  The
         draws are canvas-level like x_T: ``noise_fn`` tags ``("inpaint" | "renoise" | "step", stage, k, r)``, r counting
         down from R - 1, or Philox purposes 2, 3 and 1 at iteration ``k R + (R - 1 - r)`` - ``sample``'s, so a 1 x 1 lattice
-        draws what ``sample(batch_size=1, inpaint_images=...)`` draws.  2M keeps the fused estimate of a step's last slot as
-        its history; a self-conditioned UNet carries the previous slot's.  ``init_canvas`` (one image, or one per UNet)
+        draws what ``sample(batch_size=1, inpaint_images=...)`` draws.  2M and 3M keep the fused estimate of a step's last
+        slot as their history (3M: of the last two steps); a self-conditioned UNet carries the previous slot's.  ``init_canvas`` (one image, or one per UNet)
         and ``init_skip_steps`` (``normalize_init_canvas``; counted in ``sample_steps`` where given): the stage starts from
         ``z + nearest(2 init - 1)`` and walks steps ``skip .. T - 1``; a step keeps its index - table row, streams, tags -
         and 2M is first order on the first step walked.  Every stage, with or without them, starts through kd_tiles_start,
@@ -2030,7 +2088,8 @@ class Imagen(nn.Module):
         `shards = (devices, normalize_shards' dict of this stage)`: the canvas over several shards, one per entry of
         `devices`, in this one host thread - every call below is issued under the shard's device on that device's
         current stream, and the shards meet through events alone (nothing waits on the host inside a step).  Every shard
-        holds the WHOLE canvas - x, the fused estimate, under 2M with resampling the slot's estimate - and a tile store
+        holds the WHOLE canvas - x, the fused estimate, under 3M the one before it, under 2M / 3M with resampling the slot's
+        estimate - and a tile store
         of its own and halo tiles, with a `tile_of` for exactly that set.  It runs kd_tiles_start itself (the bits are a
         function of the canvas element), denoises its OWN tiles as above with plans of its own (`replica` = its number),
         then the strips of the boundary tiles' estimates travel with their thresholds - kd_tiles_rows_copy packs them
@@ -2059,6 +2118,8 @@ class Imagen(nn.Module):
         init, skip = start
         tables = sched.step_tables()
         coefs = canvas_tables(tables, *solver, skip=skip)
+        third = "coef_prev2" in coefs and bool(coefs["coef_prev2"].any())   # some step reads the estimate of step k - 2
+        multistep = bool(coefs["coef_prev"].any())                           # some step reads the estimate of step k - 1
         sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
         T, tile_steps = sc.T, getattr(lib, sc.steps)
         slots = [(k, j) for k in range(skip, T) for j in range(R)]   # slot j of step k is resample r = R - 1 - j
@@ -2097,10 +2158,12 @@ class Imagen(nn.Module):
             # (scale 1, no image, no mask: 1.0 * z, the bits of the draw itself)
             E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
                                        E.ref(sh.kn_s), E.ref(sh.km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
-            # 2M under resampling: the history takes a step's estimate in its last slot only, the slots before it
-            # leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
-            sh.x0bar_slot = torch.empty(shape, device=dev, dtype=torch.float32) if R > 1 and solver[0] == "dpmpp_2m" else None
+            # a multistep solver under resampling: the history takes a step's estimate in its last slot only, the slots
+            # before it leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
+            sh.x0bar_slot = torch.empty(shape, device=dev, dtype=torch.float32) if R > 1 and multistep else None
             sh.x0bar = torch.zeros(shape, device=dev, dtype=torch.float32)
+            # third order: one more canvas; the estimate of step k overwrites that of step k - 2 (three pointers rotate)
+            sh.x0bar2 = torch.zeros(shape, device=dev, dtype=torch.float32) if third else None
             sh.store = torch.empty((sh.N, Cn, S, S), device=dev, dtype=torch.float32)
             sh.thr = torch.empty((sh.N,), device=dev, dtype=torch.float32) if dynamic_threshold else None
             sh.tile_of = torch.tensor(lay["tile_of"], dtype=torch.int32).to(dev).contiguous()
@@ -2190,6 +2253,7 @@ class Imagen(nn.Module):
 
         def step(sh, i, k, j):   # the canvas step of slot i = (k, j) on the shard's canvas, over its own and halo tiles
             A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
+            P2 = float(coefs["coef_prev2"][k]) if third else 0.0
             z = sh.inject("step", k, j) if Sn != 0.0 else None
             # (z: memory of torch's current stream, handed on only behind this launch)
             it = k * R + j
@@ -2198,13 +2262,20 @@ class Imagen(nn.Module):
             nxt = slots[i + 1] if exists(kn) and i + 1 < len(slots) else None   # the last slot mixes nothing: the end pastes
             zm = sh.inject("inpaint", *nxt) if exists(nxt) else None
             a_mix, s_mix = mix(nxt[0]) if exists(nxt) else (0.0, 0.0)
-            est = sh.x0bar if j == R - 1 or sh.x0bar_slot is None else sh.x0bar_slot
-            E.check(lib.kd_tiles_fuse_update_known(
-                E.ptr(sh.x), E.ptr(sh.x0bar), E.ptr(est), E.ptr(sh.store), E.ptr(sh.thr), C.c_void_p(sh.tile_of.data_ptr()), sh.N,
-                Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it),
-                int(renoise), float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
-                E.ref(sh.kn_s) if exists(nxt) else None, E.ref(sh.km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
-                E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0, stream()))
+            last = j == R - 1 or sh.x0bar_slot is None
+            # (third order: a step's last slot writes its estimate over that of step k - 2, each thread behind its own read)
+            est = (sh.x0bar2 if third else sh.x0bar) if last else sh.x0bar_slot
+            head = (E.ptr(sh.x), E.ptr(sh.x0bar), E.ptr(est), E.ptr(sh.store), E.ptr(sh.thr), C.c_void_p(sh.tile_of.data_ptr()), sh.N,
+                    Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it),
+                    int(renoise), float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
+                    E.ref(sh.kn_s) if exists(nxt) else None, E.ref(sh.km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
+                    E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0)
+            if third:
+                E.check(lib.kd_tiles_fuse_update_hist2(*head, E.ptr(sh.x0bar2), P2, stream()))
+                if last:   # the ring advances: this step's estimate is the next step's first history
+                    sh.x0bar, sh.x0bar2 = sh.x0bar2, sh.x0bar
+            else:
+                E.check(lib.kd_tiles_fuse_update_known(*head, stream()))
             sh.latest = est
 
         def link(e):   # one pair of shards: the strip buffer on either side, the descriptors of the pack and of the unpack
@@ -2324,7 +2395,7 @@ class Imagen(nn.Module):
         sc = _StepSchedule(sched.step_tables(), name, eta, skip)
         args.objective = _OBJECTIVES[objective]
         if exists(stack):
-            if name == "ddpm" or (name == "ddim" and eta > 0):   # DDIM(0) and 2M draw nothing in the step
+            if name == "ddpm" or sc.draws:   # DDIM(0), 2M and 3M draw nothing in the step
                 args.d_noise_step = stack("step", sc.T)
             if has_inpaint:
                 args.d_noise_inpaint = stack("inpaint", sc.T)
@@ -2417,7 +2488,7 @@ class ElucidatedImagen(Imagen):
 
     def sample_tiled(self, *args, **kwargs):
         raise NotImplementedError("ElucidatedImagen.sample_tiled: fused-tile canvas sampling runs the DDPM-trained samplers of "
-                                  "Imagen (ancestral, DDIM, DPM-Solver++(2M)); the EDM Heun sampler has no canvas step")
+                                  "Imagen (ancestral, DDIM, DPM-Solver++); the EDM Heun sampler has no canvas step")
 
     def _stage_loop(self, lib, h, args, img, *, stage, sched, objective, has_inpaint, R, stack, trace, skip=0,
                     self_cond=False, solver=None):

@@ -528,7 +528,7 @@ def outpaint_canvas(sample_fn: Callable, num_patches_width: int, overlap: float 
 
 def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch.device, use_graph: bool = True,
                      seed: Optional[int] = None, max_batch=1, per_patch_seeds: bool = False, sampler=None,
-                     sampler_eta=0.0, sample_steps=None):
+                     sampler_eta=None, sample_steps=None):
     """sample_fn over the drop-in `imagen_pytorch.Imagen` (HIP engine).  `load_imagen(stage)` returns
     the Imagen holding the real unet of that stage (the reference re-loads one stage at a time,
     sample_ultra_res.py:79; a cache keeps all three resident here).  With `max_batch` = 1 each patch
@@ -546,13 +546,15 @@ def imagen_sample_fn(load_imagen: Callable, inpaint_resample: int, device: torch
 
     `sampler`, `sampler_eta`, `sample_steps` (each one value for every stage, or {stage: value}; a stage the dict leaves out
     keeps the default) go to every `sample()` call of the stage, `warm()`'s included: few-step sampling of the patches
-    (`Imagen.sample`)."""
+    (`Imagen.sample`; `sampler_eta` None: 0, and 1 for the `_sde` samplers)."""
     cache = {}
 
     def solver_kw(stage):
         pick = lambda v, d: v.get(stage, d) if isinstance(v, dict) else v
-        kw = dict(sampler=pick(sampler, None), sampler_eta=pick(sampler_eta, 0.0), sample_steps=pick(sample_steps, None))
-        return {k: v for k, v in kw.items() if v is not None and not (k == "sampler_eta" and v == 0)}   # defaults: the call of before
+        kw = dict(sampler=pick(sampler, None), sampler_eta=pick(sampler_eta, None), sample_steps=pick(sample_steps, None))
+        if kw["sampler_eta"] == 0 and not str(kw["sampler"]).endswith("_sde"):   # (an _sde sampler refuses an explicit 0 itself)
+            kw["sampler_eta"] = None
+        return {k: v for k, v in kw.items() if v is not None}   # defaults: the call of before
 
     def task_seed(stage, task):
         return seed + 7919 * stage + 104729 * hash(task) % (2 ** 31)

@@ -46,7 +46,7 @@ def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, d
                 normalize_shards(tiling, len(devices))
             into, more = first_stage(tiling[stages[-1] - 1], device) if first_stage else (None, {})
             kw = dict(kw, **more)
-        sampler, eta, steps = (_per_unet(v, d, n) for v, d in zip(solver, (None, 0.0, None)))
+        sampler, eta, steps = (_per_unet(v, d, n) for v, d in zip(solver, (None, None, None)))
         starts = {name: _per_unet(kw[name], None, n) for name in ("init_canvas", "init_skip_steps") if name in kw}
         canvas = imagen.to(device).sample_tiled(sampler=sampler, sampler_eta=eta, sample_steps=steps, start_at_unet_number=stage,
                                                 stop_at_unet_number=stage, start_image_or_video=canvas, device=device,
@@ -56,7 +56,7 @@ def _run_stages(load_imagen, stages, device, canvas, solver, first_stage=None, d
 
 
 def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None, grid: Optional[Sequence[int]] = None,
-                 overlap: float = 0.25, stages: Sequence[int] = (1, 2, 3), tile_batch: int = 16, sampler=None, sampler_eta=0.0,
+                 overlap: float = 0.25, stages: Sequence[int] = (1, 2, 3), tile_batch: int = 16, sampler=None, sampler_eta=None,
                  sample_steps=None, seed: Optional[int] = None, cond_images: Optional[torch.Tensor] = None, present=None,
                  tile_weights: str = "uniform", use_graph: bool = True, noise_fn: Optional[Callable] = None,
                  start_canvas: Optional[torch.Tensor] = None, device: Optional[torch.device] = None, known=None,
@@ -67,7 +67,7 @@ def fused_canvas(load_imagen: Callable, num_patches_width: Optional[int] = None,
     the slots that hold a tile (None: all); every stage is one `sample_tiled(start_at_unet_number=stage,
     stop_at_unet_number=stage)` call on the previous stage's canvas (`start_canvas` when `stages` does not begin at 1).
     `sampler`, `sampler_eta`, `sample_steps`: one value for every stage, or {stage: value} (a stage the dict leaves out
-    keeps the default).  `cond_images` [tiles, Cc, h, w]: one per present tile, for every stage.  Returns the last stage's
+    keeps the default; `sampler_eta` None: 0, and 1 for the `_sde` samplers).  `cond_images` [tiles, Cc, h, w]: one per present tile, for every stage.  Returns the last stage's
     canvas [1, C, Hc, Wc] in [0, 1].  `known = (image [1, C, Hk, Wk], mask [Hk, Wk])` with `known_resample_times`: the
     pixels every stage keeps (`sample_tiled(known_image=, known_mask=)`, read at each stage's canvas size);
     `init_canvas`, `init_skip_steps`: one value for every stage or {stage: value} - the stage starts from the image at
@@ -135,7 +135,7 @@ def level_background(zoomed_image: torch.Tensor, width: int) -> torch.Tensor:
 def fused_level(load_imagen: Callable, zoomed_image: torch.Tensor, geom: G.GridGeometry, positions: Sequence[G.Pos], *,
                 overlap: float = 0.25, version: str = "ultra", fill_color: Optional[float] = None, window: int = G.PATCH_SIZE,
                 stages: Sequence[int] = (1, 2, 3), tile_batch: int = 16, tile_weights: str = "uniform", sampler=None,
-                sampler_eta=0.0, sample_steps=None, seed: Optional[int] = None, noise_fn: Optional[Callable] = None,
+                sampler_eta=None, sample_steps=None, seed: Optional[int] = None, noise_fn: Optional[Callable] = None,
                 use_graph: bool = True, background: bool = True, device: Optional[torch.device] = None,
                 canvas: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None, known_resample_times: int = 1,
                 refine_skip_steps=None, devices=None) -> torch.Tensor:
