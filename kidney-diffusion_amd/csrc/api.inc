@@ -1266,12 +1266,9 @@ int kd_tiles_fuse_update_known(float* d_x, const float* d_hist, float* d_x0bar_o
                                float rn_a, float rn_b, const float* d_rn_noise, uint64_t rn_stream_id,
                                const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, float mix_a, float mix_s,
                                const float* d_mix_noise, uint64_t mix_stream_id, void* stream) {
-  TileImage kn;
-  TileMask mk;
-  const TileMix mix{tile_image_of(known, &kn), tile_mask_of(mask, &mk), mix_a, mix_s, d_mix_noise, mix_stream_id};
-  return launch_tiles_fuse_update(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P,
-                                  Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
-                                  (hipStream_t)stream);
+  return kd_tiles_fuse_update_hist2(d_x, d_hist, d_x0bar_out, d_x0_tiles, d_thr, d_tile_of, N, C, S, st, ny, nx, ramp, A, B, P, Sn,
+                                    d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, known, mask, mix_a,
+                                    mix_s, d_mix_noise, mix_stream_id, nullptr, 0.0f, stream);
 }
 int kd_tiles_fuse_update_hist2(float* d_x, const float* d_hist, float* d_x0bar_out, const float* d_x0_tiles, const float* d_thr,
                                const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, int ramp, float A, float B,
@@ -1286,22 +1283,25 @@ int kd_tiles_fuse_update_hist2(float* d_x, const float* d_hist, float* d_x0bar_o
                                   Sn, d_noise, seed, stream_id, renoise, rn_a, rn_b, d_rn_noise, rn_stream_id, mix,
                                   (hipStream_t)stream, d_hist2, P2);
 }
-int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
-                            int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
-                            void* stream) {
+// the finish over the canvas rows [y_lo, y_hi); y_hi < 0 is the launcher's "through the last row"
+static int tiles_finalize(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out, int Ho,
+                          int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, int y_lo, int y_hi,
+                          void* stream) {
   TileImage kn;
   TileMask mk;
   return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
-                               tile_mask_of(mask, &mk), 0, -1, (hipStream_t)stream);
+                               tile_mask_of(mask, &mk), y_lo, y_hi, (hipStream_t)stream);
+}
+int kd_tiles_finalize_known(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
+                            int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask,
+                            void* stream) {
+  return tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, known, mask, 0, -1, stream);
 }
 int kd_tiles_finalize_rows(const float* d_x, const int* d_tile_of, int N, int C, int S, int st, int ny, int nx, float* d_out,
                            int Ho, int Wo, int oy, int ox, const kd_tiles_image_t* known, const kd_tiles_mask_t* mask, int y_lo,
                            int y_hi, void* stream) {
-  TileImage kn;
-  TileMask mk;
   KD_REQUIRE(y_hi >= 0, "tiles finalize rows: y_hi must not be negative");
-  return launch_tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, tile_image_of(known, &kn),
-                               tile_mask_of(mask, &mk), y_lo, y_hi, (hipStream_t)stream);
+  return tiles_finalize(d_x, d_tile_of, N, C, S, st, ny, nx, d_out, Ho, Wo, oy, ox, known, mask, y_lo, y_hi, stream);
 }
 int kd_tiles_rows_copy(const float* d_src, int src_tiles, int src_rows, float* d_dst, int dst_tiles, int dst_rows,
                        const float* d_thr_src, float* d_thr_dst, int n, int C, int S, const int* desc, void* stream) {

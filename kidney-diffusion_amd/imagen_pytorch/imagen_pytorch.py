@@ -20,7 +20,6 @@ import ctypes as C
 import math
 import os
 import re
-from types import SimpleNamespace
 from typing import Callable, Optional
 
 import torch
@@ -1527,6 +1526,39 @@ def normalize_init_canvas(init_canvas, init_skip_steps, *, steps, channels, star
 _OBJECTIVES = {"noise": 0, "v": 1, "x_start": 2}
 
 
+def normalize_into(into, *, streamed, channels, Hc, Wc, unet=None):
+    """``sample_tiled(into=(canvas, oy, ox))`` as ``(canvas, int(oy), int(ox))``; None stays None.  ``canvas`` is a contiguous
+    fp32 [1, channels, Ho, Wo] that holds the ``Hc x Wc`` canvas of the last sampled UNet (number ``unet``, for the message)
+    at row ``oy``, column ``ox``.  Raises ValueError for ``into`` without ``streamed`` (only kd_tiles_finalize_rows writes a
+    stage in place), anything that is not such a triple, an offset or a canvas width that is no multiple of 4 (the kernels
+    move 16 bytes), a window out of bounds, and - last, so that every other rule can be met without a GPU - a canvas that
+    is not on the device."""
+    import numbers
+
+    if into is None:
+        return None
+    if not streamed:
+        raise ValueError("sample_tiled(into=...) needs streamed=True: only kd_tiles_finalize writes a stage in place")
+    if not isinstance(into, (tuple, list)) or len(into) != 3 or not torch.is_tensor(into[0]):
+        raise ValueError("into must be (canvas [1, C, Ho, Wo], oy, ox)")
+    dst, oy, ox = into
+    if dst.dtype != torch.float32:
+        raise ValueError(f"into: the canvas must be float32, got {dst.dtype}")
+    if dst.dim() != 4 or dst.shape[0] != 1 or dst.shape[1] != channels or not dst.is_contiguous():
+        raise ValueError(f"into: the canvas must be a contiguous [1, {channels}, Ho, Wo], got shape {tuple(dst.shape)}")
+    if any(not isinstance(v, numbers.Integral) or isinstance(v, bool) for v in (oy, ox)):
+        raise ValueError(f"into: the offset (oy, ox) must be two ints, got ({oy!r}, {ox!r})")
+    if oy % 4 != 0 or ox % 4 != 0 or dst.shape[3] % 4 != 0:
+        raise ValueError(f"into: the offset (oy, ox) = ({oy}, {ox}) and the canvas width {dst.shape[3]} must be multiples "
+                         "of 4 (the kernels move 16 bytes)")
+    if oy < 0 or ox < 0 or oy + Hc > dst.shape[2] or ox + Wc > dst.shape[3]:
+        raise ValueError(f"into: the {Hc} x {Wc} canvas of unet {unet} at ({oy}, {ox}) is out of bounds of the "
+                         f"{dst.shape[2]} x {dst.shape[3]} canvas")
+    if not dst.is_cuda:
+        raise ValueError(f"into: the canvas must live on the device, got {dst.device}")
+    return dst, int(oy), int(ox)
+
+
 def _f32(t, device):
     return None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
 
@@ -1931,7 +1963,7 @@ class Imagen(nn.Module):
         tiles per UNet forward, their thresholded x0 estimates are averaged where tiles overlap (``tile_weights``) and the
         update of ``sampler`` (None / ``"ddpm"``, ``"ddim"`` with ``sampler_eta``, ``"dpmpp_2m"``, ``"dpmpp_3m"`` and the
         ``_sde`` names; ``sample_steps`` as in ``sample``) runs once, on the canvas, with canvas-level noise
-        (kd_tiles_fuse_update_known; kd_tiles_fuse_update_hist2 for the third-order names).  There is no inpainting, no
+        (kd_tiles_fuse_update_hist2; without a second history for all but the third-order names).  There is no inpainting, no
         resampling and no order among the tiles, and the canvas does not depend on ``tile_batch`` beyond the rounding of
         plans of different batch sizes.
 
@@ -1946,7 +1978,7 @@ class Imagen(nn.Module):
         Three arguments carry a stage to the sizes of a magnification level (a 40960 x 40960 canvas of 1024-pixel tiles);
         a call without them keeps its bits.  ``streamed=True``: the low-res conditioning tiles are cut
         straight out of the previous canvas (kd_tiles_gather_lowres: no resized, augmented canvas is built) and the stage
-        ends in one pass into a zero canvas (kd_tiles_finalize_known: no host mask, no temporaries) - bit-equal to
+        ends in one pass into a zero canvas (kd_tiles_finalize_rows: no host mask, no temporaries) - bit-equal to
         ``streamed=False``.  ``cond_crops``: a ``TileCondCrops`` in the place of ``cond_images`` - the tiles'
         conditioning images are windows of one image, cut per chunk by kd_tiles_cond_gather, bit-equal to
         ``cond_images=cond_images_for_grid(...)``.  ``into=(canvas, oy, ox)`` (needs ``streamed``): the last sampled stage
@@ -1966,15 +1998,15 @@ class Imagen(nn.Module):
         and ``init_skip_steps`` (``normalize_init_canvas``; counted in ``sample_steps`` where given): the stage starts from
         ``z + nearest(2 init - 1)`` and walks steps ``skip .. T - 1``; a step keeps its index - table row, streams, tags -
         and 2M is first order on the first step walked.  Every stage, with or without them, starts through kd_tiles_start,
-        steps through kd_tiles_fuse_update_known (update, re-noise and the next slot's mix in the one canvas pass) and ends
-        through kd_tiles_finalize_known (``streamed``) or the same clamp and paste in torch; a call without them passes
+        steps through kd_tiles_fuse_update_hist2 (update, re-noise and the next slot's mix in the one canvas pass) and ends
+        through kd_tiles_finalize_rows (``streamed``) or the same clamp and paste in torch; a call without them passes
         NULL sources and keeps its bits.  ``known_image`` may be a window of the ``into`` canvas itself.
 
         ``devices``: a sequence of CUDA devices, one per SHARD of the canvas (``normalize_devices``, ``normalize_shards``);
-        None or one device is the call of before, with its bits.  The lattice rows are dealt over the shards in
+        None or one device is one shard that holds the whole lattice.  The lattice rows are dealt over the shards in
         contiguous bands balanced by present tiles; every shard denoises the tiles of its band with plans of its own on
         its device, the overlap strips of the boundary tiles' estimates cross per step (kd_tiles_rows_copy), and the
-        canvas comes back on ``devices[0]`` (where ``into`` must live) - the canvas of ``devices=None`` bit for bit
+        canvas comes back on ``devices[0]`` (where ``into`` must live) - the canvas of one shard bit for bit
         wherever the chunks of both calls have one batch size, and within the rounding of plans of different batch
         sizes otherwise.  A device may repeat (``[d, d]``: two shards on one GPU, each with its own plans).  One process,
         one host thread, no collectives; ``noise_fn`` is refused with more than one shard."""
@@ -1998,7 +2030,7 @@ class Imagen(nn.Module):
         tiling = normalize_tiling(self.image_sizes, grid, overlap, present, tile_weights)
         n_tiles = len(tiling[0]["origins"])
         devices = normalize_devices(devices, noise_fn)
-        sharding = normalize_shards(tiling, len(devices)) if exists(devices) and len(devices) > 1 else None
+        sharding = normalize_shards(tiling, len(devices) if exists(devices) else 1)
         if exists(devices):
             device = devices[0]
         if exists(cond_images) and (cond_images.dim() != 4 or cond_images.shape[0] != n_tiles):
@@ -2016,28 +2048,8 @@ class Imagen(nn.Module):
             if not isinstance(cond_crops, TileCondCrops):
                 raise ValueError(f"cond_crops must be a TileCondCrops, got {type(cond_crops).__name__}")
             crops = (cond_crops,) + cond_crops.checked(n_tiles)
-        if exists(into):
-            if not streamed:
-                raise ValueError("sample_tiled(into=...) needs streamed=True: only kd_tiles_finalize writes a stage in place")
-            if not isinstance(into, (tuple, list)) or len(into) != 3 or not torch.is_tensor(into[0]):
-                raise ValueError("into must be (canvas [1, C, Ho, Wo], oy, ox)")
-            dst, oy, ox = into
-            g = tiling[last - 1]
-            if dst.dtype != torch.float32:
-                raise ValueError(f"into: the canvas must be float32, got {dst.dtype}")
-            if dst.dim() != 4 or dst.shape[0] != 1 or dst.shape[1] != self.channels or not dst.is_contiguous():
-                raise ValueError(f"into: the canvas must be a contiguous [1, {self.channels}, Ho, Wo], got shape {tuple(dst.shape)}")
-            if any(not isinstance(v, numbers.Integral) or isinstance(v, bool) for v in (oy, ox)):
-                raise ValueError(f"into: the offset (oy, ox) must be two ints, got ({oy!r}, {ox!r})")
-            if oy % 4 != 0 or ox % 4 != 0 or dst.shape[3] % 4 != 0:
-                raise ValueError(f"into: the offset (oy, ox) = ({oy}, {ox}) and the canvas width {dst.shape[3]} must be multiples "
-                                 "of 4 (the kernels move 16 bytes)")
-            if oy < 0 or ox < 0 or oy + g["Hc"] > dst.shape[2] or ox + g["Wc"] > dst.shape[3]:
-                raise ValueError(f"into: the {g['Hc']} x {g['Wc']} canvas of unet {last} at ({oy}, {ox}) is out of bounds of the "
-                                 f"{dst.shape[2]} x {dst.shape[3]} canvas")
-            if not dst.is_cuda:
-                raise ValueError(f"into: the canvas must live on the device, got {dst.device}")
-            into = (dst, int(oy), int(ox))
+        into = normalize_into(into, streamed=streamed, channels=self.channels, Hc=tiling[last - 1]["Hc"], Wc=tiling[last - 1]["Wc"],
+                              unet=last)
         known = normalize_known(known_image, known_mask, known_resample_times, channels=self.channels)
         starts = normalize_init_canvas(init_canvas, init_skip_steps,
                                        steps=[default(st, T) for (_, _, st), T in zip(solvers, self._num_steps())],
@@ -2049,13 +2061,15 @@ class Imagen(nn.Module):
         if exists(canvas):
             g = tiling[start_at_unet_number - 2]
             canvas = F.interpolate(canvas, (g["Hc"], g["Wc"]), mode="nearest")
-        if exists(sharding):   # every shard's device by its index: two spellings of one device are one device
+        if exists(devices) and len(devices) > 1:   # every shard's device by its index: two spellings of one device are one device
             devices = [d if exists(d.index) else torch.device("cuda", torch.cuda.current_device()) for d in devices]
             if any(d.index >= torch.cuda.device_count() for d in devices):
                 raise ValueError(f"devices={devices} name a device this process does not see ({torch.cuda.device_count()} visible)")
             device = devices[0]
             if exists(into) and into[0].device != device:   # before any forward: the stage ends on devices[0]
                 raise ValueError(f"into: with devices=... the canvas must live on devices[0] = {device}, got {into[0].device}")
+        else:
+            devices = [device]
         outputs = []
         for num, unet, sched, obj, dyn, cs, solver in self._stages(solvers, cond_scale, start_at_unet_number,
                                                                   stop_at_unet_number):
@@ -2063,7 +2077,7 @@ class Imagen(nn.Module):
                                        noise_fn, int(seed), use_graph, int(tile_batch), text_embeds=text_embeds,
                                        text_masks=text_masks, cond_scale=cs, solver=solver, streamed=bool(streamed),
                                        crops=crops, into=into if num == last else None, known=known, start=starts[num - 1],
-                                       shards=(devices, sharding[num - 1]) if exists(sharding) else None)
+                                       shards=(devices, sharding[num - 1]))
             outputs.append(canvas)
         return outputs if return_all_unet_outputs else outputs[-1]
 
@@ -2071,307 +2085,46 @@ class Imagen(nn.Module):
                      lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds=None, text_masks=None, cond_scale=1.0,
                      solver=("ddpm", 0.0), streamed=False, crops=None, into=None, known=(None, None, 1), start=(None, 0),
                      shards=None, _poison_halo=False):
-        """One stage of sample_tiled: the canvas from x_T to the unnormalised sample.  kd_tiles_start writes x_T; then, per
-        resample slot of the schedule steps skip .. T - 1 and chunk of at most `tile_batch` tiles: gather the chunk out of
-        the canvas into the plan's stable buffers, one iteration kd_solver_sample_steps(k, k + 1) with DDIM(0)
-        coefficients (first order: no history, no draw; its tile-level update is discarded), the x0 estimates and
-        thresholds into the tile store; then ONE kd_tiles_fuse_update_known with the canvas sampler's coefficients of
-        step k.  A ragged last chunk runs the plan of its own batch size.
-        `streamed`: the chunk's low-res tiles come from the previous canvas (kd_tiles_gather_lowres) and the stage ends
-        with kd_tiles_finalize_known, into `into = (canvas, oy, ox)` or a zero canvas; `crops`: (TileCondCrops, Cs, W, tile
-        channels, top, shifts) - the chunk's conditioning tiles come from its image (kd_tiles_cond_gather).
-        `known = (image, mask, R)` / `start = (init image, skip)`: the same three calls carry them - the start adds the init
-        image and the first mix, the canvas step also re-noises and mixes the known pixels for the next slot, the end
-        pastes them.  Without them (R = 1, skip = 0) the sources are NULL, a step has one slot and the calls give the
-        bits of the Philox draw, kd_tiles_fuse_update and kd_tiles_finalize.
+        """One stage of sample_tiled, driven through imagen_pytorch/_canvas.py: a _CanvasStage (what every shard reads), one
+        _CanvasShard per entry of `shards = (devices, normalize_shards' dict of this stage)` - one shard is the whole
+        lattice on its device - and one _StripLink per pair of shards that trade strips.  Every shard starts its canvas;
+        per resample slot every shard denoises its own tiles, the links trade, every shard takes the canvas step; at the
+        end every shard finishes the canvas rows it owns, onto devices[0] (`device`): `streamed` through
+        kd_tiles_finalize_rows into `into = (canvas, oy, ox)` or a zero canvas, else in torch.
+        `_poison_halo` is for tests alone (no public call passes it): _CanvasShard.poison_halo before each slot."""
+        from . import _canvas
 
-        `shards = (devices, normalize_shards' dict of this stage)`: the canvas over several shards, one per entry of
-        `devices`, in this one host thread - every call below is issued under the shard's device on that device's
-        current stream, and the shards meet through events alone (nothing waits on the host inside a step).  Every shard
-        holds the WHOLE canvas - x, the fused estimate, under 3M the one before it, under 2M / 3M with resampling the slot's
-        estimate - and a tile store
-        of its own and halo tiles, with a `tile_of` for exactly that set.  It runs kd_tiles_start itself (the bits are a
-        function of the canvas element), denoises its OWN tiles as above with plans of its own (`replica` = its number),
-        then the strips of the boundary tiles' estimates travel with their thresholds - kd_tiles_rows_copy packs them
-        into one buffer per pair of shards, one `copy_` moves it, kd_tiles_rows_copy unpacks it into the receiver's halo
-        slots - and every shard runs the one kd_tiles_fuse_update_known over own and halo.
-        THE INVARIANT: after the canvas step every pixel of a shard's band extent - the canvas rows its own tiles cover -
-        holds the bits of the single-device canvas, in x, in the fused estimate, in the history and so in the
-        self-conditioning carry gathered from it.  Every tile covering such a pixel is an own or a halo tile and covers
-        it inside its strip, the fusion order follows the lattice slot and not the store, the update is pointwise and
-        its noise is keyed by the canvas element; so the next gather of the own tiles, which reads nothing outside the
-        extent, reads only exact pixels.  Outside its extent a shard's canvas holds garbage (fused from halo rows that were
-        never sent) and is never read.  At the end every shard finalises the canvas rows it owns: the first straight into
-        the destination on devices[0], the others into a band of those rows (kd_tiles_finalize_rows) that one copy takes
-        there.  The previous canvas, the conditioning source, the known image, the mask and the init image are copied to
-        each device once per stage; a source already on a shard's device is read in place.
-        `_poison_halo` is for tests alone (no public call passes it): NaN in every halo slot of every shard's store, and in
-        its threshold, before each slot, so that only the received strips hold numbers."""
-        lib = E.load()
-        Cn, S, st, ny, nx, Hc, Wc = self.channels, geo["S"], geo["st"], geo["ny"], geo["nx"], geo["Hc"], geo["Wc"]
-        origins = geo["origins"]
-        shape = (1, Cn, Hc, Wc)
-        stream = E.current_stream
-        _, stage_seed, _ = _stage_noise(lib, noise_fn, seed, stage, device)
-
-        kn, km, R = known
-        init, skip = start
-        tables = sched.step_tables()
-        coefs = canvas_tables(tables, *solver, skip=skip)
-        third = "coef_prev2" in coefs and bool(coefs["coef_prev2"].any())   # some step reads the estimate of step k - 2
-        multistep = bool(coefs["coef_prev"].any())                           # some step reads the estimate of step k - 1
-        sc = _StepSchedule(tables, "ddim", eta=0.0)   # the tiles' own iteration: first order, no draw
-        T, tile_steps = sc.T, getattr(lib, sc.steps)
-        slots = [(k, j) for k in range(skip, T) for j in range(R)]   # slot j of step k is resample r = R - 1 - j
-        mix = lambda k: (float(tables["alpha"][k]), float(tables["sigma"][k]))   # (a, s) of the mix before a slot of step k
-        with_text = exists(text_embeds) and unet.cond_on_text
-        ls = a = s = None
-        if unet.lowres_cond:
-            ls = self.lowres_noise_schedule.log_snr(torch.full((1,), lowres_level, dtype=torch.float32))
-            a, s = log_snr_to_alpha_sigma(ls)
-        if exists(crops):
-            cc, Cs, W, Ct, top, shifts = crops
-            assert Ct == unet.cond_images_channels, "invalid number of channels in conditioning image"
-        if exists(cond_images):
-            assert cond_images.shape[1] == unet.cond_images_channels, "invalid number of channels in conditioning image"
-
-        # one shard: the whole lattice on `device`
-        layout = [dict(own=list(range(len(origins))), tiles=list(range(len(origins))), base=0, tile_of=geo["tile_of"], halo=[],
-                       owned=(0, Hc))] if shards is None else shards[1]["shards"]
-        devs = [device] if shards is None else shards[0]
-        exchange = [] if shards is None else shards[1]["exchange"]
-
-        def setup(num, dev, lay):   # the canvas, the store, the sources and the plans of one shard, on its device
-            f32 = lambda t: _f32(t, dev)
-            sh = SimpleNamespace(num=num, dev=dev, own=lay["own"], first=lay["own"][0], base=lay["base"], N=len(lay["tiles"]),
-                                 halo=[lay["tiles"].index(t) for t in lay["halo"]], owned=lay["owned"])
-            gauss = _stage_noise(lib, noise_fn, seed, stage, dev)[0]
-            sh.inject = lambda kind, k, j: f32(noise_fn((kind, stage, k, R - 1 - j), shape)) if exists(noise_fn) else None
-            # the sources that exist stay where they lie: views of the caller's tensors, described to the kernels
-            here = lambda t: t.is_cuda and t.device.index == default(dev.index, torch.cuda.current_device())
-            sh.kn, sh.init = (t if t is None or here(t) else f32(t) for t in (kn, init))
-            sh.km = km if km is None or here(km) else km.to(dev)
-            sh.kn_s, sh.km_s, init_s = E.tiles_image(sh.kn), E.tiles_mask(sh.km), E.tiles_image(sh.init)
-            x = sh.x = torch.empty(shape, device=dev, dtype=torch.float32)
-            z = f32(noise_fn(("init", stage), shape)) if exists(noise_fn) else None
-            zm = sh.inject("inpaint", skip, 0) if exists(kn) else None
-            # (scale 1, no image, no mask: 1.0 * z, the bits of the draw itself)
-            E.check(lib.kd_tiles_start(E.ptr(x), Cn, Hc, Wc, self._start_scale(stage), E.ptr(z), stage_seed, E.ref(init_s),
-                                       E.ref(sh.kn_s), E.ref(sh.km_s), *mix(skip), E.ptr(zm), E.stream_id(2, skip * R), stream()))
-            # a multistep solver under resampling: the history takes a step's estimate in its last slot only, the slots
-            # before it leave theirs (a self-conditioned UNet's carry) in a canvas of their own (written before it is read)
-            sh.x0bar_slot = torch.empty(shape, device=dev, dtype=torch.float32) if R > 1 and multistep else None
-            sh.x0bar = torch.zeros(shape, device=dev, dtype=torch.float32)
-            # third order: one more canvas; the estimate of step k overwrites that of step k - 2 (three pointers rotate)
-            sh.x0bar2 = torch.zeros(shape, device=dev, dtype=torch.float32) if third else None
-            sh.store = torch.empty((sh.N, Cn, S, S), device=dev, dtype=torch.float32)
-            sh.thr = torch.empty((sh.N,), device=dev, dtype=torch.float32) if dynamic_threshold else None
-            sh.tile_of = torch.tensor(lay["tile_of"], dtype=torch.int32).to(dev).contiguous()
-            sh.lowres = sh.lowres_z = sh.prev = sh.cond = sh.src = cond_shape = None
-            if unet.lowres_cond:
-                if streamed:   # no canvas is built: every chunk is cut out of prev_canvas (injected noise stays a canvas)
-                    sh.prev = f32(prev_canvas)
-                    assert sh.prev.dim() == 4 and tuple(sh.prev.shape[:2]) == (1, Cn), "the previous canvas must be [1, C, H, W]"
-                    sh.lowres_z = f32(noise_fn(("lowres", stage), shape)) if exists(noise_fn) else None
-                else:
-                    lowres = F.interpolate(prev_canvas.to(dev), (Hc, Wc), mode="nearest") * 2 - 1
-                    sh.lowres = (float(a) * lowres + float(s) * gauss(("lowres", stage), shape, (16 << 32) | 1)).contiguous()
-            if exists(cond_images):
-                sh.cond = f32(resize_image_to(f32(cond_images), S))
-                cond_shape = tuple(sh.cond.shape[1:])
-            elif exists(crops):
-                src = cc.image
-                sh.src = f32(src.float() / 255.0 if src.dtype == torch.uint8 else src)   # moved once; stays for the stage
-                sh.win_of, sh.centre_of = (None if m is None else m.to(dev) for m in cond_crop_maps(cc.window, S, cc.centre_width))
-                cond_shape = (Ct, S, S)
-            # one plan, one set of stable buffers and one argument struct per batch size (the full chunks' and the ragged one's)
-            plans, n_own = {}, len(sh.own)
-            sh.plans = plans
-            for b in sorted({min(tile_batch, n_own - n0) for n0 in range(0, n_own, tile_batch)}):
-                io = _StageIO(self, unet, b, S, dev, dynamic_threshold=dynamic_threshold, use_graph=use_graph,
-                              key=stage_seed, replica=num)   # (DDIM(0) draws nothing)
-                args = io.args
-                args.objective = _OBJECTIVES[objective]
-                p = plans[b] = dict(io=io, args=args, img=io.buf("img", (b, Cn, S, S)))
-                if unet.lowres_cond:
-                    p["lowres"] = io.buf("lowres", (b, Cn, S, S))
-                    args.d_lowres = E.ptr(p["lowres"])
-                    io.lowres_level(ls)
-                if exists(cond_shape):
-                    p["cond"] = io.buf("cond", (b,) + cond_shape)
-                    args.d_cond_images = E.ptr(p["cond"])
-                if unet.self_cond:
-                    p["self_cond"] = io.buf("tile_self_cond", (b, Cn, S, S))
-                h = p["h"] = unet.engine(b, S, dev, with_text=with_text, replica=num)
-                if with_text:   # one row for the canvas, given to every tile of the chunk
-                    rows = lambda t: None if t is None else t.expand(b, *t.shape[1:])
-                    io.text(h, rows(text_embeds), rows(text_masks), cond_scale)
-            sh.latest = sh.x0bar   # the canvas that holds the fused estimate of the previous slot
-            return sh
-
-        def denoise(sh, i, k):   # the own tiles of the shard through slot i (of step k): their estimates into its store
-            def gather(src, dst, t0, b):   # dst [b, C, S, S] <- tiles t0 .. t0 + b - 1 of the canvas-shaped src
-                yx = (C.c_int * (2 * b))(*[v for o in origins[t0:t0 + b] for v in o])
-                E.check(lib.kd_tiles_gather(E.ptr(src), E.ptr(dst), b, Cn, Hc, Wc, S, yx, stream()))
-
-            def gather_lowres(dst, t0, b):   # dst [b, C, S, S] <- a (2 nearest(prev_canvas) - 1) + s z over tiles t0 ..
-                yx = (C.c_int * (2 * b))(*[v for o in origins[t0:t0 + b] for v in o])
-                E.check(lib.kd_tiles_gather_lowres(E.ptr(sh.prev), sh.prev.shape[2], sh.prev.shape[3], E.ptr(dst), b,
-                                                   Cn, Hc, Wc, S, yx, float(a), float(s), E.ptr(sh.lowres_z), stage_seed,
-                                                   (16 << 32) | 1, stream()))
-
-            def gather_cond(dst, t0, b):   # dst [b, Ct, S, S] <- the conditioning windows of tiles t0 .. t0 + b - 1
-                yx = (C.c_int * (2 * b))(*[v for f in shifts[t0:t0 + b] for v in f])
-                E.check(lib.kd_tiles_cond_gather(E.ptr(sh.src), Cs, W, E.ptr(dst), b, S, yx, top, C.c_void_p(sh.win_of.data_ptr()),
-                                                 C.c_void_p(sh.centre_of.data_ptr()) if exists(sh.centre_of) else None,
-                                                 float(cc.fill), stream()))
-
-            n_own = len(sh.own)
-            for n0 in range(0, n_own, tile_batch):
-                b = min(tile_batch, n_own - n0)
-                t0, at = sh.first + n0, sh.base + n0   # the chunk's first tile: its number on the canvas, its slot in the store
-                p = sh.plans[b]
-                gather(sh.x, p["img"], t0, b)
-                if unet.lowres_cond and streamed:
-                    gather_lowres(p["lowres"], t0, b)
-                elif unet.lowres_cond:
-                    gather(sh.lowres, p["lowres"], t0, b)
-                if exists(sh.cond):
-                    p["cond"].copy_(sh.cond[t0:t0 + b])
-                elif exists(crops):
-                    gather_cond(p["cond"], t0, b)
-                if unet.self_cond and i > 0:   # the carry is the FUSED estimate of the slot before (the first starts from zeros)
-                    gather(sh.latest, p["self_cond"], t0, b)
-                    E.check(lib.kd_sample_set_self_cond(p["h"], E.ptr(p["self_cond"]), stream()))
-                elif unet.self_cond and k > 0:   # a first step walked behind step 0: the plan holds another call's carry
-                    E.check(lib.kd_sample_set_self_cond(p["h"], None, stream()))
-                p["args"].keep_self_cond = int(i > 0)   # (the later slots of step 0 keep the carry just set)
-                E.check(tile_steps(p["h"], C.byref(sc.struct), C.byref(p["args"]), E.ptr(p["img"]), k, k + 1, stream()))
-                E.check(lib.kd_sample_last(p["h"], 1, E.ptr(sh.store[at:at + b]), stream()))
-                if dynamic_threshold:
-                    E.check(lib.kd_sample_last(p["h"], 2, E.ptr(sh.thr[at:at + b]), stream()))
-
-        def step(sh, i, k, j):   # the canvas step of slot i = (k, j) on the shard's canvas, over its own and halo tiles
-            A, B, P, Sn = (float(coefs[c][k]) for c in ("coef_x", "coef_x0", "coef_prev", "coef_noise"))
-            P2 = float(coefs["coef_prev2"][k]) if third else 0.0
-            z = sh.inject("step", k, j) if Sn != 0.0 else None
-            # (z: memory of torch's current stream, handed on only behind this launch)
-            it = k * R + j
-            renoise = j < R - 1 and k < T - 1
-            zr = sh.inject("renoise", k, j) if renoise else None
-            nxt = slots[i + 1] if exists(kn) and i + 1 < len(slots) else None   # the last slot mixes nothing: the end pastes
-            zm = sh.inject("inpaint", *nxt) if exists(nxt) else None
-            a_mix, s_mix = mix(nxt[0]) if exists(nxt) else (0.0, 0.0)
-            last = j == R - 1 or sh.x0bar_slot is None
-            # (third order: a step's last slot writes its estimate over that of step k - 2, each thread behind its own read)
-            est = (sh.x0bar2 if third else sh.x0bar) if last else sh.x0bar_slot
-            head = (E.ptr(sh.x), E.ptr(sh.x0bar), E.ptr(est), E.ptr(sh.store), E.ptr(sh.thr), C.c_void_p(sh.tile_of.data_ptr()), sh.N,
-                    Cn, S, st, ny, nx, int(geo["weights"] == "ramp"), A, B, P, Sn, E.ptr(z), stage_seed, E.stream_id(1, it),
-                    int(renoise), float(tables["rn_a"][k]), float(tables["rn_b"][k]), E.ptr(zr), E.stream_id(3, it),
-                    E.ref(sh.kn_s) if exists(nxt) else None, E.ref(sh.km_s) if exists(nxt) else None, a_mix, s_mix, E.ptr(zm),
-                    E.stream_id(2, nxt[0] * R + nxt[1]) if exists(nxt) else 0)
-            if third:
-                E.check(lib.kd_tiles_fuse_update_hist2(*head, E.ptr(sh.x0bar2), P2, stream()))
-                if last:   # the ring advances: this step's estimate is the next step's first history
-                    sh.x0bar, sh.x0bar2 = sh.x0bar2, sh.x0bar
-            else:
-                E.check(lib.kd_tiles_fuse_update_known(*head, stream()))
-            sh.latest = est
-
-        def link(e):   # one pair of shards: the strip buffer on either side, the descriptors of the pack and of the unpack
-            src, dst = parts[e["src"]], parts[e["dst"]]
-            rows = max(r for _, _, r in e["items"])
-            n = len(e["items"])
-            slot_of = lambda part, t: layout[part.num]["tiles"].index(t)
-            flat = lambda quads: (C.c_int * (4 * n))(*[v for q in quads for v in q])
-            ln = SimpleNamespace(src=src, dst=dst, n=n, rows=rows, ready=torch.cuda.Event(), freed=torch.cuda.Event(), sent=False,
-                                 pack=flat((slot_of(src, t), m, r0, r) for m, (t, r0, r) in enumerate(e["items"])),
-                                 unpack=flat((m, slot_of(dst, t), r0, r) for m, (t, r0, r) in enumerate(e["items"])))
-            # [n strips of C x rows x S | n thresholds], one allocation: what travels is one contiguous buffer
-            words = n * Cn * rows * S
-            ln.out = torch.empty(words + n, device=src.dev, dtype=torch.float32)
-            ln.inn = torch.empty(words + n, device=dst.dev, dtype=torch.float32)
-            ln.words = words
-            return ln
-
-        def trade(ln):   # the strips of one pair: packed where they were made, moved, unpacked into the halo slots
-            tail = lambda buf: C.c_void_p(buf.data_ptr() + 4 * ln.words) if dynamic_threshold else None
-            with torch.cuda.device(ln.src.dev):
-                if ln.sent:   # the buffer is written again only behind the copy that read it
-                    torch.cuda.current_stream().wait_event(ln.freed)
-                E.check(lib.kd_tiles_rows_copy(E.ptr(ln.src.store), ln.src.N, S, E.ptr(ln.out), ln.n, ln.rows, E.ptr(ln.src.thr),
-                                               tail(ln.out), ln.n, Cn, S, ln.pack, stream()))
-                ln.ready.record()
-            with torch.cuda.device(ln.dst.dev):
-                torch.cuda.current_stream().wait_event(ln.ready)
-                ln.inn.copy_(ln.out, non_blocking=True)
-                ln.freed.record()
-                ln.sent = True
-                E.check(lib.kd_tiles_rows_copy(E.ptr(ln.inn), ln.n, ln.rows, E.ptr(ln.dst.store), ln.dst.N, S, tail(ln.inn),
-                                               E.ptr(ln.dst.thr), ln.n, Cn, S, ln.unpack, stream()))
-
-        parts = []
-        for num, (dev, lay) in enumerate(zip(devs, layout)):
-            with torch.cuda.device(dev):
-                parts.append(setup(num, dev, lay))
-        links = [link(e) for e in exchange]
-        for i, (k, j) in enumerate(slots):
+        devs, layout = shards
+        st = _canvas._CanvasStage(self, unet, stage, geo, sched, objective, dynamic_threshold, prev_canvas, cond_images,
+                                  lowres_level, noise_fn, seed, use_graph, tile_batch, text_embeds, text_masks, cond_scale, solver,
+                                  streamed, crops, known, start)
+        on, parts = torch.cuda.device, []
+        for num, (dev, lay) in enumerate(zip(devs, layout["shards"])):
+            with on(dev):
+                parts.append(_canvas._CanvasShard(st, num, dev, lay))
+                parts[-1].start()
+        links = [_canvas._StripLink(st, parts[e["src"]], parts[e["dst"]], e["items"]) for e in layout["exchange"]]
+        for i, (k, j) in enumerate(st.slots):
             for sh in parts:
-                with torch.cuda.device(sh.dev):
-                    if _poison_halo and sh.halo:
-                        sh.store[sh.halo] = float("nan")
-                        if dynamic_threshold:
-                            sh.thr[sh.halo] = float("nan")
-                    denoise(sh, i, k)
+                with on(sh.dev):
+                    if _poison_halo:
+                        sh.poison_halo()
+                    sh.denoise(i, k)
             for ln in links:
-                trade(ln)
+                ln.trade()
             for sh in parts:
-                with torch.cuda.device(sh.dev):
-                    step(sh, i, k, j)
-
-        head = parts[0]
-        if streamed:   # one pass, in place: the covered pixels into `into` (or a zero canvas), nothing else touched
-            with torch.cuda.device(head.dev):
-                out, oy, ox = into if exists(into) else (torch.zeros(shape, device=head.dev, dtype=torch.float32), 0, 0)
-                assert out.device == head.x.device, f"into: the canvas lives on {out.device}, the stage runs on {head.x.device}"
-                if len(parts) == 1:
-                    E.check(lib.kd_tiles_finalize_known(E.ptr(head.x), C.c_void_p(head.tile_of.data_ptr()), head.N, Cn, S, st, ny, nx,
-                                                        E.ptr(out), out.shape[2], out.shape[3], oy, ox, E.ref(head.kn_s),
-                                                        E.ref(head.km_s), stream()))
-                    return out
-            holes = len(origins) < ny * nx   # an uncovered pixel keeps the destination's bits: a band then starts from them
-            for sh in parts:
-                y0, y1 = sh.owned
-                window = out[:, :, oy + y0:oy + y1, ox:ox + Wc]
-                with torch.cuda.device(sh.dev):
-                    if sh is head:
-                        band, Ho, Wo, by, bx = out, out.shape[2], out.shape[3], oy, ox
-                    else:
-                        band = torch.empty((1, Cn, y1 - y0, Wc), device=sh.dev, dtype=torch.float32)
-                        if holes:
-                            band.copy_(window, non_blocking=True)
-                        Ho, Wo, by, bx = y1 - y0, Wc, -y0, 0
-                    E.check(lib.kd_tiles_finalize_rows(E.ptr(sh.x), C.c_void_p(sh.tile_of.data_ptr()), sh.N, Cn, S, st, ny, nx,
-                                                       E.ptr(band), Ho, Wo, by, bx, E.ref(sh.kn_s), E.ref(sh.km_s), y0, y1, stream()))
-                if sh is not head:
-                    with torch.cuda.device(head.dev):
-                        window.copy_(band, non_blocking=True)
-            return out
-        bands = []
-        for sh in parts:   # the same clamp and paste in torch, over the rows the shard owns
-            y0, y1 = sh.owned
-            with torch.cuda.device(sh.dev):
-                covered = torch.zeros(Hc, Wc, dtype=torch.bool)
-                for ty, tx in origins:
-                    covered[ty:ty + S, tx:tx + S] = True
-                out = (sh.x[:, :, y0:y1].clamp(-1.0, 1.0) + 1) * 0.5
-                if exists(kn):   # the paste on nearest-resized copies
-                    resized = lambda t: t if tuple(t.shape[-2:]) == (Hc, Wc) else F.interpolate(t, (Hc, Wc), mode="nearest")
-                    out = torch.where(resized(sh.km[None, None].float())[:, :, y0:y1] != 0, resized(sh.kn)[:, :, y0:y1], out)
-                out = torch.where(covered[y0:y1].to(sh.dev), out, torch.zeros_like(out))
-            bands.append(out)
-        with torch.cuda.device(head.dev):
-            return bands[0] if len(bands) == 1 else torch.cat([b.to(head.dev) for b in bands], dim=2)
+                with on(sh.dev):
+                    sh.step(i, k, j)
+        head, bands, covered = parts[0], [], None if streamed else st.covered()
+        if streamed:   # in place: the covered pixels into `into` (or a zero canvas), nothing else touched
+            with on(head.dev):
+                out, oy, ox = into if exists(into) else (torch.zeros(st.shape, device=head.dev, dtype=torch.float32), 0, 0)
+            assert out.device == head.x.device, f"into: the canvas lives on {out.device}, the stage runs on {head.x.device}"
+        for sh in parts:
+            with on(sh.dev):
+                bands.append(sh.finish_rows(out, oy, ox, sh is head) if streamed else sh.finish_torch(covered))
+        with on(head.dev):
+            return out if streamed else bands[0] if len(bands) == 1 else torch.cat([b.to(head.dev) for b in bands], dim=2)
 
     def _num_steps(self):
         """Schedule steps of every UNet's sampler: what skip_steps is checked against."""

@@ -100,6 +100,28 @@ def test_sample_tiled_refuses_the_new_arguments_by_name_before_it_needs_a_gpu():
                 im.sample_tiled((2, 2), seed=3, **kw)
 
 
+def test_normalize_into_is_a_function_of_its_arguments():
+    """The rules of `into` by themselves, in their order: None passes whatever `streamed` is, `streamed` is asked for
+    before the triple is looked at, and the place is the last rule - a host canvas that meets every other one."""
+    from imagen_pytorch.imagen_pytorch import normalize_into
+
+    size = dict(channels=3, Hc=28, Wc=28, unet=1)
+    canvas = torch.zeros(1, 3, 40, 40)
+    assert normalize_into(None, streamed=False, **size) is None and normalize_into(None, streamed=True, **size) is None
+    with pytest.raises(ValueError, match="needs streamed=True"):
+        normalize_into("not a triple", streamed=False, **size)
+    with pytest.raises(ValueError, match=r"the offset \(oy, ox\) must be two ints, got \(4, 4.0\)"):
+        normalize_into((canvas, 4, 4.0), streamed=True, **size)
+    with pytest.raises(ValueError, match="the 28 x 28 canvas of unet 1 at \\(16, 0\\) is out of bounds of the 40 x 40 canvas"):
+        normalize_into((canvas, 16, 0), streamed=True, **size)
+    with pytest.raises(ValueError, match="must live on the device, got cpu"):
+        normalize_into([canvas, 12, 12], streamed=True, **size)
+    if torch.cuda.is_available():
+        dst = canvas.cuda()
+        got = normalize_into((dst, torch.tensor(12).item(), 8), streamed=True, **size)
+        assert got[0] is dst and got[1:] == (12, 8) and all(type(v) is int for v in got[1:])
+
+
 # ------------------------------------------------------------------------------------------------ the level driver
 def test_the_box_of_a_sparse_position_set():
     from ultra_res import tiled as UT

@@ -150,6 +150,29 @@ def test_bands_are_balanced_by_present_tiles():
     assert all(sh["own"] for sh in plan["shards"]) and max(len(sh["own"]) for sh in plan["shards"]) == 3
 
 
+SCATTERED = [[(3 * r + 5 * q) % 7 not in (0, 3) for q in range(7)] for r in range(5)]   # 5 x 7, two holes in every row
+
+
+@pytest.mark.parametrize("grid,present", [((4, 2), None), ((3, 2), HOLE), ((1, 1), None), ((5, 7), SCATTERED)])
+def test_one_shard_is_the_whole_lattice(grid, present):
+    """What sample_tiled(devices=None) rests on: at every stage, the one shard of normalize_shards(tiling, 1) owns every
+    tile in canvas order from slot 0 of its store, has no halo and nothing to trade, ends every canvas row, and its
+    `tile_of` is the tiling's own."""
+    tiling_of, shards_of, _ = _np()
+    if present is SCATTERED:
+        assert all(sum(row) == 5 for row in SCATTERED) and len({tuple(row) for row in SCATTERED}) == 5
+    tiling = tiling_of((16, 32, 64), grid, present=present)
+    plans = shards_of(tiling, 1)
+    assert len(plans) == len(tiling) == 3
+    for geo, plan in zip(tiling, plans):
+        (sh,) = plan["shards"]
+        every = list(range(len(geo["origins"])))
+        assert sh["own"] == every and sh["tiles"] == every and sh["base"] == 0 and sh["halo"] == []
+        assert sh["owned"] == (0, geo["Hc"])
+        assert sh["tile_of"] == geo["tile_of"]
+        assert plan["exchange"] == []
+
+
 def test_the_mag_2_level_over_8_shards():
     """53 x 53 slots of 1024^2 at stride 768 (the last stage of a mag-2 level), every slot present and a disc of tissue, over
     8 shards: every present tile is owned once, the bands hold 6 or 7 rows of the full lattice, the halo is one lattice row
