@@ -677,6 +677,15 @@ int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* 
 int kd_gate_add_nhwc(const float* d_a, const float* d_gate, const float* d_r, int ldr, float* d_y, int ldy, double* d_seg,
                      int B, int HW, int C, void* stream);
 int kd_gate_add_chunks(int B, int HW);
+/* The launch shape of an fp32 convolution / token GEMM (ConvShape, csrc/common.h), as the plan builder and the test entry
+ * points compute it once per launch.  A pure host function: it touches no device.  geom[22]: B, Hi, Wi, Cin, ldx, Ho, Wo,
+ * Cout, KH, KW, stride, pad, rr_cin, act, ldres, ldgs, out_mode (0 NHWC, 1 PixelShuffle, 2 NCHW), ldy, yoff, wz_rows,
+ * wz_count, seg_c0 - the fields of the launch's parameters that are no pointers.  has / al16: bits 1 y, 2 bias, 4 residual,
+ * 8 gated map, 16 gate, 32 split-K scratch - which of them the launch gets (y always) and which are 16-byte aligned.  cus:
+ * compute units of the device.  out[12]: 1 for the generic kernel / 0 for the buffer-load one, tile rows, tile columns,
+ * waves along each, grid x, y, z, threads per workgroup, k-splits (1 = none), 16-byte epilogue, chunks per image of the
+ * GroupNorm partials the launch can leave (0 = none).  Returns 1 (kd_last_error) where no kernel takes the shape. */
+int kd_conv_launch_shape(const int* geom, unsigned has, unsigned al16, int cus, int* out);
 /* Linear attention (dim_head 64), the kernels the plan runs, for unit tests.  kd_linattn_dwconv_nhwc: y = depthwise 3x3
  * (zero padding) of x, both [B][H][W][3 heads 64] (q | k | v), weights the library's to_{q,k,v}.2.weight [heads 64][1][3][3];
  * d_part [B][ceil(H W / kd_linattn_chunk_tokens())][heads 64][2] = (max, sum of exp(k - max)) of k per chunk of tokens.

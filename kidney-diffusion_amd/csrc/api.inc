@@ -487,6 +487,10 @@ int entry_x3_ws(EntryBufs& bufs, void** ws, hipStream_t s) {
 }
 // the launch shape of a bf16x3 GEMM of a test entry point: one per call, for the device that is current
 X3Shape entry_x3_shape(int G, int64_t M, int N, int K) { return gemm_bf16x3_shape(G, (int)M, N, K, gemm_bf16x3_device_cus()); }
+// a conv of a test entry point: its launch shape from the pointers it holds, one per call, for the device that is current
+int entry_conv(const ConvParams& p, hipStream_t s) {
+  return launch_conv_igemm(p, conv_shape(p, conv_ptrs_of(p), gemm_bf16x3_device_cus()), s);
+}
 }  // namespace
 
 // act bit 8 (0x100) selects the row-run K layout used for the small-Cin init convs
@@ -522,10 +526,12 @@ int kd_conv2d_nhwc(const float* d_x, const float* d_w_oihw, const float* d_bias,
       p.out_mode = OUT_PIXSHUF;
       p.ldy = Cout / 4;
     }
-    const int ks = conv_ksplit(p);  // small-M shapes take the split-K path, as in the plan
-    if (ks > 1) rc = bufs.get(&part, (size_t)ks * B * p.Ho * p.Wo * Cout * sizeof(float));
+    ConvPtrs ptrs = conv_ptrs_of(p);   // small-M shapes take the split-K path, as in the plan: a scratch (hipMalloc) is on offer
+    ptrs.has |= CONV_PARTIAL;
+    const ConvShape sh = conv_shape(p, ptrs, gemm_bf16x3_device_cus());
+    if (sh.ksplit > 1) rc = bufs.get(&part, (size_t)sh.ksplit * B * p.Ho * p.Wo * Cout * sizeof(float));
     p.partial = part;
-    if (!rc) rc = launch_conv_igemm(p, s);
+    if (!rc) rc = launch_conv_igemm(p, sh, s);
   }
   return entry_finish(rc, s);
 }
@@ -593,7 +599,7 @@ int kd_conv3x3_winograd_nhwc(const float* d_x, const float* d_w_oihw, const floa
     p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.out_mode = OUT_NHWC; p.ldy = Cout;
     p.wz_rows = (int)Mt; p.wz_count = 16;
-    rc = launch_conv_igemm(p, s);
+    rc = entry_conv(p, s);
   }
   if (!rc) rc = launch_wino_out(D, d_bias, nullptr, 0, d_y, B, H, W, Cout, 0, Mt, s);
   return entry_finish(rc, s);
@@ -637,7 +643,7 @@ int kd_conv3x3_winograd4_nhwc(const float* d_x, const float* d_w_oihw, const flo
     p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.out_mode = OUT_NHWC; p.ldy = Cout;
     p.wz_rows = (int)Mt; p.wz_count = 36;
-    rc = launch_conv_igemm(p, s);
+    rc = entry_conv(p, s);
   }
   if (!rc) rc = launch_wino4_out(D, d_bias, d_res, Cout, d_y, Cout, seg, B, H, W, Cout, s);
   if (!rc && seg)   // the 16-channel segments of a group are adjacent: [B][G][(Cout / G / 16) nchunk][2]
@@ -747,7 +753,7 @@ int kd_gn_conv3x3_winograd_fused_nhwc(const float* d_x, const float* d_gamma, co
   if (!rc) rc = launch_gn_fold(stats, d_gamma, d_beta, d_scale_shift, 2 * Cin, ab, B, Cin, G, s);
   if (!rc) rc = launch_wino_fused128_items(items, B, H, W, Cout, s);
   if (!rc)
-    rc = launch_wino_fused_gn128(d_x, ldx, ab, U, d_bias, d_res, Cout, d_y, B, H, W, Cin, Cout, opart, opart ? G : 0, items, s);
+    rc = launch_wino_fused_gn128(d_x, ldx, ab, U, d_bias, d_res, Cout, d_y, B, H, W, Cin, Cout, opart, opart ? G : 0, items, gemm_bf16x3_device_cus(), s);
   if (!rc && opart)
     rc = launch_gn_finalize(opart, d_out_stats, (int)wino_fused_out_stats_chunks(H, W, Cout, G), B, G,
                             (double)H * W * (Cout / G), eps, s);
@@ -827,6 +833,21 @@ int kd_global_context_gate(const float* d_x, int B, int HW, int C, const float* 
 }
 
 int kd_gate_add_chunks(int B, int HW) { return B > 0 && HW > 0 ? gate_add_chunks(B, HW) : 0; }
+int kd_conv_launch_shape(const int* geom, unsigned has, unsigned al16, int cus, int* out) {
+  KD_REQUIRE(geom && out && cus > 0, "kd_conv_launch_shape: null argument or no compute units");
+  ConvParams p{};
+  int* const field[22] = {&p.B,  &p.Hi,  &p.Wi,     &p.Cin, &p.ldx,   &p.Ho,    &p.Wo,       &p.Cout, &p.KH,   &p.KW,      &p.stride,
+                          &p.pad, &p.rr_cin, &p.act, &p.ldres, &p.ldgs, &p.out_mode, &p.ldy, &p.yoff, &p.wz_rows, &p.wz_count, &p.seg_c0};
+  for (int i = 0; i < 22; ++i) *field[i] = geom[i];
+  KD_REQUIRE(p.B > 0 && p.Ho > 0 && p.Wo > 0 && p.Cout > 0 && p.Cin > 0 && p.KH > 0 && p.KW > 0, "kd_conv_launch_shape: empty conv");
+  const ConvShape sh = conv_shape(p, ConvPtrs{has | CONV_Y, al16}, cus);
+  KD_REQUIRE(sh.variant >= 0, "kd_conv_launch_shape: no kernel takes a batched GEMM off the buffer-load fast path");
+  const ConvTile& t = conv_tile(sh.variant);
+  const int rec[12] = {t.igemm, t.bm, t.bn, t.waves_m, t.waves_n, (int)sh.grid[0], (int)sh.grid[1], (int)sh.grid[2],
+                       64 * t.waves_m * t.waves_n, sh.ksplit, sh.wide_epilogue, sh.seg_chunks};
+  std::copy(rec, rec + 12, out);
+  return 0;
+}
 
 int kd_gate_add_nhwc(const float* d_a, const float* d_gate, const float* d_r, int ldr, float* d_y, int ldy, double* d_seg,
                      int B, int HW, int C, void* stream) {
@@ -923,7 +944,7 @@ int kd_gn_conv3x3_winograd4_nhwc(const float* d_x, int ldx, const float* d_stats
       p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
       p.out_mode = OUT_NHWC; p.ldy = Cout;
       p.wz_rows = (int)Mt; p.wz_count = 36;
-      rc = launch_conv_igemm(p, s);
+      rc = entry_conv(p, s);
     }
     if (!rc)
       rc = launch_wino4_out(D, d_bias, d_res ? d_res + (size_t)b0 * HW * ldres : nullptr, ldres, d_y + (size_t)b0 * HW * Cout,
@@ -966,8 +987,9 @@ int kd_init_conv_planes_c_nchw(const float* d_x, const float* d_self_cond, const
     rc = hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, s) != hipSuccess;
     if (rc) set_error("kd_init_conv_planes_nchw: event setup failed");
   }
+  const int cus = gemm_bf16x3_device_cus();
   for (int i = 0; i < iters && !rc; ++i)
-    rc = launch_init_conv(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, s);
+    rc = launch_init_conv(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, n3 + n7 + n15, nullptr, B, S, n3, n7, n15, cus, s);
   if (!rc && ms && hipEventRecord(e1, s) != hipSuccess) {
     set_error("kd_init_conv_planes_nchw: event record failed");
     rc = 1;
@@ -1007,8 +1029,9 @@ int kd_init_conv_plain_nchw(const float* d_x, const float* d_self_cond, const fl
     rc = hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, s) != hipSuccess;
     if (rc) set_error("kd_init_conv_plain_nchw: event setup failed");
   }
+  const int cus = gemm_bf16x3_device_cus();
   for (int i = 0; i < iters && !rc; ++i)
-    rc = launch_init_plain(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, ldy, d_seg, B, S, n, ksize, s);
+    rc = launch_init_plain(d_x, d_self_cond, channels, np, wp, d_bias, d_res, d_y, ldy, d_seg, B, S, n, ksize, cus, s);
   if (!rc && ms && hipEventRecord(e1, s) != hipSuccess) {
     set_error("kd_init_conv_plain_nchw: event record failed");
     rc = 1;
@@ -1052,7 +1075,7 @@ static int final_conv_nchw(const std::string& w, const float* d_feat, const floa
     p.Ho = H; p.Wo = W; p.Cout = nf;
     p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.out_mode = OUT_NHWC; p.ldy = nf;
-    rc = launch_conv_igemm(p, s);
+    rc = entry_conv(p, s);
   }
   if (!rc) rc = launch_final_gather_k(pm, stat, d_bias, d_out, channels, ksize, B, H, W, s);
   return entry_finish(rc, s);

@@ -62,8 +62,8 @@ struct ConvParams {
   // batched 1x1 GEMM (Winograd positions): rows [z*wz_rows, (z+1)*wz_rows) use weight slab z of
   // wz_count slabs [Cout][Cin]; 0 = one weight tensor.  wz_rows must be a multiple of 128.
   int wz_rows, wz_count;
-  // split-K for small-M layers: scratch [conv_ksplit(p)][M][Cout] floats, or nullptr (never split);
-  // ksplit is filled in by launch_conv_igemm
+  // split-K for small-M layers: scratch [ConvShape::ksplit][M][Cout] floats, or nullptr (never split);
+  // ksplit is filled in by launch_conv_igemm from its ConvShape
   float* partial;
   int ksplit;
   // GroupNorm partials of the output for the layer that reads it (SegSrc): [B][seg_nseg][seg chunks][2] doubles with
@@ -72,14 +72,38 @@ struct ConvParams {
   double* seg_partial;
   int seg_nseg;
   int seg_c0;  // channel of y that is segment 0 of seg_partial (several launches can fill slices of one buffer)
-  int wide_epilogue;  // set by launch_conv_igemm: 16-byte epilogue accesses (alignment checked there)
+  int wide_epilogue;  // filled in by launch_conv_igemm from its ConvShape: 16-byte epilogue accesses
 };
 
-int launch_conv_igemm(const ConvParams& p, hipStream_t s);
-// number of K splits launch_conv_igemm uses for this shape when `partial` is provided (1 = none)
-int conv_ksplit(const ConvParams& p);
-// chunks per image of the GroupNorm partials the launch can leave (ConvParams::seg_partial), 0 = it cannot
-int conv_seg_chunks(const ConvParams& p);
+// What the launch shape needs to know of a launch's pointers, without the pointers: which of the optional ones there are
+// (`has`: CONV_RES, CONV_GATE_SRC; CONV_PARTIAL: a split-K scratch will be provided) and which addresses are 16-byte
+// aligned (`al16`; an absent pointer counts as aligned).  A plan knows both at its build (arena offsets, weight addresses)
+enum : unsigned { CONV_Y = 1, CONV_BIAS = 2, CONV_RES = 4, CONV_GATE_SRC = 8, CONV_GATE = 16, CONV_PARTIAL = 32 };
+struct ConvPtrs {
+  unsigned has, al16;
+};
+ConvPtrs conv_ptrs_of(const ConvParams& p);   // of the pointers p holds now (test entry points: theirs are real)
+// The kernels a conv can launch: the buffer-DMA kernel (fast path) and the generic one, by tile
+enum ConvVariant { CONV_BUF_256x128, CONV_BUF_128x128, CONV_BUF_128x64, CONV_BUF_64x128,
+                   CONV_IGEMM_128x32, CONV_IGEMM_128x64, CONV_IGEMM_64x128, CONV_IGEMM_128x128, CONV_VARIANTS };
+struct ConvTile {
+  int igemm, bm, bn, waves_m, waves_n;   // conv_igemm_kernel | conv_buf_kernel <bm, bn, waves_m, waves_n>, 64 waves_m waves_n threads
+};
+const ConvTile& conv_tile(int variant);   // (a host function: a table at namespace scope would land in the device code too)
+// The shape of a launch, in the spirit of X3Shape: a value that whoever emits the launch (a plan at its build, with the CU
+// count it read once; a test entry point, once per call) computes once; the scratch, the partials and the launch use that one
+struct ConvShape {
+  int variant;          // ConvVariant; -1: no kernel takes the shape (a batched GEMM off the fast path)
+  unsigned grid[3];     // tiles of M, tiles of Cout, k-splits
+  int ksplit;           // > 1: split-K (needs ConvParams::partial [ksplit][M][Cout]; the reduction kernel follows), 1: none
+  int wide_epilogue;    // 16-byte epilogue accesses
+  int seg_chunks;       // chunks per image of the GroupNorm partials the launch can leave (ConvParams::seg_partial), 0 = it cannot
+  unsigned al16;        // the pointers whose 16-byte alignment it counts on: launch_conv_igemm refuses others
+};
+// a pure function of its arguments (of p: the geometry - no pointer is read)
+ConvShape conv_shape(const ConvParams& p, ConvPtrs ptrs, int cus);
+// launches what `sh` says and decides nothing: sh must come from this p's geometry and pointers
+int launch_conv_igemm(const ConvParams& p, const ConvShape& sh, hipStream_t s);
 int64_t conv_macs(const ConvParams& p);
 
 // weight re-packing (device→device)
@@ -215,7 +239,7 @@ int launch_wino_fused128_items(void* items, int B, int H, int W, int N, hipStrea
 size_t wino_fused_out_stats_chunks(int H, int W, int N, int G);
 int launch_wino_fused_gn128(const float* x, int ldx, const float* ab, const float* U, const float* bias, const float* res,
                             int ldres, float* y, int B, int H, int W, int C, int N, double* out_partial, int out_groups,
-                            const void* items, hipStream_t s);
+                            const void* items, int cus, hipStream_t s);
 int wino_fused_gn_max_cin();   // largest Cin launch_wino_fused_gn128 takes (its affine table lives in LDS)
 // stats[b][g] = (mean, rstd) from `chunks` (sum, sum of squares) partials per (b, g), summed in index order
 int launch_gn_finalize(const double* partial, float* stats, int chunks, int B, int G, double count, float eps,
@@ -310,14 +334,14 @@ int launch_init_conv_pack(const float* w3, const float* w7, const float* w15, fl
 // y[b][py][px][0 .. n3+n7+n15) (row stride ldy) = cat(conv3, conv7, conv15)(x | sc) + (bias | res); x, sc: cx planes
 // each; sc (np = 2 cx only, nullptr = zeros); seg: GroupNorm partials [B][C/16][S*S/32][2] or nullptr
 int launch_init_conv(const float* x_nchw, const float* sc_nchw, int cx, int np, const float* wp, const float* bias, const float* res,
-                     float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s);
+                     float* y, int ldy, double* seg, int B, int S, int n3, int n7, int n15, int cus, hipStream_t s);
 // ---- Unet(init_cross_embed=False): the per-step share of one k x k conv (k = 3 | 5 | 7) of the np planes to n <= 128 channels in
 // one kernel of the same form; false where k is another size or the kernel's LDS does not hold the weights
 bool init_plain_ok(int S, int n, int k, int np);
 size_t init_plain_weight_floats(int n, int k, int np);
 int launch_init_plain_pack(const float* w_oihw, float* out, int n, int Itot, int c0, int np, int k, hipStream_t s);
 int launch_init_plain(const float* x_nchw, const float* sc_nchw, int cx, int np, const float* wp, const float* bias, const float* res,
-                      float* y, int ldy, double* seg, int B, int S, int n, int k, hipStream_t s);
+                      float* y, int ldy, double* seg, int B, int S, int n, int k, int cus, hipStream_t s);
 
 // ---- linear attention, dim_head = 64 (kernels_linattn.hip).  q | k | v are column slices of one [B][H][W][3 inner] map
 constexpr int LA_CHUNK = 64;   // tokens per chunk of the k-softmax partials

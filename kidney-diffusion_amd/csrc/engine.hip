@@ -322,7 +322,9 @@ struct kd_unet {
   kd::CondSeg* d_cond_segs = nullptr;
   uint32_t cond_row_total = 0;
   void* x3_ws = nullptr;   // slabs of the bf16x3 GEMMs' left-over tiles, allocated with the first such layer (emit_x3_gemm)
-  int cus = 0;   // CUs of the device the plan was built on: every launch shape of its bf16x3 GEMMs (X3Shape) comes from this
+  // CUs of the device the plan was built on, read once: every launch shape of the plan comes from this - its bf16x3 GEMMs
+  // (X3Shape), its fp32 convs (ConvShape) and the persistent grids of the fused Winograd conv and the init convs
+  int cus = 0;
 
   float* P(size_t off) const { return (float*)((off & COND_FLAG) ? cond_ws + (off & ~COND_FLAG) : ws + off); }
   ~kd_unet() {
@@ -780,9 +782,22 @@ struct Builder {
     const bool ext = o.out_external;
     const int res_coff = o.res_coff, o_yoff = o.yoff;
     const int Bset = x3_linear_images(x, Cout, K, stride, pad, o);   // > 0: on the bf16x3 kernel, this many images per launch
+    // The launch shape, decided here once: what the plan knows of the pointers at its build is a fact (arena offsets count
+    // from a hipMalloc base, every block starts on 256 bytes; weights have their addresses; an output the plan does not own
+    // stays off the 16-byte path).  The scratch, the partials and the launch below all follow this one value
+    const int seg_c0 = o.seg_c0 >= 0 ? o.seg_c0 : o.yoff;   // in channels of the tensor y (a slice counts from its own first)
+    p.seg_c0 = y.coff + seg_c0;                              // block channel of the partial buffer's segment 0
+    auto al16 = [](bool aligned, unsigned bit) { return aligned ? bit : 0u; };
+    ConvPtrs ptrs;
+    ptrs.has = CONV_Y | CONV_PARTIAL | (bias ? CONV_BIAS : 0) | (o.res ? CONV_RES : 0) | (o.gate_src ? CONV_GATE_SRC : 0) |
+               (o.gate ? CONV_GATE : 0);
+    ptrs.al16 = CONV_PARTIAL | al16(!ext && y.off % 16 == 0, CONV_Y) | al16((uintptr_t)bias % 16 == 0, CONV_BIAS) |
+                al16(o.res && (o.res->at() + (size_t)res_coff * sizeof(float)) % 16 == 0, CONV_RES) |
+                al16(o.gate_src && o.gate_src->at() % 16 == 0, CONV_GATE_SRC) | al16(o.gate && o.gate->at() % 16 == 0, CONV_GATE);
+    const ConvShape sh = conv_shape(p, ptrs, u->cus);
     // small-M layers (batch-1 patches): split-K scratch, released right after the launch is recorded
     // (one in-order stream: the next op that reuses the block runs after the reduction)
-    const int ks = conv_ksplit(p);
+    const int ks = sh.ksplit;
     T part;
     if (ks > 1) {   // (scratch of this launch pair, not conditioning state: never in the cond region / table)
       auto ph = scope(phase == Phase::Cond ? Phase::Step : phase);
@@ -792,22 +807,15 @@ struct Builder {
     // GroupNorm partials of the output, left by the epilogue (channels [yoff, yoff + Cout) of y, or the Cout / 4
     // shuffled channels): several launches filling slices of one tensor (init conv) share the chunk count
     size_t sego = 0;
-    int seg_nseg = 0, seg_c0 = 0, seg_nchunk = 0;
+    int seg_nseg = 0, seg_nchunk = 0;
     if (o.want_seg && !ext && step_op()) {
       const int cw = o.out_mode == OUT_PIXSHUF ? Cout / 4 : Cout;
-      seg_c0 = o.seg_c0 >= 0 ? o.seg_c0 : o.yoff;   // in channels of the tensor y (a slice counts from its own first)
       const int span = o.seg_c0 >= 0 ? o.seg_cn : cw;
-      ConvParams probe = p;
-      // (the residual's channel offset decides the alignment of its rows: checked here, at plan time)
-      probe.res = o.res ? (const float*)(uintptr_t)(4096 + (o.res->at() % 4096) + (size_t)res_coff * sizeof(float)) : nullptr;
-      probe.gate_src = o.gate_src ? (const float*)16 : nullptr;
-      probe.seg_c0 = y.coff + seg_c0;
-      probe.partial = ks > 1 ? (float*)16 : nullptr;   // split-K: statistics from the reduction kernel, one chunk per pixel
       // (the bf16x3 form of a 1x1 conv whose tiles are cut in k leaves its partials from the summing launch, a chunk per 8 rows)
       const bool lin3 = Bset > 0;
-      int nchunk = conv_seg_chunks(probe) > 0 && lin3 && o.out_mode == OUT_NHWC
+      int nchunk = sh.seg_chunks > 0 && lin3 && o.out_mode == OUT_NHWC
                        ? Ho * Wo / gemm_bf16x3_shape(1, Bset * Ho * Wo, Cout, x.C, u->cus).seg_rows()
-                       : conv_seg_chunks(probe);
+                       : sh.seg_chunks;
       // (the bf16x3 PixelShuffle epilogue takes maps 16 pixels wide - conv_buf_kernel's wants 32 - with the same chunks: four
       // sub-positions per 32 input pixels)
       if (lin3 && o.out_mode == OUT_PIXSHUF && nchunk == 0 && (Ho * Wo) % 32 == 0 && ((Cout >> 2) & 31) == 0)
@@ -882,9 +890,8 @@ struct Builder {
       if (seg) {
         q.seg_partial = seg.d();
         q.seg_nseg = seg_nseg;
-        q.seg_c0 = p.yoff - o_yoff + seg_c0;   // block channel of the partial buffer's segment 0
       }
-      return launch_conv_igemm(q, s);
+      return launch_conv_igemm(q, sh, s);
     });
     if (ks > 1) free(part);
     int cin = o.cin_logical > 0 ? o.cin_logical : x.C;
@@ -1470,9 +1477,10 @@ struct Builder {
     const std::string shape_key = std::to_string(Bx) + "x" + std::to_string(H) + "x" + std::to_string(W) + "x" + std::to_string(Cout);
     const float* items = cached("winof128_items:" + shape_key, wino_fused128_items_count(Bx, H, W, Cout) * 4,
                                 [&](float* dst) { KD_THROW_IF(launch_wino_fused128_items(dst, Bx, H, W, Cout, 0)); });
+    const int cus = u->cus;
     emit([=](hipStream_t s) {
       return launch_wino_fused_gn128(xr.f(), ldx, abr.f(), U, bias, rr.f(), ldres, yr.f(), Bx, H, W, Cin, Cout, seg.d(),
-                                     so_ ? Cout / 16 : 0, items, s);
+                                     so_ ? Cout / 16 : 0, items, cus, s);
     }, "wino fused M" + std::to_string((int64_t)Bx * H * W) + " Cin" + std::to_string(Cin) + " Cout" +
            std::to_string(Cout), m);
     free(ab);

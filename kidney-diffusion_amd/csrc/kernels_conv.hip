@@ -254,7 +254,7 @@ __device__ __forceinline__ void store_tile_regs_pixshuf(const ConvParams& p,
 // to the wave and leaves as 4 stores (+ 4 loads per added map) instead of 16 (+ 16).  A workgroup's vector-memory
 // instructions - DMA pieces, epilogue loads and stores - share one address pipe per CU, and the short-K 1x1 convs
 // on the big maps are bound by it: a 128 x 64 x 256 tile is 48 DMA pieces and 64 four-byte epilogue instructions
-// per wave.  Needs full 32-row tiles inside one image, Cout % 4 == 0 and 16-byte aligned rows (conv_wide_ok).
+// per wave.  Needs full 32-row tiles inside one image, Cout % 4 == 0 and 16-byte aligned rows (conv_shape).
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool STATS>
 __device__ __forceinline__ void store_tile_regs_wide(const ConvParams& p, float* lds,
                                                      f32x16 (&acc)[BM / WAVES_M / 32][BN / WAVES_N / 32], int64_t m0,
@@ -795,7 +795,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(ConvParams p, i
     float v[4] = {s[0], s[1], s[2], s[3]};
     epilogue_store<4>(p, m, n, v);
     if (p.seg_partial) {
-      // GroupNorm partials of the finished rows (conv_seg_chunks: NHWC, Cout % 16 == 0): one chunk per output pixel, the
+      // GroupNorm partials of the finished rows (ConvShape::seg_chunks: NHWC, Cout % 16 == 0): one chunk per output pixel, the
       // four lanes that hold a 16-channel segment of a row are adjacent (idx = m C4 + n / 4, C4 % 4 == 0)
       double d1 = (double)((v[0] + v[1]) + (v[2] + v[3]));
       double d2 = (double)fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3])));
@@ -825,7 +825,8 @@ int64_t conv_macs(const ConvParams& p) {
   return (int64_t)p.B * p.Ho * p.Wo * p.Cout * p.Cin * p.KH * p.KW;
 }
 
-// Shape conditions of the buffer-DMA fast path (pointer alignment is checked at launch).
+// ------------------------------------------------------------------------------ launch shape
+// Shape conditions of the buffer-DMA fast path.
 static bool fast_shape_ok(const ConvParams& p) {
   const int64_t w_bytes = (int64_t)(p.wz_rows > 0 ? p.wz_count : p.KH * p.KW) * p.Cout * p.Cin * 4;
   // the fast kernel addresses the activations with 32-bit byte offsets relative to the image of the
@@ -838,13 +839,66 @@ static bool fast_shape_ok(const ConvParams& p) {
          (gemm || span * img_bytes < 0x7fffffff);
 }
 
+const ConvTile& conv_tile(int variant) {
+  static const ConvTile tiles[CONV_VARIANTS] = {{0, 256, 128, 4, 2}, {0, 128, 128, 2, 2}, {0, 128, 64, 2, 2}, {0, 64, 128, 1, 4},
+                                                {1, 128, 32, 4, 1},  {1, 128, 64, 2, 2},  {1, 64, 128, 1, 4}, {1, 128, 128, 2, 2}};
+  return tiles[variant];
+}
+
+ConvPtrs conv_ptrs_of(const ConvParams& p) {
+  const void* const q[6] = {p.y, p.bias, p.res, p.gate_src, p.gate, p.partial};
+  ConvPtrs r{0, 0};
+  for (int i = 0; i < 6; ++i) {
+    if (q[i]) r.has |= 1u << i;
+    if (((uintptr_t)q[i] & 15) == 0) r.al16 |= 1u << i;
+  }
+  return r;
+}
+
+// Tile of the buffer-DMA kernel for a fast-path shape (fast_shape_ok) that is not split in K
+static ConvVariant fast_tile(const ConvParams& p, int64_t M, int cus) {
+  const int64_t tiles256 = ((M + 255) / 256) * ((p.Cout + 127) / 128);
+  // 256x128 (one 8-wave workgroup per CU) needs a K loop long enough to amortise its serial
+  // prologue/epilogue; short-K 1x1 convs run as two 128x128 workgroups per CU, which overlap one
+  // tile's epilogue with the other's loop (measured in the step: 3x3 Cin=128 layers still prefer 256x128)
+  const int k_chunks = p.KH * p.KW * (p.Cin / BK);
+  if (p.wz_rows > 0) {
+    // Batched position GEMMs of the Winograd layers: M = positions x tiles is a few thousand rows, so the launch is a
+    // handful of tile rounds and the last, partly filled round decides its time (36 x 256 rows x 1024 columns: 576
+    // tiles of 128 x 128 on 512 slots = two rounds for 1.1 rounds of work).  Pick the tile shape whose rounds are
+    // fullest, larger tiles winning ties by their better operand reuse (weights: per-tile efficiency seen in the step)
+    struct Cand { ConvVariant v; int per_cu; double w; };
+    const Cand cands[3] = {{CONV_BUF_256x128, 1, 1.00}, {CONV_BUF_128x128, 2, 0.97}, {CONV_BUF_128x64, 3, 0.92}};
+    ConvVariant best = CONV_BUF_128x64;
+    double best_eff = 0.0;
+    for (const Cand& c : cands) {
+      const ConvTile& t = conv_tile(c.v);
+      if (p.wz_rows % t.bm) continue;   // a tile must lie in one weight slab
+      const int64_t tiles = ((M + t.bm - 1) / t.bm) * ((p.Cout + t.bn - 1) / t.bn);
+      const int64_t slots = (int64_t)cus * c.per_cu;
+      const double eff = c.w * (double)tiles / (double)(((tiles + slots - 1) / slots) * slots);
+      if (eff > best_eff + 1e-9) {
+        best_eff = eff;
+        best = c.v;
+      }
+    }
+    return best;
+  }
+  // 1x1 convs with K <= 256 (ResnetBlock skip convs with the gate epilogue, pixel-shuffle upsamples)
+  // move as many bytes as they compute: three 128x64 workgroups per CU keep more loads in flight
+  // (measured -12..16 % on them; the Winograd GEMMs of the same K lose 4 % with this shape)
+  if (p.KH * p.KW == 1 && k_chunks <= 8) return CONV_BUF_128x64;
+  if (tiles256 >= 512 && (p.KH * p.KW > 1 || k_chunks >= 64)) return CONV_BUF_256x128;
+  if (((M + 127) / 128) * ((p.Cout + 127) / 128) >= 512) return CONV_BUF_128x128;
+  return CONV_BUF_128x64;   // few tiles (deep 16x16 levels, attention projections): 128x64 tiles, 3 workgroups per CU
+}
+
 // Number of K splits for a conv whose M x Cout tiles cannot fill the chip (batch-1 patches of the
 // ultra-res grid: M = 64 .. 1024 pixels against K = 9 x 2048): enough workgroups for ~3 per CU, at
-// least 4 chunks each.  1 = no split.  The caller provides ConvParams::partial [ksplit][M][Cout].
-int conv_ksplit(const ConvParams& p) {
+// least 4 chunks each.  1 = no split.
+static int conv_ksplit(const ConvParams& p, int64_t M) {
   if (!fast_shape_ok(p) || p.wz_rows > 0 || p.Cout < 64 || (p.Cout & 3)) return 1;
-  const int64_t M = (int64_t)p.B * p.Ho * p.Wo;
-  // (M <= 64 runs 64 x 128 tiles, see launch_conv_igemm: half as many tiles as 128 x 64 counts here)
+  // (M <= 64 runs 64 x 128 tiles: half as many tiles as 128 x 64 counts here)
   const int64_t tiles = M <= 64 ? (p.Cout + 127) / 128 : ((M + 127) / 128) * ((p.Cout + 63) / 64);
   const int nchunks = p.KH * p.KW * (p.Cin / BK);
   if (tiles >= 256 || nchunks < 16) return 1;
@@ -854,169 +908,98 @@ int conv_ksplit(const ConvParams& p) {
   return (nchunks + per - 1) / per;
 }
 
-// Chunks per image of the GroupNorm partials this launch can leave in its epilogue (ConvParams::seg_partial), or 0
-// when its epilogue cannot (split-K, the LDS-staged epilogue, ragged shapes): the plan then keeps the statistics pass.
-int conv_seg_chunks(const ConvParams& p) {
+ConvShape conv_shape(const ConvParams& p, ConvPtrs ptrs, int cus) {
   const int64_t hw = (int64_t)p.Ho * p.Wo, M = (int64_t)p.B * hw;
-  if (p.partial && conv_ksplit(p) > 1)   // split-K: the reduction kernel leaves one chunk per output pixel (16-byte path)
-    return (p.out_mode == OUT_NHWC && !(p.Cout & 15) && !((p.yoff - p.seg_c0) & 15) && !(p.ldy & 3) && !(p.yoff & 3) &&
-            (!p.res || (!(p.ldres & 3) && !((uintptr_t)p.res & 15))) && (!p.gate_src || !(p.ldgs & 3)) && hw < 0x7fffffff)
-               ? (int)hw
-               : 0;
-  if ((hw & 31) || (p.Cout & 15) || ((p.yoff - p.seg_c0) & 15)) return 0;
-  if (p.out_mode == OUT_NHWC) {
-    if (p.act != ACT_NONE || (p.gate_src && p.res)) return 0;
-    return (int)(hw >> 5);
-  }
-  if (p.out_mode == OUT_PIXSHUF) {
+  const bool res = ptrs.has & CONV_RES, gate = ptrs.has & CONV_GATE_SRC;
+  auto al = [&](unsigned bit) { return (ptrs.al16 & bit) != 0 || !(ptrs.has & bit); };
+  ConvShape sh{};
+  sh.al16 = ptrs.al16 | ~ptrs.has;
+  sh.ksplit = (ptrs.has & CONV_PARTIAL) ? conv_ksplit(p, M) : 1;
+  const bool seg_cols = !(p.Cout & 15) && !((p.yoff - p.seg_c0) & 15);   // whole 16-channel segments of the partials
+  if (sh.ksplit > 1) {
+    // 64-row tiles for an 8x8 map of a batch-1 patch (a 128-row tile would spend half its MFMAs on padding and these
+    // launches, K up to 9 x 3072, were bound by exactly that: 124 us for 226 MB of weights), 128 columns
+    sh.variant = M <= 64 ? CONV_BUF_64x128 : CONV_BUF_128x64;
+    sh.wide_epilogue = p.Cout % 4 == 0;   // the raw partial tiles [z][M][Cout] with 16-byte stores
+    // the reduction kernel leaves one chunk per output pixel (its 16-byte path)
+    if (p.out_mode == OUT_NHWC && seg_cols && !(p.ldy & 3) && !(p.yoff & 3) && (!res || (!(p.ldres & 3) && al(CONV_RES))) &&
+        (!gate || !(p.ldgs & 3)) && hw < 0x7fffffff)
+      sh.seg_chunks = (int)hw;
+  } else {
     const bool fast = fast_shape_ok(p) && M > 64;
-    if (!fast || ((p.Cout >> 2) & 31) || (p.Wo & 31) || p.gate_src || p.res) return 0;
-    return (int)(hw >> 5) * 4;
+    // 16-byte epilogue (store_tile_regs_wide): output rows, and those of every map the epilogue adds, start on 16-byte
+    // boundaries; whole 32-row MFMA tiles (and one image per tile where a per-image gate is applied).  The narrow epilogue
+    // takes the unaligned and ragged shapes
+    const bool wide_ok = M % 32 == 0 && p.Cout % 4 == 0 && p.ldy % 4 == 0 && p.yoff % 4 == 0 && al(CONV_Y) && al(CONV_BIAS) &&
+                         (!res || (al(CONV_RES) && p.ldres % 4 == 0)) &&
+                         (!gate || (al(CONV_GATE_SRC) && al(CONV_GATE) && p.ldgs % 4 == 0 && hw % 32 == 0));
+    sh.wide_epilogue = wide_ok && (p.out_mode == OUT_NHWC || (fast && p.out_mode == OUT_PIXSHUF));
+    if (fast) sh.variant = fast_tile(p, M, cus);
+    else if (p.wz_rows > 0) sh.variant = -1;   // batched GEMM: the buffer-load fast path only
+    else if (p.Cout <= 32) sh.variant = CONV_IGEMM_128x32;
+    else if (p.Cout <= 64) sh.variant = CONV_IGEMM_128x64;
+    else if (M <= 64) sh.variant = CONV_IGEMM_64x128;
+    else sh.variant = CONV_IGEMM_128x128;
+    // partials from the epilogue: whole 32-row tiles of one image (not after an activation, not with gate and residual)
+    if (!(hw & 31) && seg_cols) {
+      if (p.out_mode == OUT_NHWC && p.act == ACT_NONE && !(gate && res)) sh.seg_chunks = (int)(hw >> 5);
+      if (p.out_mode == OUT_PIXSHUF && fast && !((p.Cout >> 2) & 31) && !(p.Wo & 31) && !gate && !res)
+        sh.seg_chunks = (int)(hw >> 5) * 4;
+    }
   }
-  return 0;
-}
-
-// Tile shape of the buffer-DMA kernel for a fast-path shape (fast_shape_ok)
-static int launch_conv_fast(const ConvParams& p, int64_t M, hipStream_t s) {
-  const int64_t tiles256 = ((M + 255) / 256) * ((p.Cout + 127) / 128);
-  // 256x128 (one 8-wave workgroup per CU) needs a K loop long enough to amortise its serial
-  // prologue/epilogue; short-K 1x1 convs run as two 128x128 workgroups per CU, which overlap one
-  // tile's epilogue with the other's loop (measured in the step: 3x3 Cin=128 layers still prefer 256x128)
-  const int k_chunks = p.KH * p.KW * (p.Cin / BK);
-  static const int shortk = kd_switch("KD_SHORTK_TILE", 0);   // experiment switch
-  if (p.wz_rows > 0) {
-    // Batched position GEMMs of the Winograd layers: M = positions x tiles is a few thousand rows, so the launch is a
-    // handful of tile rounds and the last, partly filled round decides its time (36 x 256 rows x 1024 columns: 576
-    // tiles of 128 x 128 on 512 slots = two rounds for 1.1 rounds of work).  Pick the tile shape whose rounds are
-    // fullest, larger tiles winning ties by their better operand reuse (weights: per-tile efficiency seen in the step)
-    static int cus = 0;
-    if (!cus) {
-      hipDeviceProp_t prop;
-      int dev = 0;
-      KD_HIP_CHECK(hipGetDevice(&dev));
-      KD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-      cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    struct Cand { int bm, bn, per_cu; double w; };
-    const Cand cands[3] = {{256, 128, 1, 1.00}, {128, 128, 2, 0.97}, {128, 64, 3, 0.92}};
-    int best = 2;
-    double best_eff = 0.0;
-    for (int i = 0; i < 3; ++i) {
-      if (p.wz_rows % cands[i].bm) continue;   // a tile must lie in one weight slab
-      const int64_t tiles = ((M + cands[i].bm - 1) / cands[i].bm) * ((p.Cout + cands[i].bn - 1) / cands[i].bn);
-      const int64_t slots = (int64_t)cus * cands[i].per_cu;
-      const double eff = cands[i].w * (double)tiles / (double)(((tiles + slots - 1) / slots) * slots);
-      if (eff > best_eff + 1e-9) {
-        best_eff = eff;
-        best = i;
-      }
-    }
-    if (kd_switch("KD_WZ_TILE", 0) > 0 && p.wz_rows % 256 == 0) best = kd_switch("KD_WZ_TILE", 0) - 1;   // experiment: force a shape
-    if (best == 0) {
-      dim3 grid((unsigned)((M + 255) / 256), (p.Cout + 127) / 128);
-      hipLaunchKernelGGL((conv_buf_kernel<256, 128, 4, 2, 2>), grid, dim3(512), 0, s, p);
-    } else if (best == 1) {
-      dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 127) / 128);
-      hipLaunchKernelGGL((conv_buf_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, s, p);
-    } else {
-      dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 63) / 64);
-      hipLaunchKernelGGL((conv_buf_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
-    }
-  } else if (p.KH * p.KW == 1 && k_chunks <= 8 && p.wz_rows == 0 && shortk == 1 &&
-      ((M + 127) / 128) * ((p.Cout + 127) / 128) >= 256) {
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_buf_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, s, p);
-  } else if (p.KH * p.KW == 1 && k_chunks <= 8 && p.wz_rows == 0 && shortk == 2 && tiles256 >= 256) {
-    dim3 grid((unsigned)((M + 255) / 256), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_buf_kernel<256, 128, 4, 2, 2>), grid, dim3(512), 0, s, p);
-  } else if (p.KH * p.KW == 1 && k_chunks <= 8 && p.wz_rows == 0) {
-    // 1x1 convs with K <= 256 (ResnetBlock skip convs with the gate epilogue, pixel-shuffle upsamples)
-    // move as many bytes as they compute: three 128x64 workgroups per CU keep more loads in flight
-    // (measured -12..16 % on them; the Winograd GEMMs of the same K lose 4 % with this shape)
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 63) / 64);
-    hipLaunchKernelGGL((conv_buf_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
-  } else if (tiles256 >= 512 && (p.KH * p.KW > 1 || k_chunks >= 64)) {
-    dim3 grid((unsigned)((M + 255) / 256), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_buf_kernel<256, 128, 4, 2, 2>), grid, dim3(512), 0, s, p);
-  } else if (((M + 127) / 128) * ((p.Cout + 127) / 128) >= 512) {
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_buf_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, s, p);
-  } else {  // few tiles (deep 16x16 levels, attention projections): 128x64 tiles, 3 workgroups per CU
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 63) / 64);
-    hipLaunchKernelGGL((conv_buf_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, p);
+  if (sh.variant >= 0) {
+    const ConvTile& t = conv_tile(sh.variant);
+    sh.grid[0] = (unsigned)((M + t.bm - 1) / t.bm);
+    sh.grid[1] = (unsigned)((p.Cout + t.bn - 1) / t.bn);
+    sh.grid[2] = (unsigned)sh.ksplit;
   }
-  KD_HIP_CHECK(hipGetLastError());
-  return 0;
+  return sh;
 }
 
-// 16-byte epilogue (store_tile_regs_wide): NHWC output whose rows, and those of every map the epilogue adds, start on
-// 16-byte boundaries; whole 32-row MFMA tiles (and one image per tile where a per-image gate is applied)
-static bool conv_wide_ok(const ConvParams& p) {
-  const int64_t M = (int64_t)p.B * p.Ho * p.Wo;
-  auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  return p.ksplit <= 1 && M % 32 == 0 && p.Cout % 4 == 0 && p.ldy % 4 == 0 && p.yoff % 4 == 0 && al(p.y) && al(p.bias) &&
-         (!p.res || (al(p.res) && p.ldres % 4 == 0)) &&
-         (!p.gate_src || (al(p.gate_src) && al(p.gate) && p.ldgs % 4 == 0 && (p.Ho * p.Wo) % 32 == 0)) &&
-         (!p.seg_partial || ((p.Ho * p.Wo) % 32 == 0 && p.Cout % 16 == 0));
+template <int BM, int BN, int WM, int WN, int MINW>
+static void launch_buf(const ConvParams& q, const ConvShape& sh, hipStream_t s) {
+  hipLaunchKernelGGL((conv_buf_kernel<BM, BN, WM, WN, MINW>), dim3(sh.grid[0], sh.grid[1], sh.grid[2]), dim3(WM * WN * 64), 0, s, q);
+}
+template <int BM, int BN, int WM, int WN>
+static void launch_generic(const ConvParams& q, const ConvShape& sh, hipStream_t s) {
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN>), dim3(sh.grid[0], sh.grid[1], sh.grid[2]), dim3(WM * WN * 64), 0, s, q);
 }
 
-int launch_conv_igemm(const ConvParams& p, hipStream_t s) {
+int launch_conv_igemm(const ConvParams& p, const ConvShape& sh, hipStream_t s) {
   KD_REQUIRE(p.Cin % 4 == 0 && p.ldx % 4 == 0, "igemm needs Cin and ldx multiples of 4");
-  KD_REQUIRE(!p.seg_partial || (conv_seg_chunks(p) > 0 && p.seg_nseg > 0),
-             "conv: this launch cannot leave GroupNorm partials (see conv_seg_chunks)");
+  KD_REQUIRE(!p.seg_partial || (sh.seg_chunks > 0 && p.seg_nseg > 0),
+             "conv: this launch cannot leave GroupNorm partials (see ConvShape::seg_chunks)");
   KD_REQUIRE(((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.w & 15) == 0, "igemm operands must be 16-B aligned");
+  KD_REQUIRE((sh.al16 & ~conv_ptrs_of(p).al16 & 63) == 0,
+             "conv: a pointer lacks the 16-byte alignment the launch shape was built for");
   if (p.out_mode == OUT_PIXSHUF) KD_REQUIRE(p.Cout % 4 == 0, "pixel-shuffle needs Cout % 4 == 0");
   int64_t M = (int64_t)p.B * p.Ho * p.Wo;
   KD_REQUIRE(M > 0 && p.Cout > 0, "empty conv");
   if (p.wz_rows > 0)
     KD_REQUIRE(p.KH * p.KW == 1 && p.wz_rows % 128 == 0 && M == (int64_t)p.wz_rows * p.wz_count,
                "batched GEMM: 1x1 only, slab rows a multiple of 128, M = rows x slabs");
-  const int ks = p.partial ? conv_ksplit(p) : 1;
-  if (ks > 1) {
-    KD_REQUIRE(((uintptr_t)p.partial & 15) == 0, "split-K partial buffer must be 16-B aligned");
+  KD_REQUIRE(sh.variant >= 0 && sh.variant < CONV_VARIANTS, "batched GEMM needs the buffer-load fast path (Cin % 32 == 0, Cout > 32)");
+  if (sh.ksplit > 1) {
+    KD_REQUIRE(p.partial && ((uintptr_t)p.partial & 15) == 0, "split-K partial buffer must be 16-B aligned");
     KD_REQUIRE(!p.seg_partial || ((((uintptr_t)p.y | (uintptr_t)p.res) & 15) == 0),
                "split-K conv: GroupNorm partials come from the 16-byte path of the reduction (aligned output / residual)");
-    ConvParams q = p;
-    q.ksplit = ks;
-    q.wide_epilogue = p.Cout % 4 == 0 &&   // the raw partial tiles [z][M][Cout] with 16-byte stores
-                      kd_switch("KD_CONV_WIDE", 1) != 0;
-    if (M <= 64) {
-      // an 8x8 map of a batch-1 patch: 64-row tiles (a 128-row tile would spend half its MFMAs on padding and
-      // these launches, K up to 9 x 3072, were bound by exactly that: 124 us for 226 MB of weights), 128 columns
-      dim3 grid(1, (p.Cout + 127) / 128, ks);
-      hipLaunchKernelGGL((conv_buf_kernel<64, 128, 1, 4, 3>), grid, dim3(256), 0, s, q);
-    } else {
-      dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 63) / 64, ks);
-      hipLaunchKernelGGL((conv_buf_kernel<128, 64, 2, 2, 3>), grid, dim3(256), 0, s, q);
-    }
+  }
+  ConvParams q = p;
+  q.ksplit = sh.ksplit;
+  q.wide_epilogue = sh.wide_epilogue;
+  switch (sh.variant) {
+    case CONV_BUF_256x128: launch_buf<256, 128, 4, 2, 2>(q, sh, s); break;
+    case CONV_BUF_128x128: launch_buf<128, 128, 2, 2, 2>(q, sh, s); break;
+    case CONV_BUF_128x64: launch_buf<128, 64, 2, 2, 3>(q, sh, s); break;
+    case CONV_BUF_64x128: launch_buf<64, 128, 1, 4, 3>(q, sh, s); break;
+    case CONV_IGEMM_128x32: launch_generic<128, 32, 4, 1>(q, sh, s); break;
+    case CONV_IGEMM_128x64: launch_generic<128, 64, 2, 2>(q, sh, s); break;
+    case CONV_IGEMM_64x128: launch_generic<64, 128, 1, 4>(q, sh, s); break;
+    case CONV_IGEMM_128x128: launch_generic<128, 128, 2, 2>(q, sh, s); break;
+  }
+  if (sh.ksplit > 1) {
     const int64_t total = M * (p.Cout / 4);
     hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, M);
-    KD_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  const bool fast = fast_shape_ok(p) && M > 64;
-  if (fast && (p.out_mode == OUT_NHWC || p.out_mode == OUT_PIXSHUF) && conv_wide_ok(p) &&
-      kd_switch("KD_CONV_WIDE", 1) != 0) {   // (A/B switch)
-    ConvParams q = p;
-    q.wide_epilogue = 1;
-    return launch_conv_fast(q, M, s);
-  }
-  if (fast) return launch_conv_fast(p, M, s);
-  KD_REQUIRE(p.wz_rows == 0, "batched GEMM needs the buffer-load fast path (Cin % 32 == 0, Cout > 32)");
-  ConvParams g = p;
-  g.wide_epilogue = p.out_mode == OUT_NHWC && conv_wide_ok(p) && kd_switch("KD_CONV_WIDE", 1) != 0;
-  if (p.Cout <= 32) {
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 31) / 32);
-    hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1>), grid, dim3(256), 0, s, g);
-  } else if (p.Cout <= 64) {
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 63) / 64);
-    hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 2, 2>), grid, dim3(256), 0, s, g);
-  } else if (M <= 64) {
-    dim3 grid((unsigned)((M + 63) / 64), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 1, 4>), grid, dim3(256), 0, s, g);
-  } else {
-    dim3 grid((unsigned)((M + 127) / 128), (p.Cout + 127) / 128);
-    hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, g);
   }
   KD_HIP_CHECK(hipGetLastError());
   return 0;

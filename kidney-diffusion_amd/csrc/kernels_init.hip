@@ -405,7 +405,8 @@ static int launch_init_conv_np(const InitConvParams& p, int n3, size_t smem, int
 }
 
 int launch_init_conv(const float* x, const float* sc, int cx, int np, const float* wp, const float* bias, const float* res, float* y,
-                     int ldy, double* seg, int B, int S, int n3, int n7, int n15, hipStream_t s) {
+                     int ldy, double* seg, int B, int S, int n3, int n7, int n15, int cus, hipStream_t s) {
+  KD_REQUIRE(cus > 0, "init conv kernel: CU count missing");
   KD_REQUIRE(init_conv_fused_ok(S, n3, n7, n15, np), "init conv kernel: image size % 32, weights must fit LDS");
   KD_REQUIRE(ldy % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
                  ((uintptr_t)wp & 15) == 0,
@@ -415,14 +416,6 @@ int launch_init_conv(const float* x, const float* sc, int cx, int np, const floa
   InitConvParams p{x, wp, bias, res, y, seg, B, S, ldy, n3, n7, n15, np == 2 * cx ? sc : nullptr, cx};
   const size_t smem = init_conv_lds_floats(n3, n7, n15, np) * sizeof(float);
   const int ntiles = B * (S / IC_TW) * (S / IC_TH);
-  static int cus = 0;
-  if (!cus) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    KD_HIP_CHECK(hipGetDevice(&dev));
-    KD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
   const int grid = ntiles < cus ? ntiles : cus;   // persistent: one workgroup per CU keeps the weights in LDS
   int rc = 1;
   switch (np) {
@@ -600,7 +593,8 @@ static int launch_init_plain_k(const InitPlainParams& p, int np, size_t smem, in
 }
 
 int launch_init_plain(const float* x, const float* sc, int cx, int np, const float* wp, const float* bias, const float* res, float* y,
-                      int ldy, double* seg, int B, int S, int n, int k, hipStream_t s) {
+                      int ldy, double* seg, int B, int S, int n, int k, int cus, hipStream_t s) {
+  KD_REQUIRE(cus > 0, "plain init conv kernel: CU count missing");
   KD_REQUIRE(init_plain_ok(S, n, k, np), "plain init conv kernel: kernel size 3 | 5 | 7, image size % 32, weights must fit LDS");
   KD_REQUIRE(B >= 1 && (int64_t)B * (S / IC_TW) * (S / IC_TH) < 0x7fffffff, "plain init conv kernel: batch out of range");
   KD_REQUIRE(ldy % 4 == 0 && ldy >= n && ((uintptr_t)y & 15) == 0 && ((uintptr_t)res & 15) == 0 && ((uintptr_t)bias & 15) == 0 &&
@@ -611,14 +605,6 @@ int launch_init_plain(const float* x, const float* sc, int cx, int np, const flo
   InitPlainParams p{x, np == 2 * cx ? sc : nullptr, wp, bias, res, y, seg, B, S, ldy, n, cx};
   const size_t smem = init_plain_lds_floats(n, k, np) * sizeof(float);
   const int ntiles = B * (S / IC_TW) * (S / IC_TH);
-  static int cus = 0;
-  if (!cus) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    KD_HIP_CHECK(hipGetDevice(&dev));
-    KD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
   const int grid = ntiles < cus ? ntiles : cus;   // persistent: one workgroup per CU keeps the weights in LDS
   int rc = 1;
   switch (k) {

@@ -562,7 +562,8 @@ int launch_wino_fused128_items(void* items, int B, int H, int W, int N, hipStrea
 
 int launch_wino_fused_gn128(const float* x, int ldx, const float* ab, const float* U, const float* bias, const float* res,
                             int ldres, float* y, int B, int H, int W, int C, int N, double* out_partial, int out_groups,
-                            const void* items, hipStream_t s) {
+                            const void* items, int cus, hipStream_t s) {
+  KD_REQUIRE(cus > 0, "GroupNorm-fused Winograd conv: CU count missing");
   KD_REQUIRE(ldx >= C && ldx % 4 == 0 && (int64_t)H * W * ldx * 4 < 0x7fffffff && ((uintptr_t)x & 15) == 0,
              "GroupNorm-fused Winograd conv: bad input row stride");
   KD_REQUIRE(wino_fused128_ok(B, H, W, C, N),
@@ -575,15 +576,8 @@ int launch_wino_fused_gn128(const float* x, int ldx, const float* ab, const floa
   KD_REQUIRE(items != nullptr, "GroupNorm-fused Winograd conv: item table missing (launch_wino_fused128_items)");
   KD_REQUIRE(!res || (int64_t)H * W * ldres * 4 < 0x7fffffff, "GroupNorm-fused Winograd conv: residual images above 2 GB");
   const unsigned grid = (unsigned)wino_fused128_items_count(B, H, W, N);
-  static int cus = 0;
-  if (!cus) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    KD_HIP_CHECK(hipGetDevice(&dev));
-    KD_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : 8;   // a multiple of the 8 XCDs
-  }
-  const unsigned pgrid = grid < (unsigned)cus ? grid : (unsigned)cus;   // persistent: one workgroup per CU
+  const unsigned slots = cus >= 8 ? (unsigned)cus / 8 * 8 : 8;   // a multiple of the 8 XCDs
+  const unsigned pgrid = grid < slots ? grid : slots;   // persistent: one workgroup per CU
   static const int prio = kd_switch("KD_FWINO_PRIO", 1);
   hipLaunchKernelGGL(wino_fused_gn128_kernel, dim3(pgrid), dim3(1024), 0, s, x, ldx, ab, U, bias, res, ldres, y, B, H, W, C, N,
                      out_partial, out_groups, (const int4*)items, prio);

@@ -257,7 +257,7 @@ Builder::InitConv Builder::init_conv(const Model& m) {
     const int64_t mc = (int64_t)B * S * S * np * k * k * dim;
     emit([=](hipStream_t s) {
       if (check_inputs()) return 1;
-      return launch_init_plain(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, dim, k, s);
+      return launch_init_plain(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, dim, k, io->cus, s);
     }, "init conv plain fused k" + std::to_string(k) + " S" + std::to_string(S) + " C" + std::to_string(dim) + (u->self_cond ? " self-cond" : ""), mc);
     count_macs(mc, (int64_t)B * S * S * k * (((k * np + 1) / 2) * 2) * ((dim + 31) / 32 * 32));
   } else if (fused_init) {
@@ -288,7 +288,7 @@ Builder::InitConv Builder::init_conv(const Model& m) {
     const int64_t mc = (int64_t)B * S * S * np * (9 * n3 + 49 * n7 + 225 * n15);
     emit([=](hipStream_t s) {
       if (check_inputs()) return 1;
-      return launch_init_conv(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, n3, n7, n15, s);
+      return launch_init_conv(io->in_x, io->in_self_cond, Ci, np, wp, biasp, rr.f(), yr.f(), ldy, seg.d(), Bx, S, n3, n7, n15, io->cus, s);
     }, "init conv fused S" + std::to_string(S) + " C" + std::to_string(dim) + (u->self_cond ? " self-cond" : ""), mc);
     // K runs (3 / 7 / 15 kernel rows of np k values, padded to even) x 32-row tiles
     const int r3 = 3 * (((3 * np + 1) / 2) * 2), r7 = 7 * (((7 * np + 1) / 2) * 2), r15 = 15 * (((15 * np + 1) / 2) * 2);

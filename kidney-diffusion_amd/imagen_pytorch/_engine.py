@@ -257,6 +257,7 @@ SIGNATURES = {
                                [C.c_int, C.c_void_p]),
     "kd_gate_add_nhwc": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "kd_gate_add_chunks": (C.c_int, [C.c_int, C.c_int]),
+    "kd_conv_launch_shape": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_void_p]),
     "kd_gn_fold_seg": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                  C.c_float] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] * 4 +
                        [C.c_float, C.c_void_p]),

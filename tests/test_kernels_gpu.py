@@ -49,6 +49,8 @@ CONV_REL = 2e-6
     (1, 9, 7, 512, 200, 3, 1, 1, 1),       # split-K, ragged M = 63 and Cout = 200, SiLU after the reduction
     (1, 16, 16, 512, 320, 1, 1, 0, 2),     # split-K of a 1x1 conv (16 chunks), GELU
     (2, 8, 8, 96, 128, 2, 2, 0, 0),        # M = 32, K too short to split: generic small-M kernel
+    (1, 128, 128, 288, 512, 1, 1, 0, 0),   # fast path, 128x128 tiles: 9 k-chunks (past the short-K form), 512 tiles
+    (1, 12, 12, 36, 72, 1, 1, 0, 0),       # generic kernel, 128x128 tiles: Cin not /32, Cout > 64, M > 64
 ])
 def test_conv_igemm(lib, device, B, H, W, Cin, Cout, K, stride, pad, act):
     E = engine()
